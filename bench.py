@@ -18,7 +18,9 @@ Inputs are synthetic (no BOP data or checkpoints exist offline), generated on th
 the timed region; every timed byte is already resident in HBM.  Weak scaling: each rank owns
 --images images, image i of the sequence lives on rank i // images.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline
+(`value`, `ms_per_step`, the last step's final Chamfer); --dump-outputs DIR also writes what the last timed step
+computed as DIR/<name>.npy (rank 0's view, float32 / float64).  Everything else is measured only with --full:
   roofline      K1 (the dominant kernel): algorithmic 2*P*N*D FLOP per launch / its average launch
                 duration measured live with HIP events on the launch stream, against the dense
                 bf16 MFMA peak; `traffic` from profiles/ (rocprofv3 --pmc) when committed.
@@ -26,7 +28,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with two extra o
                 here) timed on a bounded sample of the same workload on this box's host cores.
 and, untimed, `parity_check` (the last step recomputed by the oracle) and `estimate_pose` (the reference's other per-image
 path, poseEstSurf.estimate_pose, at its own size: ms per call of the matrix-free and of the materialised route) and
-`reference_shape` (the reference's own 75 x 75 / 12-D / 80 000-key per-image loop through sequence.register_crops).
+`reference_shape` (the reference's own 75 x 75 / 12-D / 80 000-key per-image loop through sequence.register_crops),
+`acceptance`, `ransac_all_hypotheses`, `f32_step`, `screened_step`, `roofline_nn`, `roofline_ransac`, `nn_stage` and
+`stage_ms_per_step`.
 """
 from __future__ import annotations
 
@@ -104,7 +108,47 @@ def parse_args():
     ap.add_argument("--no-parity-check", action="store_true", help="skip the untimed oracle re-computation of the last step")
     ap.add_argument("--no-f32-step", action="store_true", help="skip the untimed step on f32 descriptors (the reference's precision)")
     ap.add_argument("--no-screened-step", action="store_true", help="skip the untimed |k| = 8 step pair (K1 unscreened / behind the FP6 screen)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel timing inside the timed steps, rooflines, the untimed extra steps "
+                         "(all hypotheses, f32, |k| = 8), acceptance, parity check, estimate_pose / reference shape, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+# K1's per-query outputs of one image are dumped whole up to this many rows, beyond it as a fixed sorted sample
+DUMP_K1_ROWS = 1 << 20
+
+
+def dump_outputs(out_dir: str, last: dict) -> None:
+    """What the last timed step handed back on rank 0, one .npy per array: every image's pose (all-gathered), this rank's
+    RANSAC status, K1's arg-max / log-probability for this rank's first image, the verification's result and the ICP +
+    final Chamfer of the picked image.  float64 throughout, except K1's f32 log-probabilities."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    arrs = {"poses": np.asarray(last["poses_all"], np.float64).reshape(-1, 3, 4)} if "poses_all" in last else {}
+    if "_status_local" in last:
+        arrs["status"] = last["_status_local"].cpu().numpy().astype(np.float64)
+    if last.get("_k1_first") is not None:
+        idx, logp = (t.cpu().numpy() for t in last["_k1_first"])
+        rows = np.arange(idx.shape[0])
+        if rows.size > DUMP_K1_ROWS:
+            rows = np.sort(np.random.default_rng(0).choice(rows.size, DUMP_K1_ROWS, replace=False))
+            arrs["k1_rows"] = rows.astype(np.float64)
+        arrs["k1_idx"] = idx[rows].astype(np.float64)
+        arrs["k1_logp"] = logp[rows].astype(np.float32)
+    if last.get("chamfer_table") is not None:
+        arrs["chamfer_table"] = np.asarray(last["chamfer_table"], np.float64)
+    for k in ("picked_image", "final_chamfer", "icp_fitness", "icp_rmse"):
+        if last.get(k) is not None:
+            arrs[k] = np.array([last[k]], np.float64)
+    if last.get("_icp_T") is not None:
+        arrs["icp_T"] = np.asarray(last["_icp_T"], np.float64).reshape(4, 4)
+    for name, a in arrs.items():
+        np.save(d / f"{name}.npy", a)
 
 
 def make_model(dev, N, D, tau=5.0, obj="tless"):
@@ -638,7 +682,7 @@ def main():
                 init = np.linalg.inv(np.vstack([pose, [0, 0, 0, 1]]))                               # icp.py:88-92
                 T, fit, rmse = registration.icp_point_to_point(src, lower, 20, init, max_iter=args.icp_iters, spatial_order=False)
                 out.update(final_chamfer=registration.final_chamfer(src, lower, T, cad), icp_fitness=fit,
-                           icp_rmse=rmse, rot_err_rad=synth.rot_angle(pose[:, :3], R_gt[best]),
+                           icp_rmse=rmse, _icp_T=T, rot_err_rad=synth.rot_angle(pose[:, :3], R_gt[best]),
                            trans_err_mm=float(np.linalg.norm(pose[:, 3] - t_gt[best])))
         return out
 
@@ -706,7 +750,7 @@ def main():
     # K1 with the chip to itself (untimed region, rank 0): the in-step figure below shares the GPU with the
     # RANSAC chains and the previous batch's verification, this one is the kernel alone
     k1_alone_ms = k1_clock_mhz = k1_rechecked = k1_screen = None
-    if rank == 0:
+    if args.full and rank == 0:
         g_rows = Q_all[:max(args.group, 1)].reshape(-1, D)
         dig = dict(rows_per_image=P) if sequence.EPILOGUE_DIGITS else {}      # the call the step makes
         ops.corr_argmax(g_rows, model.keys, log2_prescaled=model.log2_queries, screened=model.screened, **dig)
@@ -739,13 +783,14 @@ def main():
                                  "within T of L_q; flop_per_launch stays the ALGORITHMIC 2 P N D"}
     # untimed region, rank 0: the brute-force NN rate at the Chamfer-pair shape and the exact-f32 K1 on one image
     nn_live = f32_exact = nn_vote = k2_live = None
-    if rank == 0:
+    if args.full and rank == 0:
         nn_live = measure_nn(pts, dev)
         k2_live = measure_ransac(dev, pts, Kcam, M=int(0.8 * P), H=max(args.itr, 4096))
         if args.verify == "vote":
             nn_vote = measure_nn_vote(cad_d, pts, dev, items=min(4096, n_local * n_total))
         f32_exact = measure_k1_f32(Q_all[0], keys_f32, dev, args.k1 != "natural")
-    ops.enable_timing(True)
+    # per-entry-point HIP events inside the timed steps feed the roofline / stage figures of --full only
+    ops.enable_timing(args.full)
     step_done.clear()
     last, dt, dts = timed(args.warmup, args.steps, args.confidence)
     step_intervals_ms = [(b - a) * 1e3 for a, b in zip(step_done[:-1], step_done[1:])]
@@ -753,17 +798,20 @@ def main():
     ops.enable_timing(False)
     # the ICP result of the last step lives on the rank that owned the chosen image: bring it to rank 0
     if world > 1 and args.ablate != "noverify":
-        vals = torch.zeros(5, dtype=torch.float64, device=shard._coll_device())
+        vals = torch.zeros(21, dtype=torch.float64, device=shard._coll_device())
         if rank == last["icp_rank"]:
             vals[:] = torch.tensor([last["final_chamfer"], last["icp_fitness"], last["icp_rmse"], last["rot_err_rad"],
-                                    last["trans_err_mm"]], dtype=torch.float64)
+                                    last["trans_err_mm"], *np.asarray(last["_icp_T"]).reshape(16)], dtype=torch.float64)
         torch.distributed.broadcast(vals, src=last["icp_rank"])
         v = [float(x) for x in vals.cpu()]
-        last.update(final_chamfer=v[0], icp_fitness=v[1], icp_rmse=v[2], rot_err_rad=v[3], trans_err_mm=v[4])
+        last.update(final_chamfer=v[0], icp_fitness=v[1], icp_rmse=v[2], rot_err_rad=v[3], trans_err_mm=v[4],
+                    _icp_T=np.array(v[5:]).reshape(4, 4))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     # untimed tail, every rank: the reference's per-image acceptance bookkeeping (inference.py:299-320, the T-LESS branch:
     # ADD-S of the pose and of its rotation alone against 0.1 x diameter) for the last step's block, summed over ranks
     acceptance = None
-    if args.ablate != "noverify":
+    if args.full and args.ablate != "noverify":
         acc = sequence.acceptance_counts(cad_d, pts, R_gt[lo:hi], t_gt[lo:hi], last["_poses_local"], last["_status_local"],
                                          diameter, dataset="tless")
         fin = np.isfinite(acc["final_error"])
@@ -780,7 +828,7 @@ def main():
     # second short timed loop (untimed for `value`): the same step with EVERY hypothesis scored (confidence 1), so the
     # line carries the cv2-default figure and the score-everything one side by side
     all_hyp = None
-    if args.confidence < 1.0 and args.ablate != "noverify":
+    if args.full and args.confidence < 1.0 and args.ablate != "noverify":
         k = max(2, min(4, args.steps))
         last_all, dt_all, _ = timed(args.warmup + args.steps, k, 1.0)
         all_hyp = {"value": n_total * k / dt_all, "unit": "images/s", "steps": k, "ms_per_step": dt_all / k * 1e3,
@@ -799,7 +847,7 @@ def main():
     # UNTIMED: the same step at the reference's own precision (inference.py:142-149 is an f32 matmul): f32 keys, f32 queries,
     # K1 on the f16-plane route; a few steps, every rank (the step has collectives)
     f32_step = None
-    if args.group > 1 and args.ablate != "noverify" and not args.no_f32_step:
+    if args.full and args.group > 1 and args.ablate != "noverify" and not args.no_f32_step:
         k = max(2, min(4, args.steps))
         cur["model"] = sequence.SequenceModel(keys=keys_f32, pts=pts)
         cur["Q"] = (Q_all.float() / (ops.LOG2E if args.k1 != "natural" else 1.0)).contiguous()
@@ -825,7 +873,8 @@ def main():
     # (ISR_DTYPE_BF16_LOG2_SCREENED) can skip — unscreened and screened on the same data.  (At the bench's |k| = 5 every term
     # of the sums counts and the screened dtype hands every block to the dense kernel: DESIGN.md section 4 K1d.)
     screened_step = None
-    if args.group > 1 and args.ablate != "noverify" and not args.no_screened_step and D == 64 and args.k1 != "natural" and args.object == "tless":
+    if (args.full and args.group > 1 and args.ablate != "noverify" and not args.no_screened_step and D == 64 and args.k1 != "natural"
+            and args.object == "tless"):
         keys8 = make_model(dev, N, D, tau=8.0, obj=args.object)[0]
         Q8 = torch.empty_like(Q_all)
         for j, i in enumerate(range(lo, hi)):
@@ -866,18 +915,6 @@ def main():
         del Q8
 
     if rank == 0:
-        calls, ms, flop = timing.get("corr_argmax", (0, 0.0, 0.0))
-        k1_ms = ms / max(calls, 1)
-        k1 = flop / max(calls, 1) / (k1_ms * 1e-3) if calls else 0.0
-        # HBM bytes per launch come from PMC counters, which cannot be read inside a timed run: a separate
-        # rocprofv3 --pmc pass of this very command (tools/pmc_traffic.sh) writes profiles/k1_hbm_traffic.json
-        traffic = traffic_src = None
-        pmc = ROOT / "profiles" / "k1_hbm_traffic.json"
-        if pmc.exists() and (P, N, D) == (307200, 20000, 64):   # measured for this configuration only
-            rec = json.loads(pmc.read_text()).get("per_launch", {}).get(str(max(args.group, 1)))
-            if rec:
-                traffic, traffic_src = rec["hbm_bytes"], "profiles/k1_hbm_traffic.json: " + rec.get("source", "rocprofv3 --pmc")
-        ncalls, nms, pairs = timing.get("nn_batched", (0, 0.0, 0.0))
         verification = ("consecutive-pair Chamfer pick (one f64 min-table all-reduce)" if args.verify == "pick" else
                         "n x n ADD-S vote, rows sharded (row-sum all-gather)")
         last_pub = {k: v for k, v in last.items() if k not in ("poses_all", "chamfer_table") and not k.startswith("_")}
@@ -904,75 +941,91 @@ def main():
                        "step_overlap": ("none" if args.no_pipeline else
                                         "verification (all-gather, pick/vote, ICP, final Chamfer) of batch s "
                                         "overlaps the registration of batch s+1")},
-            "final_chamfer": last.get("final_chamfer"), "last_step": last_pub, "acceptance": acceptance,
+            "final_chamfer": last.get("final_chamfer"), "last_step": last_pub,
             "object": args.object,
             "step_intervals_ms": {"what": "host time between consecutive steps' verification results on this rank (the last one includes the "
                                           "pipeline's drain)", "values": [round(v, 2) for v in step_intervals_ms]},
             "per_rank_ms_per_step": {"min": min(dts) / args.steps * 1e3, "max": max(dts) / args.steps * 1e3,
                                      "all": [d / args.steps * 1e3 for d in dts]},
-            "ransac_all_hypotheses": all_hyp,
-            "f32_step": f32_step,
-            "screened_step": screened_step,
-            "roofline": {"kernel": ({"screened": "corr_quant_fp6_kernel x2 + corr_fp6_lower_kernel + corr_fp6_sparse_kernel (the whole "
-                                                 "isr_corr_argmax call; HIP events around it)",
-                                     "log2": "corr_bf16_direct_kernel", "natural": "corr_bf16_kernel"}[args.k1])
-                                   + " (K1 getCors: MFMA GEMM + online LSE + argmax)",
-                         "screen": k1_screen,
-                         "k1_domain": args.k1,
-                         "bound": "mfma", "achieved": k1 * 1e-12, "peak": PEAK_BF16_MFMA * 1e-12,
-                         "unit": "TFLOP/s", "frac": k1 / PEAK_BF16_MFMA, "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes": 2.0 * P * max(args.group, 1) * D + 2.0 * N * D + 8.0 * P * max(args.group, 1),
-                         "ms_per_launch": k1_ms, "launches": calls,
-                         "ms_per_launch_covers": ("HIP events on the K1 stream around the opening half of each call: corr_keynorm_kernel + "
-                                                  "the chip-filling kernel (the closing kernels — fallback, finalize, recheck, merge — run on "
-                                                  "the group's side stream: isr_corr_argmax_phase)" if sequence.K1_SPLIT_CLOSE and args.group > 1
-                                                  else "HIP events on the K1 stream around the whole isr_corr_argmax call"),
-                         "clock_mhz_under_kernel": k1_clock_mhz,
-                         "frac_at_held_clock": (k1 / (PEAK_BF16_MFMA * k1_clock_mhz / 2400.0)) if k1_clock_mhz else None,
-                         "clock_note": "peak is quoted at the 2400 MHz boost clock; frac_at_held_clock scales it to the clock "
-                                       "one workgroup of the kernel measured (alone on the GPU, untimed region)",
-                         "queries_decided_by_exact_recheck": k1_rechecked,
-                         "alone": {"ms_per_launch": k1_alone_ms,
-                                   "frac": (flop / max(calls, 1) / (k1_alone_ms * 1e-3) / PEAK_BF16_MFMA
-                                            if calls and k1_alone_ms else None),
-                                   "note": "same launch with nothing else on the GPU (incl. finalize), untimed region"},
-                         "flop_per_launch": flop / max(calls, 1), "images_per_launch": max(args.group, 1),
-                         "exp_per_s": flop / max(calls, 1) / (2.0 * D) / (k1_ms * 1e-3) if calls else 0.0,
-                         "f32_exact": f32_exact},
-            "roofline_nn": nn_live,
-            "roofline_nn_vote": nn_vote,
-            "roofline_ransac": k2_live,
-            # K3 is no longer one kernel at one rate: single-item calls (ICP steps, final Chamfer) scan every
-            # target (nn_search_kernel, VALU-bound), the batched Chamfer pick runs the block-cooperative grid
-            # search, which evaluates only the candidates near each query cell.  Reported: the rate in
-            # brute-force-EQUIVALENT pairs (B Nq Nt per call) — a throughput figure, not a roofline fraction.
-            "nn_stage": {"kernels": "nn_search_kernel (brute force: ICP, final Chamfer, vote items) / nn_tile_search_kernel "
-                                    "(block-cooperative grid: batched pick)",
-                         "equivalent_pairs_per_s": pairs / (nms * 1e-3) if ncalls else 0.0, "calls": ncalls,
-                         "ms_per_step": nms / args.steps,
-                         "note": "brute-force rate measured live: roofline_nn; DESIGN.md section 4 (K3/K4)"},
-            "stage_ms_per_step": {k: v[1] / args.steps for k, v in timing.items()},
         }
-        if world == 1 and not args.no_estimate_pose:
-            try:
-                line["estimate_pose"] = measure_estimate_pose(dev)
-            except Exception as e:
-                line["estimate_pose"] = {"error": repr(e)}
-            try:
-                line["reference_shape"] = measure_reference_shape(dev)
-            except Exception as e:
-                line["reference_shape"] = {"error": repr(e)}
-        if not args.no_parity_check and args.ablate != "noverify":
-            try:
-                line["parity_check"] = parity_check(args, model, Q_all[0], keys, pts, last, R_gt, t_gt, upper, lower, cad)
-            except Exception as e:  # the GPU line must survive a checker-side failure
-                line["parity_check"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
-            try:
-                line["cpu_baseline"] = cpu_baseline(args, keys, pts, images[0][0], images[0][1], Kcam, upper,
-                                                    lower, cad, R_gt, t_gt)
-            except Exception as e:  # the GPU line must survive a checker-side failure
-                line["cpu_baseline"] = {"value": None, "error": repr(e), "kind": "port"}
+        if args.full:
+            calls, ms, flop = timing.get("corr_argmax", (0, 0.0, 0.0))
+            k1_ms = ms / max(calls, 1)
+            k1 = flop / max(calls, 1) / (k1_ms * 1e-3) if calls else 0.0
+            # HBM bytes per launch come from PMC counters, which cannot be read inside a timed run: a separate
+            # rocprofv3 --pmc pass of this very command (tools/pmc_traffic.sh) writes profiles/k1_hbm_traffic.json
+            traffic = traffic_src = None
+            pmc = ROOT / "profiles" / "k1_hbm_traffic.json"
+            if pmc.exists() and (P, N, D) == (307200, 20000, 64):   # measured for this configuration only
+                rec = json.loads(pmc.read_text()).get("per_launch", {}).get(str(max(args.group, 1)))
+                if rec:
+                    traffic, traffic_src = rec["hbm_bytes"], "profiles/k1_hbm_traffic.json: " + rec.get("source", "rocprofv3 --pmc")
+            ncalls, nms, pairs = timing.get("nn_batched", (0, 0.0, 0.0))
+            line.update({
+                "acceptance": acceptance,
+                "ransac_all_hypotheses": all_hyp,
+                "f32_step": f32_step,
+                "screened_step": screened_step,
+                "roofline": {"kernel": ({"screened": "corr_quant_fp6_kernel x2 + corr_fp6_lower_kernel + corr_fp6_sparse_kernel (the whole "
+                                                     "isr_corr_argmax call; HIP events around it)",
+                                         "log2": "corr_bf16_direct_kernel", "natural": "corr_bf16_kernel"}[args.k1])
+                                       + " (K1 getCors: MFMA GEMM + online LSE + argmax)",
+                             "screen": k1_screen,
+                             "k1_domain": args.k1,
+                             "bound": "mfma", "achieved": k1 * 1e-12, "peak": PEAK_BF16_MFMA * 1e-12,
+                             "unit": "TFLOP/s", "frac": k1 / PEAK_BF16_MFMA, "traffic": traffic, "traffic_source": traffic_src,
+                             "algorithmic_bytes": 2.0 * P * max(args.group, 1) * D + 2.0 * N * D + 8.0 * P * max(args.group, 1),
+                             "ms_per_launch": k1_ms, "launches": calls,
+                             "ms_per_launch_covers": ("HIP events on the K1 stream around the opening half of each call: corr_keynorm_kernel + "
+                                                      "the chip-filling kernel (the closing kernels — fallback, finalize, recheck, merge — run on "
+                                                      "the group's side stream: isr_corr_argmax_phase)" if sequence.K1_SPLIT_CLOSE and args.group > 1
+                                                      else "HIP events on the K1 stream around the whole isr_corr_argmax call"),
+                             "clock_mhz_under_kernel": k1_clock_mhz,
+                             "frac_at_held_clock": (k1 / (PEAK_BF16_MFMA * k1_clock_mhz / 2400.0)) if k1_clock_mhz else None,
+                             "clock_note": "peak is quoted at the 2400 MHz boost clock; frac_at_held_clock scales it to the clock "
+                                           "one workgroup of the kernel measured (alone on the GPU, untimed region)",
+                             "queries_decided_by_exact_recheck": k1_rechecked,
+                             "alone": {"ms_per_launch": k1_alone_ms,
+                                       "frac": (flop / max(calls, 1) / (k1_alone_ms * 1e-3) / PEAK_BF16_MFMA
+                                                if calls and k1_alone_ms else None),
+                                       "note": "same launch with nothing else on the GPU (incl. finalize), untimed region"},
+                             "flop_per_launch": flop / max(calls, 1), "images_per_launch": max(args.group, 1),
+                             "exp_per_s": flop / max(calls, 1) / (2.0 * D) / (k1_ms * 1e-3) if calls else 0.0,
+                             "f32_exact": f32_exact},
+                "roofline_nn": nn_live,
+                "roofline_nn_vote": nn_vote,
+                "roofline_ransac": k2_live,
+                # K3 is no longer one kernel at one rate: single-item calls (ICP steps, final Chamfer) scan every
+                # target (nn_search_kernel, VALU-bound), the batched Chamfer pick runs the block-cooperative grid
+                # search, which evaluates only the candidates near each query cell.  Reported: the rate in
+                # brute-force-EQUIVALENT pairs (B Nq Nt per call) — a throughput figure, not a roofline fraction.
+                "nn_stage": {"kernels": "nn_search_kernel (brute force: ICP, final Chamfer, vote items) / nn_tile_search_kernel "
+                                        "(block-cooperative grid: batched pick)",
+                             "equivalent_pairs_per_s": pairs / (nms * 1e-3) if ncalls else 0.0, "calls": ncalls,
+                             "ms_per_step": nms / args.steps,
+                             "note": "brute-force rate measured live: roofline_nn; DESIGN.md section 4 (K3/K4)"},
+                "stage_ms_per_step": {k: v[1] / args.steps for k, v in timing.items()},
+            })
+            if world == 1 and not args.no_estimate_pose:
+                try:
+                    line["estimate_pose"] = measure_estimate_pose(dev)
+                except Exception as e:
+                    line["estimate_pose"] = {"error": repr(e)}
+                try:
+                    line["reference_shape"] = measure_reference_shape(dev)
+                except Exception as e:
+                    line["reference_shape"] = {"error": repr(e)}
+            if not args.no_parity_check and args.ablate != "noverify":
+                try:
+                    line["parity_check"] = parity_check(args, model, Q_all[0], keys, pts, last, R_gt, t_gt, upper, lower, cad)
+                except Exception as e:  # the GPU line must survive a checker-side failure
+                    line["parity_check"] = {"error": repr(e)}
+            if world == 1 and not args.no_cpu_baseline:
+                try:
+                    line["cpu_baseline"] = cpu_baseline(args, keys, pts, images[0][0], images[0][1], Kcam, upper,
+                                                        lower, cad, R_gt, t_gt)
+                except Exception as e:  # the GPU line must survive a checker-side failure
+                    line["cpu_baseline"] = {"value": None, "error": repr(e), "kind": "port"}
         print(json.dumps(line), flush=True)
     if torch.distributed.is_initialized():
         torch.distributed.barrier()
