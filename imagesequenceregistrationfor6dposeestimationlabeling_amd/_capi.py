@@ -109,6 +109,9 @@ SIGNATURES = {
     "isr_zbuf_score_direct": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "isr_refine_objective": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "isr_refine_objective_full": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "isr_refine_objective_batch_workspace_bytes": (_sz, [_i]),
+    "isr_refine_objective_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp,
+                                        _sz, _vp]),
     "isr_add_metric": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
     "isr_icp_workspace_bytes": (_sz, [_i, _i]),
     "isr_icp_point_to_point": (_i, [_vp, _i, _vp, _i, _d, _i, _d, _d, _vp, _vp, _vp, _sz, _vp]),

@@ -2,6 +2,7 @@
 and enqueue the HIP kernels on torch's current stream.  No arithmetic happens here."""
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 
 import numpy as np
@@ -874,6 +875,46 @@ def add_metric(verts: torch.Tensor, Ta: torch.Tensor | None, Tb: torch.Tensor | 
     with torch.cuda.device(dev):
         rc = lib().isr_add_metric(ptr(verts), verts.shape[0], ptr(Ta), ptr(Tb), B, ptr(out), current_stream(dev))
     check(rc, "isr_add_metric")
+    return out
+
+
+def refine_objective_batch(X_all: torch.Tensor, keys_all: torch.Tensor, offs, query_imgs: torch.Tensor,
+                           denom_imgs: torch.Tensor, K: torch.Tensor, item_img: torch.Tensor, Rt: torch.Tensor, nout: int = 4,
+                           interpolation: int = 0, *, offs_dev: torch.Tensor | None = None, n_items: int | None = None,
+                           out: torch.Tensor | None = None) -> torch.Tensor:
+    """isr_refine_objective_batch: (n_items, nout) f64, row i = the refine objective of image item_img[i] at pose Rt[i]
+    (nout 4: score, d/dt; 13: + d/dR), the bits of isr_refine_objective(_full) on that item alone.
+    X_all (sum N, 3), keys_all (sum N, e) f32; offs the n_img + 1 row offsets on the HOST (sequence or array; offs_dev its
+    device copy, made here when not given); query_imgs (n_img, res, res, e), denom_imgs (n_img, res, res) f32; K (n_img, 9)
+    f64; item_img (>= n_items,) i32; Rt (>= n_items, 12) f64 — device tensors.  n_items defaults to len(item_img)."""
+    dev = require_cuda(X_all, keys_all, query_imgs, denom_imgs, K, item_img, Rt, offs_dev)
+    offs_h = np.ascontiguousarray(np.asarray(offs, dtype=np.int32))
+    n_img = offs_h.shape[0] - 1
+    n = item_img.shape[0] if n_items is None else int(n_items)
+    for name, t, dt in (("X_all", X_all, torch.float32), ("keys_all", keys_all, torch.float32),
+                        ("query_imgs", query_imgs, torch.float32), ("denom_imgs", denom_imgs, torch.float32),
+                        ("K", K, torch.float64), ("item_img", item_img, torch.int32), ("Rt", Rt, torch.float64)):
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"refine_objective_batch: {name} must be a contiguous {dt} tensor")
+    res, e = query_imgs.shape[1], query_imgs.shape[-1]
+    if (query_imgs.shape != (n_img, res, res, e) or denom_imgs.shape != (n_img, res, res) or K.numel() != 9 * n_img
+            or keys_all.shape != (X_all.shape[0], e) or X_all.shape[1:] != (3,) or n_img < 1
+            or int(offs_h[-1]) != X_all.shape[0] or item_img.shape[0] < n or Rt.numel() < 12 * n):
+        raise ValueError(f"refine_objective_batch: X_all {tuple(X_all.shape)} keys_all {tuple(keys_all.shape)} offs "
+                         f"{offs_h.tolist()[:4]}... query_imgs {tuple(query_imgs.shape)} denom_imgs {tuple(denom_imgs.shape)} "
+                         f"K {tuple(K.shape)} item_img {tuple(item_img.shape)} Rt {tuple(Rt.shape)} n_items {n}")
+    if offs_dev is None:
+        offs_dev = torch.from_numpy(offs_h).to(dev)
+    if out is None:
+        out = torch.empty((n, nout), dtype=torch.float64, device=dev)
+    L = lib()
+    ws = workspace(dev, L.isr_refine_objective_batch_workspace_bytes(n), "refine_obj_batch")
+    with torch.cuda.device(dev), _timed("refine_objective_batch", 0.0):
+        rc = L.isr_refine_objective_batch(ptr(X_all), ptr(keys_all), offs_h.ctypes.data_as(ctypes.c_void_p), ptr(offs_dev),
+                                          n_img, e, ptr(query_imgs), ptr(denom_imgs), res, int(interpolation), ptr(K),
+                                          ptr(item_img), ptr(Rt), n, ptr(out), int(nout), ptr(ws), ws.numel(),
+                                          current_stream(dev))
+    check(rc, "isr_refine_objective_batch")
     return out
 
 

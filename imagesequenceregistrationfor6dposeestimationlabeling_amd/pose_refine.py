@@ -147,3 +147,229 @@ def refine_pose(R, t, query_img, renderer, obj_idx, K_crop, obj_, neural_radianc
     pose = np.array([0, 0, 0, t[0], t[1], t[2]], dtype=np.float64)
     result = minimize(fun=obj, x0=pose, jac=lambda p: obj(p, return_grad=True), method=method)
     return R, result.x[3:], result.fun
+
+
+# ---------------------------------------------------------------------------------------------- a16 for a block of crops
+
+class _Abort(BaseException):
+    """Ends a lockstep worker whose siblings or caller failed (BaseException: scipy does not catch it)."""
+
+
+def lockstep_minimize(x0s, batch_eval, method='BFGS', **minimize_kw):
+    """One scipy.optimize.minimize per problem, each on a worker thread, their evaluations served in lockstep rounds.
+
+    batch_eval(requests) gets [(problem, x), ...] — one pending point per live problem — and returns [(fun, jac), ...] in the
+    same order; it is called on the calling thread only (the only thread that touches torch / HIP).  A worker's `fun` and `jac`
+    post their point and block; when every live worker is blocked or finished the caller evaluates all pending points with one
+    batch_eval call.  `fun` and `jac` at the point last evaluated for a problem share that evaluation (RefineObjective._eval).
+    Every run sees only its own values, so problem k's result is that of minimize(fun_k, x0s[k], jac=jac_k, method=method,
+    **minimize_kw).  A worker's exception (or batch_eval's) is re-raised here after every worker has ended.
+    Returns (list of OptimizeResult, number of batch_eval calls)."""
+    import threading
+
+    n = len(x0s)
+    cond = threading.Condition()     # the caller waits on it alone: notified only when the round is complete
+    wake = [threading.Event() for _ in range(n)]     # one per worker: a served round wakes each worker once
+    pending = {}                     # problem -> x posted and not yet served
+    served = {}                      # problem -> (fun, jac) of its pending point
+    state = {"live": n, "abort": False, "error": None}
+    results = [None] * n
+
+    def request(k, x):
+        with cond:
+            if state["abort"]:
+                raise _Abort()
+            pending[k] = x
+            if len(pending) == state["live"]:
+                cond.notify()
+        wake[k].wait()
+        wake[k].clear()
+        with cond:
+            if state["abort"]:
+                raise _Abort()
+            return served.pop(k)
+
+    def worker(k):
+        last = [None, None]          # x bytes, (fun, jac)
+
+        def evaluate(x):
+            x = np.array(x, dtype=np.float64)
+            key = x.tobytes()
+            if last[0] != key:
+                last[1] = request(k, x)
+                last[0] = key
+            return last[1]
+
+        try:
+            results[k] = minimize(fun=lambda x: evaluate(x)[0], x0=np.asarray(x0s[k], np.float64),
+                                  jac=lambda x: evaluate(x)[1], method=method, **minimize_kw)
+        except _Abort:
+            pass
+        except BaseException as exc:          # noqa: BLE001 — handed to the caller
+            with cond:
+                if state["error"] is None:
+                    state["error"] = exc
+                state["abort"] = True
+            for ev in wake:
+                ev.set()
+        finally:
+            with cond:
+                state["live"] -= 1
+                if state["abort"] or len(pending) >= state["live"]:
+                    cond.notify()
+
+    threads = [threading.Thread(target=worker, args=(k,), daemon=True) for k in range(n)]
+    for th in threads:
+        th.start()
+    rounds = 0
+    try:
+        while True:
+            with cond:
+                while not state["abort"] and state["live"] > 0 and len(pending) < state["live"]:
+                    cond.wait()
+                if state["abort"] or state["live"] == 0:
+                    break
+                reqs = sorted(pending.items())
+                pending.clear()
+            vals = batch_eval(reqs)
+            rounds += 1
+            if len(vals) != len(reqs):
+                raise ValueError(f"batch_eval returned {len(vals)} results for {len(reqs)} requests")
+            with cond:
+                for (k, _), v in zip(reqs, vals):
+                    served[k] = v
+            for k, _ in reqs:
+                wake[k].set()
+    except BaseException:
+        with cond:
+            state["abort"] = True
+        for ev in wake:
+            ev.set()
+        for th in threads:
+            th.join()
+        raise
+    for th in threads:
+        th.join()
+    if state["error"] is not None:
+        raise state["error"]
+    return results, rounds
+
+
+def refine_poses(Rs, ts, query_imgs, renderer, obj_idx, K_crops, obj_, neural_radiance_field, keys_verts,
+                 interpolation='bilinear', n_samples_denom=10960, method='BFGS', *, seeds=None, optimize_rotation=False,
+                 stats=None):
+    """refine_pose for a block of B crops of one object, the B BFGS runs in lockstep (lockstep_minimize): every round is one
+    pinned H2D copy of the pending poses, ONE isr_refine_objective_batch launch for all of them, one D2H copy and one
+    synchronise — instead of one launch + synchronise per image and evaluation.
+    Rs (B,3,3), ts (B,3), query_imgs (B,res,res,e), K_crops one (3,3) or (B,3,3).  Image b's (R, t, fun) is bit for bit
+    refine_pose(Rs[b], ts[b], query_imgs[b], ..., generator=torch.Generator(dev).manual_seed(seeds[b])) (seeds default
+    range(B)): the same renderer / batched_customForward calls per image, the same key sample and denominator image, the same
+    objective bits, the same scipy run.  Returns a list of B (R, t, fun).  stats (a dict, optional) receives rounds,
+    n_eval (item evaluations per image) and launches."""
+    if interpolation not in INTERPOLATION:
+        raise ValueError(f"interpolation={interpolation!r}: F.grid_sample knows {sorted(INTERPOLATION)}")
+    query_imgs = _dev(query_imgs, torch.float32)
+    B = len(Rs)
+    if query_imgs.ndim != 4 or query_imgs.shape[0] != B or len(ts) != B or query_imgs.shape[1] != query_imgs.shape[2]:
+        raise ValueError(f"refine_poses: {B} rotations, {len(ts)} translations, query_imgs {tuple(query_imgs.shape)} "
+                         "(B,res,res,e)")
+    if B == 0:
+        return []
+    dev = query_imgs.device
+    res, e = query_imgs.shape[1], query_imgs.shape[3]
+    Ks = np.asarray(K_crops, np.float64)
+    K_b = [K_crops] * B if Ks.ndim == 2 else [K_crops[b] for b in range(B)]     # the renderer gets what refine_pose would
+    Ks = np.broadcast_to(Ks, (B, 3, 3)) if Ks.ndim == 2 else Ks.reshape(B, 3, 3)
+    seeds = list(range(B)) if seeds is None else list(seeds)
+    Rs_in = list(Rs)                                    # handed to the renderer and returned as given, as refine_pose does
+    Rs = [np.asarray(R, np.float64).reshape(3, 3) for R in Rs_in]
+    ts = [np.asarray(t, np.float64).reshape(3) for t in ts]
+    # the renders first: an image with nothing visible fails before anything is launched
+    renders = []
+    for b in range(B):
+        coord_img = renderer.render(obj_idx, K_b[b], Rs_in[b], np.expand_dims(ts[b], axis=1))
+        coord_img = coord_img.cpu().numpy() if isinstance(coord_img, torch.Tensor) else np.asarray(coord_img)
+        mask = coord_img[..., 3] == 1.
+        if not mask.any():
+            raise ValueError(f"refine_poses: image {b} renders no visible surface point at its start pose")
+        renders.append((coord_img, mask))
+    Xs, keys = [], []
+    for coord_img, mask in renders:                     # pose_refine.py:38-53, per image, as refine_pose does it
+        coord_norm_masked = torch.from_numpy(np.ascontiguousarray(coord_img[..., :3][mask])).to(dev)
+        coord_masked = coord_norm_masked * obj_.scale + torch.from_numpy(np.asarray(obj_.offset)).to(dev)
+        coord_nerf = torch.from_numpy((coord_masked.cpu().numpy() * 1.8 / obj_.diameter).astype("float32")).to(dev)
+        feat = neural_radiance_field.batched_customForward(coord_nerf).detach().clone()
+        Xs.append(coord_masked.float())
+        keys.append(feat[..., :feat.shape[-1] - 1].float())
+    # the B lse-only denominator calls back to back (each image's own key sample: its generator), no host synchronise
+    keys_verts = _dev(keys_verts, torch.float32)
+    denoms = []
+    for b in range(B):
+        g = torch.Generator(device=dev).manual_seed(int(seeds[b]))
+        perm = torch.randperm(len(keys_verts), device=dev, generator=g)[:n_samples_denom]
+        denoms.append(denominator_image(query_imgs[b], keys_verts[perm]).reshape(res, res))
+    # the visible sets, once per block
+    counts = [x.shape[0] for x in Xs]
+    offs = np.zeros(B + 1, np.int32)
+    offs[1:] = np.cumsum(counts)
+    X_all, keys_all = torch.cat(Xs).contiguous(), torch.cat(keys).contiguous()
+    offs_dev = torch.from_numpy(offs).to(dev)
+    q_all = query_imgs.contiguous()
+    den_all = torch.stack(denoms).contiguous()
+    K_dev = torch.from_numpy(np.ascontiguousarray(Ks.reshape(B, 9))).to(dev)
+    nout = 13 if optimize_rotation else 4
+    mode = INTERPOLATION[interpolation]
+    # one pinned staging buffer -> ONE H2D copy per round: [Rt (B,12) f64 | item_img (B,) i32]
+    stage_h = torch.empty(B * 100, dtype=torch.uint8).pin_memory()
+    stage_d = torch.empty(B * 100, dtype=torch.uint8, device=dev)
+    Rt_h, item_h = stage_h[:B * 96].view(torch.float64).view(B, 12), stage_h[B * 96:].view(torch.int32)
+    Rt_d, item_d = stage_d[:B * 96].view(torch.float64).view(B, 12), stage_d[B * 96:].view(torch.int32)
+    out_d = torch.empty((B, nout), dtype=torch.float64, device=dev)
+    out_h = torch.empty((B, nout), dtype=torch.float64).pin_memory()
+    n_eval = [0] * B
+    stream = torch.cuda.current_stream(dev)
+
+    def batch_eval(reqs):
+        n = len(reqs)
+        jac_R = []
+        Rt_np, item_np = Rt_h.numpy(), item_h.numpy()
+        for i, (b, x) in enumerate(reqs):
+            if optimize_rotation:
+                R, dR = rodrigues(x[:3])
+                jac_R.append(dR)
+            else:
+                R = Rs[b]
+            Rt_np[i] = np.concatenate([R, np.asarray(x[3:], np.float64).reshape(3, 1)], axis=1).reshape(12)
+            item_np[i] = b
+            n_eval[b] += 1
+        with torch.cuda.device(dev):
+            stage_d.copy_(stage_h, non_blocking=True)
+            ops.refine_objective_batch(X_all, keys_all, offs, q_all, den_all, K_dev, item_d, Rt_d, nout, mode,
+                                       offs_dev=offs_dev, n_items=n, out=out_d)
+            out_h[:n].copy_(out_d[:n], non_blocking=True)
+            stream.synchronize()
+        vals = []
+        out_np = out_h.numpy()
+        for i in range(n):
+            o = out_np[i].copy()
+            if optimize_rotation:                       # RefineObjective.with_rotation
+                g = np.concatenate([np.einsum("jk,ijk->i", o[4:].reshape(3, 3), jac_R[i]), o[1:4]])
+            else:                                       # RefineObjective.__call__
+                g = np.concatenate([np.zeros(3), o[1:]])
+            vals.append((float(o[0]), g))
+        return vals
+
+    if optimize_rotation:
+        from scipy.spatial.transform import Rotation
+        x0s = []
+        for b in range(B):
+            rvec = Rotation.from_matrix(Rs[b]).as_rotvec()
+            x0s.append(np.array([rvec[0], rvec[1], rvec[2], ts[b][0], ts[b][1], ts[b][2]], dtype=np.float64))
+    else:
+        x0s = [np.array([0, 0, 0, t[0], t[1], t[2]], dtype=np.float64) for t in ts]
+    results, rounds = lockstep_minimize(x0s, batch_eval, method=method)
+    if stats is not None:
+        stats.update(rounds=rounds, launches=rounds, n_eval=list(n_eval))
+    if optimize_rotation:
+        return [(rodrigues(r.x[:3])[0], r.x[3:], r.fun) for r in results]
+    return [(Rs_in[b], r.x[3:], r.fun) for b, r in enumerate(results)]

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import ops, registration, shard
+from . import ops, pose_est_surf, pose_refine, registration, shard
 
 
 @dataclass
@@ -401,6 +401,72 @@ def acceptance_counts(model_verts, surface_pts, R_gt, t_gt, poses: torch.Tensor,
     ids = [names[i] if names is not None else i for i in np.nonzero(work)[0]]
     return dict(final_error=host[0], final_errorR=host[1], work=work, rot_work=rot, workCT=int(work.sum()),
                 rotWorkCT=int(rot.sum()), correct_predicted_ids=ids)
+
+
+def estimate_and_refine(mask_lgts, query_imgs, obj_pts, obj_normals, obj_keys, obj_diameter, Ks, renderer, obj_idx, obj_,
+                        neural_radiance_field, keys_verts, model_verts, R_gt, t_gt, *, seeds=None, refine_seeds=None,
+                        estimate_kw=None, refine_kw=None) -> dict:
+    """The useSurfEval branch of inference.py:324-366 for a block of B crops of one object:
+        R, t, pose_scores, mask_scores, ... = estimate_pose(mask_lgts[b], query_imgs[b], ...)     (estimate_poses: one block)
+        if len(mask_scores) > 0:
+            bestId = torch.argsort(pose_scores)[-1];  R2, T2 = R[bestId], t[bestId]
+            finADD  = ADD(modelVerts, gtR, gtT, R2, T2)
+            _, t_ref, fun = refine_pose(R2, T2, query_imgs[b], ...)                                 (refine_poses: lockstep)
+            refADD  = ADD(modelVerts, gtR, gtT, R2, t_ref)        (R2: the branch measures the refined translation only)
+            finADDR = ADD(modelVerts, gtR, 0, R2, 0)
+            refCT += refADD < 0.1 d;  workCT += finADD < 0.1 d;  rotWorkCT += finADDR < 0.1 d
+    ADD on every dataset (the branch never uses ADD-S).  An image with no mask score is skipped, as there: never refined, never
+    counted, refined[b] False and its per-image values NaN.  Image b uses estimate seed seeds[b] and refine seed refine_seeds[b]
+    (both default b: refine_pose's key sample is torch.Generator(dev).manual_seed(refine_seeds[b])).  The three ADDs are three
+    batched add_metric launches and one copy to the host.  Ks one (3,3) or (B,3,3); R_gt (B,3,3), t_gt (B,3).
+    Returns {refined (B,) bool, R2 (B,3,3), T2 (B,3) f32, t_ref (B,3), fun (B,), finADD, refADD, finADDR (B,) f64,
+    workCT, refCT, rotWorkCT}."""
+    mask_lgts, query_imgs = registration._dev(mask_lgts, torch.float32), registration._dev(query_imgs, torch.float32)
+    B = mask_lgts.shape[0]
+    R_gt = np.asarray(R_gt, np.float64).reshape(-1, 3, 3) if np.size(R_gt) else np.zeros((0, 3, 3))
+    t_gt = np.asarray(t_gt, np.float64).reshape(-1, 3) if np.size(t_gt) else np.zeros((0, 3))
+    Ka = np.asarray(Ks, np.float64)
+    if (mask_lgts.ndim != 3 or query_imgs.ndim != 4 or query_imgs.shape[0] != B or mask_lgts.shape[1:] != query_imgs.shape[1:3]
+            or R_gt.shape[0] != B or t_gt.shape[0] != B or not (Ka.shape == (3, 3) or Ka.shape == (B, 3, 3))):
+        raise ValueError(f"estimate_and_refine: mask_lgts {tuple(mask_lgts.shape)} query_imgs {tuple(query_imgs.shape)} "
+                         f"R_gt {R_gt.shape} t_gt {t_gt.shape} Ks {Ka.shape}: (B,r,r) (B,r,r,e) (B,3,3) (B,3) (3,3)|(B,3,3)")
+    seeds = list(range(B)) if seeds is None else list(seeds)
+    refine_seeds = list(range(B)) if refine_seeds is None else list(refine_seeds)
+    nan = np.full(B, np.nan)
+    out = dict(refined=np.zeros(B, bool), R2=np.full((B, 3, 3), np.nan, np.float32), T2=np.full((B, 3), np.nan, np.float32),
+               t_ref=np.full((B, 3), np.nan), fun=nan.copy(), finADD=nan.copy(), refADD=nan.copy(), finADDR=nan.copy(),
+               workCT=0, refCT=0, rotWorkCT=0)
+    if B == 0:
+        return out
+    est = pose_est_surf.estimate_poses(mask_lgts, query_imgs, obj_pts, obj_normals, obj_keys, obj_diameter, Ka, seeds=seeds,
+                                       **(estimate_kw or {}))
+    kept = [b for b in range(B) if len(est[b][3]) > 0]
+    if not kept:
+        return out
+    best = [torch.argsort(est[b][2])[-1] for b in kept]
+    Rt2 = torch.stack([torch.cat([est[b][0][i], est[b][1][i][:, None]], dim=1) for b, i in zip(kept, best)]).cpu().numpy()
+    R2, T2 = Rt2[:, :, :3], Rt2[:, :, 3]                 # f32, the values of R[bestId].cpu().numpy(), t[bestId].cpu().numpy()
+    refined = pose_refine.refine_poses([R2[i] for i in range(len(kept))], [T2[i] for i in range(len(kept))],
+                                       query_imgs[kept], renderer, obj_idx, Ka if Ka.ndim == 2 else Ka[kept], obj_,
+                                       neural_radiance_field, keys_verts, seeds=[refine_seeds[b] for b in kept],
+                                       **(refine_kw or {}))
+    t_ref = np.stack([np.asarray(r[1], np.float64).reshape(3) for r in refined])
+    z = np.zeros(3)
+    T_gt = registration._dev(np.stack([registration._pose12(R_gt[b], t_gt[b]) for b in kept]))
+    T_gt0 = registration._dev(np.stack([registration._pose12(R_gt[b], z) for b in kept]))
+    T_fin = registration._dev(np.stack([registration._pose12(R2[i], T2[i]) for i in range(len(kept))]))
+    T_ref = registration._dev(np.stack([registration._pose12(R2[i], t_ref[i]) for i in range(len(kept))]))
+    T_fin0 = registration._dev(np.stack([registration._pose12(R2[i], z) for i in range(len(kept))]))
+    v = registration._dev(model_verts, torch.float32)
+    adds = torch.stack([ops.add_metric(v, T_gt, T_fin), ops.add_metric(v, T_gt, T_ref),
+                        ops.add_metric(v, T_gt0, T_fin0)]).cpu().numpy()          # one copy
+    d = 0.1 * obj_diameter
+    out["refined"][kept] = True
+    out["R2"][kept], out["T2"][kept], out["t_ref"][kept] = R2, T2, t_ref
+    out["fun"][kept] = [float(r[2]) for r in refined]
+    out["finADD"][kept], out["refADD"][kept], out["finADDR"][kept] = adds[0], adds[1], adds[2]
+    out.update(workCT=int((adds[0] < d).sum()), refCT=int((adds[1] < d).sum()), rotWorkCT=int((adds[2] < d).sum()))
+    return out
 
 
 def _orthonormal(R, tol=1e-9) -> bool:

@@ -214,3 +214,26 @@ def crop_batch(dev, n=128, seed=0, N=80000, D=12, H=224, ds=3, f=600.0):
         counts.append(len(src))
     return dict(feats=feats, masks=masks, Kc=Kc, R=R, t=t, pts=pts_d, keys=keys_d, counts=counts, S1=S1, D=D, ds=ds)
 
+
+
+def crop_block(B=32, seed=7, r=224, e=12, m=20000, f=700.0):
+    """B crops of ONE object in the form of crop_scene (the object, keys and camera of crop_scene(seed, r, e, m, f)), each at
+    its own random pose: mask_lgts (B,r,r), query (B,r,r,e), R (B,3,3), t (B,3)."""
+    s = crop_scene(seed, r, e, m, f)
+    rng = np.random.default_rng(seed + 1000)
+    Rs, ts = random_poses(rng, B, tz=420.0, t_sigma=5.0)
+    mls, qs = [], []
+    for b in range(B):
+        uv = project(s["K"], Rs[b], ts[b], s["pts"])
+        cam = s["pts"].astype(np.float64) @ Rs[b].T + ts[b]
+        vis = (s["normals"] @ Rs[b].T * cam).sum(1) < 0
+        ui, vi = np.rint(uv[:, 0]).astype(int), np.rint(uv[:, 1]).astype(int)
+        ok = np.nonzero(vis & (ui >= 0) & (ui < r) & (vi >= 0) & (vi < r))[0]
+        ok = ok[np.argsort(-cam[ok, 2])]
+        ml = np.full((r, r), -6.0, np.float32)
+        q = (0.3 * rng.normal(size=(r, r, e))).astype(np.float32)
+        ml[vi[ok], ui[ok]] = 6.0
+        q[vi[ok], ui[ok]] = s["keys"][ok] + 0.2 * rng.normal(size=(len(ok), e)).astype(np.float32)
+        mls.append(ml)
+        qs.append(q)
+    return dict(s, mask_lgts=np.stack(mls), query=np.stack(qs), R=Rs, t=ts, B=B)

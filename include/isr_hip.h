@@ -502,6 +502,23 @@ int isr_refine_objective_full(const float* X, const float* keys, int N, int e, c
                               const float* denom_img, int res, int interpolation, const double* Kcrop, const double* Rt,
                               double* out13, void* ws, size_t ws_bytes, isr_stream_t stream);
 
+/* a16  the same objective for many (image, pose) items in ONE launch (a block of crops refined in lockstep):
+ * item i evaluates image item_img[i] at pose Rt[i] and out[i] (nout f64) has the bits isr_refine_objective (nout = 4) or
+ * isr_refine_objective_full (nout = 13) returns for that item alone: the same grid stride and block reduction per item
+ * (grid (64, n_items) x 256), its 64 partials summed in block order, P = K [R|t] formed on the device with the host's
+ * expression (no contraction).
+ *   X_all (sum N, 3), keys_all (sum N, e) f32: the visible surface sets of the n_img images, image b at rows
+ *   offs[b] .. offs[b+1]; query_imgs (n_img,res,res,e), denom_imgs (n_img,res,res) f32; K (n_img, 9) f64;
+ *   item_img (n_items) i32; Rt (n_items, 12) f64 [R|t]; out (n_items, nout) f64 — all device memory.
+ *   offs_host: the same n_img+1 offsets in HOST memory (offs[0] = 0, every image N >= 1), checked before any launch;
+ *   offs is its device copy, the one the kernels read.  An item_img entry outside [0, n_img) gives a NaN row.
+ * n_items <= 65 535 (blockIdx.y); 0 launches nothing.  ws >= isr_refine_objective_batch_workspace_bytes(n_items). */
+size_t isr_refine_objective_batch_workspace_bytes(int n_items);
+int isr_refine_objective_batch(const float* X_all, const float* keys_all, const int32_t* offs_host, const int32_t* offs,
+                               int n_img, int e, const float* query_imgs, const float* denom_imgs, int res,
+                               int interpolation, const double* K, const int32_t* item_img, const double* Rt, int n_items,
+                               double* out, int nout, void* ws, size_t ws_bytes, isr_stream_t stream);
+
 /* a8  ADD(verts, gtR, gtT, R, T)   inference.py:116-117
  * mean_out[b] = mean_v || Ta[b] v - Tb[b] v ||  (f64; Ta/Tb (B,12) f64 [R|t], NULL = identity). */
 int isr_add_metric(const float* verts, int V, const double* Ta, const double* Tb, int B,
