@@ -112,6 +112,12 @@ SIGNATURES = {
     "isr_refine_objective_batch_workspace_bytes": (_sz, [_i]),
     "isr_refine_objective_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp,
                                         _sz, _vp]),
+    "isr_refine_bfgs_batch_workspace_bytes": (_sz, [_i]),
+    "isr_refine_bfgs_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _d, _i, _i, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "isr_bfgs_state_bytes": (_sz, []),
+    "isr_bfgs_host_init": (_i, [_vp, _sz, _i, _vp, _d, _i, _vp]),
+    "isr_bfgs_host_step": (_i, [_vp, _d, _vp, _vp, _vp, _vp]),
     "isr_add_metric": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
     "isr_icp_workspace_bytes": (_sz, [_i, _i]),
     "isr_icp_point_to_point": (_i, [_vp, _i, _vp, _i, _d, _i, _d, _d, _vp, _vp, _vp, _sz, _vp]),

@@ -918,6 +918,51 @@ def refine_objective_batch(X_all: torch.Tensor, keys_all: torch.Tensor, offs, qu
     return out
 
 
+def refine_bfgs_batch(X_all: torch.Tensor, keys_all: torch.Tensor, offs, query_imgs: torch.Tensor, denom_imgs: torch.Tensor,
+                      K: torch.Tensor, item_img: torch.Tensor, R: torch.Tensor, t0: torch.Tensor, interpolation: int = 0, *,
+                      gtol: float = 1e-5, maxiter: int | None = None, max_rounds: int = 100_000,
+                      offs_dev: torch.Tensor | None = None) -> dict:
+    """isr_refine_bfgs_batch: refine_pose's scipy BFGS over t for n_items (image item_img[i], fixed R[i], start t0[i]), run on
+    the device.  The image arguments are refine_objective_batch's; R (n, 3, 3) or (n, 9), t0 (n, 3) f64, item_img (n,) i32 —
+    device tensors.  maxiter defaults to scipy's 200 * 6.  Returns {t (n, 3), fun (n,) f64, nit, nfev, status (n,) i32 — device
+    tensors; rounds, launches — ints}.  status: scipy's (0 .. 3) or 4 = max_rounds ran out while the item was live."""
+    dev = require_cuda(X_all, keys_all, query_imgs, denom_imgs, K, item_img, R, t0, offs_dev)
+    offs_h = np.ascontiguousarray(np.asarray(offs, dtype=np.int32))
+    n_img = offs_h.shape[0] - 1
+    n = item_img.shape[0]
+    for name, t, dt in (("X_all", X_all, torch.float32), ("keys_all", keys_all, torch.float32),
+                        ("query_imgs", query_imgs, torch.float32), ("denom_imgs", denom_imgs, torch.float32),
+                        ("K", K, torch.float64), ("item_img", item_img, torch.int32), ("R", R, torch.float64),
+                        ("t0", t0, torch.float64)):
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"refine_bfgs_batch: {name} must be a contiguous {dt} tensor")
+    res, e = query_imgs.shape[1], query_imgs.shape[-1]
+    if (query_imgs.shape != (n_img, res, res, e) or denom_imgs.shape != (n_img, res, res) or K.numel() != 9 * n_img
+            or keys_all.shape != (X_all.shape[0], e) or X_all.shape[1:] != (3,) or n_img < 1
+            or int(offs_h[-1]) != X_all.shape[0] or R.numel() != 9 * n or t0.numel() != 3 * n):
+        raise ValueError(f"refine_bfgs_batch: X_all {tuple(X_all.shape)} keys_all {tuple(keys_all.shape)} offs "
+                         f"{offs_h.tolist()[:4]}... query_imgs {tuple(query_imgs.shape)} denom_imgs {tuple(denom_imgs.shape)} "
+                         f"K {tuple(K.shape)} item_img {tuple(item_img.shape)} R {tuple(R.shape)} t0 {tuple(t0.shape)}")
+    if offs_dev is None:
+        offs_dev = torch.from_numpy(offs_h).to(dev)
+    maxiter = 200 * 6 if maxiter is None else int(maxiter)
+    t_out = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    fun = torch.empty(n, dtype=torch.float64, device=dev)
+    info = torch.empty((3, n), dtype=torch.int32, device=dev)
+    stats = (ctypes.c_int32 * 2)()
+    L = lib()
+    ws = workspace(dev, L.isr_refine_bfgs_batch_workspace_bytes(n), "refine_bfgs")
+    with torch.cuda.device(dev), _timed("refine_bfgs_batch", 0.0):
+        rc = L.isr_refine_bfgs_batch(ptr(X_all), ptr(keys_all), offs_h.ctypes.data_as(ctypes.c_void_p), ptr(offs_dev), n_img,
+                                     e, ptr(query_imgs), ptr(denom_imgs), res, int(interpolation), ptr(K), ptr(item_img),
+                                     ptr(R), ptr(t0), n, float(gtol), maxiter, int(max_rounds), ptr(t_out), ptr(fun),
+                                     ptr(info[0]), ptr(info[1]), ptr(info[2]), ctypes.cast(stats, ctypes.c_void_p), ptr(ws),
+                                     ws.numel(), current_stream(dev))
+    check(rc, "isr_refine_bfgs_batch")
+    return {"t": t_out, "fun": fun, "nit": info[0], "nfev": info[1], "status": info[2], "rounds": int(stats[0]),
+            "launches": int(stats[1])}
+
+
 def corr_logsoftmax(queries: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
     """isr_corr_logsoftmax: the full (P,N) f32 log-softmax matrix (small P only: it is written out)."""
     dev = require_cuda(queries, keys)

@@ -6,7 +6,7 @@ for their key descriptors, `obj_.scale / .offset / .diameter`.  What runs in HIP
 log-sum-exp denominator image (K1's `lse` output over the sampled keys — no (H*W x 10 960) matrix)
 and the bilinear objective with its analytic translation gradient (isr_refine_objective) — the
 reference builds both with torch autograd and a cv2.Rodrigues round trip per evaluation.  BFGS stays
-scipy.optimize.minimize on the host, as in the reference.  As there, only the translation is
+scipy.optimize.minimize on the host, as in the reference (refine_poses(optimizer="device") runs a port of it on the device).  As there, only the translation is
 optimised (the objective's rotation is a constant, pose_refine.py:73-76): R is returned unchanged.
 `optimize_rotation=True` (off by default) is the evidently intended variant: the 6-vector is
 (rotation vector, translation), the device returns d score / d R as well and the host chains it with the
@@ -255,9 +255,43 @@ def lockstep_minimize(x0s, batch_eval, method='BFGS', **minimize_kw):
     return results, rounds
 
 
+_BFGS_MESSAGES = {0: "Optimization terminated successfully.", 1: "Maximum number of iterations has been exceeded.",
+                  2: "Desired error not necessarily achieved due to precision loss.",
+                  3: "NaN result encountered."}
+
+
+def bfgs_host(fun_and_grad, x0, gtol=1e-5, maxiter=None):
+    """minimize(fun, x0, jac=..., method='BFGS', options={gtol, maxiter}) by the library's BFGS state machine run as host
+    code — the code isr_refine_bfgs_batch runs on the device, one item per thread.  fun_and_grad(x) -> (f, g); it is
+    called once per distinct point.  Returns an OptimizeResult (x, fun, nit, nfev, status, success, message) with
+    n_wolfe2, the number of line searches that fell back from wolfe1 to wolfe2."""
+    from scipy.optimize import OptimizeResult
+    x0 = np.asarray(x0, np.float64).reshape(-1)
+    n = x0.shape[0]
+    maxiter = 200 * n if maxiter is None else int(maxiter)
+    L = lib()
+    state = ctypes.create_string_buffer(L.isr_bfgs_state_bytes())
+    x = np.empty(n, np.float64)
+    g = np.empty(n, np.float64)
+    fun = ctypes.c_double()
+    info = (ctypes.c_int32 * 5)()
+    check(L.isr_bfgs_host_init(state, len(state), n, x0.ctypes.data_as(ctypes.c_void_p), float(gtol), maxiter,
+                               x.ctypes.data_as(ctypes.c_void_p)), "isr_bfgs_host_init")
+    while True:
+        f, gr = fun_and_grad(x.copy())
+        g[:] = np.asarray(gr, np.float64).reshape(n)
+        check(L.isr_bfgs_host_step(state, float(f), g.ctypes.data_as(ctypes.c_void_p), x.ctypes.data_as(ctypes.c_void_p),
+                                   ctypes.byref(fun), info), "isr_bfgs_host_step")
+        if info[0]:
+            break
+    status = int(info[1])
+    return OptimizeResult(x=x.copy(), fun=fun.value, nit=int(info[2]), nfev=int(info[3]), status=status,
+                          success=status == 0, message=_BFGS_MESSAGES[status], n_wolfe2=int(info[4]))
+
+
 def refine_poses(Rs, ts, query_imgs, renderer, obj_idx, K_crops, obj_, neural_radiance_field, keys_verts,
                  interpolation='bilinear', n_samples_denom=10960, method='BFGS', *, seeds=None, optimize_rotation=False,
-                 stats=None):
+                 stats=None, optimizer="scipy", max_rounds=100_000):
     """refine_pose for a block of B crops of one object, the B BFGS runs in lockstep (lockstep_minimize): every round is one
     pinned H2D copy of the pending poses, ONE isr_refine_objective_batch launch for all of them, one D2H copy and one
     synchronise — instead of one launch + synchronise per image and evaluation.
@@ -265,7 +299,16 @@ def refine_poses(Rs, ts, query_imgs, renderer, obj_idx, K_crops, obj_, neural_ra
     refine_pose(Rs[b], ts[b], query_imgs[b], ..., generator=torch.Generator(dev).manual_seed(seeds[b])) (seeds default
     range(B)): the same renderer / batched_customForward calls per image, the same key sample and denominator image, the same
     objective bits, the same scipy run.  Returns a list of B (R, t, fun).  stats (a dict, optional) receives rounds,
-    n_eval (item evaluations per image) and launches."""
+    n_eval (item evaluations per image) and launches.
+    optimizer="device": the same renders, keys, key samples and denominator images, then ONE isr_refine_bfgs_batch call —
+    scipy's BFGS ported to a per-item state machine that runs on the device (one objective launch and one step launch per
+    round, the host reads the live count once per 8 rounds).  Each image's result equals bfgs_host driven by
+    RefineObjective bit for bit, and scipy's to rounding.  BFGS over t only (method='BFGS', optimize_rotation=False);
+    stats also receives nit and status (scipy's, or 4 when max_rounds ran out first)."""
+    if optimizer not in ("scipy", "device"):
+        raise ValueError(f"optimizer={optimizer!r}: 'scipy' or 'device'")
+    if optimizer == "device" and (method != "BFGS" or optimize_rotation):
+        raise ValueError("optimizer='device' runs BFGS over the translation only (method='BFGS', optimize_rotation=False)")
     if interpolation not in INTERPOLATION:
         raise ValueError(f"interpolation={interpolation!r}: F.grid_sample knows {sorted(INTERPOLATION)}")
     query_imgs = _dev(query_imgs, torch.float32)
@@ -317,8 +360,20 @@ def refine_poses(Rs, ts, query_imgs, renderer, obj_idx, K_crops, obj_, neural_ra
     q_all = query_imgs.contiguous()
     den_all = torch.stack(denoms).contiguous()
     K_dev = torch.from_numpy(np.ascontiguousarray(Ks.reshape(B, 9))).to(dev)
-    nout = 13 if optimize_rotation else 4
     mode = INTERPOLATION[interpolation]
+    if optimizer == "device":
+        R_dev = torch.from_numpy(np.ascontiguousarray(np.stack(Rs).reshape(B, 9))).to(dev)
+        t_dev = torch.from_numpy(np.ascontiguousarray(np.stack(ts))).to(dev)
+        item_dev = torch.arange(B, dtype=torch.int32, device=dev)
+        r = ops.refine_bfgs_batch(X_all, keys_all, offs, q_all, den_all, K_dev, item_dev, R_dev, t_dev, mode,
+                                  max_rounds=max_rounds, offs_dev=offs_dev)
+        t_h, fun_h = r["t"].cpu().numpy(), r["fun"].cpu().numpy()
+        nit, nfev, status = (r[k].cpu().numpy() for k in ("nit", "nfev", "status"))
+        if stats is not None:
+            stats.update(rounds=r["rounds"], launches=r["launches"], n_eval=nfev.tolist(), nit=nit.tolist(),
+                         status=status.tolist())
+        return [(Rs_in[b], t_h[b].copy(), float(fun_h[b])) for b in range(B)]
+    nout = 13 if optimize_rotation else 4
     # one pinned staging buffer -> ONE H2D copy per round: [Rt (B,12) f64 | item_img (B,) i32]
     stage_h = torch.empty(B * 100, dtype=torch.uint8).pin_memory()
     stage_d = torch.empty(B * 100, dtype=torch.uint8, device=dev)

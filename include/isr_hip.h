@@ -519,6 +519,34 @@ int isr_refine_objective_batch(const float* X_all, const float* keys_all, const 
                                int interpolation, const double* K, const int32_t* item_img, const double* Rt, int n_items,
                                double* out, int nout, void* ws, size_t ws_bytes, isr_stream_t stream);
 
+/* a16  refine_pose's BFGS on the device for a block of items (pose_refine.py:93-101): item i minimises the objective of
+ * image item_img[i] over t with R[i] fixed, from t0[i], by a port of scipy 1.15's minimize(method='BFGS') on the 6-vector
+ * [0, 0, 0, t] (gtol on the inf-norm, maxiter; c1 = 1e-4, c2 = 0.9, the wolfe1 / wolfe2 line searches as scipy has them).
+ * The image arguments are isr_refine_objective_batch's; every evaluation has the bits of isr_refine_objective.  R (n_items,
+ * 9), t0 (n_items, 3) f64, item_img (n_items) i32 — device.  Out (device): t_out (n_items, 3), fun_out (n_items) f64,
+ * nit_out, nfev_out (distinct evaluations), status_out (n_items) i32: scipy's status (0 gtol, 1 maxiter, 2 line search
+ * failed / value not finite, 3 NaN), or 4 when max_rounds ran out while the item was still live.
+ * One round = two launches (objective of the live items, one BFGS step per live item); rounds are enqueued in chunks and
+ * the live count is read back once per chunk, so the call returns with the stream synchronised.  stats_host (nullable,
+ * host, 2 i32) = { rounds that evaluated an item, launches }.  n_items <= 65 535; 0 launches nothing.
+ * ws >= isr_refine_bfgs_batch_workspace_bytes(n_items). */
+size_t isr_refine_bfgs_batch_workspace_bytes(int n_items);
+int isr_refine_bfgs_batch(const float* X_all, const float* keys_all, const int32_t* offs_host, const int32_t* offs,
+                          int n_img, int e, const float* query_imgs, const float* denom_imgs, int res, int interpolation,
+                          const double* K, const int32_t* item_img, const double* R, const double* t0, int n_items,
+                          double gtol, int maxiter, int max_rounds, double* t_out, double* fun_out, int32_t* nit_out,
+                          int32_t* nfev_out, int32_t* status_out, int32_t* stats_host, void* ws, size_t ws_bytes,
+                          isr_stream_t stream);
+
+/* The same BFGS state machine as host code (no device): the caller evaluates.  state: isr_bfgs_state_bytes() bytes of
+ * host memory; n in 1 .. 8.  init writes the first point (x0) to x_next; each step takes (f, g (n)) at the last point
+ * given and writes the next one to x_next, or, with info[0] = 1, the result's x.  info (5 i32) = { done, status, nit,
+ * nfev, wolfe2 fallbacks }; fun (nullable) = the current value. */
+size_t isr_bfgs_state_bytes(void);
+int isr_bfgs_host_init(void* state, size_t state_bytes, int n, const double* x0, double gtol, int maxiter,
+                       double* x_next);
+int isr_bfgs_host_step(void* state, double f, const double* g, double* x_next, double* fun, int32_t* info);
+
 /* a8  ADD(verts, gtR, gtT, R, T)   inference.py:116-117
  * mean_out[b] = mean_v || Ta[b] v - Tb[b] v ||  (f64; Ta/Tb (B,12) f64 [R|t], NULL = identity). */
 int isr_add_metric(const float* verts, int V, const double* Ta, const double* Tb, int B,

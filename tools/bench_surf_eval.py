@@ -2,8 +2,11 @@
 (estimate_pose + best pose + refine_pose, one image after the other) against (b) sequence.estimate_and_refine (estimate_poses
 for the block, refine_poses in lockstep: one batched objective launch per BFGS round).  Device-synchronised wall time after a
 warm-up, the two arms alternated; both arms must give the same R2, T2, t_ref and fun.  Prints one JSON line.
+--optimizer device: the block refines with refine_poses(optimizer="device") (scipy's BFGS as a state machine on the device,
+one isr_refine_bfgs_batch call); its t_ref and fun then agree with the per-image scipy loop to rounding, not bit for bit,
+and the record gives the largest differences and the items' BFGS statuses.
 
-    python tools/bench_surf_eval.py [--B 32] [--m 20000] [--reps 3] [--out profiles/<name>.json]
+    python tools/bench_surf_eval.py [--B 32] [--m 20000] [--reps 3] [--optimizer scipy|device] [--out profiles/<name>.json]
 
 The renderer and the feature field are stand-ins (a vectorised point z-buffer, a fixed sinusoidal field), as in the tests:
 the reference's moderngl renderer and SIREN are not part of this package."""
@@ -65,6 +68,7 @@ def main() -> None:
     ap.add_argument("--n-samples-denom", type=int, default=10960)
     ap.add_argument("--max-pose-evaluations", type=int, default=1000)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--optimizer", choices=["scipy", "device"], default="scipy")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -117,41 +121,69 @@ def main() -> None:
             pose_refine.RefineObjective = base
         return rows, t_est, t_ref, n_eval
 
+    real_refine_poses = pose_refine.refine_poses
+
     def block():
-        stats = {}
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = sequence.estimate_and_refine(ml, q, pts, nrm, keys, s["diameter"], s["K"], rend, 0, Obj, field, keys_verts,
-                                           verts, s["R"], s["t"], estimate_kw=est_kw, refine_kw=dict(ref_kw, stats=stats))
-        torch.cuda.synchronize()
-        return out, time.perf_counter() - t0, stats
+        stats, t_refine = {}, []
+
+        def timed_refine_poses(*x, **k):             # the block's refine share: refine_poses, device-synchronised
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            r = real_refine_poses(*x, **k)
+            torch.cuda.synchronize()
+            t_refine.append(time.perf_counter() - t1)
+            return r
+        pose_refine.refine_poses = timed_refine_poses
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = sequence.estimate_and_refine(ml, q, pts, nrm, keys, s["diameter"], s["K"], rend, 0, Obj, field, keys_verts,
+                                               verts, s["R"], s["t"], estimate_kw=est_kw,
+                                               refine_kw=dict(ref_kw, stats=stats, optimizer=a.optimizer))
+            torch.cuda.synchronize()
+            t = time.perf_counter() - t0
+        finally:
+            pose_refine.refine_poses = real_refine_poses
+        return out, t, stats, sum(t_refine)
 
     per_image()                      # warm-up (kernels, workspaces, side streams)
     block()
-    ta, tb = [], []
+    ta, tb, tbr = [], [], []
     for _ in range(a.reps):          # alternated arms
         rows, te, tr, n_eval = per_image()
         ta.append((te, tr))
-        out, t, stats = block()
+        out, t, stats, t_r = block()
         tb.append(t)
+        tbr.append(t_r)
     same = True
+    dt_max = dfun_max = 0.0
     for b, r in enumerate(rows):
         if r is None:
             same &= not out["refined"][b]
             continue
-        same &= bool(out["refined"][b] and np.array_equal(out["R2"][b], r[0]) and np.array_equal(out["T2"][b], r[1])
-                     and np.array_equal(out["t_ref"][b], r[2]) and out["fun"][b] == r[3])
+        same &= bool(out["refined"][b] and np.array_equal(out["R2"][b], r[0]) and np.array_equal(out["T2"][b], r[1]))
+        if a.optimizer == "scipy":
+            same &= bool(np.array_equal(out["t_ref"][b], r[2]) and out["fun"][b] == r[3])
+        else:                        # to rounding: the figures are recorded, a tolerance is the tests' business
+            dt_max = max(dt_max, float(np.max(np.abs(np.asarray(out["t_ref"][b]) - np.asarray(r[2])))))
+            dfun_max = max(dfun_max, abs(float(out["fun"][b]) - float(r[3])) / max(1.0, abs(float(r[3]))))
     med = lambda v: float(np.median(v))                                   # noqa: E731
     rec = dict(tool="bench_surf_eval", B=B, r=a.r, e=a.e, m=a.m, n_samples_denom=a.n_samples_denom,
                max_pose_evaluations=a.max_pose_evaluations, reps=a.reps, refined=int(out["refined"].sum()),
                per_image_estimate_ms_per_image=1e3 * med([x[0] for x in ta]) / B,
                per_image_refine_ms_per_image=1e3 * med([x[1] for x in ta]) / B,
                per_image_total_ms_per_image=1e3 * med([x[0] + x[1] for x in ta]) / B,
-               block_total_ms_per_image=1e3 * med(tb) / B,
+               block_total_ms_per_image=1e3 * med(tb) / B, block_refine_ms_per_image=1e3 * med(tbr) / B,
+               optimizer=a.optimizer,
                lockstep_rounds=stats["rounds"], per_image_evaluations_sum=int(sum(n_eval)),
                per_image_evaluations_max=int(max(n_eval)) if n_eval else 0, batched_item_evaluations=int(sum(stats["n_eval"])),
                outputs_equal=bool(same), workCT=out["workCT"], refCT=out["refCT"], rotWorkCT=out["rotWorkCT"],
                device=torch.cuda.get_device_name(0))
+    if a.optimizer == "device":
+        rec.update(block_launches=stats["launches"], device_bfgs_nit_max=int(max(stats["nit"])),
+                   device_bfgs_status=dict(zip(*[v.tolist() for v in np.unique(stats["status"], return_counts=True)])),
+                   t_ref_max_abs_diff_mm=dt_max, fun_max_rel_diff=dfun_max)
+        rec["device_bfgs_status"] = {str(k): int(v) for k, v in rec["device_bfgs_status"].items()}
     line = json.dumps(rec)
     print(line)
     if a.out:
