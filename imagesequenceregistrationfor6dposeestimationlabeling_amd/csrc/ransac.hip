@@ -24,7 +24,15 @@
 //                   NOT yet give the confidence:  (1 - (c/M)^4)^b > 1 - confidence  (the standard
 //                   RANSAC rule for 4-point samples, evaluated with multiplications only so that
 //                   oracle and device decide identically).  confidence >= 1: every hypothesis.
-//   3. best         arg-max count, lowest h on ties; its inlier bitmask.
+//                   Opt-in (loop = ISR_RANSAC_SEQUENTIAL): OpenCV's sequential loop instead (ransac_seq.hpp): hypothesis h
+//                   runs while h < niters, niters = min(H, cvRound(log(1 - p) / log(1 - w^4))) for the best count so far,
+//                   decided exactly; stages [0, s), [s, 3 s), ... from a run-time s = stage0, each gated by that test.
+//   3. best         arg-max count, lowest h on ties; its inlier bitmask.  Sequential loop: seq_best_kernel — the first
+//                   hypothesis with the best count among those that ran (< h_stop), n_eval = h_stop; the result does not
+//                   depend on stage0.  What still differs from cv2: a sample that repeats an index is a failed
+//                   iteration, not a redraw; no one-hypothesis special case at M == 4; the refit below, not cv2's final
+//                   solve.  inliers_mode ISR_INLIERS_RANSAC: this mask is compacted at once (step 5 runs here, before the
+//                   refit overwrites it) and reported as cv2 reports its inliers — the winner's consensus set.
 //   4. refit        Gauss-Newton on the reprojection error over the inliers, f64, fixed-shape
 //                   tree reduction of J^T J / J^T r, 6x6 Cholesky on the device.  Then ONE round of
 //                   local optimisation: the inlier mask is recomputed under the refitted pose (same
@@ -43,6 +51,7 @@
 // are the B = 1 case of the same kernels: bit-identical by construction.
 #include "isr_common.hpp"
 #include "p3p_device.hpp"
+#include "ransac_seq.hpp"
 
 namespace {
 
@@ -238,9 +247,14 @@ __host__ __device__ inline bool ransac_stop(int c, int M, int b, double one_minu
 
 // Hypotheses [h_lo, h_hi) of every image; blockIdx.y counts kHC-chunks from h_lo.  h_lo > 0: the stage
 // first applies the stopping rule at its lower boundary (best count over hypotheses < h_lo).
+// kSeq = false: the staged loop's gate, ransac_stop(c, M, h_lo, stop_arg = 1 - confidence).
+// kSeq = true:  the sequential loop's, isr_seq::seq_stop(c, M, h_lo, stop_arg = max(1 - confidence, DBL_MIN)): OpenCV's
+// loop has stopped before h_lo, so no hypothesis of the stage can run (a stage that does run is scored whole; the
+// hypotheses in it past the stop are left out by seq_best_kernel).
+template <bool kSeq>
 __global__ __launch_bounds__(kScoreThreads) void score_kernel(
     const float* __restrict__ p3d, const float* __restrict__ p2d, const int32_t* __restrict__ M_dev, int M_cap,
-    const float* __restrict__ Pm, const uint8_t* __restrict__ ok, int H, int h_lo, int h_hi, double one_minus_conf,
+    const float* __restrict__ Pm, const uint8_t* __restrict__ ok, int H, int h_lo, int h_hi, double stop_arg,
     float reperr, int32_t* __restrict__ n_inl) {
   __shared__ int32_t cnt[kHC];
   __shared__ __attribute__((aligned(16))) float Ps[kHC][12];   // the block's projection matrices: one
@@ -260,7 +274,7 @@ __global__ __launch_bounds__(kScoreThreads) void score_kernel(
     if ((threadIdx.x & 63) == 0) cmax[threadIdx.x >> 6] = c;
     __syncthreads();
     c = max(max(cmax[0], cmax[1]), max(cmax[2], cmax[3]));
-    if (ransac_stop(c, M, h_lo, one_minus_conf)) return;
+    if (kSeq ? isr_seq::seq_stop(c, M, h_lo, stop_arg) : ransac_stop(c, M, h_lo, stop_arg)) return;
   }
   const int h0 = h_lo + blockIdx.y * kHC;
   const int h1 = min(h_hi, h0 + kHC);
@@ -375,6 +389,69 @@ __global__ void best_kernel(const int32_t* __restrict__ n_inl, const uint8_t* __
   if (pose_dev && threadIdx.x < 12) {
     const int b = sh[0];
     pose_dev[threadIdx.x] = (b >= 0) ? Rt[12 * (size_t)b + threadIdx.x] : ((threadIdx.x % 5 == 0) ? 1.0 : 0.0);
+  }
+}
+
+// The sequential loop's pick (OpenCV's RANSAC loop, csrc/ransac_seq.hpp), one 256-thread block per image, H <= kMaxH:
+// thread t owns the contiguous hypotheses [t per, (t + 1) per), per = ceil(H / 256) <= 32.  An exclusive prefix-max scan
+// of the threads' maxima (wave64 shuffles, then the four wave totals through LDS) gives each thread the best count before
+// its chunk; walking the chunk, it finds its first h at which the loop stops; the block minimum is h_stop (H if none).
+// winner = arg-max count over ok hypotheses in [0, h_stop), lowest h on ties.  Same outputs as best_kernel:
+// best, status = count >= 4, the winner's pose, the cleared Gauss-Newton flag, n_eval = h_stop.
+__global__ __launch_bounds__(256) void seq_best_kernel(const int32_t* __restrict__ n_inl, const uint8_t* __restrict__ ok, int H,
+                                                       int32_t* __restrict__ best_dev, int32_t* __restrict__ status_dev,
+                                                       const double* __restrict__ Rt, double* __restrict__ pose_dev,
+                                                       int32_t* __restrict__ gn_state, const int32_t* __restrict__ M_dev,
+                                                       double num, int32_t* __restrict__ n_eval_dev) {
+  __shared__ int32_t wmax[4], wc[4], wh[4];
+  __shared__ int32_t hstop;
+  const int b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  n_inl += (size_t)b * H; ok += (size_t)b * H; Rt += (size_t)b * H * 12;
+  if (gn_state && tid == 0) { gn_state[4 * b] = 0; gn_state[4 * b + 1] = 0; }
+  const int M = M_dev[b];
+  const int per = (H + 255) / 256;
+  const int lo = min(H, tid * per), hi = min(H, lo + per);
+  int m = 0;
+  for (int h = lo; h < hi; ++h) m = max(m, ok[h] ? n_inl[h] : 0);
+  int inc = m;   // inclusive prefix max over the wave's threads
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int o = __shfl_up(inc, off, 64);
+    if (lane >= off) inc = max(inc, o);
+  }
+  if (lane == 63) wmax[wave] = inc;
+  if (tid == 0) hstop = H;
+  __syncthreads();
+  int c = __shfl_up(inc, 1, 64);
+  if (lane == 0) c = 0;
+  for (int w = 0; w < wave; ++w) c = max(c, wmax[w]);
+  for (int h = lo; h < hi; ++h) {
+    if (isr_seq::seq_stop(c, M, h, num)) { atomicMin(&hstop, h); break; }
+    c = max(c, ok[h] ? n_inl[h] : 0);
+  }
+  __syncthreads();
+  const int hs = hstop;
+  int bc = -1, bh = -1;
+  for (int h = lo; h < min(hi, hs); ++h)
+    if (ok[h] && n_inl[h] > bc) { bc = n_inl[h]; bh = h; }   // ascending h: lowest kept
+  // (count, h): higher count wins, then the lower h; bh = -1 is an empty candidate
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const int oc = __shfl_xor(bc, off, 64), oh = __shfl_xor(bh, off, 64);
+    if (oc > bc || (oc == bc && oh >= 0 && (bh < 0 || oh < bh))) { bc = oc; bh = oh; }
+  }
+  if (lane == 0) { wc[wave] = bc; wh[wave] = bh; }
+  __syncthreads();
+  if (tid < 12) {
+    bc = wc[0]; bh = wh[0];
+    for (int w = 1; w < 4; ++w)
+      if (wc[w] > bc || (wc[w] == bc && wh[w] >= 0 && (bh < 0 || wh[w] < bh))) { bc = wc[w]; bh = wh[w]; }
+    if (tid == 0) {
+      best_dev[b] = bh;
+      if (status_dev) status_dev[b] = (bh >= 0 && bc >= 4) ? 1 : 0;
+      if (n_eval_dev) n_eval_dev[b] = hs;
+    }
+    if (pose_dev) pose_dev[(size_t)b * 12 + tid] = (bh >= 0) ? Rt[12 * (size_t)bh + tid] : ((tid % 5 == 0) ? 1.0 : 0.0);
   }
 }
 
@@ -883,19 +960,34 @@ extern "C" int isr_p3p_all_roots(const double* X, const double* uv, const double
 static int score_impl(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B, const ImgDev* ib,
                       const double* Rt, const uint8_t* ok, int H, double confidence, float reperr, float* Pm,
                       int32_t* n_inl, int32_t* best_dev, uint32_t* best_mask, int32_t* status_dev, double* pose_dev,
-                      int32_t* gn_state, int32_t* n_eval_dev, hipStream_t stream) {
+                      int32_t* gn_state, int32_t* n_eval_dev, hipStream_t stream, int loop = ISR_RANSAC_STAGED,
+                      int stage0 = kStage0) {
   proj_matrix_kernel<<<dim3((H * 12 + 255) / 256, 1, B), 256, 0, stream>>>(Rt, ib, H, Pm, n_inl);
   const int nblk = (M_cap + kScoreThreads * kCPL - 1) / (kScoreThreads * kCPL);
+  if (loop == ISR_RANSAC_SEQUENTIAL) {
+    // stages [0, s), [s, 3 s), [3 s, 7 s), ... (s = stage0): which hypotheses the sequential loop runs, and which of them
+    // wins, do not depend on s — only how many are scored beyond the stop
+    const double num = isr_seq::seq_num(confidence);
+    for (int lo = 0, len = stage0; lo < H; lo += len, len *= 2) {
+      const int hi = (lo + len < H) ? lo + len : H;
+      score_kernel<true><<<dim3(nblk, (hi - lo + kHC - 1) / kHC, B), kScoreThreads, 0, stream>>>(
+          p3d, p2d, M_dev, M_cap, Pm, ok, H, lo, hi, num, reperr, n_inl);
+      if (hi == H) break;
+    }
+    seq_best_kernel<<<dim3(1, 1, B), 256, 0, stream>>>(n_inl, ok, H, best_dev, status_dev, Rt, pose_dev, gn_state, M_dev, num,
+                                                       n_eval_dev);
+  } else {
   const double omc = (confidence >= 1.0) ? 0.0 : 1.0 - confidence;
   // stages [0,32), [32,96), [96,224), ...: boundaries 32 (2^k - 1); one stage when every hypothesis is wanted
   for (int lo = 0, len = (omc > 0.0) ? kStage0 : H; lo < H; lo += len, len *= 2) {
     const int hi = (lo + len < H) ? lo + len : H;
-    score_kernel<<<dim3(nblk, (hi - lo + kHC - 1) / kHC, B), kScoreThreads, 0, stream>>>(
+    score_kernel<false><<<dim3(nblk, (hi - lo + kHC - 1) / kHC, B), kScoreThreads, 0, stream>>>(
         p3d, p2d, M_dev, M_cap, Pm, ok, H, lo, hi, omc, reperr, n_inl);
     if (hi == H) break;
   }
   best_kernel<<<dim3(1, 1, B), 256, 0, stream>>>(n_inl, ok, H, best_dev, status_dev, Rt, pose_dev, gn_state, M_dev, omc,
                                                  n_eval_dev);
+  }
   if (best_mask)
     best_mask_kernel<<<dim3((M_cap + 255) / 256, 1, B), 256, 0, stream>>>(p3d, p2d, M_dev, M_cap, H, Pm, best_dev, reperr,
                                                                           best_mask, mask_words_of(M_cap));
@@ -959,15 +1051,34 @@ extern "C" int isr_pnp_refine(const float* p3d, const float* p2d, const int32_t*
   return refine_impl(p3d, p2d, M_dev, M_cap, 1, mask, imgs, iters, Rt_io, nullptr, partial, state, isr::as_stream(stream));
 }
 
-// the chain for B <= kMaxBatch images: hypotheses, scoring, best + mask, refit, compaction
+// inlier mask -> ascending indices inl_idx, count n_inl_dev (0 for a failed image)
+static int compact_impl(const int32_t* M_dev, int M_cap, int B, const int32_t* status_dev, int32_t* inl_idx, int32_t* n_inl_dev,
+                        const RansacWs& b, hipStream_t stream) {
+  const int cb = comp_blocks_of(M_cap), mw = mask_words_of(M_cap);
+  mask_count_kernel<<<dim3(cb, 1, B), kCompBlock, 0, stream>>>(b.mask, mw, M_dev, status_dev, b.cblocks);
+  mask_scan_kernel<<<dim3(1, 1, B), 1024, 0, stream>>>(b.cblocks, cb, n_inl_dev);
+  mask_scatter_kernel<<<dim3(cb, 1, B), kCompBlock, 0, stream>>>(b.mask, mw, M_dev, status_dev, b.cblocks, inl_idx, M_cap);
+  ISR_CHECK_LAUNCH("mask compaction kernels");
+  return ISR_OK;
+}
+
+// the chain for B <= kChainMax images: hypotheses, scoring, best + mask, refit, compaction.
+// inliers_mode ISR_INLIERS_RANSAC: the winning hypothesis' consensus set is compacted straight after best_mask_kernel,
+// before the refit overwrites the mask, and the final mask under the returned pose is not needed.
 static int ransac_chain(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B, const ImgDev* ib,
                         int H, double confidence, float reperr, int refine_iters, double* pose_dev, int32_t* inl_idx,
-                        int32_t* n_inl_dev, int32_t* status_dev, int32_t* n_eval_dev, const RansacWs& b, hipStream_t stream) {
+                        int32_t* n_inl_dev, int32_t* status_dev, int32_t* n_eval_dev, const RansacWs& b, hipStream_t stream,
+                        int loop, int stage0, int inliers_mode) {
+  const bool ransac_inliers = inliers_mode == ISR_INLIERS_RANSAC;
   p3p_kernel<<<dim3((H + 63) / 64, 1, B), 64, 0, stream>>>(p3d, p2d, M_dev, M_cap, ib, H, b.Rt, b.ok, nullptr);
   ISR_CHECK_LAUNCH("p3p_kernel");
   int rc = score_impl(p3d, p2d, M_dev, M_cap, B, ib, b.Rt, b.ok, H, confidence, reperr, b.Pm, b.n_inl, b.best, b.mask,
-                      status_dev, pose_dev, b.state, n_eval_dev, stream);
+                      status_dev, pose_dev, b.state, n_eval_dev, stream, loop, stage0);
   if (rc != ISR_OK) return rc;
+  if (ransac_inliers) {
+    rc = compact_impl(M_dev, M_cap, B, status_dev, inl_idx, n_inl_dev, b, stream);
+    if (rc != ISR_OK) return rc;
+  }
   if (refine_iters > 0 && M_cap <= kSmallM) {
     // small correspondence sets: both refit rounds and the final mask in one launch, one workgroup per image
     gn_small_kernel<<<B, kRefThreads, 0, stream>>>(p3d, p2d, M_dev, M_cap, b.mask, mask_words_of(M_cap), ib, refine_iters, reperr,
@@ -982,27 +1093,45 @@ static int ransac_chain(const float* p3d, const float* p2d, const int32_t* M_dev
                                                                           b.mask, mask_words_of(M_cap));
     rc = refine_impl(p3d, p2d, M_dev, M_cap, B, b.mask, ib, refine_iters, pose_dev, status_dev, b.partial, b.state, stream);
     if (rc != ISR_OK) return rc;
+    if (ransac_inliers) return ISR_OK;
     // the reported inliers are those of the RETURNED pose: the mask once more, under the final refit
     refined_proj_kernel<<<B, 64, 0, stream>>>(pose_dev, ib, b.Pm, b.state);
     best_mask_kernel<<<dim3((M_cap + 255) / 256, 1, B), 256, 0, stream>>>(p3d, p2d, M_dev, M_cap, 1, b.Pm, nullptr, reperr,
                                                                           b.mask, mask_words_of(M_cap));
   }
   }
-  const int cb = comp_blocks_of(M_cap), mw = mask_words_of(M_cap);
-  mask_count_kernel<<<dim3(cb, 1, B), kCompBlock, 0, stream>>>(b.mask, mw, M_dev, status_dev, b.cblocks);
-  mask_scan_kernel<<<dim3(1, 1, B), 1024, 0, stream>>>(b.cblocks, cb, n_inl_dev);
-  mask_scatter_kernel<<<dim3(cb, 1, B), kCompBlock, 0, stream>>>(b.mask, mw, M_dev, status_dev, b.cblocks, inl_idx, M_cap);
-  ISR_CHECK_LAUNCH("mask compaction kernels");
+  if (ransac_inliers) return ISR_OK;
+  return compact_impl(M_dev, M_cap, B, status_dev, inl_idx, n_inl_dev, b, stream);
+}
+
+// loop / stage0 / inliers_mode of the _ex entries (stage0 = 0: the default first stage, 32 hypotheses)
+static int check_loop(const char* who, int H, int loop, int stage0, int inliers_mode, int* stage0_out) {
+  ISR_REQUIRE(loop == ISR_RANSAC_STAGED || loop == ISR_RANSAC_SEQUENTIAL, "%s: loop=%d (ISR_RANSAC_STAGED %d | ISR_RANSAC_SEQUENTIAL %d)",
+              who, loop, ISR_RANSAC_STAGED, ISR_RANSAC_SEQUENTIAL);
+  ISR_REQUIRE(inliers_mode == ISR_INLIERS_REFIT || inliers_mode == ISR_INLIERS_RANSAC,
+              "%s: inliers_mode=%d (ISR_INLIERS_REFIT %d | ISR_INLIERS_RANSAC %d)", who, inliers_mode, ISR_INLIERS_REFIT,
+              ISR_INLIERS_RANSAC);
+  const int s0 = stage0 == 0 ? kStage0 : stage0;
+  if (loop == ISR_RANSAC_STAGED)
+    ISR_REQUIRE(s0 == kStage0, "%s: stage0=%d: the staged loop's first stage is %d hypotheses", who, stage0, kStage0);
+  else
+    ISR_REQUIRE(s0 > 0 && (s0 % kHC == 0 || s0 >= H), "%s: stage0=%d must be a positive multiple of %d, or >= H=%d", who, stage0,
+                kHC, H);
+  *stage0_out = s0;
   return ISR_OK;
 }
 
-extern "C" int isr_pnp_ransac(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
-                              const double* Kcam, int H, uint64_t seed, float reperr, double confidence,
-                              int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
-                              int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes, isr_stream_t stream_) {
+extern "C" int isr_pnp_ransac_ex(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
+                                 const double* Kcam, int H, uint64_t seed, float reperr, double confidence,
+                                 int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
+                                 int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes, isr_stream_t stream_,
+                                 int loop, int stage0, int inliers_mode) {
   ISR_REQUIRE(p3d && p2d && M_dev && Kcam && pose_dev && inl_idx && n_inl_dev && status_dev,
               "isr_pnp_ransac: null pointer");
   ISR_REQUIRE(M_cap > 0 && H > 0 && H <= kMaxH, "isr_pnp_ransac: M_cap=%d H=%d (H <= %d)", M_cap, H, kMaxH);
+  int s0;
+  const int lrc = check_loop("isr_pnp_ransac", H, loop, stage0, inliers_mode, &s0);
+  if (lrc != ISR_OK) return lrc;
   if (!ws || ws_bytes < isr_pnp_ransac_workspace_bytes(M_cap, H)) {
     isr::set_error("isr_pnp_ransac: workspace %zu < %zu", ws_bytes, isr_pnp_ransac_workspace_bytes(M_cap, H));
     return ISR_ERR_WORKSPACE;
@@ -1014,18 +1143,29 @@ extern "C" int isr_pnp_ransac(const float* p3d, const float* p2d, const int32_t*
   const int urc = upload_imgs(Kcam, &seed, 1, b.imgs, isr::as_stream(stream_), "isr_pnp_ransac");
   if (urc != ISR_OK) return urc;
   return ransac_chain(p3d, p2d, M_dev, M_cap, 1, b.imgs, H, confidence, reperr, refine_iters, pose_dev, inl_idx, n_inl_dev,
-                      status_dev, n_eval_dev, b, isr::as_stream(stream_));
+                      status_dev, n_eval_dev, b, isr::as_stream(stream_), loop, s0, inliers_mode);
 }
 
-extern "C" int isr_pnp_ransac_batch(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B,
-                                    const double* Kcams, int H, const uint64_t* seeds, float reperr, double confidence,
-                                    int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
-                                    int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes,
-                                    isr_stream_t stream_) {
+extern "C" int isr_pnp_ransac(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
+                              const double* Kcam, int H, uint64_t seed, float reperr, double confidence,
+                              int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
+                              int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes, isr_stream_t stream_) {
+  return isr_pnp_ransac_ex(p3d, p2d, M_dev, M_cap, Kcam, H, seed, reperr, confidence, refine_iters, pose_dev, inl_idx, n_inl_dev,
+                           status_dev, n_eval_dev, ws, ws_bytes, stream_, ISR_RANSAC_STAGED, kStage0, ISR_INLIERS_REFIT);
+}
+
+extern "C" int isr_pnp_ransac_batch_ex(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B,
+                                       const double* Kcams, int H, const uint64_t* seeds, float reperr, double confidence,
+                                       int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
+                                       int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes,
+                                       isr_stream_t stream_, int loop, int stage0, int inliers_mode) {
   ISR_REQUIRE(p3d && p2d && M_dev && Kcams && seeds && pose_dev && inl_idx && n_inl_dev && status_dev,
               "isr_pnp_ransac_batch: null pointer");
   ISR_REQUIRE(M_cap > 0 && H > 0 && H <= kMaxH && B > 0, "isr_pnp_ransac_batch: M_cap=%d H=%d (H <= %d) B=%d", M_cap, H, kMaxH, B);
   ISR_REQUIRE(confidence > 0.0, "isr_pnp_ransac_batch: confidence=%g must be > 0 (>= 1: score every hypothesis)", confidence);
+  int s0;
+  const int lrc = check_loop("isr_pnp_ransac_batch", H, loop, stage0, inliers_mode, &s0);
+  if (lrc != ISR_OK) return lrc;
   if (!ws || ws_bytes < isr_pnp_ransac_batch_workspace_bytes(M_cap, H, B)) {
     isr::set_error("isr_pnp_ransac_batch: workspace %zu < %zu", ws_bytes, isr_pnp_ransac_batch_workspace_bytes(M_cap, H, B));
     return ISR_ERR_WORKSPACE;
@@ -1040,8 +1180,33 @@ extern "C" int isr_pnp_ransac_batch(const float* p3d, const float* p2d, const in
     if (urc != ISR_OK) return urc;
     const int rc = ransac_chain(p3d + (size_t)b0 * M_cap * 3, p2d + (size_t)b0 * M_cap * 2, M_dev + b0, M_cap, nb, wsb.imgs, H,
                                 confidence, reperr, refine_iters, pose_dev + (size_t)b0 * 12, inl_idx + (size_t)b0 * M_cap,
-                                n_inl_dev + b0, status_dev + b0, n_eval_dev ? n_eval_dev + b0 : nullptr, wsb, stream);
+                                n_inl_dev + b0, status_dev + b0, n_eval_dev ? n_eval_dev + b0 : nullptr, wsb, stream, loop, s0,
+                                inliers_mode);
     if (rc != ISR_OK) return rc;
   }
+  return ISR_OK;
+}
+
+extern "C" int isr_pnp_ransac_batch(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B,
+                                    const double* Kcams, int H, const uint64_t* seeds, float reperr, double confidence,
+                                    int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
+                                    int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes,
+                                    isr_stream_t stream_) {
+  return isr_pnp_ransac_batch_ex(p3d, p2d, M_dev, M_cap, B, Kcams, H, seeds, reperr, confidence, refine_iters, pose_dev, inl_idx,
+                                 n_inl_dev, status_dev, n_eval_dev, ws, ws_bytes, stream_, ISR_RANSAC_STAGED, kStage0,
+                                 ISR_INLIERS_REFIT);
+}
+
+// The sequential loop on host arrays, from the header the kernels use (no device): n_inl, ok (H) -> winner (-1: no
+// hypothesis with more than 3 inliers), n_eval = h_stop.
+extern "C" int isr_ransac_seq_host(const int32_t* n_inl, const uint8_t* ok, int H, int M, double confidence, int32_t* winner,
+                                   int32_t* n_eval) {
+  ISR_REQUIRE(n_inl && ok && winner && n_eval, "isr_ransac_seq_host: null pointer");
+  ISR_REQUIRE(H >= 0 && M >= 0, "isr_ransac_seq_host: H=%d M=%d", H, M);
+  ISR_REQUIRE(confidence > 0.0, "isr_ransac_seq_host: confidence=%g must be > 0", confidence);
+  int w, n;
+  isr_seq::seq_scan(n_inl, ok, H, M, isr_seq::seq_num(confidence), &w, &n);
+  *winner = w;
+  *n_eval = n;
   return ISR_OK;
 }

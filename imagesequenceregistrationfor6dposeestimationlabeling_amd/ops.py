@@ -753,14 +753,34 @@ class PnPResult:
     inl_idx: torch.Tensor   # (cap,) i32 device, first n_inl valid
     n_inl: torch.Tensor     # (1,) i32 device
     status: torch.Tensor    # (1,) i32 device
-    n_eval: torch.Tensor | None = None   # (1,) i32 device: hypotheses the staged loop scored
+    n_eval: torch.Tensor | None = None   # (1,) i32 device: hypotheses the staged loop scored (sequential: that ran)
+
+
+_LOOPS = {"staged": _capi.RANSAC_STAGED, "sequential": _capi.RANSAC_SEQUENTIAL}
+_INLIERS = {"refit": _capi.INLIERS_REFIT, "ransac": _capi.INLIERS_RANSAC}
+
+
+def _loop_args(loop: str, inliers: str, stage0) -> tuple[int, int, int]:
+    """(loop, stage0, inliers_mode) of isr_pnp_ransac(_batch)_ex; stage0 None = the default first stage (32)."""
+    if loop not in _LOOPS:
+        raise ValueError(f"loop={loop!r}: 'staged' or 'sequential'")
+    if inliers not in _INLIERS:
+        raise ValueError(f"inliers={inliers!r}: 'refit' or 'ransac'")
+    return _LOOPS[loop], 0 if stage0 is None else int(stage0), _INLIERS[inliers]
 
 
 def pnp_ransac(p3d, p2d, Kcam, H: int = 500, reperr: float = 2.0, seed: int = 0,
-               refine_iters: int = 10, M_dev=None, confidence: float = 0.99) -> PnPResult:
-    """isr_pnp_ransac, fully asynchronous: every output stays on the device.  confidence: cv2's
-    solvePnPRansac parameter (default 0.99, what the reference's call uses); >= 1 scores every hypothesis."""
+               refine_iters: int = 10, M_dev=None, confidence: float = 0.99, loop: str = "staged",
+               inliers: str = "refit", stage0: int | None = None) -> PnPResult:
+    """isr_pnp_ransac_ex, fully asynchronous: every output stays on the device.  confidence: cv2's
+    solvePnPRansac parameter (default 0.99, what the reference's call uses); >= 1 scores every hypothesis (staged loop).
+    loop="staged" (default): scoring stops at a stage boundary 32 (2^k - 1) once the confidence is reached, the best of
+    every scored hypothesis wins.  loop="sequential": OpenCV's loop — hypothesis h runs while h < niters, niters updated
+    from the best count so far; n_eval = how many ran; the result does not depend on stage0 (the first scoring stage, a
+    multiple of 32 or >= H; None = 32).  inliers="refit" (default): the inliers of the returned, refitted pose;
+    "ransac": the winning hypothesis' consensus set, as cv2 reports it.  The pose is the refitted one either way."""
     import ctypes
+    lp, s0, im = _loop_args(loop, inliers, stage0)
     dev = require_cuda(p3d, p2d)
     p3d, p2d = _f32c(p3d), _f32c(p2d)
     cap = p3d.shape[0]
@@ -774,11 +794,25 @@ def pnp_ransac(p3d, p2d, Kcam, H: int = 500, reperr: float = 2.0, seed: int = 0,
     ws = workspace(dev, L.isr_pnp_ransac_workspace_bytes(cap, H), "ransac")
     k = _kcam(Kcam)
     with torch.cuda.device(dev), _timed("pnp_ransac", 30.0 * H * cap):
-        rc = L.isr_pnp_ransac(ptr(p3d), ptr(p2d), ptr(M_dev), cap, ctypes.cast(k, ctypes.c_void_p), int(H),
-                              seed & 0xFFFFFFFFFFFFFFFF, float(reperr), float(confidence), int(refine_iters), ptr(pose),
-                              ptr(inl), ptr(n_inl), ptr(status), ptr(n_eval), ptr(ws), ws.numel(), current_stream(dev))
+        rc = L.isr_pnp_ransac_ex(ptr(p3d), ptr(p2d), ptr(M_dev), cap, ctypes.cast(k, ctypes.c_void_p), int(H),
+                                 seed & 0xFFFFFFFFFFFFFFFF, float(reperr), float(confidence), int(refine_iters), ptr(pose),
+                                 ptr(inl), ptr(n_inl), ptr(status), ptr(n_eval), ptr(ws), ws.numel(), current_stream(dev),
+                                 lp, s0, im)
     check(rc, "isr_pnp_ransac")
     return PnPResult(pose, inl, n_inl, status, n_eval)
+
+
+def ransac_seq_host(n_inl, ok, M: int, confidence: float = 0.99) -> tuple[int, int]:
+    """isr_ransac_seq_host: OpenCV's sequential RANSAC loop over host arrays of counts n_inl (H,) and model flags ok (H,),
+    from the header the kernels use (no device) -> (winner, n_eval); winner -1: no hypothesis with more than 3 inliers."""
+    c = np.ascontiguousarray(n_inl, dtype=np.int32)
+    o = np.ascontiguousarray(ok, dtype=np.uint8)
+    if c.ndim != 1 or o.shape != c.shape:
+        raise ValueError(f"ransac_seq_host: n_inl {c.shape} / ok {o.shape} must be (H,)")
+    w, n = ctypes.c_int32(0), ctypes.c_int32(0)
+    check(lib().isr_ransac_seq_host(c.ctypes.data_as(ctypes.c_void_p), o.ctypes.data_as(ctypes.c_void_p), c.shape[0], int(M),
+                                    float(confidence), ctypes.byref(w), ctypes.byref(n)), "isr_ransac_seq_host")
+    return int(w.value), int(n.value)
 
 
 # ------------------------------------------------------------------ the per-group (batched) chain
@@ -832,15 +866,18 @@ class PnPBatchResult:
     inl_idx: torch.Tensor   # (B,cap) i32 device, first n_inl[b] valid
     n_inl: torch.Tensor     # (B,) i32 device
     status: torch.Tensor    # (B,) i32 device
-    n_eval: torch.Tensor | None = None   # (B,) i32 device: hypotheses the staged loop scored per image
+    n_eval: torch.Tensor | None = None   # (B,) i32 device: hypotheses the staged loop scored (sequential: that ran) per image
 
 
 def pnp_ransac_batch(p3d, p2d, Kcams, M_dev, H: int = 500, reperr: float = 2.0, seeds=None,
-                     refine_iters: int = 10, confidence: float = 0.99) -> PnPBatchResult:
-    """isr_pnp_ransac_batch: p3d (B, cap, 3), p2d (B, cap, 2), M_dev (B,) i32; Kcams one 3x3 or (B, 3, 3)
-    host array; seeds B ints.  Every output stays on the device, nothing is pre-filled."""
+                     refine_iters: int = 10, confidence: float = 0.99, loop: str = "staged", inliers: str = "refit",
+                     stage0: int | None = None) -> PnPBatchResult:
+    """isr_pnp_ransac_batch_ex: p3d (B, cap, 3), p2d (B, cap, 2), M_dev (B,) i32; Kcams one 3x3 or (B, 3, 3)
+    host array; seeds B ints.  Every output stays on the device, nothing is pre-filled.  loop / inliers / stage0: as
+    pnp_ransac; image b's outputs equal pnp_ransac's on image b alone."""
     import ctypes
     import numpy as np
+    lp, s0, im = _loop_args(loop, inliers, stage0)
     dev = require_cuda(p3d, p2d, M_dev)
     p3d, p2d = _f32c(p3d), _f32c(p2d)
     B, cap = p3d.shape[0], p3d.shape[1]
@@ -858,10 +895,11 @@ def pnp_ransac_batch(p3d, p2d, Kcams, M_dev, H: int = 500, reperr: float = 2.0, 
     L = lib()
     ws = workspace(dev, L.isr_pnp_ransac_batch_workspace_bytes(cap, H, B), "ransac")
     with torch.cuda.device(dev), _timed("pnp_ransac", 30.0 * H * cap * B):
-        rc = L.isr_pnp_ransac_batch(ptr(p3d), ptr(p2d), ptr(M_dev), cap, B, K.ctypes.data_as(ctypes.c_void_p), int(H),
-                                    sd.ctypes.data_as(ctypes.c_void_p), float(reperr), float(confidence),
-                                    int(refine_iters), ptr(pose),
-                                    ptr(inl), ptr(n_inl), ptr(status), ptr(n_eval), ptr(ws), ws.numel(), current_stream(dev))
+        rc = L.isr_pnp_ransac_batch_ex(ptr(p3d), ptr(p2d), ptr(M_dev), cap, B, K.ctypes.data_as(ctypes.c_void_p), int(H),
+                                       sd.ctypes.data_as(ctypes.c_void_p), float(reperr), float(confidence),
+                                       int(refine_iters), ptr(pose),
+                                       ptr(inl), ptr(n_inl), ptr(status), ptr(n_eval), ptr(ws), ws.numel(), current_stream(dev),
+                                       lp, s0, im)
     check(rc, "isr_pnp_ransac_batch")
     return PnPBatchResult(pose, inl, n_inl, status, n_eval)
 

@@ -331,6 +331,39 @@ int isr_pnp_ransac_batch(const float* p3d, const float* p2d, const int32_t* M_de
                          int32_t* n_inl_dev, int32_t* status_dev, int32_t* n_eval_dev /* (B), nullable */,
                          void* ws, size_t ws_bytes, isr_stream_t stream);
 
+/* The RANSAC loop and the reported inliers, chosen per call (isr_pnp_ransac_ex / isr_pnp_ransac_batch_ex: the arguments
+ * of isr_pnp_ransac / isr_pnp_ransac_batch plus loop, stage0, inliers_mode; same workspace).  The entries above are the
+ * (ISR_RANSAC_STAGED, 32, ISR_INLIERS_REFIT) case.
+ * loop ISR_RANSAC_STAGED: the staged loop described above.
+ *      ISR_RANSAC_SEQUENTIAL: OpenCV's sequential loop (RANSACPointSetRegistrator::run + RANSACUpdateNumIters, restated
+ *      from memory): hypothesis h runs while h < niters, niters = min(H, cvRound(log(1 - confidence) / log(1 - w^4))) for
+ *      the best count so far (w = its inlier ratio; counts <= 3 leave niters at H); the winner is the first hypothesis with
+ *      the maximal count among those that ran; n_eval = the number that ran.  The rounding test is exact (multiplications
+ *      and one sqrt: csrc/ransac_seq.hpp), so the result depends on (data, seed, H, confidence) only — not on stage0.
+ * stage0: hypotheses of the first scoring stage (later stages double); 0 = 32.  The staged loop takes 0 or 32 only; the
+ *      sequential loop a positive multiple of 32, or >= H (a single stage).
+ * inliers_mode ISR_INLIERS_REFIT: the inliers of the returned (refitted) pose, as above.
+ *      ISR_INLIERS_RANSAC: the consensus set of the winning hypothesis (its mask before any refit), as cv2 returns it.
+ *      The pose is the refitted one either way. */
+#define ISR_RANSAC_STAGED 0
+#define ISR_RANSAC_SEQUENTIAL 1
+#define ISR_INLIERS_REFIT 0
+#define ISR_INLIERS_RANSAC 1
+int isr_pnp_ransac_ex(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
+                      const double* Kcam, int H, uint64_t seed, float reperr, double confidence,
+                      int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
+                      int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes, isr_stream_t stream,
+                      int loop, int stage0, int inliers_mode);
+int isr_pnp_ransac_batch_ex(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B,
+                            const double* Kcams, int H, const uint64_t* seeds, float reperr,
+                            double confidence, int refine_iters, double* pose_dev, int32_t* inl_idx,
+                            int32_t* n_inl_dev, int32_t* status_dev, int32_t* n_eval_dev,
+                            void* ws, size_t ws_bytes, isr_stream_t stream, int loop, int stage0, int inliers_mode);
+/* The sequential loop as host code, from the same header as the kernels (no device): n_inl, ok (H) HOST arrays of
+ * counts and model flags -> winner (-1: no hypothesis with more than 3 inliers) and n_eval (hypotheses that ran). */
+int isr_ransac_seq_host(const int32_t* n_inl, const uint8_t* ok, int H, int M, double confidence, int32_t* winner,
+                        int32_t* n_eval);
+
 /* ------------------------------------------------------------------------------------------
  * K3 / K4  batched brute-force nearest neighbour with fused reductions
  * replaces  sklearn KDTree(...).query(k=1)                    inference.py:118-120 (ADD-S)
