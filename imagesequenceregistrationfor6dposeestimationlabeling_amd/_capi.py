@@ -27,6 +27,8 @@ RANSAC_STAGED = 0          # ISR_RANSAC_* / ISR_INLIERS_* of include/isr_hip.h
 RANSAC_SEQUENTIAL = 1
 INLIERS_REFIT = 0
 INLIERS_RANSAC = 1
+FINAL_REFIT = 0            # ISR_FINAL_*
+FINAL_EPNP = 1
 # ISR_TUNE_* knobs of include/isr_hip.h
 TUNE = {"nn_path": 0, "nn_filter": 1, "icp_warm": 2, "nn_plan_rq": 3, "nn_plan_blocks": 4,
         "nn_tile_st": 5, "nn_tile_sq": 6, "nn_tile_tb": 7, "ep_wsum_valu": 8, "k1_f32_chain": 9, "k1_split": 10}
@@ -84,6 +86,16 @@ SIGNATURES = {
     "isr_pnp_ransac_ex": (_i, [_vp, _vp, _vp, _i, _vp, _i, _u64, _f, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
                                _i, _i, _i]),
     "isr_ransac_seq_host": (_i, [_vp, _vp, _i, _i, _d, _vp, _vp]),
+    "isr_pnp_ransac_ex2_workspace_bytes": (_sz, [_i, _i, _i]),
+    "isr_pnp_ransac_batch_ex2_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "isr_pnp_ransac_ex2": (_i, [_vp, _vp, _vp, _i, _vp, _i, _u64, _f, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
+                                _i, _i, _i, _i]),
+    "isr_pnp_ransac_batch_ex2": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _f, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
+                                      _i, _i, _i, _i]),
+    "isr_epnp_batch_workspace_bytes": (_sz, [_i, _i]),
+    "isr_epnp_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "isr_epnp_host": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "isr_epnp_jacobi_host": (_i, [_vp, _i, _vp, _vp]),
     "isr_prep_queries_workspace_bytes": (_sz, [_i, _i, _i]),
     "isr_prep_queries": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "isr_prep_queries_batch_workspace_bytes": (_sz, [_i, _i, _i, _i]),

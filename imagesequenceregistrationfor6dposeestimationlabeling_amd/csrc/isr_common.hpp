@@ -66,6 +66,15 @@ struct Workspace {
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+// EPnP over the masked correspondences of B images (csrc/epnp.hip), enqueued on `stream`: mask (B, mask_words) words, K_dev
+// the images' 3x3 cameras (row-major, K_stride doubles apart), ws epnp_ws_bytes(B) bytes.  status_dev (nullable): images
+// with status 0 are skipped, a non-finite pose sets it to 0; pose_dev (nullable): the pose of every finite result.
+// Rt_out (B, 12), err_out (B, 3), chosen_out (B): nullable.
+size_t epnp_ws_bytes(int B);
+int epnp_enqueue(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B, const uint32_t* mask,
+                 int mask_words, const double* K_dev, int K_stride, int32_t* status_dev, double* pose_dev, double* Rt_out,
+                 double* err_out, int32_t* chosen_out, void* ws, hipStream_t stream);
+
 // The order-preserving unsigned image of a float (radix select of the top-80 % cut, csrc/select_top.hip; its leading
 // 11-bit digit is what K1's epilogue counts for isr_corr_argmax_digits): u(a) < u(b)  <=>  a < b for non-NaN a, b.
 __host__ __device__ __forceinline__ uint32_t ordered_bits(float f) {

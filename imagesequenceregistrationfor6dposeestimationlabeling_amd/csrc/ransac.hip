@@ -30,8 +30,8 @@
 //   3. best         arg-max count, lowest h on ties; its inlier bitmask.  Sequential loop: seq_best_kernel — the first
 //                   hypothesis with the best count among those that ran (< h_stop), n_eval = h_stop; the result does not
 //                   depend on stage0.  What still differs from cv2: a sample that repeats an index is a failed
-//                   iteration, not a redraw; no one-hypothesis special case at M == 4; the refit below, not cv2's final
-//                   solve.  inliers_mode ISR_INLIERS_RANSAC: this mask is compacted at once (step 5 runs here, before the
+//                   iteration, not a redraw; no one-hypothesis special case at M == 4; the refit below unless final_mode
+//                   ISR_FINAL_EPNP asks for cv2's final solve.  inliers_mode ISR_INLIERS_RANSAC: this mask is compacted at once (step 5 runs here, before the
 //                   refit overwrites it) and reported as cv2 reports its inliers — the winner's consensus set.
 //   4. refit        Gauss-Newton on the reprojection error over the inliers, f64, fixed-shape
 //                   tree reduction of J^T J / J^T r, 6x6 Cholesky on the device.  Then ONE round of
@@ -42,6 +42,9 @@
 //                   evaluated once more under the final refit; cv2 reports the RANSAC model's consensus set
 //                   instead, as far as is known — a documented deviation, like the confidence rule).  A refit
 //                   over fewer than 4 correspondences is skipped (the pose it started from is kept).
+//                   Opt-in (final_mode ISR_FINAL_EPNP): cv2's final solve instead — EPnP over the winner's consensus set
+//                   (csrc/epnp.hip, csrc/epnp.hpp), no refinement after it; a non-finite EPnP pose sets status 0.  The reported
+//                   inliers are then the mask under the EPnP pose (ISR_INLIERS_REFIT) or the consensus set (ISR_INLIERS_RANSAC).
 //   5. compaction   inlier mask -> ascending int32 indices.
 // Every step reads M and the status from device memory: the whole chain is enqueued without a
 // host round trip.
@@ -1065,16 +1068,31 @@ static int compact_impl(const int32_t* M_dev, int M_cap, int B, const int32_t* s
 // the chain for B <= kChainMax images: hypotheses, scoring, best + mask, refit, compaction.
 // inliers_mode ISR_INLIERS_RANSAC: the winning hypothesis' consensus set is compacted straight after best_mask_kernel,
 // before the refit overwrites the mask, and the final mask under the returned pose is not needed.
+// final_mode ISR_FINAL_EPNP (epnp_ws: isr::epnp_ws_bytes(B) bytes): EPnP over the winner's consensus set (b.mask) replaces
+// the refit; then, as there, the consensus set itself or the mask under the returned pose is compacted.
 static int ransac_chain(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B, const ImgDev* ib,
                         int H, double confidence, float reperr, int refine_iters, double* pose_dev, int32_t* inl_idx,
                         int32_t* n_inl_dev, int32_t* status_dev, int32_t* n_eval_dev, const RansacWs& b, hipStream_t stream,
-                        int loop, int stage0, int inliers_mode) {
+                        int loop, int stage0, int inliers_mode, int final_mode = ISR_FINAL_REFIT, void* epnp_ws = nullptr) {
   const bool ransac_inliers = inliers_mode == ISR_INLIERS_RANSAC;
   p3p_kernel<<<dim3((H + 63) / 64, 1, B), 64, 0, stream>>>(p3d, p2d, M_dev, M_cap, ib, H, b.Rt, b.ok, nullptr);
   ISR_CHECK_LAUNCH("p3p_kernel");
   int rc = score_impl(p3d, p2d, M_dev, M_cap, B, ib, b.Rt, b.ok, H, confidence, reperr, b.Pm, b.n_inl, b.best, b.mask,
                       status_dev, pose_dev, b.state, n_eval_dev, stream, loop, stage0);
   if (rc != ISR_OK) return rc;
+  if (final_mode == ISR_FINAL_EPNP) {
+    // the cameras are the first 9 doubles of each ImgDev (Cam::k)
+    static_assert(sizeof(ImgDev) % sizeof(double) == 0, "ImgDev stride in doubles");
+    rc = isr::epnp_enqueue(p3d, p2d, M_dev, M_cap, B, b.mask, mask_words_of(M_cap), reinterpret_cast<const double*>(ib),
+                           (int)(sizeof(ImgDev) / sizeof(double)), status_dev, pose_dev, nullptr, nullptr, nullptr, epnp_ws, stream);
+    if (rc != ISR_OK) return rc;
+    if (!ransac_inliers) {   // the inliers of the returned pose: its mask (the consensus set is no longer needed)
+      refined_proj_kernel<<<B, 64, 0, stream>>>(pose_dev, ib, b.Pm, b.state);
+      best_mask_kernel<<<dim3((M_cap + 255) / 256, 1, B), 256, 0, stream>>>(p3d, p2d, M_dev, M_cap, 1, b.Pm, nullptr, reperr,
+                                                                            b.mask, mask_words_of(M_cap));
+    }
+    return compact_impl(M_dev, M_cap, B, status_dev, inl_idx, n_inl_dev, b, stream);
+  }
   if (ransac_inliers) {
     rc = compact_impl(M_dev, M_cap, B, status_dev, inl_idx, n_inl_dev, b, stream);
     if (rc != ISR_OK) return rc;
@@ -1195,6 +1213,109 @@ extern "C" int isr_pnp_ransac_batch(const float* p3d, const float* p2d, const in
   return isr_pnp_ransac_batch_ex(p3d, p2d, M_dev, M_cap, B, Kcams, H, seeds, reperr, confidence, refine_iters, pose_dev, inl_idx,
                                  n_inl_dev, status_dev, n_eval_dev, ws, ws_bytes, stream_, ISR_RANSAC_STAGED, kStage0,
                                  ISR_INLIERS_REFIT);
+}
+
+static int check_final(const char* who, int final_mode) {
+  ISR_REQUIRE(final_mode == ISR_FINAL_REFIT || final_mode == ISR_FINAL_EPNP, "%s: final_mode=%d (ISR_FINAL_REFIT %d | ISR_FINAL_EPNP %d)",
+              who, final_mode, ISR_FINAL_REFIT, ISR_FINAL_EPNP);
+  return ISR_OK;
+}
+
+// the _ex carve plus EPnP's scratch behind it (ISR_FINAL_EPNP)
+static size_t carve_ex2(isr::Workspace& w, int M_cap, int H, int B, RansacWs* o, void** epnp_ws) {
+  carve(w, M_cap, H, B, o);
+  *epnp_ws = w.take<char>(isr::epnp_ws_bytes(B));
+  return w.off;
+}
+
+extern "C" size_t isr_pnp_ransac_ex2_workspace_bytes(int M_cap, int H, int final_mode) {
+  if (final_mode != ISR_FINAL_EPNP) return final_mode == ISR_FINAL_REFIT ? isr_pnp_ransac_workspace_bytes(M_cap, H) : 0;
+  if (M_cap <= 0 || H <= 0) return 0;
+  isr::Workspace w(nullptr, 0);
+  RansacWs o;
+  void* e;
+  return carve_ex2(w, M_cap, H, 1, &o, &e) + 512;
+}
+
+extern "C" size_t isr_pnp_ransac_batch_ex2_workspace_bytes(int M_cap, int H, int B, int final_mode) {
+  if (final_mode != ISR_FINAL_EPNP) return final_mode == ISR_FINAL_REFIT ? isr_pnp_ransac_batch_workspace_bytes(M_cap, H, B) : 0;
+  if (M_cap <= 0 || H <= 0 || B <= 0) return 0;
+  isr::Workspace w(nullptr, 0);
+  RansacWs o;
+  void* e;
+  return carve_ex2(w, M_cap, H, B < kChainMax ? B : kChainMax, &o, &e) + 512;
+}
+
+extern "C" int isr_pnp_ransac_ex2(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
+                                  const double* Kcam, int H, uint64_t seed, float reperr, double confidence,
+                                  int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
+                                  int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes, isr_stream_t stream_,
+                                  int loop, int stage0, int inliers_mode, int final_mode) {
+  const int frc = check_final("isr_pnp_ransac", final_mode);
+  if (frc != ISR_OK) return frc;
+  if (final_mode == ISR_FINAL_REFIT)
+    return isr_pnp_ransac_ex(p3d, p2d, M_dev, M_cap, Kcam, H, seed, reperr, confidence, refine_iters, pose_dev, inl_idx,
+                             n_inl_dev, status_dev, n_eval_dev, ws, ws_bytes, stream_, loop, stage0, inliers_mode);
+  ISR_REQUIRE(p3d && p2d && M_dev && Kcam && pose_dev && inl_idx && n_inl_dev && status_dev,
+              "isr_pnp_ransac: null pointer");
+  ISR_REQUIRE(M_cap > 0 && H > 0 && H <= kMaxH, "isr_pnp_ransac: M_cap=%d H=%d (H <= %d)", M_cap, H, kMaxH);
+  int s0;
+  const int lrc = check_loop("isr_pnp_ransac", H, loop, stage0, inliers_mode, &s0);
+  if (lrc != ISR_OK) return lrc;
+  ISR_REQUIRE(confidence > 0.0, "isr_pnp_ransac: confidence=%g must be > 0 (>= 1: score every hypothesis)", confidence);
+  const size_t need = isr_pnp_ransac_ex2_workspace_bytes(M_cap, H, final_mode);
+  if (!ws || ws_bytes < need) {
+    isr::set_error("isr_pnp_ransac: workspace %zu < %zu", ws_bytes, need);
+    return ISR_ERR_WORKSPACE;
+  }
+  isr::Workspace w(ws, ws_bytes);
+  RansacWs b;
+  void* ews;
+  carve_ex2(w, M_cap, H, 1, &b, &ews);
+  const int urc = upload_imgs(Kcam, &seed, 1, b.imgs, isr::as_stream(stream_), "isr_pnp_ransac");
+  if (urc != ISR_OK) return urc;
+  return ransac_chain(p3d, p2d, M_dev, M_cap, 1, b.imgs, H, confidence, reperr, refine_iters, pose_dev, inl_idx, n_inl_dev,
+                      status_dev, n_eval_dev, b, isr::as_stream(stream_), loop, s0, inliers_mode, final_mode, ews);
+}
+
+extern "C" int isr_pnp_ransac_batch_ex2(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B,
+                                        const double* Kcams, int H, const uint64_t* seeds, float reperr, double confidence,
+                                        int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
+                                        int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes,
+                                        isr_stream_t stream_, int loop, int stage0, int inliers_mode, int final_mode) {
+  const int frc = check_final("isr_pnp_ransac_batch", final_mode);
+  if (frc != ISR_OK) return frc;
+  if (final_mode == ISR_FINAL_REFIT)
+    return isr_pnp_ransac_batch_ex(p3d, p2d, M_dev, M_cap, B, Kcams, H, seeds, reperr, confidence, refine_iters, pose_dev,
+                                   inl_idx, n_inl_dev, status_dev, n_eval_dev, ws, ws_bytes, stream_, loop, stage0, inliers_mode);
+  ISR_REQUIRE(p3d && p2d && M_dev && Kcams && seeds && pose_dev && inl_idx && n_inl_dev && status_dev,
+              "isr_pnp_ransac_batch: null pointer");
+  ISR_REQUIRE(M_cap > 0 && H > 0 && H <= kMaxH && B > 0, "isr_pnp_ransac_batch: M_cap=%d H=%d (H <= %d) B=%d", M_cap, H, kMaxH, B);
+  ISR_REQUIRE(confidence > 0.0, "isr_pnp_ransac_batch: confidence=%g must be > 0 (>= 1: score every hypothesis)", confidence);
+  int s0;
+  const int lrc = check_loop("isr_pnp_ransac_batch", H, loop, stage0, inliers_mode, &s0);
+  if (lrc != ISR_OK) return lrc;
+  const size_t need = isr_pnp_ransac_batch_ex2_workspace_bytes(M_cap, H, B, final_mode);
+  if (!ws || ws_bytes < need) {
+    isr::set_error("isr_pnp_ransac_batch: workspace %zu < %zu", ws_bytes, need);
+    return ISR_ERR_WORKSPACE;
+  }
+  hipStream_t stream = isr::as_stream(stream_);
+  for (int b0 = 0; b0 < B; b0 += kChainMax) {        // one chain of launches per kChainMax images
+    const int nb = (B - b0 < kChainMax) ? B - b0 : kChainMax;
+    isr::Workspace w(ws, ws_bytes);               // chunks run one after the other on the stream: same scratch
+    RansacWs wsb;
+    void* ews;
+    carve_ex2(w, M_cap, H, nb, &wsb, &ews);
+    const int urc = upload_imgs(Kcams + 9 * (size_t)b0, seeds + b0, nb, wsb.imgs, stream, "isr_pnp_ransac_batch");
+    if (urc != ISR_OK) return urc;
+    const int rc = ransac_chain(p3d + (size_t)b0 * M_cap * 3, p2d + (size_t)b0 * M_cap * 2, M_dev + b0, M_cap, nb, wsb.imgs, H,
+                                confidence, reperr, refine_iters, pose_dev + (size_t)b0 * 12, inl_idx + (size_t)b0 * M_cap,
+                                n_inl_dev + b0, status_dev + b0, n_eval_dev ? n_eval_dev + b0 : nullptr, wsb, stream, loop, s0,
+                                inliers_mode, final_mode, ews);
+    if (rc != ISR_OK) return rc;
+  }
+  return ISR_OK;
 }
 
 // The sequential loop on host arrays, from the header the kernels use (no device): n_inl, ok (H) -> winner (-1: no

@@ -758,29 +758,35 @@ class PnPResult:
 
 _LOOPS = {"staged": _capi.RANSAC_STAGED, "sequential": _capi.RANSAC_SEQUENTIAL}
 _INLIERS = {"refit": _capi.INLIERS_REFIT, "ransac": _capi.INLIERS_RANSAC}
+_FINALS = {"refit": _capi.FINAL_REFIT, "epnp": _capi.FINAL_EPNP}
 
 
-def _loop_args(loop: str, inliers: str, stage0) -> tuple[int, int, int]:
-    """(loop, stage0, inliers_mode) of isr_pnp_ransac(_batch)_ex; stage0 None = the default first stage (32)."""
+def _loop_args(loop: str, inliers: str, stage0, final: str = "refit"):
+    """(loop, stage0, inliers_mode) of isr_pnp_ransac(_batch)_ex, and final_mode of the _ex2 entries when `final` is
+    given; stage0 None = the default first stage (32)."""
     if loop not in _LOOPS:
         raise ValueError(f"loop={loop!r}: 'staged' or 'sequential'")
     if inliers not in _INLIERS:
         raise ValueError(f"inliers={inliers!r}: 'refit' or 'ransac'")
-    return _LOOPS[loop], 0 if stage0 is None else int(stage0), _INLIERS[inliers]
+    if final not in _FINALS:
+        raise ValueError(f"final={final!r}: 'refit' or 'epnp'")
+    return _LOOPS[loop], 0 if stage0 is None else int(stage0), _INLIERS[inliers], _FINALS[final]
 
 
 def pnp_ransac(p3d, p2d, Kcam, H: int = 500, reperr: float = 2.0, seed: int = 0,
                refine_iters: int = 10, M_dev=None, confidence: float = 0.99, loop: str = "staged",
-               inliers: str = "refit", stage0: int | None = None) -> PnPResult:
+               inliers: str = "refit", stage0: int | None = None, final: str = "refit") -> PnPResult:
     """isr_pnp_ransac_ex, fully asynchronous: every output stays on the device.  confidence: cv2's
     solvePnPRansac parameter (default 0.99, what the reference's call uses); >= 1 scores every hypothesis (staged loop).
     loop="staged" (default): scoring stops at a stage boundary 32 (2^k - 1) once the confidence is reached, the best of
     every scored hypothesis wins.  loop="sequential": OpenCV's loop — hypothesis h runs while h < niters, niters updated
     from the best count so far; n_eval = how many ran; the result does not depend on stage0 (the first scoring stage, a
     multiple of 32 or >= H; None = 32).  inliers="refit" (default): the inliers of the returned, refitted pose;
-    "ransac": the winning hypothesis' consensus set, as cv2 reports it.  The pose is the refitted one either way."""
+    "ransac": the winning hypothesis' consensus set, as cv2 reports it.  final="refit" (default): the pose is the
+    Gauss-Newton refit with its local-optimisation round; "epnp": cv2's final solve, EPnP over the winner's consensus set
+    (refine_iters unused; a non-finite EPnP pose gives status 0)."""
     import ctypes
-    lp, s0, im = _loop_args(loop, inliers, stage0)
+    lp, s0, im, fm = _loop_args(loop, inliers, stage0, final)
     dev = require_cuda(p3d, p2d)
     p3d, p2d = _f32c(p3d), _f32c(p2d)
     cap = p3d.shape[0]
@@ -791,13 +797,19 @@ def pnp_ransac(p3d, p2d, Kcam, H: int = 500, reperr: float = 2.0, seed: int = 0,
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     n_eval = torch.zeros(1, dtype=torch.int32, device=dev)
     L = lib()
-    ws = workspace(dev, L.isr_pnp_ransac_workspace_bytes(cap, H), "ransac")
+    ws = workspace(dev, L.isr_pnp_ransac_ex2_workspace_bytes(cap, H, fm), "ransac")
     k = _kcam(Kcam)
     with torch.cuda.device(dev), _timed("pnp_ransac", 30.0 * H * cap):
-        rc = L.isr_pnp_ransac_ex(ptr(p3d), ptr(p2d), ptr(M_dev), cap, ctypes.cast(k, ctypes.c_void_p), int(H),
-                                 seed & 0xFFFFFFFFFFFFFFFF, float(reperr), float(confidence), int(refine_iters), ptr(pose),
-                                 ptr(inl), ptr(n_inl), ptr(status), ptr(n_eval), ptr(ws), ws.numel(), current_stream(dev),
-                                 lp, s0, im)
+        if fm == _capi.FINAL_REFIT:
+            rc = L.isr_pnp_ransac_ex(ptr(p3d), ptr(p2d), ptr(M_dev), cap, ctypes.cast(k, ctypes.c_void_p), int(H),
+                                     seed & 0xFFFFFFFFFFFFFFFF, float(reperr), float(confidence), int(refine_iters), ptr(pose),
+                                     ptr(inl), ptr(n_inl), ptr(status), ptr(n_eval), ptr(ws), ws.numel(), current_stream(dev),
+                                     lp, s0, im)
+        else:
+            rc = L.isr_pnp_ransac_ex2(ptr(p3d), ptr(p2d), ptr(M_dev), cap, ctypes.cast(k, ctypes.c_void_p), int(H),
+                                      seed & 0xFFFFFFFFFFFFFFFF, float(reperr), float(confidence), int(refine_iters), ptr(pose),
+                                      ptr(inl), ptr(n_inl), ptr(status), ptr(n_eval), ptr(ws), ws.numel(), current_stream(dev),
+                                      lp, s0, im, fm)
     check(rc, "isr_pnp_ransac")
     return PnPResult(pose, inl, n_inl, status, n_eval)
 
@@ -813,6 +825,75 @@ def ransac_seq_host(n_inl, ok, M: int, confidence: float = 0.99) -> tuple[int, i
     check(lib().isr_ransac_seq_host(c.ctypes.data_as(ctypes.c_void_p), o.ctypes.data_as(ctypes.c_void_p), c.shape[0], int(M),
                                     float(confidence), ctypes.byref(w), ctypes.byref(n)), "isr_ransac_seq_host")
     return int(w.value), int(n.value)
+
+
+def epnp_batch(p3d, p2d, Kcams, M_dev=None, mask=None):
+    """isr_epnp_batch: EPnP (csrc/epnp.hpp) on the device.  p3d (B, cap, 3), p2d (B, cap, 2) (or one image, (cap, 3) /
+    (cap, 2)); M_dev (B,) i32 (None: cap); mask (B, ceil(cap / 32)) u32 words as int32 (None: every point below M);
+    Kcams one 3x3 or (B, 3, 3) host array -> Rt (B, 3, 4) f64, rep_err (B, 3) f64, chosen (B,) i32 (1..3; 0 and a NaN pose:
+    fewer than 4 masked points), all on the device.  Image b's result equals epnp_host on image b's points, bit for bit."""
+    import ctypes
+    dev = require_cuda(p3d, p2d, M_dev, mask)
+    p3d, p2d = _f32c(p3d), _f32c(p2d)
+    if p3d.ndim == 2:
+        p3d, p2d = p3d[None], p2d[None]
+    B, cap = p3d.shape[0], p3d.shape[1]
+    if tuple(p2d.shape) != (B, cap, 2) or p3d.shape[2] != 3:
+        raise ValueError(f"epnp_batch: p3d {tuple(p3d.shape)} / p2d {tuple(p2d.shape)} must be (B,cap,3)/(B,cap,2)")
+    if M_dev is None:
+        M_dev = torch.full((B,), cap, dtype=torch.int32, device=dev)
+    if mask is not None:
+        mask = mask.contiguous()
+        if mask.dtype != torch.int32 or tuple(mask.shape) != (B, (cap + 31) // 32):
+            raise ValueError(f"epnp_batch: mask must be a ({B}, {(cap + 31) // 32}) int32 tensor")
+    K = np.asarray(Kcams, dtype=np.float64)
+    K = np.ascontiguousarray(np.broadcast_to(K.reshape(-1, 3, 3), (B, 3, 3)) if K.size == 9 else K.reshape(B, 3, 3))
+    Rt = torch.empty((B, 3, 4), dtype=torch.float64, device=dev)
+    err = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    chosen = torch.empty(B, dtype=torch.int32, device=dev)
+    L = lib()
+    ws = workspace(dev, L.isr_epnp_batch_workspace_bytes(cap, B), "epnp")
+    with torch.cuda.device(dev):
+        rc = L.isr_epnp_batch(ptr(p3d), ptr(p2d), ptr(M_dev.contiguous()), cap, B, ptr(mask), K.ctypes.data_as(ctypes.c_void_p),
+                              ptr(Rt), ptr(err), ptr(chosen), ptr(ws), ws.numel(), current_stream(dev))
+    check(rc, "isr_epnp_batch")
+    return Rt, err, chosen
+
+
+def epnp_host(p3d, p2d, Kcam, mask=None):
+    """isr_epnp_host: the same solver as host code, the device's reduction shape replayed.  p3d (M, 3), p2d (M, 2) (cast to
+    f32), mask (ceil(M / 32),) u32 words or None -> (Rt (3, 4) f64, rep_err (3,) f64, chosen 1..3)."""
+    a = np.ascontiguousarray(np.asarray(p3d), dtype=np.float32)
+    b = np.ascontiguousarray(np.asarray(p2d), dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != 3 or b.shape != (a.shape[0], 2):
+        raise ValueError(f"epnp_host: p3d {a.shape} / p2d {b.shape} must be (M,3)/(M,2)")
+    M = a.shape[0]
+    mk = None
+    if mask is not None:
+        mk = np.ascontiguousarray(np.asarray(mask).astype(np.uint32, copy=False))
+        if mk.shape != ((M + 31) // 32,):
+            raise ValueError(f"epnp_host: mask {mk.shape} must be ({(M + 31) // 32},)")
+    k = np.ascontiguousarray(np.asarray(Kcam, dtype=np.float64).reshape(9))
+    Rt = np.empty(12, np.float64)
+    err = np.empty(3, np.float64)
+    ch = ctypes.c_int32(0)
+    vp = lambda x: None if x is None else x.ctypes.data_as(ctypes.c_void_p)
+    check(lib().isr_epnp_host(vp(a), vp(b), vp(mk), M, vp(k), vp(Rt), vp(err), ctypes.byref(ch)), "isr_epnp_host")
+    return Rt.reshape(3, 4), err, int(ch.value)
+
+
+def epnp_jacobi_host(A):
+    """isr_epnp_jacobi_host: EPnP's Jacobi eigen-decomposition of a symmetric (n, n), n <= 12 -> (eigenvalues ascending,
+    eigenvectors as columns)."""
+    a = np.ascontiguousarray(np.asarray(A, dtype=np.float64))
+    n = a.shape[0]
+    if a.shape != (n, n):
+        raise ValueError(f"epnp_jacobi_host: A {a.shape} must be square")
+    w = np.empty(n, np.float64)
+    V = np.empty((n, n), np.float64)
+    check(lib().isr_epnp_jacobi_host(a.ctypes.data_as(ctypes.c_void_p), n, w.ctypes.data_as(ctypes.c_void_p),
+                                     V.ctypes.data_as(ctypes.c_void_p)), "isr_epnp_jacobi_host")
+    return w, V
 
 
 # ------------------------------------------------------------------ the per-group (batched) chain
@@ -871,13 +952,13 @@ class PnPBatchResult:
 
 def pnp_ransac_batch(p3d, p2d, Kcams, M_dev, H: int = 500, reperr: float = 2.0, seeds=None,
                      refine_iters: int = 10, confidence: float = 0.99, loop: str = "staged", inliers: str = "refit",
-                     stage0: int | None = None) -> PnPBatchResult:
+                     stage0: int | None = None, final: str = "refit") -> PnPBatchResult:
     """isr_pnp_ransac_batch_ex: p3d (B, cap, 3), p2d (B, cap, 2), M_dev (B,) i32; Kcams one 3x3 or (B, 3, 3)
-    host array; seeds B ints.  Every output stays on the device, nothing is pre-filled.  loop / inliers / stage0: as
-    pnp_ransac; image b's outputs equal pnp_ransac's on image b alone."""
+    host array; seeds B ints.  Every output stays on the device, nothing is pre-filled.  loop / inliers / stage0 / final:
+    as pnp_ransac; image b's outputs equal pnp_ransac's on image b alone."""
     import ctypes
     import numpy as np
-    lp, s0, im = _loop_args(loop, inliers, stage0)
+    lp, s0, im, fm = _loop_args(loop, inliers, stage0, final)
     dev = require_cuda(p3d, p2d, M_dev)
     p3d, p2d = _f32c(p3d), _f32c(p2d)
     B, cap = p3d.shape[0], p3d.shape[1]
@@ -893,13 +974,15 @@ def pnp_ransac_batch(p3d, p2d, Kcams, M_dev, H: int = 500, reperr: float = 2.0, 
     status = torch.empty(B, dtype=torch.int32, device=dev)
     n_eval = torch.empty(B, dtype=torch.int32, device=dev)
     L = lib()
-    ws = workspace(dev, L.isr_pnp_ransac_batch_workspace_bytes(cap, H, B), "ransac")
+    ws = workspace(dev, L.isr_pnp_ransac_batch_ex2_workspace_bytes(cap, H, B, fm), "ransac")
     with torch.cuda.device(dev), _timed("pnp_ransac", 30.0 * H * cap * B):
-        rc = L.isr_pnp_ransac_batch_ex(ptr(p3d), ptr(p2d), ptr(M_dev), cap, B, K.ctypes.data_as(ctypes.c_void_p), int(H),
-                                       sd.ctypes.data_as(ctypes.c_void_p), float(reperr), float(confidence),
-                                       int(refine_iters), ptr(pose),
-                                       ptr(inl), ptr(n_inl), ptr(status), ptr(n_eval), ptr(ws), ws.numel(), current_stream(dev),
-                                       lp, s0, im)
+        args = (ptr(p3d), ptr(p2d), ptr(M_dev), cap, B, K.ctypes.data_as(ctypes.c_void_p), int(H),
+                sd.ctypes.data_as(ctypes.c_void_p), float(reperr), float(confidence), int(refine_iters), ptr(pose),
+                ptr(inl), ptr(n_inl), ptr(status), ptr(n_eval), ptr(ws), ws.numel(), current_stream(dev), lp, s0, im)
+        if fm == _capi.FINAL_REFIT:
+            rc = L.isr_pnp_ransac_batch_ex(*args)
+        else:
+            rc = L.isr_pnp_ransac_batch_ex2(*args, fm)
     check(rc, "isr_pnp_ransac_batch")
     return PnPBatchResult(pose, inl, n_inl, status, n_eval)
 

@@ -118,7 +118,7 @@ def filter_top(in1, frac=0.8, min_n=500):
 
 # ---------------------------------------------------------------------------------- a5 pnp
 def pnp(h3d, h2d, cam, itr=100, reperr=2, flag=SOLVEPNP_P3P, gtR=None, gtT=None, spts=None, ret=None,
-        *, seed=0, refine_iters=10, confidence=0.99, loop="staged", inliers="refit"):
+        *, seed=0, refine_iters=10, confidence=0.99, loop="staged", inliers="refit", final="refit"):
     """inference.py:123-134 (= finalposes.py:20-30 = choosePose.py:23-33).
 
     cv2.solvePnPRansac(h3d, h2d, cam, None, iterationsCount=itr, reprojectionError=reperr,
@@ -129,9 +129,10 @@ def pnp(h3d, h2d, cam, itr=100, reperr=2, flag=SOLVEPNP_P3P, gtR=None, gtT=None,
     confidence (confidence=1 scores all).  `seed` keys the Philox sampler (OpenCV's RNG is internal).
     loop="sequential" runs OpenCV's sequential loop instead of the staged one (the winner is the first hypothesis with
     the best count among those cv2's loop would run); inliers="ransac" returns the winning hypothesis' consensus set
-    instead of the inliers of the refitted pose (ops.pnp_ransac)."""
+    instead of the inliers of the refitted pose; final="epnp" returns cv2's final solve, EPnP over the winner's consensus
+    set, instead of the Gauss-Newton refit (ops.pnp_ransac)."""
     del flag, gtR, gtT, spts, ret
-    ops._loop_args(loop, inliers, None)            # an unknown value raises ValueError before anything runs
+    ops._loop_args(loop, inliers, None, final)     # an unknown value raises ValueError before anything runs
     p3d, p2d = _dev(h3d, torch.float32), _dev(h2d, torch.float32)
     if p3d.ndim != 2 or p3d.shape[1] != 3 or p2d.shape != (p3d.shape[0], 2):
         raise ValueError(f"pnp: h3d {tuple(p3d.shape)} / h2d {tuple(p2d.shape)} must be (M,3)/(M,2)")
@@ -140,7 +141,7 @@ def pnp(h3d, h2d, cam, itr=100, reperr=2, flag=SOLVEPNP_P3P, gtR=None, gtT=None,
         return 1, 1, 1
     r = ops.pnp_ransac(p3d, p2d, np.asarray(cam, np.float64), H=int(itr), reperr=float(reperr),
                        seed=int(seed), refine_iters=int(refine_iters), confidence=float(confidence), loop=loop,
-                       inliers=inliers)
+                       inliers=inliers, final=final)
     if int(r.status.item()) != 1:
         print("pose could not be estimated with these correspondences")
         return 1, 1, 1

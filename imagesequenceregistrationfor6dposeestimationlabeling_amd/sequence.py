@@ -48,10 +48,10 @@ class ImageResult:
 def register_image(model: SequenceModel, queries: torch.Tensor, pix_xy: torch.Tensor, cam,
                    itr: int = 500, reperr: float = 2.0, seed: int = 0, refine_iters: int = 10,
                    timing: list | None = None, confidence: float = 0.99, loop: str = "staged",
-                   inliers: str = "refit") -> ImageResult:
+                   inliers: str = "refit", final: str = "refit") -> ImageResult:
     """inference.py:273-293 for one image, fully enqueued (no host synchronisation):
-    getCors -> top-80 % filter -> correspondence assembly -> pnp(itr, reperr, P3P).  loop / inliers: ops.pnp_ransac's."""
-    ops._loop_args(loop, inliers, None)
+    getCors -> top-80 % filter -> correspondence assembly -> pnp(itr, reperr, P3P).  loop / inliers / final: ops.pnp_ransac's."""
+    ops._loop_args(loop, inliers, None, final)
     if timing is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -62,22 +62,22 @@ def register_image(model: SequenceModel, queries: torch.Tensor, pix_xy: torch.Te
     keep, M, _ = ops.select_top(logp)
     p3d, p2d = ops.gather_corr(idx, keep, M, model.pts, pix_xy)
     r = ops.pnp_ransac(p3d, p2d, cam, H=itr, reperr=reperr, seed=seed, refine_iters=refine_iters, M_dev=M,
-                       confidence=confidence, loop=loop, inliers=inliers)
+                       confidence=confidence, loop=loop, inliers=inliers, final=final)
     return ImageResult(r.pose, r.status, r.n_inl, r.inl_idx, keep, M, idx, logp, r.n_eval)
 
 
 def register_crop(model: SequenceModel, feat: torch.Tensor, mask: torch.Tensor, cam, c0: int = 0,
                   n_feat: int | None = None, down_sample: int = 3, itr: int = 500, reperr: float = 2.0,
                   seed: int = 0, refine_iters: int = 10, confidence: float = 0.99, loop: str = "staged",
-                  inliers: str = "refit") -> tuple[ImageResult, torch.Tensor]:
+                  inliers: str = "refit", final: str = "refit") -> tuple[ImageResult, torch.Tensor]:
     """inference.py:248-293 from the network output on: `feat` = imfeatsfull (1, H, W, C) or (H, W, C)
     channels-last on the device, `mask` = cropMask (H, W[, 3]) uint8 on the device, `cam` the cropped
     and down-sampled camera matrix (formats.crop_camera).  Sub-sampling, masking, the compaction of the
     masked descriptors into K1's operand layout and the pixel list run on the device
     (isr_prep_queries); the number of masked pixels never visits the host.  Returns the ImageResult
     (arrays have the capacity ceil(H/ds) * ceil(W/ds); idx / logp rows past the count are padding) and
-    the device count n_dev.  loop / inliers: ops.pnp_ransac's."""
-    ops._loop_args(loop, inliers, None)
+    the device count n_dev.  loop / inliers / final: ops.pnp_ransac's."""
+    ops._loop_args(loop, inliers, None, final)
     D = model.keys.shape[1] if n_feat is None else n_feat
     if model.keys.dtype == torch.bfloat16:
         dtype = "bf16_log2" if model.log2_queries else "bf16"
@@ -89,13 +89,13 @@ def register_crop(model: SequenceModel, feat: torch.Tensor, mask: torch.Tensor, 
     keep, M, _ = ops.select_top(logp, n_dev=n_dev)
     p3d, p2d = ops.gather_corr(idx, keep, M, model.pts, pix)
     r = ops.pnp_ransac(p3d, p2d, cam, H=itr, reperr=reperr, seed=seed, refine_iters=refine_iters, M_dev=M,
-                       confidence=confidence, loop=loop, inliers=inliers)
+                       confidence=confidence, loop=loop, inliers=inliers, final=final)
     return ImageResult(r.pose, r.status, r.n_inl, r.inl_idx, keep, M, idx, logp, r.n_eval), n_dev
 
 
 def register_frame(model: SequenceModel, rgb, mask, camparams, encoder, n_feat: int = 12, down_sample: int = 3,
                    itr: int = 500, reperr: float = 2.0, seed: int = 0, refine_iters: int = 10, confidence: float = 0.99,
-                   useMask: bool = True, loop: str = "staged", inliers: str = "refit"):
+                   useMask: bool = True, loop: str = "staged", inliers: str = "refit", final: str = "refit"):
     """One iteration of the reference's per-image loop, inference.py:196-293, from the raw frame to the pose with
     everything but the descriptor network in this package: the crop front end on the device
     (registration.crop_inputs: mask box, crop affine + camera matrix, warp of image and mask, useMask blanking,
@@ -103,20 +103,21 @@ def register_frame(model: SequenceModel, rgb, mask, camparams, encoder, n_feat: 
     (1, C, 224, 224) with the descriptor in channels [0, n_feat) — and then register_crop (sub-sampling, masking,
     getCors, top-80 % filter, pnp).  Returns (ImageResult, n_dev, camMat (3, 3))."""
     from . import registration
-    ops._loop_args(loop, inliers, None)
+    ops._loop_args(loop, inliers, None, final)
     inputIM, cropMask, cam, _ = registration.crop_inputs(rgb, mask, camparams, useMask=useMask, down_sample=down_sample)
     with torch.no_grad():
         imfeatsfull = torch.movedim(encoder(inputIM), 1, 3)                       # inference.py:236-237
     res, n_dev = register_crop(model, imfeatsfull, cropMask[0], cam[0], n_feat=n_feat, down_sample=down_sample, itr=itr,
                                reperr=reperr, seed=seed, refine_iters=refine_iters, confidence=confidence, loop=loop,
-                               inliers=inliers)
+                               inliers=inliers, final=final)
     return res, n_dev, cam[0]
 
 
 def register_crops(model: SequenceModel, feats: torch.Tensor, masks: torch.Tensor, cams, c0: int = 0,
                    n_feat: int | None = None, down_sample: int = 3, itr: int = 500, reperr: float = 2.0,
                    seeds=None, refine_iters: int = 10, confidence: float = 0.99, group: int = 128,
-                   n_streams: int = 1, loop: str = "staged", inliers: str = "refit") -> tuple[list[ImageResult], torch.Tensor]:
+                   n_streams: int = 1, loop: str = "staged", inliers: str = "refit",
+                   final: str = "refit") -> tuple[list[ImageResult], torch.Tensor]:
     """The reference's per-image loop (inference.py:163, 248-293) from the network output on, BATCHED: `feats`
     (n, H, W, C) channels-last on the device, `masks` (n, H, W[, 3]) uint8 on the device, `cams` (n, 3, 3) the
     cropped, down-sampled camera matrices (formats.crop_camera).  Per `group` images: ONE isr_prep_queries_batch
@@ -126,8 +127,8 @@ def register_crops(model: SequenceModel, feats: torch.Tensor, masks: torch.Tenso
     ~45 dependent launches of a few microseconds of work each; a group shares them (0.6 launches per image at
     group = 64; 128-256 crops per group fill the chip best: K1's ~9 working workgroups per crop against 768 slots).  n_streams > 1 runs K1 of group g+1 on its own stream beside the chain of group g (slower at this
     shape, see below).  Every image's outputs are bit-identical to register_crop's.
-    loop / inliers: ops.pnp_ransac's.  Returns (results, n_dev (n,) i32 on the device)."""
-    ops._loop_args(loop, inliers, None)
+    loop / inliers / final: ops.pnp_ransac's.  Returns (results, n_dev (n,) i32 on the device)."""
+    ops._loop_args(loop, inliers, None, final)
     dev = model.keys.device
     n = feats.shape[0]
     D = model.keys.shape[1] if n_feat is None else n_feat
@@ -181,7 +182,7 @@ def register_crops(model: SequenceModel, feats: torch.Tensor, masks: torch.Tenso
             keep, M, _ = ops.select_top_batch(logp_g.view(B, S), n_dev=n_dev, digit_hist=hist_g)
             p3d, p2d = ops.gather_corr_batch(idx_g.view(B, S), keep, M, model.pts, pix)
             r = ops.pnp_ransac_batch(p3d, p2d, cams[g0:g1], M, H=itr, reperr=reperr, seeds=seeds[g0:g1],
-                                     refine_iters=refine_iters, confidence=confidence, loop=loop, inliers=inliers)
+                                     refine_iters=refine_iters, confidence=confidence, loop=loop, inliers=inliers, final=final)
         iv, lv = idx_g.view(B, S), logp_g.view(B, S)
         out += [ImageResult(r.pose[b], r.status[b:b + 1], r.n_inl[b:b + 1], r.inl_idx[b], keep[b], M[b:b + 1], iv[b], lv[b],
                             r.n_eval[b:b + 1]) for b in range(B)]
@@ -198,18 +199,18 @@ def register_crops(model: SequenceModel, feats: torch.Tensor, masks: torch.Tenso
 
 def register_frames(model: SequenceModel, rgbs, masks, camparams, encoder, n_feat: int = 12, down_sample: int = 3,
                     itr: int = 500, reperr: float = 2.0, seeds=None, refine_iters: int = 10, confidence: float = 0.99,
-                    useMask: bool = True, group: int = 128, loop: str = "staged", inliers: str = "refit"):
+                    useMask: bool = True, group: int = 128, loop: str = "staged", inliers: str = "refit", final: str = "refit"):
     """The reference's per-image loop, inference.py:163-293, for a block of frames: the crop front end of every
     frame on the device in two launches (registration.crop_inputs: mask boxes, crop affines + camera matrices,
     warps, useMask blanking, normalize), ONE call of `encoder` on the (n, 3, 224, 224) batch (the caller's network,
     `encoder_rgb` of inference.py:237), then register_crops.  Returns (results, n_dev (n,), camMat (n, 3, 3))."""
-    ops._loop_args(loop, inliers, None)
+    ops._loop_args(loop, inliers, None, final)
     inputIM, cropMask, cam, _ = registration.crop_inputs(rgbs, masks, camparams, useMask=useMask, down_sample=down_sample)
     with torch.no_grad():
         imfeatsfull = torch.movedim(encoder(inputIM), 1, 3)                       # inference.py:236-237
     res, n_dev = register_crops(model, imfeatsfull, cropMask, cam, n_feat=n_feat, down_sample=down_sample, itr=itr,
                                 reperr=reperr, seeds=seeds, refine_iters=refine_iters, confidence=confidence, group=group,
-                                loop=loop, inliers=inliers)
+                                loop=loop, inliers=inliers, final=final)
     return res, n_dev, cam
 
 
@@ -248,7 +249,8 @@ def _stream_pool(dev: torch.device, n: int) -> list:
 
 def register_images(model: SequenceModel, images, cam, itr: int = 500, reperr: float = 2.0,
                     seed0: int = 0, refine_iters: int = 10, n_streams: int = 3,
-                    confidence: float = 0.99, loop: str = "staged", inliers: str = "refit") -> list[ImageResult]:
+                    confidence: float = 0.99, loop: str = "staged", inliers: str = "refit",
+                    final: str = "refit") -> list[ImageResult]:
     """Register a block of images with the stages pipelined over HIP streams.
 
     Stream 0 runs nothing but K1 (getCors) back to back — the only kernel that fills the chip;
@@ -257,14 +259,14 @@ def register_images(model: SequenceModel, images, cam, itr: int = 500, reperr: f
     tail (a 640x480 image is 1.17 rounds of resident workgroups).  Events recorded around K1 on
     stream 0 therefore bracket the kernel alone.  `images` is a sequence of (queries, pix_xy);
     `cam` one 3x3 or one per image.  The caller's current stream waits for every stream before
-    this returns; there is no host synchronisation.  loop / inliers: ops.pnp_ransac's."""
-    ops._loop_args(loop, inliers, None)
+    this returns; there is no host synchronisation.  loop / inliers / final: ops.pnp_ransac's."""
+    ops._loop_args(loop, inliers, None, final)
     dev = model.keys.device
     cur = torch.cuda.current_stream(dev)
     cam_of = (lambda j: cam) if np.ndim(cam) == 2 else (lambda j: cam[j])
     if n_streams <= 1:
         return [register_image(model, q, pix, cam_of(j), itr, reperr, seed0 + j, refine_iters, confidence=confidence,
-                               loop=loop, inliers=inliers)
+                               loop=loop, inliers=inliers, final=final)
                 for j, (q, pix) in enumerate(images)]
     pool = _stream_pool(dev, n_streams)
     for s in pool:
@@ -284,7 +286,7 @@ def register_images(model: SequenceModel, images, cam, itr: int = 500, reperr: f
             keep, M, _ = ops.select_top(logp)
             p3d, p2d = ops.gather_corr(idx, keep, M, model.pts, pix)
             r = ops.pnp_ransac(p3d, p2d, cam_of(j), H=itr, reperr=reperr, seed=seed0 + j,
-                               refine_iters=refine_iters, M_dev=M, confidence=confidence, loop=loop, inliers=inliers)
+                               refine_iters=refine_iters, M_dev=M, confidence=confidence, loop=loop, inliers=inliers, final=final)
         out.append(ImageResult(r.pose, r.status, r.n_inl, r.inl_idx, keep, M, idx, logp, r.n_eval))
     for s in pool:
         cur.wait_stream(s)
@@ -294,19 +296,20 @@ def register_images(model: SequenceModel, images, cam, itr: int = 500, reperr: f
 
 def register_group(model: SequenceModel, idx_g: torch.Tensor, logp_g: torch.Tensor, pix_xy: torch.Tensor, cams,
                    itr: int, reperr: float, seeds, refine_iters: int, confidence: float = 0.99,
-                   digit_hist: torch.Tensor | None = None, loop: str = "staged", inliers: str = "refit") -> list[ImageResult]:
+                   digit_hist: torch.Tensor | None = None, loop: str = "staged", inliers: str = "refit",
+                   final: str = "refit") -> list[ImageResult]:
     """inference.py:282-293 for a GROUP of images whose K1 results are idx_g / logp_g (B, P): the
     top-80 % filter, the correspondence assembly and pnp() run as ONE chain of launches with the
     image on blockIdx.z (isr_select_top_batch, isr_gather_corr_batch, isr_pnp_ransac_batch) — the
     same kernels as the per-image calls, so every image's outputs are bit-identical to
     register_image's.  pix_xy (P, 2) shared or (B, P, 2); cams one 3x3 or (B, 3, 3).  digit_hist (B, 2048): the cut's first
-    histogram when K1 formed it (ops.corr_argmax(..., rows_per_image=P)).  loop / inliers: ops.pnp_ransac's."""
-    ops._loop_args(loop, inliers, None)
+    histogram when K1 formed it (ops.corr_argmax(..., rows_per_image=P)).  loop / inliers / final: ops.pnp_ransac's."""
+    ops._loop_args(loop, inliers, None, final)
     B = idx_g.shape[0]
     keep, M, _ = ops.select_top_batch(logp_g, digit_hist=digit_hist)
     p3d, p2d = ops.gather_corr_batch(idx_g, keep, M, model.pts, pix_xy)
     r = ops.pnp_ransac_batch(p3d, p2d, cams, M, H=itr, reperr=reperr, seeds=seeds, refine_iters=refine_iters,
-                             confidence=confidence, loop=loop, inliers=inliers)
+                             confidence=confidence, loop=loop, inliers=inliers, final=final)
     return [ImageResult(r.pose[b], r.status[b:b + 1], r.n_inl[b:b + 1], r.inl_idx[b], keep[b], M[b:b + 1], idx_g[b], logp_g[b],
                         r.n_eval[b:b + 1])
             for b in range(B)]
@@ -314,15 +317,16 @@ def register_group(model: SequenceModel, idx_g: torch.Tensor, logp_g: torch.Tens
 
 def register_block(model: SequenceModel, queries: torch.Tensor, pix_xy: torch.Tensor, cam, itr: int = 500,
                    reperr: float = 2.0, seed0: int = 0, refine_iters: int = 10, n_streams: int = 3,
-                   group: int = 8, confidence: float = 0.99, loop: str = "staged", inliers: str = "refit") -> list[ImageResult]:
+                   group: int = 8, confidence: float = 0.99, loop: str = "staged", inliers: str = "refit",
+                   final: str = "refit") -> list[ImageResult]:
     """register_images for a block held as ONE tensor: queries (n, P, D), pix_xy (n, P, 2) or (P, 2).
     K1 runs once per `group` images on (group * P) query rows — K1's result for a query does not
     depend on the launch it rides in, so this only changes the launch shape: a 640x480 image alone is
     1.17 rounds of resident workgroups, sixteen together are 18.8, and the launch tail shrinks from
     ~20 % to ~2 % of K1's time.  The group's filter / assembly / RANSAC chain (register_group: ~30
     launches for the whole group instead of ~35 per image) runs on a side stream beside the next K1
-    launch; groups alternate between the side streams.  loop / inliers: ops.pnp_ransac's."""
-    ops._loop_args(loop, inliers, None)
+    launch; groups alternate between the side streams.  loop / inliers / final: ops.pnp_ransac's."""
+    ops._loop_args(loop, inliers, None, final)
     dev = model.keys.device
     n, P = queries.shape[0], queries.shape[1]
     cur = torch.cuda.current_stream(dev)
@@ -365,7 +369,7 @@ def register_block(model: SequenceModel, queries: torch.Tensor, pix_xy: torch.Te
             out += register_group(model, idx_g.view(g1 - g0, P), logp_g.view(g1 - g0, P),
                                   pix_xy if pix_xy.ndim == 2 else pix_xy[g0:g1], cams[g0:g1], itr, reperr,
                                   [seed0 + j for j in range(g0, g1)], refine_iters, confidence,
-                                  digit_hist=res[2] if EPILOGUE_DIGITS else None, loop=loop, inliers=inliers)
+                                  digit_hist=res[2] if EPILOGUE_DIGITS else None, loop=loop, inliers=inliers, final=final)
     for s in pool:
         cur.wait_stream(s)
     _publish(out, cur)

@@ -359,6 +359,45 @@ int isr_pnp_ransac_batch_ex(const float* p3d, const float* p2d, const int32_t* M
                             double confidence, int refine_iters, double* pose_dev, int32_t* inl_idx,
                             int32_t* n_inl_dev, int32_t* status_dev, int32_t* n_eval_dev,
                             void* ws, size_t ws_bytes, isr_stream_t stream, int loop, int stage0, int inliers_mode);
+/* The final solve, chosen per call (isr_pnp_ransac_ex2 / isr_pnp_ransac_batch_ex2: the _ex arguments plus final_mode; the
+ * _ex entries are the ISR_FINAL_REFIT case).
+ * final_mode ISR_FINAL_REFIT: the Gauss-Newton refit and its local-optimisation round, as above.
+ *      ISR_FINAL_EPNP: cv2.solvePnPRansac's final solve for flags = SOLVEPNP_P3P, restated from memory: EPnP (csrc/epnp.hpp)
+ *      over the winning hypothesis' consensus set, no refinement after it; refine_iters is unused.  The reported inliers
+ *      follow inliers_mode: ISR_INLIERS_REFIT the mask under the returned (EPnP) pose, ISR_INLIERS_RANSAC the consensus set.
+ *      A non-finite EPnP pose sets status 0 (cv2 would return it): a deliberate difference.
+ * Workspace: isr_pnp_ransac_ex2_workspace_bytes / isr_pnp_ransac_batch_ex2_workspace_bytes (= the _ex sizes for
+ * ISR_FINAL_REFIT; 0 for an unknown final_mode). */
+#define ISR_FINAL_REFIT 0
+#define ISR_FINAL_EPNP 1
+size_t isr_pnp_ransac_ex2_workspace_bytes(int M_cap, int H, int final_mode);
+size_t isr_pnp_ransac_batch_ex2_workspace_bytes(int M_cap, int H, int B, int final_mode);
+int isr_pnp_ransac_ex2(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
+                       const double* Kcam, int H, uint64_t seed, float reperr, double confidence,
+                       int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
+                       int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes, isr_stream_t stream,
+                       int loop, int stage0, int inliers_mode, int final_mode);
+int isr_pnp_ransac_batch_ex2(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B,
+                             const double* Kcams, int H, const uint64_t* seeds, float reperr,
+                             double confidence, int refine_iters, double* pose_dev, int32_t* inl_idx,
+                             int32_t* n_inl_dev, int32_t* status_dev, int32_t* n_eval_dev,
+                             void* ws, size_t ws_bytes, isr_stream_t stream, int loop, int stage0, int inliers_mode,
+                             int final_mode);
+/* EPnP on its own (device): p3d (B, M_cap, 3), p2d (B, M_cap, 2), M_dev (B); mask (B, ceil(M_cap/32)) u32 words, bit m of
+ * word m/32 (nullable: all M points); Kcams HOST (B, 9) f64.  Rt_out (B, 12) [R|t], rep_err_out (B, 3) the three
+ * candidates' mean reprojection errors, chosen_out (B) the candidate returned (1..3; 0 and a NaN pose: fewer than 4 masked
+ * points).  An image's result depends only on its own points and mask (not on M_cap, B or its position in the batch) and
+ * equals isr_epnp_host's bit for bit. */
+size_t isr_epnp_batch_workspace_bytes(int M_cap, int B);
+int isr_epnp_batch(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B, const uint32_t* mask,
+                   const double* Kcams, double* Rt_out, double* rep_err_out, int32_t* chosen_out, void* ws,
+                   size_t ws_bytes, isr_stream_t stream);
+/* The same solver as host code (no device): HOST p3d (M, 3), p2d (M, 2) f32, mask (ceil(M/32) words, nullable), K (9)
+ * -> Rt (12), rep_err (3), chosen.  ISR_ERR_ARG for fewer than 4 masked points. */
+int isr_epnp_host(const float* p3d, const float* p2d, const uint32_t* mask, int M, const double* Kcam, double* Rt,
+                  double* rep_err, int32_t* chosen);
+/* Its Jacobi eigen-decomposition (host): symmetric A (n, n), n <= 12 -> eigenvalues ascending, eigenvectors as columns. */
+int isr_epnp_jacobi_host(const double* A, int n, double* evals, double* evecs);
 /* The sequential loop as host code, from the same header as the kernels (no device): n_inl, ok (H) HOST arrays of
  * counts and model flags -> winner (-1: no hypothesis with more than 3 inliers) and n_eval (hypotheses that ran). */
 int isr_ransac_seq_host(const int32_t* n_inl, const uint8_t* ok, int H, int M, double confidence, int32_t* winner,
