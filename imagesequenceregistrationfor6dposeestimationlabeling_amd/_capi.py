@@ -18,7 +18,7 @@ _PKG = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["ISR_HIP_LIB"]) if os.environ.get("ISR_HIP_LIB") else _PKG / "libisr_hip.so"
 
 ISR_OK = 0
-ABI_VERSION = 5
+ABI_VERSION = 6
 DTYPE_BF16 = 0
 DTYPE_F32 = 1
 DTYPE_BF16_LOG2 = 2
@@ -72,42 +72,24 @@ SIGNATURES = {
     "isr_ep_corr_matrices": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "isr_mask_bbox": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "isr_crop_normalize": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "isr_select_top_workspace_bytes": (_sz, [_i]),
-    "isr_select_top": (_i, [_vp, _i, _d, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "isr_select_top_dev": (_i, [_vp, _i, _vp, _d, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "isr_select_top_batch_workspace_bytes": (_sz, [_i, _i]),
     "isr_select_top_batch": (_i, [_vp, _i, _i, _vp, _d, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "isr_select_top_batch_digits": (_i, [_vp, _i, _i, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "isr_gather_corr_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
-    "isr_pnp_ransac_batch_workspace_bytes": (_sz, [_i, _i, _i]),
-    "isr_pnp_ransac_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _f, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "isr_pnp_ransac_batch_ex": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _f, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
-                                     _i, _i, _i]),
-    "isr_pnp_ransac_ex": (_i, [_vp, _vp, _vp, _i, _vp, _i, _u64, _f, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
-                               _i, _i, _i]),
+    "isr_pnp_ransac_batch_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "isr_pnp_ransac_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _f, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
+                                  _i, _i, _i, _i]),
     "isr_ransac_seq_host": (_i, [_vp, _vp, _i, _i, _d, _vp, _vp]),
-    "isr_pnp_ransac_ex2_workspace_bytes": (_sz, [_i, _i, _i]),
-    "isr_pnp_ransac_batch_ex2_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "isr_pnp_ransac_ex2": (_i, [_vp, _vp, _vp, _i, _vp, _i, _u64, _f, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
-                                _i, _i, _i, _i]),
-    "isr_pnp_ransac_batch_ex2": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _f, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
-                                      _i, _i, _i, _i]),
     "isr_epnp_batch_workspace_bytes": (_sz, [_i, _i]),
     "isr_epnp_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "isr_epnp_host": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "isr_epnp_jacobi_host": (_i, [_vp, _i, _vp, _vp]),
-    "isr_prep_queries_workspace_bytes": (_sz, [_i, _i, _i]),
-    "isr_prep_queries": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "isr_prep_queries_batch_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "isr_prep_queries_batch": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "isr_gather_corr": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "isr_p3p_all_roots": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
-    "isr_pnp_ransac_workspace_bytes": (_sz, [_i, _i]),
     "isr_p3p_hypotheses": (_i, [_vp, _vp, _vp, _i, _vp, _i, _u64, _vp, _vp, _vp, _vp]),
     "isr_ransac_score": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "isr_pnp_refine": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
-    "isr_pnp_ransac": (_i, [_vp, _vp, _vp, _i, _vp, _i, _u64, _f, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp,
-                            _sz, _vp]),
     "isr_nn_batched_workspace_bytes": (_sz, [_i, _i, _i]),
     "isr_nn_batched": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                             _sz, _vp]),

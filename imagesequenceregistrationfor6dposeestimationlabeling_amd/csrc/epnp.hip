@@ -1,5 +1,5 @@
 // epnp.hip — EPnP on gfx950: cv2.solvePnPRansac's final solve (solvePnP(SOLVEPNP_EPNP) over the winner's consensus set),
-// for pnp(final="epnp") (isr_pnp_ransac(_batch)_ex2) and on its own (isr_epnp_batch).  The algorithm, every choice in it and
+// for pnp(final="epnp") (isr_pnp_ransac_batch, final_mode ISR_FINAL_EPNP) and on its own (isr_epnp_batch).  The algorithm, every choice in it and
 // the reduction shape are stated in csrc/epnp.hpp; isr_epnp_host runs the same header as host code.
 //
 // Ten launches per chain, the image on blockIdx.z (passes) or blockIdx.x (dense steps), M and the status read on the device:

@@ -9,8 +9,8 @@
 // and hands K1 its operands in the layout it wants: rows padded to the MFMA depth (zero columns),
 // rounded ONCE to bf16 — after the log2(e) prescale when the log2 domain is asked for — or kept f32.
 // The count of masked pixels stays on the device (n_dev): K1 runs over the capacity rows (rows past
-// the count are zero queries), isr_select_top_dev / isr_gather_corr / isr_pnp_ransac take the
-// count from the device.
+// the count are zero queries), isr_select_top_batch / isr_gather_corr_batch / isr_pnp_ransac_batch
+// take the count from the device.
 // Ordered stream compaction: per-block counts -> one-block scan -> scatter (as select_top.hip).
 #include "isr_common.hpp"
 
@@ -54,7 +54,7 @@ __device__ __forceinline__ bool masked(const uint8_t* mask, int mask_pix_stride,
 }
 
 // Every kernel carries the image on blockIdx.z (strides in elements): a group of crops costs the same three
-// launches as one; the single-image entry point is the B = 1 case of the same kernels.
+// launches as one; one image is the B = 1 call.
 __global__ __launch_bounds__(kThreads) void prep_count_kernel(const uint8_t* __restrict__ mask, int mask_pix_stride,
                                                               size_t mask_img_stride, int W, int Ws, int step, int S,
                                                               int32_t* __restrict__ block_counts) {
@@ -134,11 +134,6 @@ static size_t prep_ws_bytes(int H, int W, int step, int B) {
   return isr::align_up(((S + kThreads - 1) / kThreads) * 4 * (size_t)B, 256) + 256;
 }
 
-extern "C" size_t isr_prep_queries_workspace_bytes(int H, int W, int step) {
-  if (H <= 0 || W <= 0 || step <= 0) return 0;
-  return prep_ws_bytes(H, W, step, 1);
-}
-
 extern "C" size_t isr_prep_queries_batch_workspace_bytes(int H, int W, int step, int B) {
   if (H <= 0 || W <= 0 || step <= 0 || B <= 0) return 0;
   return prep_ws_bytes(H, W, step, B);
@@ -147,15 +142,15 @@ extern "C" size_t isr_prep_queries_batch_workspace_bytes(int H, int W, int step,
 extern "C" int isr_prep_queries_batch(const float* feat, int B, int H, int W, int C, int c0, int D, const uint8_t* mask,
                                       int mask_pix_stride, int step, int dtype, int ldq, void* Q, float* pix_xy,
                                       int32_t* n_dev, void* ws, size_t ws_bytes, isr_stream_t stream_) {
-  ISR_REQUIRE(feat && mask && Q && pix_xy && n_dev, "isr_prep_queries: null pointer");
+  ISR_REQUIRE(feat && mask && Q && pix_xy && n_dev, "isr_prep_queries_batch: null pointer");
   ISR_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && C > 0 && D > 0 && c0 >= 0 && c0 + D <= C && step > 0 && mask_pix_stride > 0,
-              "isr_prep_queries: B=%d H=%d W=%d C=%d c0=%d D=%d step=%d mask stride=%d", B, H, W, C, c0, D, step,
+              "isr_prep_queries_batch: B=%d H=%d W=%d C=%d c0=%d D=%d step=%d mask stride=%d", B, H, W, C, c0, D, step,
               mask_pix_stride);
-  ISR_REQUIRE(ldq >= D, "isr_prep_queries: ldq=%d < D=%d", ldq, D);
+  ISR_REQUIRE(ldq >= D, "isr_prep_queries_batch: ldq=%d < D=%d", ldq, D);
   ISR_REQUIRE(dtype == ISR_DTYPE_BF16 || dtype == ISR_DTYPE_F32 || dtype == ISR_DTYPE_BF16_LOG2,
-              "isr_prep_queries: dtype %d", dtype);
+              "isr_prep_queries_batch: dtype %d", dtype);
   if (!ws || ws_bytes < prep_ws_bytes(H, W, step, B)) {
-    isr::set_error("isr_prep_queries: workspace %zu < %zu", ws_bytes, prep_ws_bytes(H, W, step, B));
+    isr::set_error("isr_prep_queries_batch: workspace %zu < %zu", ws_bytes, prep_ws_bytes(H, W, step, B));
     return ISR_ERR_WORKSPACE;
   }
   hipStream_t stream = isr::as_stream(stream_);
@@ -179,11 +174,4 @@ extern "C" int isr_prep_queries_batch(const float* feat, int B, int H, int W, in
 #undef ISR_PREP
   ISR_CHECK_LAUNCH("prep_queries kernels");
   return ISR_OK;
-}
-
-extern "C" int isr_prep_queries(const float* feat, int H, int W, int C, int c0, int D, const uint8_t* mask,
-                                int mask_pix_stride, int step, int dtype, int ldq, void* Q, float* pix_xy,
-                                int32_t* n_dev, void* ws, size_t ws_bytes, isr_stream_t stream_) {
-  return isr_prep_queries_batch(feat, 1, H, W, C, c0, D, mask, mask_pix_stride, step, dtype, ldq, Q, pix_xy, n_dev, ws,
-                                ws_bytes, stream_);
 }

@@ -50,8 +50,8 @@
 // host round trip.
 // Every kernel carries an IMAGE dimension (blockIdx.z) with the cameras and seeds of up to kMaxBatch
 // images in the kernel arguments: the per-image chain of inference.py:293 over a group of images is
-// one chain of launches for the whole group (isr_pnp_ransac_batch).  The single-image entry points
-// are the B = 1 case of the same kernels: bit-identical by construction.
+// one chain of launches for the whole group (isr_pnp_ransac_batch, the one exported pnp entry).  One image
+// is the B = 1 call: its outputs do not depend on the group it rides in.
 #include "isr_common.hpp"
 #include "p3p_device.hpp"
 #include "ransac_seq.hpp"
@@ -891,7 +891,8 @@ bool make_batch(const double* Kcams, const uint64_t* seeds, int B, ImgBatch* ib)
   return true;
 }
 
-size_t carve(isr::Workspace& w, int M_cap, int H, int B, RansacWs* o) {
+// the scratch of one chain of B images; final_mode ISR_FINAL_EPNP: EPnP's scratch behind it (*epnp_ws, else nullptr)
+size_t carve(isr::Workspace& w, int M_cap, int H, int B, int final_mode, RansacWs* o, void** epnp_ws) {
   o->Rt = w.take<double>((size_t)B * H * 12);
   o->Pm = w.take<float>((size_t)B * H * 12);
   o->ok = w.take<uint8_t>((size_t)B * H);
@@ -902,6 +903,7 @@ size_t carve(isr::Workspace& w, int M_cap, int H, int B, RansacWs* o) {
   o->state = w.take<int32_t>((size_t)B * 4);
   o->cblocks = w.take<int32_t>((size_t)B * (comp_blocks_of(M_cap) + 1));
   o->imgs = w.take<ImgDev>(B);
+  *epnp_ws = final_mode == ISR_FINAL_EPNP ? w.take<char>(isr::epnp_ws_bytes(B)) : nullptr;
   return w.off;
 }
 
@@ -922,18 +924,12 @@ int upload_imgs(const double* Kcams, const uint64_t* seeds, int B, ImgDev* dst, 
 
 }  // namespace
 
-extern "C" size_t isr_pnp_ransac_workspace_bytes(int M_cap, int H) {
-  if (M_cap <= 0 || H <= 0) return 0;
+extern "C" size_t isr_pnp_ransac_batch_workspace_bytes(int M_cap, int H, int B, int final_mode) {
+  if (M_cap <= 0 || H <= 0 || B <= 0 || (final_mode != ISR_FINAL_REFIT && final_mode != ISR_FINAL_EPNP)) return 0;
   isr::Workspace w(nullptr, 0);
   RansacWs o;
-  return carve(w, M_cap, H, 1, &o) + 512;
-}
-
-extern "C" size_t isr_pnp_ransac_batch_workspace_bytes(int M_cap, int H, int B) {
-  if (M_cap <= 0 || H <= 0 || B <= 0) return 0;
-  isr::Workspace w(nullptr, 0);
-  RansacWs o;
-  return carve(w, M_cap, H, B < kChainMax ? B : kChainMax, &o) + 512;
+  void* e;
+  return carve(w, M_cap, H, B < kChainMax ? B : kChainMax, final_mode, &o, &e) + 512;
 }
 
 extern "C" int isr_p3p_hypotheses(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
@@ -1004,8 +1000,9 @@ extern "C" int isr_ransac_score(const float* p3d, const float* p2d, const int32_
                                 void* ws, size_t ws_bytes, isr_stream_t stream_) {
   ISR_REQUIRE(p3d && p2d && M_dev && Kcam && Rt && ok && n_inl && best_dev, "isr_ransac_score: null pointer");
   ISR_REQUIRE(M_cap > 0 && H > 0 && H <= kMaxH, "isr_ransac_score: M_cap=%d H=%d (H <= %d)", M_cap, H, kMaxH);
-  if (!ws || ws_bytes < isr_pnp_ransac_workspace_bytes(M_cap, H)) {
-    isr::set_error("isr_ransac_score: workspace %zu < %zu", ws_bytes, isr_pnp_ransac_workspace_bytes(M_cap, H));
+  const size_t need = isr_pnp_ransac_batch_workspace_bytes(M_cap, H, 1, ISR_FINAL_REFIT);   // the carve of one image
+  if (!ws || ws_bytes < need) {
+    isr::set_error("isr_ransac_score: workspace %zu < %zu", ws_bytes, need);
     return ISR_ERR_WORKSPACE;
   }
   isr::Workspace w(ws, ws_bytes);
@@ -1122,180 +1119,31 @@ static int ransac_chain(const float* p3d, const float* p2d, const int32_t* M_dev
   return compact_impl(M_dev, M_cap, B, status_dev, inl_idx, n_inl_dev, b, stream);
 }
 
-// loop / stage0 / inliers_mode of the _ex entries (stage0 = 0: the default first stage, 32 hypotheses)
-static int check_loop(const char* who, int H, int loop, int stage0, int inliers_mode, int* stage0_out) {
-  ISR_REQUIRE(loop == ISR_RANSAC_STAGED || loop == ISR_RANSAC_SEQUENTIAL, "%s: loop=%d (ISR_RANSAC_STAGED %d | ISR_RANSAC_SEQUENTIAL %d)",
-              who, loop, ISR_RANSAC_STAGED, ISR_RANSAC_SEQUENTIAL);
-  ISR_REQUIRE(inliers_mode == ISR_INLIERS_REFIT || inliers_mode == ISR_INLIERS_RANSAC,
-              "%s: inliers_mode=%d (ISR_INLIERS_REFIT %d | ISR_INLIERS_RANSAC %d)", who, inliers_mode, ISR_INLIERS_REFIT,
-              ISR_INLIERS_RANSAC);
-  const int s0 = stage0 == 0 ? kStage0 : stage0;
-  if (loop == ISR_RANSAC_STAGED)
-    ISR_REQUIRE(s0 == kStage0, "%s: stage0=%d: the staged loop's first stage is %d hypotheses", who, stage0, kStage0);
-  else
-    ISR_REQUIRE(s0 > 0 && (s0 % kHC == 0 || s0 >= H), "%s: stage0=%d must be a positive multiple of %d, or >= H=%d", who, stage0,
-                kHC, H);
-  *stage0_out = s0;
-  return ISR_OK;
-}
-
-extern "C" int isr_pnp_ransac_ex(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
-                                 const double* Kcam, int H, uint64_t seed, float reperr, double confidence,
-                                 int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
-                                 int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes, isr_stream_t stream_,
-                                 int loop, int stage0, int inliers_mode) {
-  ISR_REQUIRE(p3d && p2d && M_dev && Kcam && pose_dev && inl_idx && n_inl_dev && status_dev,
-              "isr_pnp_ransac: null pointer");
-  ISR_REQUIRE(M_cap > 0 && H > 0 && H <= kMaxH, "isr_pnp_ransac: M_cap=%d H=%d (H <= %d)", M_cap, H, kMaxH);
-  int s0;
-  const int lrc = check_loop("isr_pnp_ransac", H, loop, stage0, inliers_mode, &s0);
-  if (lrc != ISR_OK) return lrc;
-  if (!ws || ws_bytes < isr_pnp_ransac_workspace_bytes(M_cap, H)) {
-    isr::set_error("isr_pnp_ransac: workspace %zu < %zu", ws_bytes, isr_pnp_ransac_workspace_bytes(M_cap, H));
-    return ISR_ERR_WORKSPACE;
-  }
-  isr::Workspace w(ws, ws_bytes);
-  RansacWs b;
-  carve(w, M_cap, H, 1, &b);
-  ISR_REQUIRE(confidence > 0.0, "isr_pnp_ransac: confidence=%g must be > 0 (>= 1: score every hypothesis)", confidence);
-  const int urc = upload_imgs(Kcam, &seed, 1, b.imgs, isr::as_stream(stream_), "isr_pnp_ransac");
-  if (urc != ISR_OK) return urc;
-  return ransac_chain(p3d, p2d, M_dev, M_cap, 1, b.imgs, H, confidence, reperr, refine_iters, pose_dev, inl_idx, n_inl_dev,
-                      status_dev, n_eval_dev, b, isr::as_stream(stream_), loop, s0, inliers_mode);
-}
-
-extern "C" int isr_pnp_ransac(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
-                              const double* Kcam, int H, uint64_t seed, float reperr, double confidence,
-                              int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
-                              int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes, isr_stream_t stream_) {
-  return isr_pnp_ransac_ex(p3d, p2d, M_dev, M_cap, Kcam, H, seed, reperr, confidence, refine_iters, pose_dev, inl_idx, n_inl_dev,
-                           status_dev, n_eval_dev, ws, ws_bytes, stream_, ISR_RANSAC_STAGED, kStage0, ISR_INLIERS_REFIT);
-}
-
-extern "C" int isr_pnp_ransac_batch_ex(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B,
-                                       const double* Kcams, int H, const uint64_t* seeds, float reperr, double confidence,
-                                       int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
-                                       int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes,
-                                       isr_stream_t stream_, int loop, int stage0, int inliers_mode) {
-  ISR_REQUIRE(p3d && p2d && M_dev && Kcams && seeds && pose_dev && inl_idx && n_inl_dev && status_dev,
-              "isr_pnp_ransac_batch: null pointer");
-  ISR_REQUIRE(M_cap > 0 && H > 0 && H <= kMaxH && B > 0, "isr_pnp_ransac_batch: M_cap=%d H=%d (H <= %d) B=%d", M_cap, H, kMaxH, B);
-  ISR_REQUIRE(confidence > 0.0, "isr_pnp_ransac_batch: confidence=%g must be > 0 (>= 1: score every hypothesis)", confidence);
-  int s0;
-  const int lrc = check_loop("isr_pnp_ransac_batch", H, loop, stage0, inliers_mode, &s0);
-  if (lrc != ISR_OK) return lrc;
-  if (!ws || ws_bytes < isr_pnp_ransac_batch_workspace_bytes(M_cap, H, B)) {
-    isr::set_error("isr_pnp_ransac_batch: workspace %zu < %zu", ws_bytes, isr_pnp_ransac_batch_workspace_bytes(M_cap, H, B));
-    return ISR_ERR_WORKSPACE;
-  }
-  hipStream_t stream = isr::as_stream(stream_);
-  for (int b0 = 0; b0 < B; b0 += kChainMax) {        // one chain of launches per kChainMax images
-    const int nb = (B - b0 < kChainMax) ? B - b0 : kChainMax;
-    isr::Workspace w(ws, ws_bytes);               // chunks run one after the other on the stream: same scratch
-    RansacWs wsb;
-    carve(w, M_cap, H, nb, &wsb);
-    const int urc = upload_imgs(Kcams + 9 * (size_t)b0, seeds + b0, nb, wsb.imgs, stream, "isr_pnp_ransac_batch");
-    if (urc != ISR_OK) return urc;
-    const int rc = ransac_chain(p3d + (size_t)b0 * M_cap * 3, p2d + (size_t)b0 * M_cap * 2, M_dev + b0, M_cap, nb, wsb.imgs, H,
-                                confidence, reperr, refine_iters, pose_dev + (size_t)b0 * 12, inl_idx + (size_t)b0 * M_cap,
-                                n_inl_dev + b0, status_dev + b0, n_eval_dev ? n_eval_dev + b0 : nullptr, wsb, stream, loop, s0,
-                                inliers_mode);
-    if (rc != ISR_OK) return rc;
-  }
-  return ISR_OK;
-}
-
 extern "C" int isr_pnp_ransac_batch(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B,
                                     const double* Kcams, int H, const uint64_t* seeds, float reperr, double confidence,
                                     int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
                                     int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes,
-                                    isr_stream_t stream_) {
-  return isr_pnp_ransac_batch_ex(p3d, p2d, M_dev, M_cap, B, Kcams, H, seeds, reperr, confidence, refine_iters, pose_dev, inl_idx,
-                                 n_inl_dev, status_dev, n_eval_dev, ws, ws_bytes, stream_, ISR_RANSAC_STAGED, kStage0,
-                                 ISR_INLIERS_REFIT);
-}
-
-static int check_final(const char* who, int final_mode) {
-  ISR_REQUIRE(final_mode == ISR_FINAL_REFIT || final_mode == ISR_FINAL_EPNP, "%s: final_mode=%d (ISR_FINAL_REFIT %d | ISR_FINAL_EPNP %d)",
-              who, final_mode, ISR_FINAL_REFIT, ISR_FINAL_EPNP);
-  return ISR_OK;
-}
-
-// the _ex carve plus EPnP's scratch behind it (ISR_FINAL_EPNP)
-static size_t carve_ex2(isr::Workspace& w, int M_cap, int H, int B, RansacWs* o, void** epnp_ws) {
-  carve(w, M_cap, H, B, o);
-  *epnp_ws = w.take<char>(isr::epnp_ws_bytes(B));
-  return w.off;
-}
-
-extern "C" size_t isr_pnp_ransac_ex2_workspace_bytes(int M_cap, int H, int final_mode) {
-  if (final_mode != ISR_FINAL_EPNP) return final_mode == ISR_FINAL_REFIT ? isr_pnp_ransac_workspace_bytes(M_cap, H) : 0;
-  if (M_cap <= 0 || H <= 0) return 0;
-  isr::Workspace w(nullptr, 0);
-  RansacWs o;
-  void* e;
-  return carve_ex2(w, M_cap, H, 1, &o, &e) + 512;
-}
-
-extern "C" size_t isr_pnp_ransac_batch_ex2_workspace_bytes(int M_cap, int H, int B, int final_mode) {
-  if (final_mode != ISR_FINAL_EPNP) return final_mode == ISR_FINAL_REFIT ? isr_pnp_ransac_batch_workspace_bytes(M_cap, H, B) : 0;
-  if (M_cap <= 0 || H <= 0 || B <= 0) return 0;
-  isr::Workspace w(nullptr, 0);
-  RansacWs o;
-  void* e;
-  return carve_ex2(w, M_cap, H, B < kChainMax ? B : kChainMax, &o, &e) + 512;
-}
-
-extern "C" int isr_pnp_ransac_ex2(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
-                                  const double* Kcam, int H, uint64_t seed, float reperr, double confidence,
-                                  int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
-                                  int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes, isr_stream_t stream_,
-                                  int loop, int stage0, int inliers_mode, int final_mode) {
-  const int frc = check_final("isr_pnp_ransac", final_mode);
-  if (frc != ISR_OK) return frc;
-  if (final_mode == ISR_FINAL_REFIT)
-    return isr_pnp_ransac_ex(p3d, p2d, M_dev, M_cap, Kcam, H, seed, reperr, confidence, refine_iters, pose_dev, inl_idx,
-                             n_inl_dev, status_dev, n_eval_dev, ws, ws_bytes, stream_, loop, stage0, inliers_mode);
-  ISR_REQUIRE(p3d && p2d && M_dev && Kcam && pose_dev && inl_idx && n_inl_dev && status_dev,
-              "isr_pnp_ransac: null pointer");
-  ISR_REQUIRE(M_cap > 0 && H > 0 && H <= kMaxH, "isr_pnp_ransac: M_cap=%d H=%d (H <= %d)", M_cap, H, kMaxH);
-  int s0;
-  const int lrc = check_loop("isr_pnp_ransac", H, loop, stage0, inliers_mode, &s0);
-  if (lrc != ISR_OK) return lrc;
-  ISR_REQUIRE(confidence > 0.0, "isr_pnp_ransac: confidence=%g must be > 0 (>= 1: score every hypothesis)", confidence);
-  const size_t need = isr_pnp_ransac_ex2_workspace_bytes(M_cap, H, final_mode);
-  if (!ws || ws_bytes < need) {
-    isr::set_error("isr_pnp_ransac: workspace %zu < %zu", ws_bytes, need);
-    return ISR_ERR_WORKSPACE;
-  }
-  isr::Workspace w(ws, ws_bytes);
-  RansacWs b;
-  void* ews;
-  carve_ex2(w, M_cap, H, 1, &b, &ews);
-  const int urc = upload_imgs(Kcam, &seed, 1, b.imgs, isr::as_stream(stream_), "isr_pnp_ransac");
-  if (urc != ISR_OK) return urc;
-  return ransac_chain(p3d, p2d, M_dev, M_cap, 1, b.imgs, H, confidence, reperr, refine_iters, pose_dev, inl_idx, n_inl_dev,
-                      status_dev, n_eval_dev, b, isr::as_stream(stream_), loop, s0, inliers_mode, final_mode, ews);
-}
-
-extern "C" int isr_pnp_ransac_batch_ex2(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B,
-                                        const double* Kcams, int H, const uint64_t* seeds, float reperr, double confidence,
-                                        int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
-                                        int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes,
-                                        isr_stream_t stream_, int loop, int stage0, int inliers_mode, int final_mode) {
-  const int frc = check_final("isr_pnp_ransac_batch", final_mode);
-  if (frc != ISR_OK) return frc;
-  if (final_mode == ISR_FINAL_REFIT)
-    return isr_pnp_ransac_batch_ex(p3d, p2d, M_dev, M_cap, B, Kcams, H, seeds, reperr, confidence, refine_iters, pose_dev,
-                                   inl_idx, n_inl_dev, status_dev, n_eval_dev, ws, ws_bytes, stream_, loop, stage0, inliers_mode);
+                                    isr_stream_t stream_, int loop, int stage0, int inliers_mode, int final_mode) {
+  ISR_REQUIRE(final_mode == ISR_FINAL_REFIT || final_mode == ISR_FINAL_EPNP,
+              "isr_pnp_ransac_batch: final_mode=%d (ISR_FINAL_REFIT %d | ISR_FINAL_EPNP %d)", final_mode, ISR_FINAL_REFIT,
+              ISR_FINAL_EPNP);
   ISR_REQUIRE(p3d && p2d && M_dev && Kcams && seeds && pose_dev && inl_idx && n_inl_dev && status_dev,
               "isr_pnp_ransac_batch: null pointer");
   ISR_REQUIRE(M_cap > 0 && H > 0 && H <= kMaxH && B > 0, "isr_pnp_ransac_batch: M_cap=%d H=%d (H <= %d) B=%d", M_cap, H, kMaxH, B);
   ISR_REQUIRE(confidence > 0.0, "isr_pnp_ransac_batch: confidence=%g must be > 0 (>= 1: score every hypothesis)", confidence);
-  int s0;
-  const int lrc = check_loop("isr_pnp_ransac_batch", H, loop, stage0, inliers_mode, &s0);
-  if (lrc != ISR_OK) return lrc;
-  const size_t need = isr_pnp_ransac_batch_ex2_workspace_bytes(M_cap, H, B, final_mode);
+  ISR_REQUIRE(loop == ISR_RANSAC_STAGED || loop == ISR_RANSAC_SEQUENTIAL,
+              "isr_pnp_ransac_batch: loop=%d (ISR_RANSAC_STAGED %d | ISR_RANSAC_SEQUENTIAL %d)", loop, ISR_RANSAC_STAGED,
+              ISR_RANSAC_SEQUENTIAL);
+  ISR_REQUIRE(inliers_mode == ISR_INLIERS_REFIT || inliers_mode == ISR_INLIERS_RANSAC,
+              "isr_pnp_ransac_batch: inliers_mode=%d (ISR_INLIERS_REFIT %d | ISR_INLIERS_RANSAC %d)", inliers_mode,
+              ISR_INLIERS_REFIT, ISR_INLIERS_RANSAC);
+  const int s0 = stage0 == 0 ? kStage0 : stage0;   // 0: the default first stage, 32 hypotheses
+  if (loop == ISR_RANSAC_STAGED)
+    ISR_REQUIRE(s0 == kStage0, "isr_pnp_ransac_batch: stage0=%d: the staged loop's first stage is %d hypotheses", stage0, kStage0);
+  else
+    ISR_REQUIRE(s0 > 0 && (s0 % kHC == 0 || s0 >= H), "isr_pnp_ransac_batch: stage0=%d must be a positive multiple of %d, or >= H=%d",
+                stage0, kHC, H);
+  const size_t need = isr_pnp_ransac_batch_workspace_bytes(M_cap, H, B, final_mode);
   if (!ws || ws_bytes < need) {
     isr::set_error("isr_pnp_ransac_batch: workspace %zu < %zu", ws_bytes, need);
     return ISR_ERR_WORKSPACE;
@@ -1306,7 +1154,7 @@ extern "C" int isr_pnp_ransac_batch_ex2(const float* p3d, const float* p2d, cons
     isr::Workspace w(ws, ws_bytes);               // chunks run one after the other on the stream: same scratch
     RansacWs wsb;
     void* ews;
-    carve_ex2(w, M_cap, H, nb, &wsb, &ews);
+    carve(w, M_cap, H, nb, final_mode, &wsb, &ews);
     const int urc = upload_imgs(Kcams + 9 * (size_t)b0, seeds + b0, nb, wsb.imgs, stream, "isr_pnp_ransac_batch");
     if (urc != ISR_OK) return urc;
     const int rc = ransac_chain(p3d + (size_t)b0 * M_cap * 3, p2d + (size_t)b0 * M_cap * 2, M_dev + b0, M_cap, nb, wsb.imgs, H,

@@ -12,8 +12,8 @@
 // more in the scatter; histograms use LDS atomics then one integer global atomic per bin per
 // block, so results are deterministic.  The kept count stays on the device (M_dev).
 // Every kernel carries an IMAGE dimension (blockIdx.z): the per-image loop of inference.py:163 over a
-// group of images becomes ten launches for the whole group (isr_select_top_batch); the single-image
-// entry points are the B = 1 case of the same kernels, so results are bit-identical by construction.
+// group of images becomes ten launches for the whole group (isr_select_top_batch); one image is the
+// B = 1 call, and an image's results do not depend on the group it rides in.
 #include "isr_common.hpp"
 
 namespace {
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(kThreads) void hist_kernel(const float* __restrict_
   constexpr int NB = 1 << BITS;
   __shared__ int32_t h[NB];
   x += blockIdx.z * ld; st += blockIdx.z; hist += (size_t)blockIdx.z * kHistInts;
-  const int P = st->n;   // the element count: the host's P, or the device-side count (isr_select_top_dev)
+  const int P = st->n;   // the element count: the host's P, or the device-side count (n_dev)
   if (blockIdx.x * kChunk >= P) return;   // block-uniform: nothing of this image falls in this block
   for (int i = threadIdx.x; i < NB; i += kThreads) h[i] = 0;
   __syncthreads();
@@ -273,11 +273,6 @@ static size_t select_ws_bytes(int P, int B) {
          isr::align_up(nblocks * 4 * B, 256) + 256;
 }
 
-extern "C" size_t isr_select_top_workspace_bytes(int P) {
-  if (P <= 0) return 0;
-  return select_ws_bytes(P, 1);
-}
-
 extern "C" size_t isr_select_top_batch_workspace_bytes(int P, int B) {
   if (P <= 0 || B <= 0) return 0;
   return select_ws_bytes(P, B);
@@ -289,7 +284,7 @@ static int select_top_impl(const float* logp, int P, int64_t ld, int B, const in
                            int32_t* keep, int32_t* M_dev, float* thr_dev, void* ws, size_t ws_bytes,
                            isr_stream_t stream_, const int32_t* digits = nullptr) {
   if (!ws || ws_bytes < select_ws_bytes(P, B)) {
-    isr::set_error("isr_select_top: workspace %zu < %zu", ws_bytes, select_ws_bytes(P, B));
+    isr::set_error("isr_select_top_batch: workspace %zu < %zu", ws_bytes, select_ws_bytes(P, B));
     return ISR_ERR_WORKSPACE;
   }
   hipStream_t stream = isr::as_stream(stream_);
@@ -316,32 +311,15 @@ static int select_top_impl(const float* logp, int P, int64_t ld, int B, const in
   return ISR_OK;
 }
 
-extern "C" int isr_select_top(const float* logp, int P, double frac, int min_n, int32_t* keep,
-                              int32_t* M_dev, float* thr_dev, void* ws, size_t ws_bytes,
-                              isr_stream_t stream_) {
-  ISR_REQUIRE(logp && keep && M_dev, "isr_select_top: null pointer");
-  ISR_REQUIRE(P > 0, "isr_select_top: P=%d (the reference indexes an empty sort and raises)", P);
-  const long rank = select_rank(P, frac, min_n);
-  ISR_REQUIRE(rank >= 0 && rank < P, "isr_select_top: rank %ld out of range for P=%d (IndexError in the reference)", rank, P);
-  return select_top_impl(logp, P, P, 1, nullptr, frac, min_n, keep, M_dev, thr_dev, ws, ws_bytes, stream_);
-}
-
-extern "C" int isr_select_top_dev(const float* logp, int P_cap, const int32_t* n_dev, double frac, int min_n,
-                                  int32_t* keep, int32_t* M_dev, float* thr_dev, void* ws, size_t ws_bytes,
-                                  isr_stream_t stream_) {
-  ISR_REQUIRE(logp && keep && M_dev && n_dev, "isr_select_top_dev: null pointer");
-  ISR_REQUIRE(P_cap > 0, "isr_select_top_dev: P_cap=%d", P_cap);
-  return select_top_impl(logp, P_cap, P_cap, 1, n_dev, frac, min_n, keep, M_dev, thr_dev, ws, ws_bytes, stream_);
-}
-
 extern "C" int isr_select_top_batch(const float* logp, int P, int B, const int32_t* n_dev, double frac, int min_n,
                                     int32_t* keep, int32_t* M_dev, float* thr_dev, void* ws, size_t ws_bytes,
                                     isr_stream_t stream_) {
   ISR_REQUIRE(logp && keep && M_dev, "isr_select_top_batch: null pointer");
-  ISR_REQUIRE(P > 0 && B > 0 && B <= 65535, "isr_select_top_batch: P=%d B=%d", P, B);
+  ISR_REQUIRE(P > 0 && B > 0 && B <= 65535, "isr_select_top_batch: P=%d B=%d (P = 0: the reference indexes an empty sort and raises)",
+              P, B);
   if (!n_dev) {
     const long rank = select_rank(P, frac, min_n);
-    ISR_REQUIRE(rank >= 0 && rank < P, "isr_select_top_batch: rank %ld out of range for P=%d", rank, P);
+    ISR_REQUIRE(rank >= 0 && rank < P, "isr_select_top_batch: rank %ld out of range for P=%d (IndexError in the reference)", rank, P);
   }
   return select_top_impl(logp, P, P, B, n_dev, frac, min_n, keep, M_dev, thr_dev, ws, ws_bytes, stream_);
 }
@@ -364,14 +342,6 @@ static int gather_impl(const int32_t* idx, const int32_t* keep, const int32_t* M
                                                                                  p3d, p2d, (int64_t)P, pix_stride);
   ISR_CHECK_LAUNCH("gather_kernel");
   return ISR_OK;
-}
-
-extern "C" int isr_gather_corr(const int32_t* idx, const int32_t* keep, const int32_t* M_dev, int P,
-                               const float* pts, int N, const float* pix_xy, float* p3d, float* p2d,
-                               isr_stream_t stream) {
-  ISR_REQUIRE(idx && keep && M_dev && pts && pix_xy && p3d && p2d, "isr_gather_corr: null pointer");
-  ISR_REQUIRE(P > 0 && N > 0, "isr_gather_corr: P=%d N=%d", P, N);
-  return gather_impl(idx, keep, M_dev, P, 1, pts, pix_xy, 0, p3d, p2d, stream);
 }
 
 extern "C" int isr_gather_corr_batch(const int32_t* idx, const int32_t* keep, const int32_t* M_dev, int P, int B,

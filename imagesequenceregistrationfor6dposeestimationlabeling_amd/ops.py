@@ -518,66 +518,26 @@ def corr_recheck_count_f32(D: int) -> int:
 
 
 def select_top(logp: torch.Tensor, frac: float = 0.8, min_n: int = 500, n_dev: torch.Tensor | None = None):
-    """isr_select_top: keep (P,) i32 (first M entries valid, ascending), M_dev (1,) i32, thr (1,) f32.
-    n_dev: (1,) i32 on the device — only the first n_dev values are the input (isr_select_top_dev)."""
-    dev = require_cuda(logp, n_dev)
-    logp = _f32c(logp).reshape(-1)
-    P = logp.numel()
-    keep = torch.empty(P, dtype=torch.int32, device=dev)
-    M_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-    thr = torch.empty(1, dtype=torch.float32, device=dev)
-    L = lib()
-    ws = workspace(dev, L.isr_select_top_workspace_bytes(P), "select")
-    with torch.cuda.device(dev), _timed("select_top", 4.0 * P):
-        if n_dev is None:
-            rc = L.isr_select_top(ptr(logp), P, float(frac), int(min_n), ptr(keep), ptr(M_dev), ptr(thr),
-                                  ptr(ws), ws.numel(), current_stream(dev))
-        else:
-            rc = L.isr_select_top_dev(ptr(logp), P, ptr(n_dev), float(frac), int(min_n), ptr(keep), ptr(M_dev),
-                                      ptr(thr), ptr(ws), ws.numel(), current_stream(dev))
-    check(rc, "isr_select_top")
-    return keep, M_dev, thr
+    """select_top_batch of one image: logp (P,) -> keep (P,) i32 (first M entries valid, ascending), M_dev (1,) i32,
+    thr (1,) f32.  n_dev: (1,) i32 on the device — only the first n_dev values are the input."""
+    keep, M_dev, thr = select_top_batch(logp.reshape(1, -1), frac, min_n, n_dev)
+    return keep[0], M_dev, thr
 
 
 def prep_queries(feat: torch.Tensor, mask: torch.Tensor, c0: int = 0, D: int | None = None, step: int = 3,
                  dtype: str = "bf16_log2"):
-    """isr_prep_queries: the network's channels-last feature map -> K1's query operand.
-    feat (H, W, C) or (1, H, W, C) f32; mask (H, W) or (H, W, k) uint8 (channel 0 is used, as
-    cropMask[:, :, 0]); dtype 'bf16' | 'bf16_log2' | 'f32'.
-    Returns Q (S, Dpad) [S = capacity = ceil(H/step) * ceil(W/step)], pix_xy (S, 2) f32, n_dev (1,) i32."""
-    dev = require_cuda(feat, mask)
-    feat = feat.reshape(feat.shape[-3:]) if feat.ndim == 4 else feat
-    feat = _f32c(feat)
-    H, W, C = feat.shape
-    D = C - c0 if D is None else D
-    if mask.dtype != torch.uint8:
-        mask = (mask != 0).to(torch.uint8)
-    mask = mask.contiguous()
-    stride = 1 if mask.ndim == 2 else mask.shape[2]
-    if tuple(mask.shape[:2]) != (H, W):
-        raise ValueError(f"mask {tuple(mask.shape)} does not match the feature map {(H, W)}")
-    code = {"bf16": _capi.DTYPE_BF16, "bf16_log2": _capi.DTYPE_BF16_LOG2, "f32": _capi.DTYPE_F32}[dtype]
-    Dpad = D if dtype == "f32" else (16 if D <= 16 else 32 if D <= 32 else 64 if D <= 64 else 128)
-    if D > 128 or (dtype == "f32" and D > 64):
-        raise ValueError(f"D={D} not supported by K1")
-    S = ((H + step - 1) // step) * ((W + step - 1) // step)
-    Q = torch.empty((S, Dpad), dtype=torch.float32 if dtype == "f32" else torch.bfloat16, device=dev)
-    pix = torch.zeros((S, 2), dtype=torch.float32, device=dev)
-    n_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-    L = lib()
-    ws = workspace(dev, L.isr_prep_queries_workspace_bytes(H, W, step), "prep")
-    with torch.cuda.device(dev):
-        rc = L.isr_prep_queries(ptr(feat), H, W, C, int(c0), int(D), ptr(mask), int(stride), int(step), code, Dpad,
-                                ptr(Q), ptr(pix), ptr(n_dev), ptr(ws), ws.numel(), current_stream(dev))
-    check(rc, "isr_prep_queries")
-    return Q, pix, n_dev
+    """prep_queries_batch of one crop: feat (H, W, C) or (1, H, W, C) f32; mask (H, W) or (H, W, k) uint8.
+    Returns Q (S, Dpad), pix_xy (S, 2) f32, n_dev (1,) i32."""
+    Q, pix, n_dev = prep_queries_batch(feat.reshape(1, *feat.shape[-3:]), mask[None], c0, D, step, dtype)
+    return Q[0], pix[0], n_dev
 
 
 def prep_queries_batch(feat: torch.Tensor, mask: torch.Tensor, c0: int = 0, D: int | None = None, step: int = 3,
                        dtype: str = "bf16_log2"):
-    """isr_prep_queries_batch: a GROUP of crops in three launches.  feat (B, H, W, C) f32 channels-last; mask
-    (B, H, W) or (B, H, W, k) uint8 (channel 0 is used).  Returns Q (B, S, Dpad) with zero rows past each image's
-    count, pix_xy (B, S, 2) f32, n_dev (B,) i32 — S = ceil(H/step) * ceil(W/step)."""
+    """isr_prep_queries_batch: the network's channels-last feature maps -> K1's query operand, a GROUP of crops in three
+    launches.  feat (B, H, W, C) f32; mask (B, H, W) or (B, H, W, k) uint8 (channel 0 is used, as cropMask[:, :, 0]);
+    dtype 'bf16' | 'bf16_log2' | 'f32'.  Returns Q (B, S, Dpad) with zero rows past each image's count, pix_xy (B, S, 2)
+    f32, n_dev (B,) i32 — S = capacity = ceil(H/step) * ceil(W/step)."""
     dev = require_cuda(feat, mask)
     if feat.ndim != 4:
         raise ValueError(f"prep_queries_batch: feat {tuple(feat.shape)} must be (B, H, W, C)")
@@ -650,17 +610,9 @@ def crop_normalize(rgb: torch.Tensor, mask: torch.Tensor, M, out_size: int = 224
 
 
 def gather_corr(idx, keep, M_dev, pts, pix_xy):
-    """isr_gather_corr: p3d (P,3) f32, p2d (P,2) f32 (first M rows valid)."""
-    dev = require_cuda(idx, keep, M_dev, pts, pix_xy)
-    pts, pix_xy = _f32c(pts), _f32c(pix_xy)
-    P = idx.numel()
-    p3d = torch.empty((P, 3), dtype=torch.float32, device=dev)
-    p2d = torch.empty((P, 2), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib().isr_gather_corr(ptr(idx), ptr(keep), ptr(M_dev), P, ptr(pts), pts.shape[0],
-                                   ptr(pix_xy), ptr(p3d), ptr(p2d), current_stream(dev))
-    check(rc, "isr_gather_corr")
-    return p3d, p2d
+    """gather_corr_batch of one image: idx, keep (P,), pix_xy (P, 2) -> p3d (P,3) f32, p2d (P,2) f32 (first M rows valid)."""
+    p3d, p2d = gather_corr_batch(idx.reshape(1, -1), keep.reshape(1, -1), M_dev, pts, pix_xy)
+    return p3d[0], p2d[0]
 
 
 def _kcam(K) -> "ctypes.Array":
@@ -720,7 +672,7 @@ def ransac_score(p3d, p2d, Kcam, Rt, ok, reperr: float, M_dev=None):
     best = torch.empty(1, dtype=torch.int32, device=dev)
     mask = torch.zeros((cap + 31) // 32, dtype=torch.int32, device=dev)
     L = lib()
-    ws = workspace(dev, L.isr_pnp_ransac_workspace_bytes(cap, H), "ransac")
+    ws = workspace(dev, L.isr_pnp_ransac_batch_workspace_bytes(cap, H, 1, _capi.FINAL_REFIT), "ransac")
     k = _kcam(Kcam)
     with torch.cuda.device(dev):
         rc = L.isr_ransac_score(ptr(p3d), ptr(p2d), ptr(M_dev), cap, ctypes.cast(k, ctypes.c_void_p),
@@ -756,14 +708,22 @@ class PnPResult:
     n_eval: torch.Tensor | None = None   # (1,) i32 device: hypotheses the staged loop scored (sequential: that ran)
 
 
+@dataclass
+class PnPBatchResult:
+    pose: torch.Tensor      # (B,3,4) f64 device
+    inl_idx: torch.Tensor   # (B,cap) i32 device, first n_inl[b] valid
+    n_inl: torch.Tensor     # (B,) i32 device
+    status: torch.Tensor    # (B,) i32 device
+    n_eval: torch.Tensor | None = None   # (B,) i32 device: hypotheses the staged loop scored (sequential: that ran) per image
+
+
 _LOOPS = {"staged": _capi.RANSAC_STAGED, "sequential": _capi.RANSAC_SEQUENTIAL}
 _INLIERS = {"refit": _capi.INLIERS_REFIT, "ransac": _capi.INLIERS_RANSAC}
 _FINALS = {"refit": _capi.FINAL_REFIT, "epnp": _capi.FINAL_EPNP}
 
 
 def _loop_args(loop: str, inliers: str, stage0, final: str = "refit"):
-    """(loop, stage0, inliers_mode) of isr_pnp_ransac(_batch)_ex, and final_mode of the _ex2 entries when `final` is
-    given; stage0 None = the default first stage (32)."""
+    """(loop, stage0, inliers_mode, final_mode) of isr_pnp_ransac_batch; stage0 None = the default first stage (32)."""
     if loop not in _LOOPS:
         raise ValueError(f"loop={loop!r}: 'staged' or 'sequential'")
     if inliers not in _INLIERS:
@@ -773,10 +733,31 @@ def _loop_args(loop: str, inliers: str, stage0, final: str = "refit"):
     return _LOOPS[loop], 0 if stage0 is None else int(stage0), _INLIERS[inliers], _FINALS[final]
 
 
+def _pnp_ransac(p3d, p2d, M_dev, Kcams, seeds, H, reperr, confidence, refine_iters, modes) -> PnPBatchResult:
+    """isr_pnp_ransac_batch, the one body of pnp_ransac and pnp_ransac_batch: p3d (B, cap, 3), p2d (B, cap, 2) f32
+    contiguous, M_dev (B,) i32 on the device; Kcams / seeds HOST pointers to (B, 9) f64 / (B,) u64; modes =
+    _loop_args(...).  Every output stays on the device, nothing is pre-filled."""
+    dev = p3d.device
+    B, cap = p3d.shape[0], p3d.shape[1]
+    pose = torch.empty((B, 3, 4), dtype=torch.float64, device=dev)
+    inl = torch.empty((B, cap), dtype=torch.int32, device=dev)
+    n_inl = torch.empty(B, dtype=torch.int32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    n_eval = torch.empty(B, dtype=torch.int32, device=dev)
+    L = lib()
+    ws = workspace(dev, L.isr_pnp_ransac_batch_workspace_bytes(cap, H, B, modes[3]), "ransac")
+    with torch.cuda.device(dev), _timed("pnp_ransac", 30.0 * H * cap * B):
+        rc = L.isr_pnp_ransac_batch(ptr(p3d), ptr(p2d), ptr(M_dev), cap, B, Kcams, int(H), seeds, float(reperr),
+                                    float(confidence), int(refine_iters), ptr(pose), ptr(inl), ptr(n_inl), ptr(status),
+                                    ptr(n_eval), ptr(ws), ws.numel(), current_stream(dev), *modes)
+    check(rc, "isr_pnp_ransac_batch")
+    return PnPBatchResult(pose, inl, n_inl, status, n_eval)
+
+
 def pnp_ransac(p3d, p2d, Kcam, H: int = 500, reperr: float = 2.0, seed: int = 0,
                refine_iters: int = 10, M_dev=None, confidence: float = 0.99, loop: str = "staged",
                inliers: str = "refit", stage0: int | None = None, final: str = "refit") -> PnPResult:
-    """isr_pnp_ransac_ex, fully asynchronous: every output stays on the device.  confidence: cv2's
+    """pnp_ransac_batch of one image, fully asynchronous: every output stays on the device.  confidence: cv2's
     solvePnPRansac parameter (default 0.99, what the reference's call uses); >= 1 scores every hypothesis (staged loop).
     loop="staged" (default): scoring stops at a stage boundary 32 (2^k - 1) once the confidence is reached, the best of
     every scored hypothesis wins.  loop="sequential": OpenCV's loop — hypothesis h runs while h < niters, niters updated
@@ -785,33 +766,12 @@ def pnp_ransac(p3d, p2d, Kcam, H: int = 500, reperr: float = 2.0, seed: int = 0,
     "ransac": the winning hypothesis' consensus set, as cv2 reports it.  final="refit" (default): the pose is the
     Gauss-Newton refit with its local-optimisation round; "epnp": cv2's final solve, EPnP over the winner's consensus set
     (refine_iters unused; a non-finite EPnP pose gives status 0)."""
-    import ctypes
-    lp, s0, im, fm = _loop_args(loop, inliers, stage0, final)
+    modes = _loop_args(loop, inliers, stage0, final)
     dev = require_cuda(p3d, p2d)
     p3d, p2d = _f32c(p3d), _f32c(p2d)
-    cap = p3d.shape[0]
-    M_dev = _m_dev(M_dev, dev, cap)
-    pose = torch.empty((3, 4), dtype=torch.float64, device=dev)
-    inl = torch.empty(cap, dtype=torch.int32, device=dev)
-    n_inl = torch.zeros(1, dtype=torch.int32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    n_eval = torch.zeros(1, dtype=torch.int32, device=dev)
-    L = lib()
-    ws = workspace(dev, L.isr_pnp_ransac_ex2_workspace_bytes(cap, H, fm), "ransac")
-    k = _kcam(Kcam)
-    with torch.cuda.device(dev), _timed("pnp_ransac", 30.0 * H * cap):
-        if fm == _capi.FINAL_REFIT:
-            rc = L.isr_pnp_ransac_ex(ptr(p3d), ptr(p2d), ptr(M_dev), cap, ctypes.cast(k, ctypes.c_void_p), int(H),
-                                     seed & 0xFFFFFFFFFFFFFFFF, float(reperr), float(confidence), int(refine_iters), ptr(pose),
-                                     ptr(inl), ptr(n_inl), ptr(status), ptr(n_eval), ptr(ws), ws.numel(), current_stream(dev),
-                                     lp, s0, im)
-        else:
-            rc = L.isr_pnp_ransac_ex2(ptr(p3d), ptr(p2d), ptr(M_dev), cap, ctypes.cast(k, ctypes.c_void_p), int(H),
-                                      seed & 0xFFFFFFFFFFFFFFFF, float(reperr), float(confidence), int(refine_iters), ptr(pose),
-                                      ptr(inl), ptr(n_inl), ptr(status), ptr(n_eval), ptr(ws), ws.numel(), current_stream(dev),
-                                      lp, s0, im, fm)
-    check(rc, "isr_pnp_ransac")
-    return PnPResult(pose, inl, n_inl, status, n_eval)
+    r = _pnp_ransac(p3d[None], p2d[None], _m_dev(M_dev, dev, p3d.shape[0]), ctypes.cast(_kcam(Kcam), ctypes.c_void_p),
+                    ctypes.byref(ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF)), H, reperr, confidence, refine_iters, modes)
+    return PnPResult(r.pose[0], r.inl_idx[0], r.n_inl, r.status, r.n_eval)
 
 
 def ransac_seq_host(n_inl, ok, M: int, confidence: float = 0.99) -> tuple[int, int]:
@@ -941,50 +901,24 @@ def gather_corr_batch(idx, keep, M_dev, pts, pix_xy):
     return p3d, p2d
 
 
-@dataclass
-class PnPBatchResult:
-    pose: torch.Tensor      # (B,3,4) f64 device
-    inl_idx: torch.Tensor   # (B,cap) i32 device, first n_inl[b] valid
-    n_inl: torch.Tensor     # (B,) i32 device
-    status: torch.Tensor    # (B,) i32 device
-    n_eval: torch.Tensor | None = None   # (B,) i32 device: hypotheses the staged loop scored (sequential: that ran) per image
-
-
 def pnp_ransac_batch(p3d, p2d, Kcams, M_dev, H: int = 500, reperr: float = 2.0, seeds=None,
                      refine_iters: int = 10, confidence: float = 0.99, loop: str = "staged", inliers: str = "refit",
                      stage0: int | None = None, final: str = "refit") -> PnPBatchResult:
-    """isr_pnp_ransac_batch_ex: p3d (B, cap, 3), p2d (B, cap, 2), M_dev (B,) i32; Kcams one 3x3 or (B, 3, 3)
+    """isr_pnp_ransac_batch: p3d (B, cap, 3), p2d (B, cap, 2), M_dev (B,) i32; Kcams one 3x3 or (B, 3, 3)
     host array; seeds B ints.  Every output stays on the device, nothing is pre-filled.  loop / inliers / stage0 / final:
     as pnp_ransac; image b's outputs equal pnp_ransac's on image b alone."""
-    import ctypes
-    import numpy as np
-    lp, s0, im, fm = _loop_args(loop, inliers, stage0, final)
+    modes = _loop_args(loop, inliers, stage0, final)
     dev = require_cuda(p3d, p2d, M_dev)
     p3d, p2d = _f32c(p3d), _f32c(p2d)
-    B, cap = p3d.shape[0], p3d.shape[1]
+    B = p3d.shape[0]
     K = np.asarray(Kcams, dtype=np.float64)
     K = np.ascontiguousarray(np.broadcast_to(K.reshape(-1, 3, 3), (B, 3, 3)) if K.size == 9 else K.reshape(B, 3, 3))
     sd = np.ascontiguousarray(np.asarray([0] * B if seeds is None else [int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds],
                                          dtype=np.uint64))
     if sd.shape != (B,):
         raise ValueError("pnp_ransac_batch: one seed per image")
-    pose = torch.empty((B, 3, 4), dtype=torch.float64, device=dev)
-    inl = torch.empty((B, cap), dtype=torch.int32, device=dev)
-    n_inl = torch.empty(B, dtype=torch.int32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    n_eval = torch.empty(B, dtype=torch.int32, device=dev)
-    L = lib()
-    ws = workspace(dev, L.isr_pnp_ransac_batch_ex2_workspace_bytes(cap, H, B, fm), "ransac")
-    with torch.cuda.device(dev), _timed("pnp_ransac", 30.0 * H * cap * B):
-        args = (ptr(p3d), ptr(p2d), ptr(M_dev), cap, B, K.ctypes.data_as(ctypes.c_void_p), int(H),
-                sd.ctypes.data_as(ctypes.c_void_p), float(reperr), float(confidence), int(refine_iters), ptr(pose),
-                ptr(inl), ptr(n_inl), ptr(status), ptr(n_eval), ptr(ws), ws.numel(), current_stream(dev), lp, s0, im)
-        if fm == _capi.FINAL_REFIT:
-            rc = L.isr_pnp_ransac_batch_ex(*args)
-        else:
-            rc = L.isr_pnp_ransac_batch_ex2(*args, fm)
-    check(rc, "isr_pnp_ransac_batch")
-    return PnPBatchResult(pose, inl, n_inl, status, n_eval)
+    return _pnp_ransac(p3d, p2d, M_dev, K.ctypes.data_as(ctypes.c_void_p), sd.ctypes.data_as(ctypes.c_void_p), H, reperr,
+                       confidence, refine_iters, modes)
 
 
 def add_metric(verts: torch.Tensor, Ta: torch.Tensor | None, Tb: torch.Tensor | None) -> torch.Tensor:

@@ -74,7 +74,7 @@ def register_crop(model: SequenceModel, feat: torch.Tensor, mask: torch.Tensor, 
     channels-last on the device, `mask` = cropMask (H, W[, 3]) uint8 on the device, `cam` the cropped
     and down-sampled camera matrix (formats.crop_camera).  Sub-sampling, masking, the compaction of the
     masked descriptors into K1's operand layout and the pixel list run on the device
-    (isr_prep_queries); the number of masked pixels never visits the host.  Returns the ImageResult
+    (isr_prep_queries_batch); the number of masked pixels never visits the host.  Returns the ImageResult
     (arrays have the capacity ceil(H/ds) * ceil(W/ds); idx / logp rows past the count are padding) and
     the device count n_dev.  loop / inliers / final: ops.pnp_ransac's."""
     ops._loop_args(loop, inliers, None, final)

@@ -30,8 +30,10 @@ extern "C" {
 /* v4 (round 4): isr_corr_argmax accepts idx = logp = NULL (lse-only call), f32 rows run as f16 planes by default
  * (ISR_TUNE_K1_F32_CHAIN values 0-4), new isr_corr_topk / isr_corr_topk_workspace_bytes.
  * v5 (round 5): ISR_DTYPE_BF16_LOG2_SCREENED, isr_corr_argmax_screen_redone; isr_corr_topk_workspace_bytes sized by the key
- * ranges a call uses; isr_corr_argmax_digits + isr_select_top_batch_digits (the cut's first histogram from K1's epilogue); isr_corr_argmax_phase (a call's closing kernels on another stream). */
-#define ISR_ABI_VERSION 5
+ * ranges a call uses; isr_corr_argmax_digits + isr_select_top_batch_digits (the cut's first histogram from K1's epilogue); isr_corr_argmax_phase (a call's closing kernels on another stream).
+ * v6: the single-image entries of the per-image chain are gone; one image is the B = 1 call of the _batch entry.
+ * isr_pnp_ransac_batch takes loop, stage0, inliers_mode and final_mode, and its sizer takes final_mode. */
+#define ISR_ABI_VERSION 6
 
 #define ISR_OK 0
 #define ISR_ERR_ARG (-1)         /* bad shape / null pointer / unsupported value */
@@ -191,24 +193,18 @@ int isr_corr_topk(const float* Q, const float* K, int P, int N, int D, int ldq, 
  * replaces  imfeats[:, ::3, ::3]; inputMask[::3, ::3]; maskIds = torch.where(inputMask);
  *           maskedfeats = imfeats[0][maskIds]; ep2d[:,0] = maskIds[1]; ep2d[:,1] = maskIds[0]
  *           inference.py:248-279
- * feat (H, W, C) f32 channels-last (the network output after movedim), descriptor = channels
- * [c0, c0 + D); mask (H, W) bytes, `mask_pix_stride` bytes between pixels (3 for cropMask[:, :, 0] of
+ * A GROUP of B crops as one chain of three launches (image = blockIdx.z; one crop is B = 1): the per-image
+ * loop of inference.py:163, 248-279 batched.
+ * feat (B, H, W, C) f32 channels-last (the network output after movedim), descriptor = channels
+ * [c0, c0 + D); mask (B, H, W) bytes, `mask_pix_stride` bytes between pixels (3 for cropMask[:, :, 0] of
  * an interleaved BGR mask), non-zero = inside; every `step`-th row and column.
- * Q: capacity S = ceil(H/step) * ceil(W/step) rows of ldq elements (bf16 or f32 by dtype; with
- *   ISR_DTYPE_BF16_LOG2 the values are multiplied by log2(e) before their one rounding), masked
+ * Q (B, S, ldq): capacity S = ceil(H/step) * ceil(W/step) rows per image of ldq elements (bf16 or f32 by
+ *   dtype; with ISR_DTYPE_BF16_LOG2 the values are multiplied by log2(e) before their one rounding), masked
  *   pixels compacted in row-major order, all other rows and the columns [D, ldq) zero.
- * pix_xy (S, 2) f32 = (column, row) in the subsampled grid; *n_dev = number of masked pixels. */
-size_t isr_prep_queries_workspace_bytes(int H, int W, int step);
-int isr_prep_queries(const float* feat, int H, int W, int C, int c0, int D, const uint8_t* mask,
-                     int mask_pix_stride, int step, int dtype, int ldq, void* Q, float* pix_xy,
-                     int32_t* n_dev, void* ws, size_t ws_bytes, isr_stream_t stream);
-
-/* The same for a GROUP of B crops as one chain of three launches (image = blockIdx.z): the per-image loop of
- * inference.py:163, 248-279 batched.  feat (B, H, W, C), mask (B, H, W) x mask_pix_stride bytes per pixel;
- * Q (B, S, ldq), pix_xy (B, S, 2), n_dev (B).  Rows past n_dev[b] of image b are zero queries: K1 runs ONCE
- * over the B * S capacity rows (a query's result does not depend on the launch it rides in), and
- * isr_select_top_batch / isr_gather_corr_batch / isr_pnp_ransac_batch take the ragged counts from n_dev.
- * Same kernels as isr_prep_queries: image b's rows are bit-identical to the single-image call. */
+ * pix_xy (B, S, 2) f32 = (column, row) in the subsampled grid; n_dev (B) = number of masked pixels.
+ * Rows past n_dev[b] of image b are zero queries: K1 runs ONCE over the B * S capacity rows (a query's result
+ * does not depend on the launch it rides in), and isr_select_top_batch / isr_gather_corr_batch /
+ * isr_pnp_ransac_batch take the ragged counts from n_dev.  Image b's rows do not depend on B. */
 size_t isr_prep_queries_batch_workspace_bytes(int H, int W, int step, int B);
 int isr_prep_queries_batch(const float* feat, int B, int H, int W, int C, int c0, int D, const uint8_t* mask,
                            int mask_pix_stride, int step, int dtype, int ldq, void* Q, float* pix_xy,
@@ -234,22 +230,15 @@ int isr_crop_normalize(const uint8_t* rgb, const uint8_t* mask, int B, int H, in
  * replaces  torch.sort(in1[:,0])[0][-perc+1] ; torch.where(in1[:,0] > thr)   inference.py:282-290
  * n = P; if n > min_n: perc = (int)(frac*n), rank = n - perc + 1 else rank = 1  (0-based rank into
  * the ascending order); thr = rank-th smallest logp; keep = ascending indices p with logp[p] > thr.
- * keep has capacity P; *M_dev (device int32) receives the number kept; *thr_dev (nullable) thr.
- */
-size_t isr_select_top_workspace_bytes(int P);
-int isr_select_top(const float* logp, int P, double frac, int min_n, int32_t* keep, int32_t* M_dev,
-                   float* thr_dev, void* ws, size_t ws_bytes, isr_stream_t stream);
-
-/* The same cut when the element count lives on the device (after isr_prep_queries): the first
- * min(P_cap, *n_dev) values of logp are the input; a count of 0, or a rank the reference would
- * raise IndexError for, keeps nothing (*M_dev = 0, thr = +inf).  Workspace as for P_cap. */
-int isr_select_top_dev(const float* logp, int P_cap, const int32_t* n_dev, double frac, int min_n,
-                       int32_t* keep, int32_t* M_dev, float* thr_dev, void* ws, size_t ws_bytes,
-                       isr_stream_t stream);
-
-/* The cut for a GROUP of B images in one chain of ten launches (the per-image loop of inference.py:163
- * over the group): logp (B, P), keep (B, P), M_dev (B), thr_dev (B, nullable); n_dev (B) device counts
- * or NULL (every image has P values).  Same kernels as the single-image calls: identical results. */
+ * A GROUP of B images in one chain of ten launches (the per-image loop of inference.py:163 over the
+ * group; one image is B = 1): logp (B, P), keep (B, P), M_dev (B) receives the number kept, thr_dev
+ * (B, nullable) thr.  P = 0 is refused (the reference indexes an empty sort and raises).
+ * n_dev NULL: every image has P values, and a rank outside [0, P) is refused (IndexError in the
+ *   reference).
+ * n_dev (B) device counts (after isr_prep_queries_batch): the first min(P, n_dev[b]) values of image b
+ *   are its input; a count of 0, or a rank the reference would raise IndexError for, keeps nothing
+ *   (M_dev[b] = 0, thr = +inf).
+ * Image b's results do not depend on B. */
 size_t isr_select_top_batch_workspace_bytes(int P, int B);
 int isr_select_top_batch(const float* logp, int P, int B, const int32_t* n_dev, double frac, int min_n,
                          int32_t* keep, int32_t* M_dev, float* thr_dev, void* ws, size_t ws_bytes,
@@ -262,14 +251,10 @@ int isr_select_top_batch_digits(const float* logp, int P, int B, const int32_t* 
                                 size_t ws_bytes, isr_stream_t stream);
 
 /* a3  correspondence assembly  (inference.py:274-280, 289-290)
- * p3d[m] = pts[idx[keep[m]]], p2d[m] = pix_xy[keep[m]]  for m < *M_dev.  pts (N,3), pix_xy (P,2)
- * = (col,row) of every query pixel, both f32.  p3d (P,3) / p2d (P,2) have capacity P rows. */
-int isr_gather_corr(const int32_t* idx, const int32_t* keep, const int32_t* M_dev, int P,
-                    const float* pts, int N, const float* pix_xy, float* p3d, float* p2d,
-                    isr_stream_t stream);
-
-/* a3 for a group of B images: idx, keep (B, P), M_dev (B), p3d (B, P, 3), p2d (B, P, 2); pix_xy is
- * (P, 2) shared by all images (shared_pix != 0, e.g. a full pixel grid) or (B, P, 2). */
+ * p3d[b, m] = pts[idx[b, keep[b, m]]], p2d[b, m] = pix_xy[keep[b, m]]  for m < M_dev[b].  pts (N,3) f32;
+ * pix_xy f32 = (col,row) of every query pixel, (P, 2) shared by all images (shared_pix != 0, e.g. a full
+ * pixel grid or one image) or (B, P, 2).  idx, keep (B, P), M_dev (B); p3d (B, P, 3) / p2d (B, P, 2) have
+ * capacity P rows per image. */
 int isr_gather_corr_batch(const int32_t* idx, const int32_t* keep, const int32_t* M_dev, int P, int B,
                           const float* pts, int N, const float* pix_xy, int shared_pix, float* p3d,
                           float* p2d, isr_stream_t stream);
@@ -286,25 +271,15 @@ int isr_gather_corr_batch(const int32_t* idx, const int32_t* keep, const int32_t
  * isr_ransac_score: n_inl[h] = #{m : z>0 and |proj_h(p3d[m]) - p2d[m]|^2 <= reperr^2} in f32,
  *   evaluated division-free; best_dev = argmax (lowest h on ties, ok hypotheses only),
  *   best_mask = inlier bitmask of the best hypothesis, ceil(M_cap/32) words (nullable);
- *   ws as for isr_pnp_ransac.
+ *   ws: isr_pnp_ransac_batch_workspace_bytes(M_cap, H, 1, ISR_FINAL_REFIT).
  * isr_pnp_refine: `iters` Gauss-Newton steps (f64) on the reprojection error over the masked
  *   correspondences, starting from Rt_io (12 f64), result written back.
- * isr_pnp_ransac: the three above + inlier index compaction, one enqueue.  `confidence` is
- *   cv2.solvePnPRansac's parameter of that name (its default, which the reference uses, is 0.99):
- *   hypotheses are scored in stages [0,32), [32,96), [96,224), ... and a stage runs only while
- *   (1 - (c/M)^4)^b > 1 - confidence for the best count c after the b hypotheses before it;
- *   confidence >= 1 scores all H (isr_ransac_score always does).
- *   pose_dev: 12 f64 [R|t];  inl_idx: capacity M_cap;  n_inl_dev: i32;  status_dev: i32
- *   (1 = pose found, 0 = failed: the Python mirror then returns the reference's (1,1,1));
- *   n_eval_dev (nullable): i32, how many of the H hypotheses the staged loop scored.
- *   The inliers reported are those of the RETURNED pose (after the refit and its local-optimisation round).
  * Kcam: host pointer, 9 doubles row-major.
  */
 /* Diagnostics: EVERY root of the device P3P solver for S independent 3-point problems (the production
  * kernels keep one per sample): X (S,3,3), uv (S,3,2) device f64 -> poses (S,4,12) [R|t], n_roots (S). */
 int isr_p3p_all_roots(const double* X, const double* uv, const double* Kcam, int S, double* poses,
                       int32_t* n_roots, isr_stream_t stream);
-size_t isr_pnp_ransac_workspace_bytes(int M_cap, int H);
 int isr_p3p_hypotheses(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
                        const double* Kcam, int H, uint64_t seed, double* Rt, uint8_t* ok,
                        int32_t* sample, isr_stream_t stream);
@@ -315,74 +290,49 @@ int isr_ransac_score(const float* p3d, const float* p2d, const int32_t* M_dev, i
 int isr_pnp_refine(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
                    const uint32_t* mask, const double* Kcam, int iters, double* Rt_io, void* ws,
                    size_t ws_bytes, isr_stream_t stream);
-int isr_pnp_ransac(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
-                   const double* Kcam, int H, uint64_t seed, float reperr, double confidence,
-                   int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
-                   int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes, isr_stream_t stream);
 
-/* isr_pnp_ransac for a GROUP of B images as one chain of launches (image = blockIdx.z of every kernel):
- * p3d (B, M_cap, 3), p2d (B, M_cap, 2), M_dev (B); Kcams HOST (B, 9) f64, seeds HOST (B) u64;
- * pose_dev (B, 12), inl_idx (B, M_cap), n_inl_dev (B), status_dev (B).  Same kernels as the
- * single-image call: image b's outputs are bit-identical to isr_pnp_ransac on image b alone. */
-size_t isr_pnp_ransac_batch_workspace_bytes(int M_cap, int H, int B);
-int isr_pnp_ransac_batch(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B,
-                         const double* Kcams, int H, const uint64_t* seeds, float reperr,
-                         double confidence, int refine_iters, double* pose_dev, int32_t* inl_idx,
-                         int32_t* n_inl_dev, int32_t* status_dev, int32_t* n_eval_dev /* (B), nullable */,
-                         void* ws, size_t ws_bytes, isr_stream_t stream);
-
-/* The RANSAC loop and the reported inliers, chosen per call (isr_pnp_ransac_ex / isr_pnp_ransac_batch_ex: the arguments
- * of isr_pnp_ransac / isr_pnp_ransac_batch plus loop, stage0, inliers_mode; same workspace).  The entries above are the
- * (ISR_RANSAC_STAGED, 32, ISR_INLIERS_REFIT) case.
- * loop ISR_RANSAC_STAGED: the staged loop described above.
+/* isr_pnp_ransac_batch: hypotheses, scoring, the final solve and inlier index compaction for a GROUP of B
+ * images, one enqueue, one chain of launches (image = blockIdx.z of every kernel; one image is B = 1).
+ * p3d (B, M_cap, 3), p2d (B, M_cap, 2), M_dev (B); Kcams HOST (B, 9) f64 row-major, seeds HOST (B) u64.
+ * pose_dev (B, 12) f64 [R|t];  inl_idx (B, M_cap);  n_inl_dev (B);  status_dev (B) (1 = pose found, 0 = failed:
+ * the Python mirror then returns the reference's (1,1,1));  n_eval_dev (B, nullable): how many of the H
+ * hypotheses were scored (staged loop) or ran (sequential loop).  Image b's outputs do not depend on B or
+ * on its position in the group.
+ * confidence: cv2.solvePnPRansac's parameter of that name (its default, which the reference uses, is 0.99).
+ * loop ISR_RANSAC_STAGED: hypotheses are scored in stages [0,32), [32,96), [96,224), ... and a stage runs only
+ *      while (1 - (c/M)^4)^b > 1 - confidence for the best count c after the b hypotheses before it;
+ *      confidence >= 1 scores all H (isr_ransac_score always does).  The best of every scored hypothesis wins.
  *      ISR_RANSAC_SEQUENTIAL: OpenCV's sequential loop (RANSACPointSetRegistrator::run + RANSACUpdateNumIters, restated
  *      from memory): hypothesis h runs while h < niters, niters = min(H, cvRound(log(1 - confidence) / log(1 - w^4))) for
  *      the best count so far (w = its inlier ratio; counts <= 3 leave niters at H); the winner is the first hypothesis with
- *      the maximal count among those that ran; n_eval = the number that ran.  The rounding test is exact (multiplications
- *      and one sqrt: csrc/ransac_seq.hpp), so the result depends on (data, seed, H, confidence) only — not on stage0.
+ *      the maximal count among those that ran.  The rounding test is exact (multiplications and one sqrt:
+ *      csrc/ransac_seq.hpp), so the result depends on (data, seed, H, confidence) only — not on stage0.
  * stage0: hypotheses of the first scoring stage (later stages double); 0 = 32.  The staged loop takes 0 or 32 only; the
  *      sequential loop a positive multiple of 32, or >= H (a single stage).
- * inliers_mode ISR_INLIERS_REFIT: the inliers of the returned (refitted) pose, as above.
- *      ISR_INLIERS_RANSAC: the consensus set of the winning hypothesis (its mask before any refit), as cv2 returns it.
- *      The pose is the refitted one either way. */
+ * final_mode ISR_FINAL_REFIT: the Gauss-Newton refit of the winner over its inliers, then one round of local
+ *      optimisation (the inliers of the refitted pose, refit on them); refine_iters steps per refit.
+ *      ISR_FINAL_EPNP: cv2.solvePnPRansac's final solve for flags = SOLVEPNP_P3P, restated from memory: EPnP (csrc/epnp.hpp)
+ *      over the winning hypothesis' consensus set, no refinement after it; refine_iters is unused.  A non-finite EPnP
+ *      pose sets status 0 (cv2 would return it): a deliberate difference.
+ * inliers_mode ISR_INLIERS_REFIT: the inliers of the returned pose (the mask under the final refit or the EPnP pose).
+ *      ISR_INLIERS_RANSAC: the consensus set of the winning hypothesis (its mask before the final solve), as cv2 returns it.
+ * The arguments are checked in this order, before anything is enqueued: final_mode, pointers, sizes, confidence, loop,
+ * inliers_mode, stage0, workspace.
+ * Workspace: isr_pnp_ransac_batch_workspace_bytes (0 for an unknown final_mode; ISR_FINAL_EPNP needs more than
+ * ISR_FINAL_REFIT). */
 #define ISR_RANSAC_STAGED 0
 #define ISR_RANSAC_SEQUENTIAL 1
 #define ISR_INLIERS_REFIT 0
 #define ISR_INLIERS_RANSAC 1
-int isr_pnp_ransac_ex(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
-                      const double* Kcam, int H, uint64_t seed, float reperr, double confidence,
-                      int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
-                      int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes, isr_stream_t stream,
-                      int loop, int stage0, int inliers_mode);
-int isr_pnp_ransac_batch_ex(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B,
-                            const double* Kcams, int H, const uint64_t* seeds, float reperr,
-                            double confidence, int refine_iters, double* pose_dev, int32_t* inl_idx,
-                            int32_t* n_inl_dev, int32_t* status_dev, int32_t* n_eval_dev,
-                            void* ws, size_t ws_bytes, isr_stream_t stream, int loop, int stage0, int inliers_mode);
-/* The final solve, chosen per call (isr_pnp_ransac_ex2 / isr_pnp_ransac_batch_ex2: the _ex arguments plus final_mode; the
- * _ex entries are the ISR_FINAL_REFIT case).
- * final_mode ISR_FINAL_REFIT: the Gauss-Newton refit and its local-optimisation round, as above.
- *      ISR_FINAL_EPNP: cv2.solvePnPRansac's final solve for flags = SOLVEPNP_P3P, restated from memory: EPnP (csrc/epnp.hpp)
- *      over the winning hypothesis' consensus set, no refinement after it; refine_iters is unused.  The reported inliers
- *      follow inliers_mode: ISR_INLIERS_REFIT the mask under the returned (EPnP) pose, ISR_INLIERS_RANSAC the consensus set.
- *      A non-finite EPnP pose sets status 0 (cv2 would return it): a deliberate difference.
- * Workspace: isr_pnp_ransac_ex2_workspace_bytes / isr_pnp_ransac_batch_ex2_workspace_bytes (= the _ex sizes for
- * ISR_FINAL_REFIT; 0 for an unknown final_mode). */
 #define ISR_FINAL_REFIT 0
 #define ISR_FINAL_EPNP 1
-size_t isr_pnp_ransac_ex2_workspace_bytes(int M_cap, int H, int final_mode);
-size_t isr_pnp_ransac_batch_ex2_workspace_bytes(int M_cap, int H, int B, int final_mode);
-int isr_pnp_ransac_ex2(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
-                       const double* Kcam, int H, uint64_t seed, float reperr, double confidence,
-                       int refine_iters, double* pose_dev, int32_t* inl_idx, int32_t* n_inl_dev,
-                       int32_t* status_dev, int32_t* n_eval_dev, void* ws, size_t ws_bytes, isr_stream_t stream,
-                       int loop, int stage0, int inliers_mode, int final_mode);
-int isr_pnp_ransac_batch_ex2(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B,
-                             const double* Kcams, int H, const uint64_t* seeds, float reperr,
-                             double confidence, int refine_iters, double* pose_dev, int32_t* inl_idx,
-                             int32_t* n_inl_dev, int32_t* status_dev, int32_t* n_eval_dev,
-                             void* ws, size_t ws_bytes, isr_stream_t stream, int loop, int stage0, int inliers_mode,
-                             int final_mode);
+size_t isr_pnp_ransac_batch_workspace_bytes(int M_cap, int H, int B, int final_mode);
+int isr_pnp_ransac_batch(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap, int B,
+                         const double* Kcams, int H, const uint64_t* seeds, float reperr,
+                         double confidence, int refine_iters, double* pose_dev, int32_t* inl_idx,
+                         int32_t* n_inl_dev, int32_t* status_dev, int32_t* n_eval_dev,
+                         void* ws, size_t ws_bytes, isr_stream_t stream, int loop, int stage0, int inliers_mode,
+                         int final_mode);
 /* EPnP on its own (device): p3d (B, M_cap, 3), p2d (B, M_cap, 2), M_dev (B); mask (B, ceil(M_cap/32)) u32 words, bit m of
  * word m/32 (nullable: all M points); Kcams HOST (B, 9) f64.  Rt_out (B, 12) [R|t], rep_err_out (B, 3) the three
  * candidates' mean reprojection errors, chosen_out (B) the candidate returned (1..3; 0 and a NaN pose: fewer than 4 masked

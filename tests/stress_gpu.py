@@ -259,7 +259,7 @@ def crop_case(c):
 
 
 def prep_case(c):
-    """inference.py:248-279 literally (torch CPU) against isr_prep_queries."""
+    """inference.py:248-279 literally (torch CPU) against ops.prep_queries."""
     H, W = int(rng.integers(1, 260)), int(rng.integers(1, 260))
     C = int(rng.integers(12, 24)); ds = int(rng.choice([1, 2, 3, 4])); ch = int(rng.choice([0, 1, 3]))
     dtype = str(rng.choice(["f32", "bf16", "bf16_log2"]))

@@ -118,19 +118,17 @@ def test_argument_errors(hip_lib):
     assert b"null" in L.isr_last_error()
     assert L.isr_epnp_batch(None, None, None, 16, 1, None, None, None, None, None, None, 0, None) == -1
     assert L.isr_epnp_jacobi_host(None, 3, None, None) == -1
-    # final_mode of the _ex2 entries: checked first, no device touched
-    rc = L.isr_pnp_ransac_ex2(None, None, None, 100, None, 100, 0, 2.0, 0.99, 10, None, None, None, None, None, None, 0,
-                              None, 0, 0, 0, 7)
-    assert rc == -1 and b"final_mode" in L.isr_last_error()
-    rc = L.isr_pnp_ransac_batch_ex2(None, None, None, 100, 2, None, 100, None, 2.0, 0.99, 10, None, None, None, None, None,
-                                    None, 0, None, 0, 0, 0, -1)
-    assert rc == -1 and b"final_mode" in L.isr_last_error()
-    # workspace sizes: REFIT = the _ex sizes, EPNP larger, unknown 0
-    assert L.isr_pnp_ransac_ex2_workspace_bytes(5000, 500, 0) == L.isr_pnp_ransac_workspace_bytes(5000, 500)
-    assert L.isr_pnp_ransac_batch_ex2_workspace_bytes(5000, 500, 7, 0) == L.isr_pnp_ransac_batch_workspace_bytes(5000, 500, 7)
-    assert L.isr_pnp_ransac_ex2_workspace_bytes(5000, 500, 1) > L.isr_pnp_ransac_workspace_bytes(5000, 500)
-    assert L.isr_pnp_ransac_batch_ex2_workspace_bytes(5000, 500, 7, 1) > L.isr_pnp_ransac_batch_workspace_bytes(5000, 500, 7)
-    assert L.isr_pnp_ransac_ex2_workspace_bytes(5000, 500, 2) == 0
+    # final_mode of isr_pnp_ransac_batch: checked first, no device touched
+    for B, fm in [(1, 7), (2, -1)]:
+        rc = L.isr_pnp_ransac_batch(None, None, None, 100, B, None, 100, None, 2.0, 0.99, 10, None, None, None, None, None,
+                                    None, 0, None, 0, 0, 0, fm)
+        assert rc == -1 and b"final_mode" in L.isr_last_error()
+    # workspace sizes: REFIT positive, EPNP larger, unknown 0
+    sz = L.isr_pnp_ransac_batch_workspace_bytes
+    for B in (1, 7):
+        assert sz(5000, 500, B, 0) > 0
+        assert sz(5000, 500, B, 1) > sz(5000, 500, B, 0)
+        assert sz(5000, 500, B, 2) == 0
     assert L.isr_epnp_batch_workspace_bytes(0, 1) == 0
 
 

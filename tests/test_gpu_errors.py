@@ -44,7 +44,8 @@ def test_bad_arguments_are_reported(cuda0):
                            ws.data_ptr(), ws.numel(), None)
     assert rc == -1 and b"dtype" in L.isr_last_error()
     # the reference indexes an empty sort and raises: so does the filter on P = 0
-    rc = L.isr_select_top(lp.data_ptr(), 0, 0.8, 500, out.data_ptr(), out.data_ptr(), None, ws.data_ptr(), ws.numel(), None)
+    rc = L.isr_select_top_batch(lp.data_ptr(), 0, 1, None, 0.8, 500, out.data_ptr(), out.data_ptr(), None, ws.data_ptr(), ws.numel(),
+                                None)
     assert rc == -1
     # ICP needs a positive correspondence radius
     rc = L.isr_icp_point_to_point(lp.data_ptr(), 2, lp.data_ptr(), 2, -1.0, 30, 1e-6, 1e-6, lp.data_ptr(), lp.data_ptr(),

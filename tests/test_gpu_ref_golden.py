@@ -26,7 +26,7 @@ def test_getcors_vs_reference_output(cuda0):
 
 
 def test_filter_vs_reference_output(cuda0):
-    """isr_select_top vs the reference's statements inference.py:282-288: integer-exact kept set and
+    """ops.select_top vs the reference's statements inference.py:282-288: integer-exact kept set and
     the same threshold value, both branches (n > 500, n <= 500), tied values included."""
     from imagesequenceregistrationfor6dposeestimationlabeling_amd import ops, registration
     g = np.load(G / "ref_filter.npz")
@@ -196,7 +196,7 @@ def test_prune_vs_reference_statements(cuda0):
 def test_masked_queries_getcors_filter_assembly_vs_reference_statements(cuda0):
     """The per-image front of inference.py on the device against its statements :252-263, :265-280, :282-290 executed from the
     reference (ref_assembly.npz): every third pixel of the network output under the mask in the reference's order
-    (masked_queries / isr_prep_queries), getCors' indices (exact f32 path, 12 channels: the split route), the top-80 % cut on
+    (masked_queries / ops.prep_queries), getCors' indices (exact f32 path, 12 channels: the split route), the top-80 % cut on
     the reference's own values, and the 3-D / 2-D arrays handed to pnp — both branches of the 500-correspondence rule."""
     from imagesequenceregistrationfor6dposeestimationlabeling_amd import ops, registration as reg, sequence
     g = np.load(G / "ref_assembly.npz")

@@ -1,4 +1,4 @@
-"""GPU parity: isr_select_top / isr_gather_corr vs the literal reference expressions
+"""GPU parity: ops.select_top / ops.gather_corr (isr_select_top_batch / isr_gather_corr_batch at B = 1) vs the literal reference expressions
 (inference.py:274-290) evaluated with torch on the CPU — integer-exact given identical values."""
 import numpy as np
 import pytest

@@ -98,43 +98,32 @@ def test_rule_examples(hip_lib):
     assert ref.literal_loop(counts, np.ones(500, np.uint8), 110, 500, 1.0) == (0, ref.update_exact(1.0, 110, 100, 500))
 
 
-def _args(hip_lib, **over):
-    """isr_pnp_ransac_ex arguments with host buffers standing in for device pointers (nothing is dereferenced before the
-    checks under test)."""
+def _args(B, **over):
+    """isr_pnp_ransac_batch arguments for B images with host buffers standing in for device pointers (nothing is dereferenced
+    before the checks under test)."""
     buf = ctypes.create_string_buffer(1 << 12)
-    K = (ctypes.c_double * 9)(768.0, 0, 319.5, 0, 768.0, 239.5, 0, 0, 1)
-    a = dict(p3d=buf, p2d=buf, M_dev=buf, M_cap=64, Kcam=K, H=500, seed=0, reperr=2.0, confidence=0.99, refine_iters=10,
-             pose=buf, inl=buf, n_inl=buf, status=buf, n_eval=None, ws=None, ws_bytes=0, stream=None, loop=1, stage0=0,
-             inliers_mode=0)
-    a.update(over)
-    return list(a.values())
-
-
-def _batch_args(**over):
-    buf = ctypes.create_string_buffer(1 << 12)
-    K = (ctypes.c_double * 9)(768.0, 0, 319.5, 0, 768.0, 239.5, 0, 0, 1)
-    seeds = (ctypes.c_uint64 * 1)(0)
-    a = dict(p3d=buf, p2d=buf, M_dev=buf, M_cap=64, B=1, Kcams=K, H=500, seeds=seeds, reperr=2.0, confidence=0.99,
+    K = (ctypes.c_double * (9 * B))(*[768.0, 0, 319.5, 0, 768.0, 239.5, 0, 0, 1] * B)
+    seeds = (ctypes.c_uint64 * B)(*range(B))
+    a = dict(p3d=buf, p2d=buf, M_dev=buf, M_cap=64, B=B, Kcams=K, H=500, seeds=seeds, reperr=2.0, confidence=0.99,
              refine_iters=10, pose=buf, inl=buf, n_inl=buf, status=buf, n_eval=None, ws=None, ws_bytes=0, stream=None, loop=1,
-             stage0=0, inliers_mode=0)
+             stage0=0, inliers_mode=0, final_mode=0)
     a.update(over)
     return list(a.values())
 
 
-@pytest.mark.parametrize("entry", ["isr_pnp_ransac_ex", "isr_pnp_ransac_batch_ex"])
-def test_ex_entries_reject_bad_arguments(hip_lib, entry):
-    args = _args if entry == "isr_pnp_ransac_ex" else (lambda lib, **o: _batch_args(**o))
-    fn = getattr(hip_lib, entry)
+@pytest.mark.parametrize("B", [1, 3])
+def test_pnp_entry_rejects_bad_arguments(hip_lib, B):
+    fn = hip_lib.isr_pnp_ransac_batch
     bad = [dict(loop=2), dict(loop=-1), dict(inliers_mode=2), dict(inliers_mode=-1),
            dict(stage0=48), dict(stage0=-32), dict(loop=0, stage0=64), dict(loop=0, stage0=500),
-           dict(p3d=None), dict(pose=None), dict(Kcam=None) if entry == "isr_pnp_ransac_ex" else dict(seeds=None)]
+           dict(final_mode=2), dict(p3d=None), dict(pose=None), dict(Kcams=None), dict(seeds=None)]
     for over in bad:
-        assert fn(*args(hip_lib, **over)) == -1, over
+        assert fn(*_args(B, **over)) == -1, over
         assert hip_lib.isr_last_error(), over
     # valid choices pass the checks and stop at the missing workspace (-2): still no device call
     for over in [dict(), dict(stage0=32), dict(stage0=96), dict(stage0=500), dict(stage0=8192), dict(inliers_mode=1),
-                 dict(loop=0), dict(loop=0, stage0=32, inliers_mode=1)]:
-        assert fn(*args(hip_lib, **over)) == -2, over
+                 dict(loop=0), dict(loop=0, stage0=32, inliers_mode=1), dict(final_mode=1)]:
+        assert fn(*_args(B, **over)) == -2, over
 
 
 def test_seq_host_rejects_bad_arguments(hip_lib):

@@ -119,7 +119,7 @@ def test_lockstep_no_problems():
 
 def test_refine_batch_arg_errors(hip_lib):
     L = hip_lib
-    assert L.isr_abi_version() == 5
+    assert L.isr_abi_version() == 6
     assert L.isr_refine_objective_batch_workspace_bytes(0) == 0
     assert L.isr_refine_objective_batch_workspace_bytes(3) >= 3 * 64 * 14 * 8
     offs = (ctypes.c_int32 * 3)(0, 5, 9)
