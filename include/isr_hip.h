@@ -183,7 +183,7 @@ int isr_corr_logsoftmax(const void* Q, const void* K, int P, int N, int D, int l
  * without the (P x N) matrix.  f32 rows, D <= 128, 1 <= k <= 8; lse (P) = the rows' log-sum-exps from an lse-only
  * isr_corr_argmax call on the same rows.  Per query the k largest k-ordered-fmaf-chain logits (the values
  * isr_corr_logsoftmax writes), descending, equal values by ascending key: idx (P, k) int32 (-1 where N < k), vals (P, k) =
- * logit - lse. */
+ * logit - lse.  Where N < k the slots j >= N hold idx -1 and vals -inf. */
 size_t isr_corr_topk_workspace_bytes(int P, int N);
 int isr_corr_topk(const float* Q, const float* K, int P, int N, int D, int ldq, int ldk, int k, const float* lse,
                   int32_t* idx, float* vals, void* ws, size_t ws_bytes, isr_stream_t stream);
@@ -204,7 +204,8 @@ int isr_corr_topk(const float* Q, const float* K, int P, int N, int D, int ldq, 
  * pix_xy (B, S, 2) f32 = (column, row) in the subsampled grid; n_dev (B) = number of masked pixels.
  * Rows past n_dev[b] of image b are zero queries: K1 runs ONCE over the B * S capacity rows (a query's result
  * does not depend on the launch it rides in), and isr_select_top_batch / isr_gather_corr_batch /
- * isr_pnp_ransac_batch take the ragged counts from n_dev.  Image b's rows do not depend on B. */
+ * isr_pnp_ransac_batch take the ragged counts from n_dev.  Image b's rows do not depend on B.
+ * pix_xy rows past n_dev[b] are not written: a caller that reads them pre-fills them (ops.prep_queries_batch zeroes them). */
 size_t isr_prep_queries_batch_workspace_bytes(int H, int W, int step, int B);
 int isr_prep_queries_batch(const float* feat, int B, int H, int W, int C, int c0, int D, const uint8_t* mask,
                            int mask_pix_stride, int step, int dtype, int ldq, void* Q, float* pix_xy,
@@ -271,13 +272,15 @@ int isr_gather_corr_batch(const int32_t* idx, const int32_t* keep, const int32_t
  * isr_ransac_score: n_inl[h] = #{m : z>0 and |proj_h(p3d[m]) - p2d[m]|^2 <= reperr^2} in f32,
  *   evaluated division-free; best_dev = argmax (lowest h on ties, ok hypotheses only),
  *   best_mask = inlier bitmask of the best hypothesis, ceil(M_cap/32) words (nullable);
- *   ws: isr_pnp_ransac_batch_workspace_bytes(M_cap, H, 1, ISR_FINAL_REFIT).
+ *   ws: isr_pnp_ransac_batch_workspace_bytes(M_cap, H, 1, ISR_FINAL_REFIT).  Every word of best_mask is written (bits at
+ *   m >= M zero): a caller need not pre-fill it.
  * isr_pnp_refine: `iters` Gauss-Newton steps (f64) on the reprojection error over the masked
  *   correspondences, starting from Rt_io (12 f64), result written back.
  * Kcam: host pointer, 9 doubles row-major.
  */
 /* Diagnostics: EVERY root of the device P3P solver for S independent 3-point problems (the production
- * kernels keep one per sample): X (S,3,3), uv (S,3,2) device f64 -> poses (S,4,12) [R|t], n_roots (S). */
+ * kernels keep one per sample): X (S,3,3), uv (S,3,2) device f64 -> poses (S,4,12) [R|t], n_roots (S).
+ * Only the rows [0, n_roots[s]) of poses[s] are written; a caller that reads the others pre-fills them (ops.p3p_all_roots). */
 int isr_p3p_all_roots(const double* X, const double* uv, const double* Kcam, int S, double* poses,
                       int32_t* n_roots, isr_stream_t stream);
 int isr_p3p_hypotheses(const float* p3d, const float* p2d, const int32_t* M_dev, int M_cap,
@@ -298,6 +301,8 @@ int isr_pnp_refine(const float* p3d, const float* p2d, const int32_t* M_dev, int
  * the Python mirror then returns the reference's (1,1,1));  n_eval_dev (B, nullable): how many of the H
  * hypotheses were scored (staged loop) or ran (sequential loop).  Image b's outputs do not depend on B or
  * on its position in the group.
+ * At status 0: n_inl_dev[b] = 0, and pose_dev[b] is written but is no result: the best scored hypothesis unrefined, or [I | 0]
+ * when no hypothesis was solved (fewer than 4 correspondences).  inl_idx[b, n_inl_dev[b]:] is never defined.
  * confidence: cv2.solvePnPRansac's parameter of that name (its default, which the reference uses, is 0.99).
  * loop ISR_RANSAC_STAGED: hypotheses are scored in stages [0,32), [32,96), [96,224), ... and a stage runs only
  *      while (1 - (c/M)^4)^b > 1 - confidence for the best count c after the b hypotheses before it;
