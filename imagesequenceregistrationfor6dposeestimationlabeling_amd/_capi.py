@@ -124,6 +124,8 @@ SIGNATURES = {
     "isr_add_metric": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
     "isr_icp_workspace_bytes": (_sz, [_i, _i]),
     "isr_icp_point_to_point": (_i, [_vp, _i, _vp, _i, _d, _i, _d, _d, _vp, _vp, _vp, _sz, _vp]),
+    "isr_icp_point_to_point_batch_workspace_bytes": (_sz, [_i, _i, _i]),
+    "isr_icp_point_to_point_batch": (_i, [_vp, _sz, _i, _vp, _i, _i, _d, _i, _d, _d, _vp, _vp, _sz, _vp]),
     "isr_rel_pose_table": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
 }
 

@@ -23,6 +23,7 @@
 // CPU statement of the same arithmetic.
 #include "isr_common.hpp"
 
+#include <cstddef>
 #include <cstdlib>
 
 namespace {
@@ -115,17 +116,29 @@ __global__ __launch_bounds__(256) void tile_box_kernel(const float* __restrict__
 // winner that displaces a near-tied predecessor raises the flag too, and so does the packed atomicMin when the value
 // it displaces (or fails to displace) — another target split's winner — is a near tie.  Cost in the fast path: none
 // (the comparisons are against thx instead of best).  On 20 000-point clouds one or two queries per pass are flagged.
-template <int RQ, bool FILTER, bool EXACT = false, bool CULL = false>
+// ITEMS = true (isr_icp_point_to_point_batch): blockIdx.z is an independent ICP problem.  Besides warm / packed / amb, which
+// every instantiation indexes by item, the item owns its source cloud (qry_item_stride floats apart, 0 = shared), its
+// transform (the first 12 of its kIcpItemDoubles state doubles at Tq) and its done flag (skip points at item 0's, one
+// IcpState apart).  A flag of its own, so that the instantiations of the single call and of isr_nn_batched keep their code.
+constexpr int kIcpItemDoubles = 20;   // T 4x4 | fitness, inlier_rmse, iterations, inliers
+constexpr int kIcpStateInts = 8;      // sizeof(IcpState) / 4 (asserted below the struct)
+template <int RQ, bool FILTER, bool EXACT = false, bool CULL = false, bool ITEMS = false>
 __global__ __launch_bounds__(kThreads) void nn_search_kernel(
     const float* __restrict__ qry, int Nq, const float* __restrict__ tgt, int Nt,
     const double* __restrict__ Tq, const double* __restrict__ Tt, int split_len, int nsplit,
     float* __restrict__ part_d2, int32_t* __restrict__ part_idx, const int32_t* __restrict__ skip,
     const int32_t* __restrict__ unresolved, unsigned long long* __restrict__ packed = nullptr,
     const int32_t* __restrict__ warm = nullptr, int32_t* __restrict__ amb = nullptr,
-    const float* __restrict__ t2_bound = nullptr, const float* __restrict__ tile_box = nullptr, float cull_r2 = 0.f) {
+    const float* __restrict__ t2_bound = nullptr, const float* __restrict__ tile_box = nullptr, float cull_r2 = 0.f,
+    size_t qry_item_stride = 0) {
   __shared__ __attribute__((aligned(16))) float lds[2][FILTER ? 4 : 3][kTile];   // FILTER: -2x, -2y, -2z, |t|^2; else x, y, z
   __shared__ float tile_t2[2][kThreads / 64];                       // largest |t|^2 of a tile, per staging wave
-  if (skip && *skip) return;  // device-side ICP loop: converged, later iterations are no-ops
+  if (ITEMS) {
+    if (skip[(size_t)blockIdx.z * kIcpStateInts]) return;   // this item has stopped: its workgroups leave, the others go on
+    qry += (size_t)blockIdx.z * qry_item_stride;
+  } else if (skip && *skip) {
+    return;  // device-side ICP loop: converged, later iterations are no-ops
+  }
   if (unresolved && *unresolved == 0) return;
 
   const int tid = threadIdx.x;
@@ -140,7 +153,7 @@ __global__ __launch_bounds__(kThreads) void nn_search_kernel(
     }
     if (!__syncthreads_or(mine)) return;
   }
-  const double* tq = Tq ? Tq + 12 * (size_t)b : nullptr;
+  const double* tq = Tq ? Tq + (ITEMS ? kIcpItemDoubles : 12) * (size_t)b : nullptr;
   const double* tt = Tt ? Tt + 12 * (size_t)b : nullptr;
 
   float qx[RQ], qy[RQ], qz[RQ], q2[RQ], best[RQ], thr[RQ];
@@ -577,6 +590,8 @@ struct IcpState {
   int32_t iter, done;
   int32_t ticket, pad;   // workgroups that have delivered their sums in the current pass
 };
+static_assert(sizeof(IcpState) == kIcpStateInts * sizeof(int32_t) && offsetof(IcpState, done) == 5 * sizeof(int32_t),
+              "nn_search_kernel<.., ITEMS> steps from one item's done flag to the next by kIcpStateInts");
 
 // Cyclic Jacobi on a symmetric 4x4; every loop has constant bounds and is unrolled so A and V
 // stay in registers (indexed dynamically they live in scratch memory: 60 us per call instead of 10).
@@ -702,16 +717,29 @@ __device__ void icp_reduce_and_update(const double* __restrict__ part_sums, int 
 // winner, radius test, the 18 sums by the same fixed tree), re-arms the packed slots, and takes a
 // ticket; the LAST workgroup to arrive (agent-scope fences order the block sums before the ticket)
 // runs the update.  Two launches per ICP iteration, no partial arrays.
+// blockIdx.y is the problem (isr_icp_point_to_point_batch; the single call is a grid of one): every per-problem pointer
+// moves to the item's slice — source (src_item_stride floats apart, 0 = shared), packed / prev_idx / amb (Ns apart), block
+// sums (gridDim.x rows apart), IcpState (own ticket: the last workgroup OF THE ITEM runs its update), T and result
+// (out_item_stride doubles apart) — and the code below is the single problem's, sum for sum.
 __global__ __launch_bounds__(kThreads) void icp_finalize_update_kernel(
     const float* __restrict__ src, int Ns, const float* __restrict__ tgt, int Nt, double radius,
     unsigned long long* __restrict__ packed, int32_t* __restrict__ prev_idx, int32_t* __restrict__ amb,
     double* __restrict__ part_sums, int max_iter,
-    double rel_fitness, double rel_rmse, double* __restrict__ T, IcpState* __restrict__ st, double* __restrict__ result) {
+    double rel_fitness, double rel_rmse, double* __restrict__ T, IcpState* __restrict__ st, double* __restrict__ result,
+    size_t src_item_stride = 0, size_t out_item_stride = 0) {
   __shared__ double red[kThreads / 64][kNV];
   __shared__ int last;
   __shared__ int nflag, flist[kThreads];
   __shared__ double wd[4][kThreads / 64];
   __shared__ int wi[4][kThreads / 64];
+  {
+    const size_t b = blockIdx.y;
+    src += b * src_item_stride;
+    packed += b * Ns; prev_idx += b * Ns; amb += b * Ns;
+    part_sums += b * gridDim.x * kNV;
+    st += b;
+    T += b * out_item_stride; result += b * out_item_stride;
+  }
   if (st->done) return;
   const int tid = threadIdx.x;
   const int qi = blockIdx.x * kThreads + tid;
@@ -814,10 +842,14 @@ __global__ __launch_bounds__(kThreads) void icp_finalize_update_kernel(
   icp_reduce_and_update(part_sums, gridDim.x, Ns, max_iter, rel_fitness, rel_rmse, T, st, result);
 }
 
-__global__ void icp_init_kernel(IcpState* st, double* T, unsigned long long* packed, int32_t* amb, int Ns) {
+// (blockIdx.y: the problem, as in icp_finalize_update_kernel)
+__global__ void icp_init_kernel(IcpState* st, double* T, unsigned long long* packed, int32_t* amb, int Ns,
+                                size_t out_item_stride = 0) {
+  const size_t b = blockIdx.y;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < Ns) { packed[i] = ~0ull; amb[i] = 0; }
+  if (i < Ns) { packed[b * Ns + i] = ~0ull; amb[b * Ns + i] = 0; }
   if (i != 0) return;
+  st += b; T += b * out_item_stride;
   st->prev_fit = 0; st->prev_rmse = 0; st->iter = 0; st->done = 0; st->ticket = 0;
   T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1;
 }
@@ -907,7 +939,8 @@ constexpr int kFilterMinTiles = 4;
 void launch_search(const NNPlan& p, const dim3& grid, hipStream_t stream, const float* qry, int Nq, const float* tgt, int Nt,
                    const double* tq, const double* tt, float* part_d2, int32_t* part_idx, const int32_t* skip,
                    const int32_t* unresolved, unsigned long long* packed, const int32_t* warm, int32_t* amb = nullptr,
-                   const float* t2_bound = nullptr, const float* tile_box = nullptr, float cull_r2 = 0.f) {
+                   const float* t2_bound = nullptr, const float* tile_box = nullptr, float cull_r2 = 0.f,
+                   bool items = false, size_t qry_item_stride = 0) {
   bool filter = warm != nullptr || p.split_len >= kFilterMinTiles * kTile;
   // tuning hook (experiments only) for cold searches; a warm start always takes the filter loop (its tie rule —
   // equal distance, lower index — is what makes a warm-started lane return the cold winner)
@@ -921,6 +954,15 @@ void launch_search(const NNPlan& p, const dim3& grid, hipStream_t stream, const 
 #define ISR_SEARCH_X(RQv, Fv)                                                                                            \
   nn_search_kernel<RQv, Fv, true, Fv><<<grid, kThreads, 0, stream>>>(qry, Nq, tgt, Nt, tq, tt, p.split_len, p.nsplit, part_d2, \
                                                                      part_idx, skip, unresolved, packed, warm, amb, t2_bound, tile_box, cull_r2)
+#define ISR_SEARCH_ITEMS(RQv, Fv)                                                                                        \
+  nn_search_kernel<RQv, Fv, true, Fv, true><<<grid, kThreads, 0, stream>>>(qry, Nq, tgt, Nt, tq, tt, p.split_len, p.nsplit,    \
+                                                                           part_d2, part_idx, skip, unresolved, packed, warm, \
+                                                                           amb, t2_bound, tile_box, cull_r2, qry_item_stride)
+  if (items) {     // the batched ICP loop: the single call's searches with the problem on blockIdx.z
+    if (p.rq == 4) { if (filter) ISR_SEARCH_ITEMS(4, true); else ISR_SEARCH_ITEMS(4, false); }
+    else { if (filter) ISR_SEARCH_ITEMS(1, true); else ISR_SEARCH_ITEMS(1, false); }
+    return;
+  }
   if (amb) {       // the ICP loop: near ties are flagged for the exact decision (packed slots, no target transform)
     if (p.rq == 4) { if (filter) ISR_SEARCH_X(4, true); else ISR_SEARCH_X(4, false); }
     else { if (filter) ISR_SEARCH_X(1, true); else ISR_SEARCH_X(1, false); }
@@ -928,6 +970,7 @@ void launch_search(const NNPlan& p, const dim3& grid, hipStream_t stream, const 
   }
   if (p.rq == 4) { if (filter) ISR_SEARCH(4, true); else ISR_SEARCH(4, false); }
   else { if (filter) ISR_SEARCH(1, true); else ISR_SEARCH(1, false); }
+#undef ISR_SEARCH_ITEMS
 #undef ISR_SEARCH_X
 #undef ISR_SEARCH
 }
@@ -1090,5 +1133,66 @@ extern "C" int isr_icp_point_to_point(const float* src, int Ns, const float* tgt
                                                                    max_iter, rel_fitness, rel_rmse, T_io, st, result);
   }
   ISR_CHECK_LAUNCH("icp kernels");
+  return ISR_OK;
+}
+
+// The loop above for B independent problems against one target, the item on a grid axis: the same 3 + 2 (max_iter + 1)
+// launches whatever B is.  Every item keeps the single call's arithmetic — the search returns the lexicographic minimum of
+// (f32 d2, index) whatever the key ranges, near ties are decided in f64 over all targets, the sums are reduced per 256-row
+// block and across blocks in the fixed order of icp_reduce_and_update, which depends on Ns alone — so item b's 20 doubles
+// are those of isr_icp_point_to_point on (src_b, tgt, T0_b).  An item that has stopped raises its own done flag: its
+// workgroups of the remaining launches leave at once.
+extern "C" size_t isr_icp_point_to_point_batch_workspace_bytes(int Ns, int Nt, int B) {
+  if (Ns <= 0 || Nt <= 0 || B <= 0) return 0;
+  const NNPlan p = make_plan(Ns, Nt, B, true);
+  return isr::align_up((size_t)B * p.fblocks * kNV * sizeof(double), 256) + isr::align_up((size_t)B * sizeof(IcpState), 256) +
+         isr::align_up((size_t)B * Ns * 8, 256) + 2 * isr::align_up((size_t)B * Ns * 4, 256) +
+         isr::align_up((size_t)((Nt + kTile - 1) / kTile) * 6 * sizeof(float), 256) + 2048;
+}
+
+extern "C" int isr_icp_point_to_point_batch(const float* src, size_t src_item_stride, int Ns, const float* tgt, int Nt, int B,
+                                            double threshold, int max_iter, double rel_fitness, double rel_rmse,
+                                            double* state, void* ws, size_t ws_bytes, isr_stream_t stream_) {
+  ISR_REQUIRE(src && tgt && state, "isr_icp_point_to_point_batch: null pointer");
+  ISR_REQUIRE(Ns > 0 && Nt > 0 && B >= 0 && B <= 65535, "isr_icp_point_to_point_batch: Ns=%d Nt=%d must be positive, B=%d in [0, 65535]",
+              Ns, Nt, B);
+  ISR_REQUIRE(threshold > 0 && max_iter >= 0, "isr_icp_point_to_point_batch: threshold=%g must be positive, max_iter=%d non-negative",
+              threshold, max_iter);
+  ISR_REQUIRE(src_item_stride == 0 || src_item_stride >= 3 * (size_t)Ns,
+              "isr_icp_point_to_point_batch: src_item_stride=%zu must be 0 (one source for all items) or at least 3*Ns=%zu floats",
+              src_item_stride, 3 * (size_t)Ns);
+  if (B == 0) return ISR_OK;
+  if (!ws || ws_bytes < isr_icp_point_to_point_batch_workspace_bytes(Ns, Nt, B)) {
+    isr::set_error("isr_icp_point_to_point_batch: workspace %zu < %zu", ws_bytes,
+                   isr_icp_point_to_point_batch_workspace_bytes(Ns, Nt, B));
+    return ISR_ERR_WORKSPACE;
+  }
+  hipStream_t stream = isr::as_stream(stream_);
+  // with B items on the grid the target needs fewer key ranges than the single call's plan cuts
+  const NNPlan p = make_plan(Ns, Nt, B, true);
+  isr::Workspace w(ws, ws_bytes);
+  double* part_sums = w.take<double>((size_t)B * p.fblocks * kNV);
+  IcpState* st = w.take<IcpState>(B);
+  unsigned long long* packed = w.take<unsigned long long>((size_t)B * Ns);
+  int32_t* prev_idx = w.take<int32_t>((size_t)B * Ns);
+  int32_t* amb = w.take<int32_t>((size_t)B * Ns);
+  float* t2_bound = w.take<float>(1);
+  float* tile_box = w.take<float>((size_t)((Nt + kTile - 1) / kTile) * 6);
+  const bool warm = isr::tuning(ISR_TUNE_ICP_WARM) != 0;
+  icp_init_kernel<<<dim3((Ns + kThreads - 1) / kThreads, B), kThreads, 0, stream>>>(st, state, packed, amb, Ns, kIcpItemDoubles);
+  // the target is shared: its bound and its tile boxes once per call
+  cloud_r2max_kernel<<<1, kThreads, 0, stream>>>(tgt, Nt, t2_bound);
+  const float cull_r2 = (float)(threshold * threshold * 1.0001 + 1e-6);
+  if (ISR_ICP_CULL) tile_box_kernel<<<(Nt + kTile - 1) / kTile, 256, 0, stream>>>(tgt, Nt, tile_box);
+  const dim3 grid(p.qblocks, p.nsplit, B);
+  for (int it = 0; it <= max_iter; ++it) {
+    const int32_t* w_idx = (it > 0 && warm) ? prev_idx : nullptr;
+    launch_search(p, grid, stream, src, Ns, tgt, Nt, state, nullptr, nullptr, nullptr, &st->done, nullptr, packed, w_idx, amb,
+                  t2_bound, ISR_ICP_CULL ? tile_box : nullptr, cull_r2, true, src_item_stride);
+    icp_finalize_update_kernel<<<dim3(p.fblocks, B), kThreads, 0, stream>>>(src, Ns, tgt, Nt, threshold, packed, prev_idx, amb,
+                                                                             part_sums, max_iter, rel_fitness, rel_rmse, state,
+                                                                             st, state + 16, src_item_stride, kIcpItemDoubles);
+  }
+  ISR_CHECK_LAUNCH("icp batch kernels");
   return ISR_OK;
 }

@@ -169,6 +169,33 @@ def nn_batched(qry: torch.Tensor, tgt: torch.Tensor, Tq: torch.Tensor | None = N
     return NNResult(sum_d, sum_d2, n_in, nn_idx, nn_d, cov)
 
 
+def icp_point_to_point_batch(sources: torch.Tensor, target: torch.Tensor, state: torch.Tensor, threshold: float,
+                             max_iter: int = 30, rel_fitness: float = 1e-6, rel_rmse: float = 1e-6) -> torch.Tensor:
+    """isr_icp_point_to_point_batch: B point-to-point ICP loops against one target in one call, in place on `state`.
+    sources (Ns,3) f32 — one source, B starts — or (B,Ns,3); target (Nt,3) f32; state (B,20) f64 contiguous, per item
+    T 4x4 row-major (start in, result out) | fitness, inlier_rmse, iterations, correspondences.  Returns `state`."""
+    dev = require_cuda(sources, target, state)
+    if sources.dtype != torch.float32 or target.dtype != torch.float32 or not (sources.is_contiguous() and target.is_contiguous()):
+        raise ValueError("icp_point_to_point_batch: sources and target must be contiguous float32")
+    if state.dtype != torch.float64 or state.ndim != 2 or state.shape[1] != 20 or not state.is_contiguous():
+        raise ValueError(f"icp_point_to_point_batch: state must be contiguous (B,20) float64, got {tuple(state.shape)} {state.dtype}")
+    if target.ndim != 2 or target.shape[1] != 3 or sources.ndim not in (2, 3) or sources.shape[-1] != 3:
+        raise ValueError(f"icp_point_to_point_batch: sources {tuple(sources.shape)} must be (Ns,3) or (B,Ns,3), target "
+                         f"{tuple(target.shape)} (Nt,3)")
+    B, Ns, Nt = state.shape[0], sources.shape[-2], target.shape[0]
+    if sources.ndim == 3 and sources.shape[0] != B:
+        raise ValueError(f"icp_point_to_point_batch: sources {tuple(sources.shape)} and state {tuple(state.shape)} disagree on B")
+    stride = 3 * Ns if sources.ndim == 3 else 0
+    L = lib()
+    ws = workspace(dev, L.isr_icp_point_to_point_batch_workspace_bytes(Ns, Nt, B), "icp")
+    with torch.cuda.device(dev), _timed("icp_batch", float(B) * Ns * Nt * (max_iter + 1)):
+        rc = L.isr_icp_point_to_point_batch(ptr(sources), stride, Ns, ptr(target), Nt, B, float(threshold), int(max_iter),
+                                            float(rel_fitness), float(rel_rmse), ptr(state), ptr(ws), ws.numel(),
+                                            current_stream(dev))
+    check(rc, "isr_icp_point_to_point_batch")
+    return state
+
+
 @dataclass
 class DistField:
     """Distances from the cell centres of a uniform grid to a (static) cloud: what isr_adds_bounds reads."""

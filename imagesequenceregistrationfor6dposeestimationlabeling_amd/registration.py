@@ -369,3 +369,114 @@ def final_chamfer(source, target, T, cad_points):
     d = ops.nn_batched(cad, tgt, None, None, want_dist=True)
     mean_ba = float(torch.minimum(c.nn_d, d.nn_d).mean().item())
     return 0.5 * (mean_ab + mean_ba)
+
+
+# ------------------------------------------------------------- a14 / a15 for many starts at once
+def _dev_strict(x, dtype, what) -> torch.Tensor:
+    """Host ARRAYS are copied to the device (plumbing); a torch tensor must already live there."""
+    if isinstance(x, torch.Tensor):
+        if not x.is_cuda:
+            raise IsrError(f"{what}: got a CPU tensor; libisr_hip operates on device tensors only (there is no CPU fallback)")
+        return x.to(dtype)
+    return torch.from_numpy(np.ascontiguousarray(x)).to(device()).to(dtype)
+
+
+def morton_order_batch(points: torch.Tensor) -> torch.Tensor:
+    """morton_order for every cloud of a (B,N,3) stack at once: row b is morton_order(points[b]) (the same arithmetic per
+    element, a stable sort per row)."""
+    p = points.to(torch.float32)
+    if p.shape[1] <= 1:
+        return torch.arange(p.shape[1], device=p.device).expand(p.shape[0], -1)
+    lo = p.amin(1, keepdim=True)
+    ext = (p.amax(1, keepdim=True) - lo).amax(2, keepdim=True).clamp_min(1e-30)
+    q = ((p - lo) * (1023.0 / ext)).to(torch.int64).clamp_(0, 1023)
+
+    def spread(x):
+        x = (x | (x << 16)) & 0x30000FF
+        x = (x | (x << 8)) & 0x300F00F
+        x = (x | (x << 4)) & 0x30C30C3
+        return (x | (x << 2)) & 0x9249249
+
+    code = spread(q[..., 0]) | (spread(q[..., 1]) << 1) | (spread(q[..., 2]) << 2)
+    return torch.argsort(code, dim=1, stable=True)
+
+
+def _batch_clouds(sources, target, what):
+    src, tgt = _dev_strict(sources, torch.float32, what), _dev_strict(target, torch.float32, what)
+    if src.ndim not in (2, 3) or src.shape[-1] != 3 or tgt.ndim != 2 or tgt.shape[1] != 3:
+        raise ValueError(f"{what}: sources {tuple(src.shape)} must be (Ns,3) or (B,Ns,3) and target {tuple(tgt.shape)} (Nt,3)")
+    return src.contiguous(), tgt.contiguous()
+
+
+def icp_batch_state(sources, target, threshold, inits=None, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6,
+                    spatial_order=True) -> np.ndarray:
+    """icp_point_to_point_batch's work; returns the (B,20) f64 state block of isr_icp_point_to_point_batch on the host —
+    per item T (16) | fitness, inlier_rmse, iterations, correspondences."""
+    what = "icp_point_to_point_batch"
+    src, tgt = _batch_clouds(sources, target, what)
+    if inits is None:
+        B = src.shape[0] if src.ndim == 3 else 1
+        T0 = np.broadcast_to(np.eye(4), (B, 4, 4))
+    else:
+        T0 = inits.detach().cpu().numpy() if isinstance(inits, torch.Tensor) else np.asarray(inits, np.float64)
+        if T0.ndim != 3 or T0.shape[1:] != (4, 4):
+            raise ValueError(f"{what}: inits {tuple(T0.shape)} must be (B,4,4)")
+        B = T0.shape[0]
+    if src.ndim == 3 and src.shape[0] != B:
+        raise ValueError(f"{what}: sources {tuple(src.shape)} and inits {tuple(T0.shape)} disagree on B")
+    dev = src.device
+    if B == 0:
+        return np.zeros((0, 20))
+    if spatial_order and min(src.shape[-2], tgt.shape[0]) > MORTON_MIN_ROWS:
+        tgt = tgt[morton_order(tgt)].contiguous()
+        if src.ndim == 2:
+            src = src[morton_order(src)].contiguous()
+        else:
+            src = torch.gather(src, 1, morton_order_batch(src)[:, :, None].expand(-1, -1, 3)).contiguous()
+    state = torch.empty((B, 20), dtype=torch.float64, device=dev)        # per item: T (16) | result (4)
+    state[:, :16] = torch.from_numpy(np.array(T0, np.float64).reshape(B, 16)).to(dev)
+    ops.icp_point_to_point_batch(src, tgt, state, threshold, max_iter, rel_fitness, rel_rmse)
+    return state.cpu().numpy()
+
+
+def icp_point_to_point_batch(sources, target, threshold, inits=None, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6,
+                             spatial_order=True):
+    """icp_point_to_point for B starts in one call (isr_icp_point_to_point_batch): the vote's other choices beside the
+    first one icp.py:37-39 reads.  sources (Ns,3) — one source, B starts — or (B,Ns,3); target (Nt,3); inits (B,4,4), None =
+    identity (B from `sources`, 1 for a single cloud).  Host arrays are copied to the device; torch tensors must be on it.
+    Returns NumPy arrays (T (B,4,4) f64, fitness (B,) f64, inlier_rmse (B,) f64, iterations (B,) int64) after ONE
+    device->host copy.  Item b's numbers are bit for bit those of icp_point_to_point(sources[b], target, threshold, inits[b],
+    ...): with spatial_order the target and EACH item's source are put in the row order morton_order gives that cloud, under
+    the same MORTON_MIN_ROWS rule.  Every item stops on its own; the launches are those of one problem."""
+    h = icp_batch_state(sources, target, threshold, inits, max_iter, rel_fitness, rel_rmse, spatial_order)
+    return h[:, :16].reshape(-1, 4, 4).copy(), h[:, 16].copy(), h[:, 17].copy(), h[:, 18].astype(np.int64)
+
+
+def final_chamfer_batch(sources, target, Ts, cad_points):
+    """final_chamfer (icp.py:110-117) for B transforms at once -> (B,) f64 NumPy, one device->host copy.
+    sources (Ns,3), one cloud under B transforms: four isr_nn_batched calls for the whole batch (source -> CAD and CAD ->
+    source with the B transforms, target <-> CAD once).  sources (B,Ns,3): isr_nn_batched shares its query cloud among the
+    items, so the two searches that involve the source run once per item; the two between target and CAD still run once."""
+    what = "final_chamfer_batch"
+    src, tgt = _batch_clouds(sources, target, what)
+    cad = _dev_strict(cad_points, torch.float32, what).contiguous()
+    T = Ts.detach().cpu().numpy() if isinstance(Ts, torch.Tensor) else np.asarray(Ts, np.float64)
+    if T.ndim != 3 or T.shape[1:] != (4, 4) or (src.ndim == 3 and src.shape[0] != T.shape[0]):
+        raise ValueError(f"{what}: Ts {tuple(T.shape)} must be (B,4,4), B that of sources {tuple(src.shape)}")
+    if cad.ndim != 2 or cad.shape[1] != 3:
+        raise ValueError(f"{what}: cad_points {tuple(cad.shape)} must be (V,3)")
+    B, Ns = T.shape[0], src.shape[-2]
+    if B == 0:
+        return np.zeros(0)
+    Tm = _dev(np.ascontiguousarray(T[:, :3, :], np.float64).reshape(B, 12))
+    b = ops.nn_batched(tgt, cad, None, None)
+    d = ops.nn_batched(cad, tgt, None, None, want_dist=True)
+    if src.ndim == 2:
+        a_sum = ops.nn_batched(src, cad, Tm, None).sum_d
+        c_d = ops.nn_batched(cad, src, None, Tm, want_dist=True).nn_d
+    else:
+        a_sum = torch.cat([ops.nn_batched(src[i], cad, Tm[i:i + 1], None).sum_d for i in range(B)])
+        c_d = torch.cat([ops.nn_batched(cad, src[i], None, Tm[i:i + 1], want_dist=True).nn_d for i in range(B)])
+    mean_ab = (a_sum + b.sum_d) / (Ns + tgt.shape[0])
+    mean_ba = torch.minimum(c_d, d.nn_d).mean(dim=1)
+    return (0.5 * (mean_ab + mean_ba)).cpu().numpy()

@@ -632,3 +632,66 @@ def vote_choose_image(model_verts, surface_pts, R_gt, t_gt, R_pred, t_pred, diam
     sums = shard.allgather_rows(sums_local, n)[:, 0].cpu().numpy().astype(np.float64)
     image_id = int(np.argmax(sums))
     return image_id, np.argsort(-sums, kind="stable")[:top], err
+
+
+# ------------------------------------------------------------------ icp.py for every listed choice
+def pick_refined(fitness, inlier_rmse, n_inliers, chamfer=None):
+    """Which refined choice labels the object -> position in the list, or None when none qualifies.
+    With final Chamfer values: their FIRST minimum (registration.choose_best's rule, verfication.py:105-106).  Without: the
+    highest fitness, then the lowest inlier rmse, then the earliest position.  An item with fewer than 3 correspondences
+    (its ICP never moved: no rigid fit exists) or with a NaN in the numbers that decide never wins."""
+    fit, rmse = np.asarray(fitness, np.float64), np.asarray(inlier_rmse, np.float64)
+    n = np.asarray(n_inliers, np.float64)
+    ok = np.isfinite(fit) & np.isfinite(rmse) & (n >= 3)        # a NaN count compares False
+    if chamfer is not None:
+        c = np.asarray(chamfer, np.float64)
+        ok &= np.isfinite(c)
+        if not ok.any():
+            return None
+        return int(np.argmin(np.where(ok, c, np.inf)))
+    if not ok.any():
+        return None
+    best = None
+    for i in np.nonzero(ok)[0]:
+        if best is None or fit[i] > fit[best] or (fit[i] == fit[best] and rmse[i] < rmse[best]):
+            best = int(i)
+    return best
+
+
+def refine_top_choices(upper, lower, R_gt, t_gt, R_pred, t_pred, choices, threshold=20.0, cad_points=None, **icp_kw):
+    """icp.py:37-117 for EVERY image listed in `choices` (the lines of top_50_choices.txt) instead of the first.
+    Per choice i: source_i = (upper @ R_gt[i].T + t_gt[i]).astype(float32), formed in f64 on the host (icp.py:68); start
+    init_i = inv([R_pred[i] | t_pred[i]]) (icp.py:88-92); target = lower.  One registration.icp_point_to_point_batch for all
+    of them, one registration.final_chamfer_batch when cad_points is given; icp_kw goes to the former (max_iter, ...).
+    A choice whose predicted pose is a failure (formats.is_failure, or non-finite) is not run: NaN results, iterations -1,
+    never best.  Returns a dict: choices (k,) int64, T (k,4,4), fitness, inlier_rmse (k,) f64, iterations (k,) int64,
+    chamfer (k,) f64 or None, best (position in choices, pick_refined's rule; None when every choice failed) and
+    image_id (choices[best] or None).  choices[0]'s numbers are what icp.py computes today."""
+    from . import formats
+    choices = np.asarray(choices, np.int64).reshape(-1)
+    k = len(choices)
+    up = np.asarray(upper, np.float64)
+    run, srcs, inits = [], [], []
+    for pos, i in enumerate(choices):
+        R, t = R_pred[i], t_pred[i]
+        if formats.is_failure(R, t) or not (np.all(np.isfinite(np.asarray(R, np.float64))) and
+                                            np.all(np.isfinite(np.asarray(t, np.float64)))):
+            continue
+        P = np.vstack([np.hstack([np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3, 1)]),
+                       [0, 0, 0, 1]])
+        run.append(pos)
+        srcs.append((up @ np.asarray(R_gt[i], np.float64).T + np.asarray(t_gt[i], np.float64).reshape(3)).astype(np.float32))
+        inits.append(np.linalg.inv(P))
+    out = {"choices": choices, "T": np.full((k, 4, 4), np.nan), "fitness": np.full(k, np.nan),
+           "inlier_rmse": np.full(k, np.nan), "iterations": np.full(k, -1, np.int64),
+           "chamfer": None if cad_points is None else np.full(k, np.nan), "best": None, "image_id": None}
+    if not run:
+        return out
+    srcs = np.stack(srcs)
+    T, fit, rmse, iters = registration.icp_point_to_point_batch(srcs, lower, threshold, np.stack(inits), **icp_kw)
+    out["T"][run], out["fitness"][run], out["inlier_rmse"][run], out["iterations"][run] = T, fit, rmse, iters
+    if cad_points is not None:
+        out["chamfer"][run] = registration.final_chamfer_batch(srcs, lower, T, cad_points)
+    out["best"] = pick_refined(out["fitness"], out["inlier_rmse"], np.rint(out["fitness"] * up.shape[0]), out["chamfer"])
+    out["image_id"] = None if out["best"] is None else int(choices[out["best"]])
+    return out

@@ -594,6 +594,26 @@ int isr_icp_point_to_point(const float* src, int Ns, const float* tgt, int Nt, d
                            int max_iter, double rel_fitness, double rel_rmse, double* T_io,
                            double* result, void* ws, size_t ws_bytes, isr_stream_t stream);
 
+/* a14, B starts at once: the loop of isr_icp_point_to_point for B independent problems against ONE target, the problem on
+ * a grid axis — the same 3 + 2 (max_iter + 1) launches whatever B is (icp.py reads the first line of top_50_choices.txt;
+ * this runs the others beside it).
+ * src: item b's source cloud starts at src + b * src_item_stride floats; 0 = one source for all items, else >= 3 * Ns.
+ * state: device, (B, 20) f64, one block per item = the T_io and result of the single call side by side:
+ *   [0, 16)  T, 4x4 row-major: the item's start on entry, its result on return (bottom row rewritten as 0 0 0 1)
+ *   [16, 20) fitness, inlier_rmse, iterations done, correspondences — always written.
+ * Item b's 20 doubles are bit for bit those of isr_icp_point_to_point on (src_b, tgt, T0_b) with the same scalars: the
+ * searches return the same winners whatever the key ranges and the sums are reduced in an order that depends on Ns alone.
+ * Every item stops on its own (a device flag per item; its workgroups of the remaining launches leave at once).  An item
+ * that stops at iteration 0 — max_iter = 0, or fewer than 3 correspondences — keeps the rotation and translation it came
+ * with and reports the evaluation of that start: iterations 0, and with no target within the threshold fitness 0, rmse 0,
+ * correspondences 0.
+ * B = 0 is a no-op (ISR_OK); B <= 65535.  Workspace: isr_icp_point_to_point_batch_workspace_bytes(Ns, Nt, B), 0 for
+ * non-positive sizes. */
+size_t isr_icp_point_to_point_batch_workspace_bytes(int Ns, int Nt, int B);
+int isr_icp_point_to_point_batch(const float* src, size_t src_item_stride, int Ns, const float* tgt, int Nt, int B,
+                                 double threshold, int max_iter, double rel_fitness, double rel_rmse, double* state,
+                                 void* ws, size_t ws_bytes, isr_stream_t stream);
+
 /* a10 / a12  relative-pose tables, rows [i0, i1) of the n x n table, written as (i1-i0, n, 12) f64.
  * mode 0: compute_rel_poses       choosePose.py:43-51  ->  [R_i^T R_j | t_j - t_i]
  * mode 1: calculate_relative_pose verfication.py:9-19  ->  [R_j|t_j] * inv([R_i|t_i])
