@@ -1,0 +1,6 @@
+def __getattr__(name):
+    # the renderer's public names, resolved on first use (importing the package stays free of torch)
+    if name in ("ObjCoordRenderer", "Mesh"):
+        from . import render
+        return getattr(render, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

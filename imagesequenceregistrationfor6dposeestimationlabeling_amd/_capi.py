@@ -127,6 +127,9 @@ SIGNATURES = {
     "isr_icp_point_to_point_batch_workspace_bytes": (_sz, [_i, _i, _i]),
     "isr_icp_point_to_point_batch": (_i, [_vp, _sz, _i, _vp, _i, _i, _d, _i, _d, _d, _vp, _vp, _sz, _vp]),
     "isr_rel_pose_table": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "isr_render_coords_batch_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "isr_render_coords_batch": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _f, _d, _d, _i, _vp, _vp, _sz, _vp]),
+    "isr_render_coords_host": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _f, _d, _d, _i, _vp]),
 }
 
 

@@ -166,3 +166,89 @@ def crop_camera(K, bbox_xywh, out_size: int = 224, pad: float = 1.2, down_sample
     cam[:2] /= down_sample
     cam[:2, 2] -= 0.5
     return cam
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def read_ply(path: Path | str):
+    """A triangle mesh from an ASCII or binary_little_endian PLY file (what BOP's models/obj_*.ply are) ->
+    (vertices (V,3) f64, faces (F,3) i32).  Vertex properties other than x, y, z (normals, colours, texture coordinates) and
+    elements other than vertex and face are skipped; a face that is not a triangle raises ValueError."""
+    data = Path(path).read_bytes()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    body = data.index(b"\n", end) + 1
+    fmt, elements = None, []                                 # elements: [name, count, [(prop, type) | (prop, count type, item type)]]
+    for line in data[:end].decode("ascii", "replace").splitlines()[1:]:
+        tok = line.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append([tok[1], int(tok[2]), []])
+        elif tok[0] == "property":
+            if not elements:
+                raise ValueError(f"{path}: property before any element")
+            if tok[1] == "list":
+                elements[-1][2].append((tok[4], _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]]))
+            else:
+                elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]]))
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"{path}: PLY format {fmt!r} is not supported (ascii or binary_little_endian)")
+    verts = faces = None
+    if fmt == "ascii":
+        lines = iter(data[body:].decode("ascii").splitlines())
+        for name, count, props in elements:
+            rows = []
+            while len(rows) < count:
+                ln = next(lines).split()
+                if ln:
+                    rows.append(ln)
+            if name == "vertex":
+                col = [i for want in "xyz" for i, p in enumerate(props) if p[0] == want]
+                if len(col) != 3 or any(len(p) != 2 for p in props):
+                    raise ValueError(f"{path}: vertex element needs scalar x, y, z")
+                verts = np.array([[float(r[c]) for c in col] for r in rows], np.float64).reshape(count, 3)
+            elif name == "face":
+                if len(props) < 1 or len(props[0]) != 3:
+                    raise ValueError(f"{path}: face element needs a leading index list")
+                for r in rows:
+                    if int(r[0]) != 3:
+                        raise ValueError(f"{path}: a face with {int(r[0])} vertices (triangles only)")
+                faces = np.array([[int(x) for x in r[1:4]] for r in rows], np.int64).reshape(count, 3)
+    else:
+        off = body
+        for name, count, props in elements:
+            if all(len(p) == 2 for p in props):
+                dt = np.dtype([(p[0], "<" + p[1]) for p in props])
+                block = np.frombuffer(data, dt, count, off)
+                off += count * dt.itemsize
+                if name == "vertex":
+                    if not all(k in dt.names for k in "xyz"):
+                        raise ValueError(f"{path}: vertex element needs scalar x, y, z")
+                    verts = np.stack([block[k].astype(np.float64) for k in "xyz"], axis=1)
+            elif name == "face" and len(props[0]) == 3:
+                # triangles make every record the same size: read it as one, and verify the counts
+                dt = np.dtype([("n", "<" + props[0][1]), ("idx", "<" + props[0][2], (3,))] +
+                              [(p[0], "<" + p[1]) for p in props[1:] if len(p) == 2])
+                if any(len(p) == 3 for p in props[1:]):
+                    raise ValueError(f"{path}: a second list property on faces is not supported")
+                if off + count * dt.itemsize > len(data):
+                    raise ValueError(f"{path}: face data is short (triangles only)")
+                block = np.frombuffer(data, dt, count, off)
+                off += count * dt.itemsize
+                if (block["n"] != 3).any():
+                    raise ValueError(f"{path}: a face that is not a triangle (triangles only)")
+                faces = block["idx"].astype(np.int64)
+            else:
+                raise ValueError(f"{path}: list property on element {name!r} is not supported")
+    if verts is None or faces is None:
+        raise ValueError(f"{path}: needs a vertex and a face element")
+    if len(faces) and (faces.min() < 0 or faces.max() >= len(verts)):
+        raise ValueError(f"{path}: face index outside the {len(verts)} vertices")
+    return verts, np.ascontiguousarray(faces, np.int32)

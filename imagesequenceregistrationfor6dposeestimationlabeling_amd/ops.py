@@ -1063,3 +1063,63 @@ def corr_logsoftmax(queries: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
         rc = L.isr_corr_logsoftmax(ptr(q), ptr(k), P, N, D, D, D, dtype, ptr(out), N, ptr(ws), ws.numel(), current_stream(dev))
     check(rc, "isr_corr_logsoftmax")
     return out
+
+
+def render_state_words(h: int, w: int) -> int:
+    """4-byte words of one frame-buffer block of isr_render_coords_batch: h*w*4 colour | h*w depth | 4 counters."""
+    return 5 * h * w + 4
+
+
+def render_coords_batch(verts: torch.Tensor, faces: torch.Tensor, K: torch.Tensor, Rt: torch.Tensor, h: int, w: int,
+                        offset: torch.Tensor, scale: float, near: float = 10.0, far: float = 10000.0, clear: bool = True,
+                        state: torch.Tensor | None = None) -> torch.Tensor:
+    """isr_render_coords_batch: the mesh verts (V,3) f32, faces (F,3) i32 drawn at B poses Rt (B,12) f64 with cameras K (B,9)
+    f64 into `state` (B, 5*h*w+4) f32 (allocated when None; required for clear=False, which draws on top of it).
+    Returns `state`: [:, :4*h*w] is the (h,w,4) colour, [:, 4*h*w:5*h*w] the depth, the last 4 words the i32 counters."""
+    dev = require_cuda(verts, faces, K, Rt, offset, state)
+    if (verts.dtype != torch.float32 or faces.dtype != torch.int32 or offset.dtype != torch.float32 or K.dtype != torch.float64
+            or Rt.dtype != torch.float64 or not all(t.is_contiguous() for t in (verts, faces, K, Rt, offset))):
+        raise ValueError("render_coords_batch: contiguous verts f32, faces i32, offset f32, K f64, Rt f64")
+    if verts.ndim != 2 or verts.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3 or offset.numel() != 3:
+        raise ValueError(f"render_coords_batch: verts {tuple(verts.shape)} (V,3), faces {tuple(faces.shape)} (F,3), offset (3)")
+    B = Rt.numel() // 12
+    if Rt.numel() != B * 12 or K.numel() != B * 9:
+        raise ValueError(f"render_coords_batch: Rt {tuple(Rt.shape)} (B,12) and K {tuple(K.shape)} (B,9) disagree")
+    words = render_state_words(h, w)
+    if state is None:
+        if not clear:
+            raise ValueError("render_coords_batch: clear=False draws on top of `state`, which must be given")
+        state = torch.empty((B, words), dtype=torch.float32, device=dev)
+    elif state.dtype != torch.float32 or state.numel() != B * words or not state.is_contiguous():
+        raise ValueError(f"render_coords_batch: state must be contiguous (B, {words}) float32, got {tuple(state.shape)} {state.dtype}")
+    L = lib()
+    V, F = verts.shape[0], faces.shape[0]
+    ws = workspace(dev, L.isr_render_coords_batch_workspace_bytes(V, F, h, w, B), "render")
+    with torch.cuda.device(dev), _timed("render_coords", float(B) * F):
+        rc = L.isr_render_coords_batch(ptr(verts), V, ptr(faces), F, ptr(K), ptr(Rt), B, h, w, ptr(offset), float(scale),
+                                       float(near), float(far), 1 if clear else 0, ptr(state), ptr(ws), ws.numel(),
+                                       current_stream(dev))
+    check(rc, "isr_render_coords_batch")
+    return state
+
+
+def render_coords_host(verts, faces, K, Rt, h: int, w: int, offset, scale: float, near: float = 10.0, far: float = 10000.0,
+                       clear: bool = True, state=None):
+    """isr_render_coords_host: the same rasteriser as host code, one item.  NumPy in (verts (V,3) cast to f32, faces (F,3) to
+    i32, K (3,3), Rt (3,4) or (12,)), -> state (5*h*w+4,) f32 (`state` is drawn on, in place, when given)."""
+    v = np.ascontiguousarray(verts, np.float32)
+    f = np.ascontiguousarray(faces, np.int32)
+    k = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+    rt = np.ascontiguousarray(np.asarray(Rt, np.float64).reshape(12))
+    o = np.ascontiguousarray(np.asarray(offset, np.float32).reshape(3))
+    words = render_state_words(h, w)
+    if state is None:
+        if not clear:
+            raise ValueError("render_coords_host: clear=False draws on top of `state`, which must be given")
+        state = np.empty(words, np.float32)
+    elif state.dtype != np.float32 or state.size != words or not state.flags.c_contiguous:
+        raise ValueError(f"render_coords_host: state must be contiguous ({words},) float32")
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    check(lib().isr_render_coords_host(vp(v), v.shape[0], vp(f), f.shape[0], vp(k), vp(rt), h, w, vp(o), float(scale),
+                                       float(near), float(far), 1 if clear else 0, vp(state)), "isr_render_coords_host")
+    return state

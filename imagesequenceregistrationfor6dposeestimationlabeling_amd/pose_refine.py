@@ -298,7 +298,9 @@ def refine_poses(Rs, ts, query_imgs, renderer, obj_idx, K_crops, obj_, neural_ra
     Rs (B,3,3), ts (B,3), query_imgs (B,res,res,e), K_crops one (3,3) or (B,3,3).  Image b's (R, t, fun) is bit for bit
     refine_pose(Rs[b], ts[b], query_imgs[b], ..., generator=torch.Generator(dev).manual_seed(seeds[b])) (seeds default
     range(B)): the same renderer / batched_customForward calls per image, the same key sample and denominator image, the same
-    objective bits, the same scipy run.  Returns a list of B (R, t, fun).  stats (a dict, optional) receives rounds,
+    objective bits, the same scipy run.  A renderer with render_batch (render.ObjCoordRenderer) draws the block's images in
+    one call and their visible coordinates are compacted on the device; any other renderer is called once per image as
+    refine_pose calls it.  Returns a list of B (R, t, fun).  stats (a dict, optional) receives rounds,
     n_eval (item evaluations per image) and launches.
     optimizer="device": the same renders, keys, key samples and denominator images, then ONE isr_refine_bfgs_batch call —
     scipy's BFGS ported to a per-item state machine that runs on the device (one objective launch and one step launch per
@@ -328,22 +330,42 @@ def refine_poses(Rs, ts, query_imgs, renderer, obj_idx, K_crops, obj_, neural_ra
     Rs = [np.asarray(R, np.float64).reshape(3, 3) for R in Rs_in]
     ts = [np.asarray(t, np.float64).reshape(3) for t in ts]
     # the renders first: an image with nothing visible fails before anything is launched
-    renders = []
-    for b in range(B):
-        coord_img = renderer.render(obj_idx, K_b[b], Rs_in[b], np.expand_dims(ts[b], axis=1))
-        coord_img = coord_img.cpu().numpy() if isinstance(coord_img, torch.Tensor) else np.asarray(coord_img)
-        mask = coord_img[..., 3] == 1.
-        if not mask.any():
-            raise ValueError(f"refine_poses: image {b} renders no visible surface point at its start pose")
-        renders.append((coord_img, mask))
     Xs, keys = [], []
-    for coord_img, mask in renders:                     # pose_refine.py:38-53, per image, as refine_pose does it
-        coord_norm_masked = torch.from_numpy(np.ascontiguousarray(coord_img[..., :3][mask])).to(dev)
+    if hasattr(renderer, "render_batch"):
+        # one call for the block's images; the visible coordinates never leave the device until the field's input is formed
+        imgs = renderer.render_batch(obj_idx, Ks, Rs_in, ts).to(dev)
+        mask = imgs[..., 3] == 1.
+        counts = mask.reshape(B, -1).sum(1).cpu().numpy()
+        if (counts == 0).any():
+            raise ValueError(f"refine_poses: image {int(np.argmax(counts == 0))} renders no visible surface point at its start pose")
+        ends = np.cumsum(counts)
+        # row-major compaction, image after image: the order of coord_img[..., :3][mask]; then refine_pose's arithmetic,
+        # element by element, on the whole block at once
+        coord_norm_masked = imgs[..., :3][mask]
         coord_masked = coord_norm_masked * obj_.scale + torch.from_numpy(np.asarray(obj_.offset)).to(dev)
         coord_nerf = torch.from_numpy((coord_masked.cpu().numpy() * 1.8 / obj_.diameter).astype("float32")).to(dev)
-        feat = neural_radiance_field.batched_customForward(coord_nerf).detach().clone()
-        Xs.append(coord_masked.float())
-        keys.append(feat[..., :feat.shape[-1] - 1].float())
+        X_block = coord_masked.float()
+        for b in range(B):
+            lo, hi = int(ends[b] - counts[b]), int(ends[b])
+            feat = neural_radiance_field.batched_customForward(coord_nerf[lo:hi].clone()).detach().clone()
+            Xs.append(X_block[lo:hi])
+            keys.append(feat[..., :feat.shape[-1] - 1].float())
+    else:
+        renders = []
+        for b in range(B):
+            coord_img = renderer.render(obj_idx, K_b[b], Rs_in[b], np.expand_dims(ts[b], axis=1))
+            coord_img = coord_img.cpu().numpy() if isinstance(coord_img, torch.Tensor) else np.asarray(coord_img)
+            mask = coord_img[..., 3] == 1.
+            if not mask.any():
+                raise ValueError(f"refine_poses: image {b} renders no visible surface point at its start pose")
+            renders.append((coord_img, mask))
+        for coord_img, mask in renders:                     # pose_refine.py:38-53, per image, as refine_pose does it
+            coord_norm_masked = torch.from_numpy(np.ascontiguousarray(coord_img[..., :3][mask])).to(dev)
+            coord_masked = coord_norm_masked * obj_.scale + torch.from_numpy(np.asarray(obj_.offset)).to(dev)
+            coord_nerf = torch.from_numpy((coord_masked.cpu().numpy() * 1.8 / obj_.diameter).astype("float32")).to(dev)
+            feat = neural_radiance_field.batched_customForward(coord_nerf).detach().clone()
+            Xs.append(coord_masked.float())
+            keys.append(feat[..., :feat.shape[-1] - 1].float())
     # the B lse-only denominator calls back to back (each image's own key sample: its generator), no host synchronise
     keys_verts = _dev(keys_verts, torch.float32)
     denoms = []

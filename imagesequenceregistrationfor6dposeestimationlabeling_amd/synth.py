@@ -237,3 +237,55 @@ def crop_block(B=32, seed=7, r=224, e=12, m=20000, f=700.0):
         mls.append(ml)
         qs.append(q)
     return dict(s, mask_lgts=np.stack(mls), query=np.stack(qs), R=Rs, t=ts, B=B)
+
+
+def make_mesh(kind, n, winding="ccw", radius=60.0, tube=0.4):
+    """A closed triangle mesh for the renderer's tests -> (vertices (V,3) f64, faces (F,3) i32).
+    kind "sphere": a UV sphere of `radius` with 3 n segments around and ceil(3 n / 2) rings (about 9 n^2 faces): both
+    angular steps are at most 2 pi / (3 n), so a face's circumradius stays below pi / n and the surface within the
+    sagitta radius (1 - cos(pi / n)) of the sphere;
+    kind "torus": major radius `radius`, tube radius tube * radius, n x n // 2 quads split in two (n * (n // 2) * 2 faces;
+    not convex, it hides parts of itself).  winding "ccw": outward normals by the right-hand rule; "cw": every face
+    reversed; "mixed": every other face reversed."""
+    n = int(n)
+    if n < 4:
+        raise ValueError(f"make_mesh: n={n} must be at least 4")
+    if kind == "sphere":
+        seg, rings = 3 * n, (3 * n + 1) // 2
+        th = np.pi * np.arange(1, rings) / rings
+        ph = 2 * np.pi * np.arange(seg) / seg
+        ring = np.stack([np.outer(np.sin(th), np.cos(ph)), np.outer(np.sin(th), np.sin(ph)),
+                         np.outer(np.cos(th), np.ones(seg))], axis=-1).reshape(-1, 3)
+        verts = radius * np.concatenate([[[0.0, 0.0, 1.0]], ring, [[0.0, 0.0, -1.0]]])
+        south = len(verts) - 1
+        at = lambda i, j: 1 + i * seg + j % seg
+        faces = []
+        for j in range(seg):
+            faces.append((0, at(0, j), at(0, j + 1)))
+            for i in range(rings - 2):
+                faces.append((at(i, j), at(i + 1, j), at(i + 1, j + 1)))
+                faces.append((at(i, j), at(i + 1, j + 1), at(i, j + 1)))
+            faces.append((south, at(rings - 2, j + 1), at(rings - 2, j)))
+    elif kind == "torus":
+        m = max(n // 2, 3)
+        u = 2 * np.pi * np.arange(n) / n
+        v = 2 * np.pi * np.arange(m) / m
+        cu, su = np.cos(u)[:, None], np.sin(u)[:, None]
+        rr = radius * (1 + tube * np.cos(v))[None, :]
+        verts = np.stack([rr * cu, rr * su, np.broadcast_to(radius * tube * np.sin(v)[None, :], (n, m))], axis=-1).reshape(-1, 3)
+        at = lambda i, j: (i % n) * m + j % m
+        faces = []
+        for i in range(n):
+            for j in range(m):
+                faces.append((at(i, j), at(i + 1, j), at(i + 1, j + 1)))
+                faces.append((at(i, j), at(i + 1, j + 1), at(i, j + 1)))
+    else:
+        raise ValueError(f"make_mesh: kind={kind!r} ('sphere' or 'torus')")
+    faces = np.asarray(faces, np.int32)
+    if winding == "cw":
+        faces = faces[:, [0, 2, 1]]
+    elif winding == "mixed":
+        faces[1::2] = faces[1::2][:, [0, 2, 1]]
+    elif winding != "ccw":
+        raise ValueError(f"make_mesh: winding={winding!r} ('ccw', 'cw' or 'mixed')")
+    return np.ascontiguousarray(verts, np.float64), np.ascontiguousarray(faces)

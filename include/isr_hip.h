@@ -621,6 +621,31 @@ int isr_icp_point_to_point_batch(const float* src, size_t src_item_stride, int N
 int isr_rel_pose_table(const double* R, const double* t, int n, int i0, int i1, int mode,
                        double* out, isr_stream_t stream);
 
+/* ---- object-coordinate renderer (csrc/render_coords.hip, rules in csrc/raster.hpp) ----
+ * renderer.py:37-117 (ObjCoordRenderer.render) without GL: the triangle mesh verts (n_vert, 3) f32, faces (n_face, 3) i32 is
+ * drawn at B poses Rt (B, 12: [R|t] row-major, f64) with B cameras K (B, 9 row-major, f64; cv convention, the centre of
+ * pixel (row r, col c) is (u, v) = (c, r), row 0 on top) into B frame buffers of h x w pixels.  offset3 (3) f32 and scale are
+ * the object's: the colour is (vertex - offset) / scale, perspective-correct, alpha 1 where the mesh is visible.
+ * `state` is the frame buffer, one block of (5*h*w + 4) 4-byte words per item: h*w*4 f32 colour (r, g, b, a per pixel) |
+ * h*w f32 depth (camera z, 0 where empty) | 4 i32 counters {faces drawn, faces dropped at the near plane, pixels covered, 0}.
+ * clear = 1: every byte of the block is written, whatever it held.  clear = 0: the draw goes on top of the colour and depth
+ * already there (a pixel counts as covered when its alpha is 1 and its depth positive; on equal f32 depth the pixel already
+ * there wins), the first two counters go on counting and the third counts the covered pixels of the result.
+ * Sub-pixel grid 1/256 px, top-left fill rule, no culling, z-buffer key (f32 depth, face index) with the lower index winning
+ * ties, fragments outside [near_, far_] discarded, a face with a vertex at z < near_ (or off the snapped grid, or with a
+ * vertex index outside [0, n_vert)) dropped whole and counted.  Item b's block depends only on its own pose and camera and
+ * equals isr_render_coords_host's bit for bit.  No float atomics: results are the same run to run.
+ * B = 0 is a no-op; B <= 65535, h, w <= 16384, 0 < near_ <= far_.  Workspace: isr_render_coords_batch_workspace_bytes
+ * (8 bytes per pixel and item), 0 for non-positive sizes; its contents on entry do not matter. */
+size_t isr_render_coords_batch_workspace_bytes(int n_vert, int n_face, int h, int w, int B);
+int isr_render_coords_batch(const float* verts, int n_vert, const int32_t* faces, int n_face, const double* K,
+                            const double* Rt, int B, int h, int w, const float* offset3, float scale, double near_,
+                            double far_, int clear, void* state, void* ws, size_t ws_bytes, isr_stream_t stream);
+/* The same rasteriser as host code (no device): HOST pointers, one item (K (9), Rt (12), one state block). */
+int isr_render_coords_host(const float* verts, int n_vert, const int32_t* faces, int n_face, const double* K,
+                           const double* Rt, int h, int w, const float* offset3, float scale, double near_, double far_,
+                           int clear, void* state);
+
 #ifdef __cplusplus
 }
 #endif
