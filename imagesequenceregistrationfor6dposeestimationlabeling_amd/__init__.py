@@ -3,4 +3,7 @@ def __getattr__(name):
     if name in ("ObjCoordRenderer", "Mesh"):
         from . import render
         return getattr(render, name)
+    if name == "KeyField":
+        from . import fields
+        return fields.KeyField
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

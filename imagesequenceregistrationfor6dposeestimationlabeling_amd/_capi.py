@@ -132,6 +132,15 @@ SIGNATURES = {
     "isr_render_coords_host": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _f, _d, _d, _i, _vp]),
 }
 
+# include/isr_field.h (the key field), bound beside SIGNATURES: isr_hip.h's entry list stays what it is
+FIELD_SIGNATURES = {
+    "isr_field_pack_bytes": (_sz, [_i, _vp]),
+    "isr_field_pack": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "isr_field_eval": (_i, [_vp, _sz, _i, _vp, _vp, _i, _vp, _i, _vp]),
+    "isr_field_eval_host": (_i, [_vp, _sz, _i, _vp, _vp, _i, _vp, _i]),
+    "isr_field_sin_host": (_i, [_vp, _sz, _vp]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libisr_hip.so (once).  Raises IsrError when it has not been built."""
@@ -147,7 +156,7 @@ def lib() -> C.CDLL:
         L = C.CDLL(str(LIB_PATH))
     except OSError as e:  # pragma: no cover
         raise IsrError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

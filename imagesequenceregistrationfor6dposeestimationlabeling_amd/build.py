@@ -65,7 +65,7 @@ def build_hip(force: bool = False, verbose: bool = False, jobs: int = 4) -> Path
     """Compile every csrc/*.hip for gfx950 and link libisr_hip.so.  Returns the library path."""
     hipcc = _hipcc()
     OBJ_DIR.mkdir(exist_ok=True)
-    headers = sorted(CSRC.glob("*.hpp")) + [PKG_DIR.parent / "include" / "isr_hip.h"]
+    headers = sorted(CSRC.glob("*.hpp")) + sorted((PKG_DIR.parent / "include").glob("*.h"))
     srcs = sources()
     objs = [OBJ_DIR / (s.stem + ".o") for s in srcs]
 

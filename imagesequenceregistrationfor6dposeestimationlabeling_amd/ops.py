@@ -1123,3 +1123,29 @@ def render_coords_host(verts, faces, K, Rt, h: int, w: int, offset, scale: float
     check(lib().isr_render_coords_host(vp(v), v.shape[0], vp(f), f.shape[0], vp(k), vp(rt), h, w, vp(o), float(scale),
                                        float(near), float(far), 1 if clear else 0, vp(state)), "isr_render_coords_host")
     return state
+
+
+def field_flops(widths) -> float:
+    """Multiply-adds x 2 of one point through a field of these widths."""
+    return 2.0 * sum(int(a) * int(b) for a, b in zip(widths[:-1], widths[1:]))
+
+
+def field_eval(pack: torch.Tensor, widths, points: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """isr_field_eval: points (N,3) f32 through the packed field (`pack`: the device copy of isr_field_pack's bytes for these
+    `widths`, fields.KeyField builds it) -> out (N, ld) f32, ld >= widths[-1] (allocated (N, widths[-1]) when None); only
+    columns < widths[-1] are written."""
+    dev = require_cuda(pack, points, out)
+    if points.dtype != torch.float32 or points.ndim != 2 or points.shape[1] != 3 or not points.is_contiguous():
+        raise ValueError(f"field_eval: points must be contiguous (N,3) float32, got {tuple(points.shape)} {points.dtype}")
+    N, o = points.shape[0], int(widths[-1])
+    if out is None:
+        out = torch.empty((N, o), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.ndim != 2 or out.shape[0] != N or not out.is_contiguous():
+        raise ValueError(f"field_eval: out must be contiguous ({N}, >= {o}) float32, got {tuple(out.shape)} {out.dtype}")
+    w = (ctypes.c_int32 * len(widths))(*[int(v) for v in widths])
+    with torch.cuda.device(dev), _timed("field_eval", N * field_flops(widths)):
+        rc = lib().isr_field_eval(ptr(pack), pack.numel() * pack.element_size(), len(widths) - 1,
+                                  ctypes.cast(w, ctypes.c_void_p), ptr(points) if N else None, N, ptr(out) if N else None,
+                                  out.shape[1], current_stream(dev))
+    check(rc, "isr_field_eval")
+    return out

@@ -22,6 +22,7 @@ from scipy.optimize import minimize
 
 from . import ops
 from ._capi import check, current_stream, lib, ptr, require_cuda
+from .fields import KeyField
 from .registration import _dev
 
 
@@ -300,8 +301,10 @@ def refine_poses(Rs, ts, query_imgs, renderer, obj_idx, K_crops, obj_, neural_ra
     range(B)): the same renderer / batched_customForward calls per image, the same key sample and denominator image, the same
     objective bits, the same scipy run.  A renderer with render_batch (render.ObjCoordRenderer) draws the block's images in
     one call and their visible coordinates are compacted on the device; any other renderer is called once per image as
-    refine_pose calls it.  Returns a list of B (R, t, fun).  stats (a dict, optional) receives rounds,
-    n_eval (item evaluations per image) and launches.
+    refine_pose calls it.  A fields.KeyField as neural_radiance_field evaluates the block's visible points in one call (its
+    rows are independent, so the slices are the per-image bits); any other field is called once per image.
+    Returns a list of B (R, t, fun).  stats (a dict, optional) receives rounds, n_eval (item evaluations per image) and
+    launches.
     optimizer="device": the same renders, keys, key samples and denominator images, then ONE isr_refine_bfgs_batch call —
     scipy's BFGS ported to a per-item state machine that runs on the device (one objective launch and one step launch per
     round, the host reads the live count once per 8 rounds).  Each image's result equals bfgs_host driven by
@@ -331,6 +334,7 @@ def refine_poses(Rs, ts, query_imgs, renderer, obj_idx, K_crops, obj_, neural_ra
     ts = [np.asarray(t, np.float64).reshape(3) for t in ts]
     # the renders first: an image with nothing visible fails before anything is launched
     Xs, keys = [], []
+    block_field = isinstance(neural_radiance_field, KeyField)     # its rows are independent: the block's points in ONE call
     if hasattr(renderer, "render_batch"):
         # one call for the block's images; the visible coordinates never leave the device until the field's input is formed
         imgs = renderer.render_batch(obj_idx, Ks, Rs_in, ts).to(dev)
@@ -345,9 +349,13 @@ def refine_poses(Rs, ts, query_imgs, renderer, obj_idx, K_crops, obj_, neural_ra
         coord_masked = coord_norm_masked * obj_.scale + torch.from_numpy(np.asarray(obj_.offset)).to(dev)
         coord_nerf = torch.from_numpy((coord_masked.cpu().numpy() * 1.8 / obj_.diameter).astype("float32")).to(dev)
         X_block = coord_masked.float()
+        feat_block = neural_radiance_field.batched_customForward(coord_nerf) if block_field else None
         for b in range(B):
             lo, hi = int(ends[b] - counts[b]), int(ends[b])
-            feat = neural_radiance_field.batched_customForward(coord_nerf[lo:hi].clone()).detach().clone()
+            if block_field:
+                feat = feat_block[lo:hi]
+            else:
+                feat = neural_radiance_field.batched_customForward(coord_nerf[lo:hi].clone()).detach().clone()
             Xs.append(X_block[lo:hi])
             keys.append(feat[..., :feat.shape[-1] - 1].float())
     else:
@@ -359,13 +367,20 @@ def refine_poses(Rs, ts, query_imgs, renderer, obj_idx, K_crops, obj_, neural_ra
             if not mask.any():
                 raise ValueError(f"refine_poses: image {b} renders no visible surface point at its start pose")
             renders.append((coord_img, mask))
+        nerf_in = []
         for coord_img, mask in renders:                     # pose_refine.py:38-53, per image, as refine_pose does it
             coord_norm_masked = torch.from_numpy(np.ascontiguousarray(coord_img[..., :3][mask])).to(dev)
             coord_masked = coord_norm_masked * obj_.scale + torch.from_numpy(np.asarray(obj_.offset)).to(dev)
             coord_nerf = torch.from_numpy((coord_masked.cpu().numpy() * 1.8 / obj_.diameter).astype("float32")).to(dev)
-            feat = neural_radiance_field.batched_customForward(coord_nerf).detach().clone()
             Xs.append(coord_masked.float())
+            if block_field:
+                nerf_in.append(coord_nerf)
+                continue
+            feat = neural_radiance_field.batched_customForward(coord_nerf).detach().clone()
             keys.append(feat[..., :feat.shape[-1] - 1].float())
+        if block_field:
+            feat_block = neural_radiance_field.batched_customForward(torch.cat(nerf_in))
+            keys = [f[..., :f.shape[-1] - 1] for f in feat_block.split([x.shape[0] for x in nerf_in])]
     # the B lse-only denominator calls back to back (each image's own key sample: its generator), no host synchronise
     keys_verts = _dev(keys_verts, torch.float32)
     denoms = []
