@@ -141,6 +141,14 @@ FIELD_SIGNATURES = {
     "isr_field_sin_host": (_i, [_vp, _sz, _vp]),
 }
 
+# include/isr_fps.h (farthest-point sampling), bound the same way
+FPS_SIGNATURES = {
+    "isr_fps_workspace_bytes": (_sz, [_i, _i]),
+    "isr_fps_sample": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "isr_fps_sample_host": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "isr_fps_launch_floor": (_i, [_i, _vp]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libisr_hip.so (once).  Raises IsrError when it has not been built."""
@@ -156,7 +164,7 @@ def lib() -> C.CDLL:
         L = C.CDLL(str(LIB_PATH))
     except OSError as e:  # pragma: no cover
         raise IsrError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES, **FPS_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

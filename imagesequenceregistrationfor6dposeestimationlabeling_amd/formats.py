@@ -24,6 +24,25 @@ def load_model(UH, dataset: str, objid, base: Path | str = "."):
     return pts, feats, (np.load(nrm) if nrm.exists() else None)
 
 
+def save_model(pts, feats, normals, UH, dataset: str, objid, base: Path | str = ".") -> Path:
+    """The writer of what load_model reads (genFeat.py:226-228): vert1_scaled.npy (N,3) f32, feat1_scaled.npy (N,D) f32 and,
+    unless `normals` is None, normals_scaled.npy (N,3) f64, in <base>/<UH>_<dataset>_obj_<objid>/<objid>poseEst/.
+    Returns that directory."""
+    pts, feats = np.asarray(pts, np.float32), np.asarray(feats, np.float32)
+    if pts.ndim != 2 or pts.shape[1] != 3 or feats.ndim != 2 or feats.shape[0] != pts.shape[0]:
+        raise ValueError(f"save_model: pts {pts.shape} and feats {feats.shape}")
+    d = Path(base) / root_dir(UH, dataset, objid) / f"{objid}poseEst"
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "vert1_scaled.npy", pts)
+    np.save(d / "feat1_scaled.npy", feats)
+    if normals is not None:
+        normals = np.asarray(normals, np.float64)
+        if normals.shape != pts.shape:
+            raise ValueError(f"save_model: normals {normals.shape} for pts {pts.shape}")
+        np.save(d / "normals_scaled.npy", normals)
+    return d
+
+
 def is_failure(R, t=None) -> bool:
     """pnp()'s failure sentinel is the int triple (1, 1, 1) (inference.py:130-134)."""
     return isinstance(R, (int, np.integer)) or np.ndim(R) == 0

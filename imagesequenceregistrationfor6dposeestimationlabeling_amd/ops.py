@@ -1149,3 +1149,57 @@ def field_eval(pack: torch.Tensor, widths, points: torch.Tensor, out: torch.Tens
                                   out.shape[1], current_stream(dev))
     check(rc, "isr_field_eval")
     return out
+
+
+def _host_i32(v, B: int, what: str):
+    """A HOST (B,) int32 array for the C ABI (None stays None)."""
+    if v is None:
+        return None
+    a = np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v).astype(np.int64).reshape(-1)
+    if a.size != B:
+        raise ValueError(f"fps_sample: {what} has {a.size} entries for {B} clouds")
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError(f"fps_sample: {what} does not fit int32")
+    return np.ascontiguousarray(a, np.int32)
+
+
+def fps_sample(points: torch.Tensor, K: int, lengths=None, start=None, want_radius: bool = False):
+    """isr_fps_sample: farthest-point sampling of points (B,M,3) or (M,3) f32 -> idx (B,K) or (K,) int32, and with
+    want_radius (idx, radius2) with radius2 f32 of the same shape (csrc/fps.hpp states the rule; rows k >= length hold -1 / 0).
+    lengths, start: HOST integers per cloud (array-like, or a tensor that is copied to the host), None = all M / 0.
+    K - 1 dependent steps, one launch each, on the current stream; nothing synchronises."""
+    dev = require_cuda(points)
+    single = points.ndim == 2
+    pts = _f32c(points.unsqueeze(0) if single else points)
+    if pts.ndim != 3 or pts.shape[2] != 3:
+        raise ValueError(f"fps_sample: points must be (B,M,3) or (M,3), got {tuple(points.shape)}")
+    B, M, K = pts.shape[0], pts.shape[1], int(K)
+    lens, st = _host_i32(lengths, B, "lengths"), _host_i32(start, B, "start")
+    L = lib()
+    idx = torch.empty((B, max(K, 0)), dtype=torch.int32, device=dev)
+    rad = torch.empty((B, max(K, 0)), dtype=torch.float32, device=dev) if want_radius else None
+    nbytes = L.isr_fps_workspace_bytes(B, M)
+    ws = workspace(dev, nbytes, "fps")
+    hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    with torch.cuda.device(dev), _timed("fps_sample", float(B) * M * max(K - 1, 0)):
+        rc = L.isr_fps_sample(ptr(pts), B, M, hp(lens), hp(st), K, ptr(idx), ptr(rad), ptr(ws), ws.numel(), current_stream(dev))
+    check(rc, "isr_fps_sample")
+    if single:
+        idx, rad = idx[0], (None if rad is None else rad[0])
+    return (idx, rad) if want_radius else idx
+
+
+def fps_sample_host(points, K: int, lengths=None, start=None):
+    """isr_fps_sample_host: the same sampling as host code, NumPy (B,M,3) or (M,3) -> (idx int32, radius2 f32).  For tests."""
+    p = np.ascontiguousarray(points, np.float32)
+    single = p.ndim == 2
+    p = p[None] if single else p
+    if p.ndim != 3 or p.shape[2] != 3:
+        raise ValueError(f"fps_sample_host: points must be (B,M,3) or (M,3), got {p.shape}")
+    B, M, K = p.shape[0], p.shape[1], int(K)
+    lens, st = _host_i32(lengths, B, "lengths"), _host_i32(start, B, "start")
+    idx = np.empty((B, max(K, 0)), np.int32)
+    rad = np.empty((B, max(K, 0)), np.float32)
+    hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    check(lib().isr_fps_sample_host(hp(p), B, M, hp(lens), hp(st), K, hp(idx), hp(rad)), "isr_fps_sample_host")
+    return (idx[0], rad[0]) if single else (idx, rad)

@@ -56,6 +56,31 @@ class Mesh:
         self.scale = float(r if scale is None else scale)
         self.diameter = float(2 * self.scale if diameter is None else diameter)
 
+    def vertex_normals(self) -> np.ndarray:
+        """(V,3) f64 unit vertex normals: the sum of the adjacent faces' unit normals (right-hand rule over the face's vertex
+        order), each weighted by the face's corner angle at the vertex, normalised.  This is what trimesh's default
+        Trimesh.vertex_normals computes, which genFeat.py:209-210 saves for the keys (restated from memory of trimesh: it is
+        not installed beside this package to compare against).  A zero-area face contributes nothing; a vertex with no face,
+        or whose weighted normals cancel, gets (0, 0, 0)."""
+        v, f = self.mesh.vertices, self.mesh.faces.astype(np.int64)
+        out = np.zeros_like(v)
+        if len(f) == 0:
+            return out
+        p = v[f]                                                  # (F, 3 corners, 3)
+        n = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+        area2 = np.linalg.norm(n, axis=1)
+        ok = area2 > 0
+        n[ok] /= area2[ok, None]
+        for c in range(3):
+            e1, e2 = p[:, (c + 1) % 3] - p[:, c], p[:, (c + 2) % 3] - p[:, c]
+            l1, l2 = np.linalg.norm(e1, axis=1), np.linalg.norm(e2, axis=1)
+            cos = np.einsum("ij,ij->i", e1[ok], e2[ok]) / (l1[ok] * l2[ok])     # area > 0: both edges have length
+            np.add.at(out, f[ok, c], n[ok] * np.arccos(np.clip(cos, -1.0, 1.0))[:, None])
+        ln = np.linalg.norm(out, axis=1)
+        nz = ln > 0
+        out[nz] /= ln[nz, None]
+        return out
+
 
 class ObjCoordRenderer:
     """renderer.py:37-117.  objs[i] has .mesh.vertices, .mesh.faces, .offset, .scale (the reference's Obj, or Mesh above).

@@ -289,3 +289,17 @@ def make_mesh(kind, n, winding="ccw", radius=60.0, tube=0.4):
     elif winding != "ccw":
         raise ValueError(f"make_mesh: winding={winding!r} ('ccw', 'cw' or 'mixed')")
     return np.ascontiguousarray(verts, np.float64), np.ascontiguousarray(faces)
+
+
+def sample_surface(verts, faces, n, rng, noise=0.0, return_faces=False):
+    """n points on a triangle mesh, uniform over its area (faces drawn by area, then uniform barycentric coordinates), each
+    moved by isotropic Gaussian noise of that sigma -> (n,3) f64; with return_faces also the face index of every point."""
+    v, f = np.asarray(verts, np.float64), np.asarray(faces, np.int64)
+    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    area = np.linalg.norm(np.cross(b - a, c - a), axis=1)
+    fi = rng.choice(len(f), size=int(n), p=area / area.sum())
+    r1, r2 = np.sqrt(rng.uniform(size=int(n)))[:, None], rng.uniform(size=int(n))[:, None]
+    pts = (1 - r1) * a[fi] + r1 * (1 - r2) * b[fi] + r1 * r2 * c[fi]
+    if noise:
+        pts = pts + noise * rng.normal(size=pts.shape)
+    return (pts, fi) if return_faces else pts
