@@ -3,13 +3,13 @@ def __getattr__(name):
     if name in ("ObjCoordRenderer", "Mesh"):
         from . import render
         return getattr(render, name)
-    if name == "KeyField":
+    if name in ("KeyField", "DensityField"):
         from . import fields
-        return fields.KeyField
+        return getattr(fields, name)
     if name in ("sample_farthest_points", "thin_keys"):
         from . import sampling
         return getattr(sampling, name)
-    if name == "export_keys":
+    if name in ("export_keys", "collect_candidates"):
         from . import key_export
-        return key_export.export_keys
+        return getattr(key_export, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -149,6 +149,18 @@ FPS_SIGNATURES = {
     "isr_fps_launch_floor": (_i, [_i, _vp]),
 }
 
+# include/isr_density.h (the density field and its ray march), bound the same way
+DENSITY_SIGNATURES = {
+    "isr_density_pack_bytes": (_sz, [_i, _vp, _i]),
+    "isr_density_pack": (_i, [_i, _vp, _i, _vp, _f, _vp, _vp, _vp, _sz]),
+    "isr_density_eval": (_i, [_vp, _sz, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "isr_density_march": (_i, [_vp, _sz, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "isr_density_eval_host": (_i, [_vp, _sz, _i, _vp, _i, _vp, _i, _vp]),
+    "isr_density_march_host": (_i, [_vp, _sz, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "isr_density_sincos_host": (_i, [_vp, _sz, _vp, _vp]),
+    "isr_density_activations_host": (_i, [_vp, _sz, _f, _vp, _vp]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libisr_hip.so (once).  Raises IsrError when it has not been built."""
@@ -164,7 +176,7 @@ def lib() -> C.CDLL:
         L = C.CDLL(str(LIB_PATH))
     except OSError as e:  # pragma: no cover
         raise IsrError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES, **FPS_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES, **FPS_SIGNATURES, **DENSITY_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -93,3 +93,130 @@ class KeyField:
         check(lib().isr_field_eval_host(_vp(self.pack_host), self.pack_host.nbytes, self.n_layers, _vp(self._w), _vp(pts),
                                         pts.shape[0], _vp(out), self.out_features), "isr_field_eval_host")
         return out
+
+
+class DensityField:
+    """The density head of the reference's NeuralRadianceFieldFeat as a device-resident field: HarmonicEmbedding(H) ->
+    Linear + Softplus(beta) per hidden layer -> Linear(., 1) + Softplus(beta) -> 1 - exp(-x) (nerf.py:106-144, :163-177,
+    :206-228), evaluated by one kernel launch, and the ray march that turns it into surface points (pren.py:338-365 as
+    genFeat.py:185-198 and generateCors.py:299-334 use it).  weights[l] (out_l, in_l) and biases[l] for the hidden layers
+    (in_0 = 6 H, at most 4 layers of at most 256), then the output row (1, in) and its bias; frequencies (H,) f32, H <= 64."""
+
+    def __init__(self, weights, biases, frequencies, beta=10.0, device=None):
+        host = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, np.float32)
+        if len(weights) != len(biases) or len(weights) < 2:
+            raise ValueError(f"DensityField: {len(weights)} weights, {len(biases)} biases (hidden layers, then the output row)")
+        Ws, bs = [host(w) for w in weights], [host(b).reshape(-1) for b in biases]
+        self.frequencies = host(frequencies).reshape(-1)
+        self.H = int(self.frequencies.shape[0])
+        prev = 6 * self.H
+        for l, (w, b) in enumerate(zip(Ws, bs)):
+            if w.ndim != 2 or w.shape[1] != prev or b.shape[0] != w.shape[0]:
+                raise ValueError(f"DensityField: layer {l} has W {w.shape} and b {b.shape} after width {prev}")
+            prev = w.shape[0]
+        if prev != 1:
+            raise ValueError(f"DensityField: the last layer has {prev} outputs, the density is one")
+        self.widths = tuple(int(w.shape[0]) for w in Ws[:-1])
+        self.beta = float(beta)
+        L = lib()
+        self._w = np.asarray(self.widths, np.int32)
+        nbytes = L.isr_density_pack_bytes(len(self.widths), _vp(self._w), self.H)
+        if nbytes == 0:
+            raise IsrError(f"isr_density_pack_bytes failed: {L.isr_last_error().decode()}")
+        self.pack_host = np.empty(nbytes // 4, np.float32)
+        check(L.isr_density_pack(len(self.widths), _vp(self._w), self.H, _vp(self.frequencies), self.beta,
+                                 _vp(np.concatenate([w.reshape(-1) for w in Ws])), _vp(np.concatenate(bs)),
+                                 _vp(self.pack_host), nbytes), "isr_density_pack")
+        # device=None: host-only (eval_host / march_host, the tests' reference); there is no CPU fallback for the device calls
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type != "cuda":
+            raise IsrError(f"DensityField: device {self.device} is not a GPU (there is no CPU fallback)")
+        self.pack = None if self.device is None else torch.from_numpy(self.pack_host).to(self.device)
+
+    @classmethod
+    def from_linears(cls, hidden_linears, density_linear, n_harmonic=60, omega0=0.1, beta=10.0, device=None):
+        """From the torch.nn.Linear modules of the loaded network: model.mlp[0], model.mlp[2] and model.density_layer[0].
+        The frequencies are built as HarmonicEmbedding builds them (nerf.py:131-134)."""
+        linears = list(hidden_linears) + [density_linear]
+        if any(m.bias is None for m in linears):
+            raise ValueError("DensityField.from_linears: every layer needs a bias")
+        if device is None:
+            device = linears[0].weight.device
+        freqs = omega0 * (2.0 ** torch.arange(n_harmonic))
+        return cls([m.weight for m in linears], [m.bias for m in linears], freqs.to(torch.float32), beta, device)
+
+    def _need_device(self, *tensors):
+        if self.pack is None:
+            raise IsrError("DensityField was built without a device (device=None): only the _host calls are available")
+        require_cuda(self.pack, *tensors)
+
+    def _rows(self, points: torch.Tensor) -> torch.Tensor:
+        self._need_device(points)
+        if points.shape[-1] != 3:
+            raise ValueError(f"DensityField: points {tuple(points.shape)} must end in 3")
+        return points.to(torch.float32).reshape(-1, 3).contiguous()
+
+    def customForwardForDensity(self, points: torch.Tensor) -> torch.Tensor:
+        """nerf.py:417-432: points (..., 3) -> densities (..., 1), on the device."""
+        return ops.density_eval(self.pack, self.widths, self.H, self._rows(points)).reshape(*points.shape[:-1], 1)
+
+    def _bundle(self, origins, directions, lengths):
+        self._need_device(origins, directions, lengths)
+        if origins.shape[-1] != 3 or directions.shape != origins.shape or lengths.shape[:-1] != origins.shape[:-1]:
+            raise ValueError(f"DensityField: origins {tuple(origins.shape)}, directions {tuple(directions.shape)}, lengths "
+                             f"{tuple(lengths.shape)}: expected (..., 3), (..., 3), (..., P)")
+        f = lambda t, c: t.to(torch.float32).reshape(-1, c).contiguous()
+        return f(origins, 3), f(directions, 3), f(lengths, lengths.shape[-1])
+
+    def batched_forward_fordensity(self, ray_bundle, n_batches: int = 16):
+        """The reference's call of that name: any object with .origins, .directions (..., 3) and .lengths (..., P) ->
+        (densities (..., P, 1), zeros (..., P, 3)).  The points origins + directions * lengths are made in the kernel;
+        n_batches is accepted and changes nothing (rows are independent, the whole bundle is one launch)."""
+        o, d, ln = self._bundle(ray_bundle.origins, ray_bundle.directions, ray_bundle.lengths)
+        _, _, _, dens, _ = ops.density_march(self.pack, self.widths, self.H, o, d, ln, threshold=-1.0, want_densities=True)
+        shape = tuple(ray_bundle.lengths.shape)
+        return dens.reshape(*shape, 1), torch.zeros((*shape, 3), dtype=torch.float32, device=dens.device)
+
+    def grid_densities(self, res: int = 128) -> torch.Tensor:
+        """The (res, res, res) array batched_forward_forPC (nerf.py:676-700) hands to marching cubes, after its two
+        movedims: out[i, j, k] = density(t[i], t[j], t[k]), t = linspace(-1, 1, res) in f64 rounded to f32."""
+        self._need_device()
+        t = torch.from_numpy(np.linspace(-1, 1, int(res)).astype(np.float32)).to(self.device)
+        pts = torch.stack(torch.meshgrid(t, t, t, indexing="ij"), dim=-1).reshape(-1, 3).contiguous()
+        return ops.density_eval(self.pack, self.widths, self.H, pts).reshape(int(res), int(res), int(res))
+
+    def surface_points(self, origins, directions, lengths, threshold: float = 0.2, return_weights: bool = False,
+                       surface_thickness: int = 1):
+        """genFeat.py:191-193: origins + directions * max(lengths * weights) per ray -> (points (..., 3), depth (...),
+        hit (...) bool), and with return_weights the (..., P) weights of pren.py:365 as a fourth.  threshold >= 0 is the
+        reference's thresholdMode (0.2 there); a negative one gives the emission-absorption weights."""
+        if surface_thickness != 1:
+            raise ValueError("DensityField.surface_points: only surface_thickness = 1 is supported")
+        o, d, ln = self._bundle(origins, directions, lengths)
+        pts, depth, hit, _, wts = ops.density_march(self.pack, self.widths, self.H, o, d, ln, threshold=threshold,
+                                                    want_weights=return_weights)
+        lead = tuple(lengths.shape[:-1])
+        res = (pts.reshape(*lead, 3), depth.reshape(lead), hit.reshape(lead) != 0)
+        return res + (wts.reshape(lengths.shape),) if return_weights else res
+
+    def eval_host(self, points) -> np.ndarray:
+        """The same field by the host build of the same header (isr_density_eval_host): NumPy (N,3) -> (N,).  For tests."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        out = np.empty(pts.shape[0], np.float32)
+        check(lib().isr_density_eval_host(_vp(self.pack_host), self.pack_host.nbytes, len(self.widths), _vp(self._w), self.H,
+                                          _vp(pts), pts.shape[0], _vp(out)), "isr_density_eval_host")
+        return out
+
+    def march_host(self, origins, directions, lengths, threshold: float = 0.2):
+        """isr_density_march_host: NumPy (N,3), (N,3), (N,P) -> dict of points, depth, hit, densities, weights.  For tests."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        ln = np.ascontiguousarray(lengths, np.float32)
+        N, P = ln.shape
+        out = dict(points=np.empty((N, 3), np.float32), depth=np.empty(N, np.float32), hit=np.empty(N, np.int32),
+                   densities=np.empty((N, P), np.float32), weights=np.empty((N, P), np.float32))
+        check(lib().isr_density_march_host(_vp(self.pack_host), self.pack_host.nbytes, len(self.widths), _vp(self._w), self.H,
+                                           _vp(o), _vp(d), _vp(ln), N, P, float(threshold), _vp(out["densities"]),
+                                           _vp(out["weights"]), _vp(out["depth"]), _vp(out["points"]), _vp(out["hit"])),
+              "isr_density_march_host")
+        return out

@@ -52,3 +52,19 @@ def export_keys(candidates: torch.Tensor, mesh, field, diameter: float, K: int =
     feats = field.batched_customForward(pts)[..., :-1]
     scaled = pts.cpu().numpy() * np.float32(diameter / diam_scaling)
     return scaled, feats.detach().to(torch.float32).cpu().numpy(), normals, order.cpu().numpy()
+
+
+def collect_candidates(field, bundles, threshold: float = 0.2) -> torch.Tensor:
+    """genFeat.py:191-198: the surface point of every ray of every bundle (any objects with .origins, .directions (..., 3) and
+    .lengths (..., P); field a fields.DensityField), rays whose point did not leave the origin dropped (the reference's
+    `where(norm(point - origin))`: no hit, or a hit at depth 0), concatenated on the device in bundle order, rays in their
+    own order -> (M, 3) f32: export_keys' `candidates`."""
+    parts = []
+    for rb in bundles:
+        pts, _, _ = field.surface_points(rb.origins, rb.directions, rb.lengths, threshold=threshold)
+        pts = pts.reshape(-1, 3)
+        moved = torch.linalg.vector_norm(pts - rb.origins.to(torch.float32).reshape(-1, 3), dim=-1) != 0
+        parts.append(pts[moved])
+    if not parts:
+        raise ValueError("collect_candidates: no bundle")
+    return torch.cat(parts).contiguous()

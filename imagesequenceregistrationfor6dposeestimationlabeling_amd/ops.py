@@ -1151,6 +1151,66 @@ def field_eval(pack: torch.Tensor, widths, points: torch.Tensor, out: torch.Tens
     return out
 
 
+def density_flops(widths, H: int) -> float:
+    """Multiply-adds x 2 of one point through a density field: 6H -> widths... -> 1."""
+    w = [6 * int(H)] + [int(v) for v in widths] + [1]
+    return 2.0 * sum(a * b for a, b in zip(w[:-1], w[1:]))
+
+
+def _density_field_args(pack: torch.Tensor, widths):
+    w = (ctypes.c_int32 * len(widths))(*[int(v) for v in widths])
+    return ptr(pack), pack.numel() * pack.element_size(), len(widths), ctypes.cast(w, ctypes.c_void_p), w
+
+
+def density_eval(pack: torch.Tensor, widths, H: int, points: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """isr_density_eval: points (N,3) f32 through the packed density field (`pack`: the device copy of isr_density_pack's
+    bytes for these hidden `widths` and `H` frequencies, fields.DensityField builds it) -> out (N,) f32."""
+    dev = require_cuda(pack, points, out)
+    if points.dtype != torch.float32 or points.ndim != 2 or points.shape[1] != 3 or not points.is_contiguous():
+        raise ValueError(f"density_eval: points must be contiguous (N,3) float32, got {tuple(points.shape)} {points.dtype}")
+    N = points.shape[0]
+    if out is None:
+        out = torch.empty((N,), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.shape != (N,) or not out.is_contiguous():
+        raise ValueError(f"density_eval: out must be contiguous ({N},) float32, got {tuple(out.shape)} {out.dtype}")
+    pk, nbytes, nh, wp, _keep = _density_field_args(pack, widths)
+    with torch.cuda.device(dev), _timed("density_eval", N * density_flops(widths, H)):
+        rc = lib().isr_density_eval(pk, nbytes, nh, wp, int(H), ptr(points) if N else None, N, ptr(out) if N else None,
+                                    current_stream(dev))
+    check(rc, "isr_density_eval")
+    return out
+
+
+def density_march(pack: torch.Tensor, widths, H: int, origins: torch.Tensor, directions: torch.Tensor, lengths: torch.Tensor,
+                  threshold: float = 0.2, want_densities: bool = False, want_weights: bool = False):
+    """isr_density_march: origins (N,3), directions (N,3), lengths (N,P) f32 -> (points (N,3) f32, depth (N,) f32,
+    hit (N,) int32, densities (N,P) f32 or None, weights (N,P) f32 or None).  threshold >= 0: the weight is one at the first
+    density above it (the reference's thresholdMode); threshold < 0: emission-absorption weights."""
+    dev = require_cuda(pack, origins, directions, lengths)
+    for name, t, cols in (("origins", origins, 3), ("directions", directions, 3), ("lengths", lengths, None)):
+        if t.dtype != torch.float32 or t.ndim != 2 or (cols and t.shape[1] != cols) or not t.is_contiguous():
+            raise ValueError(f"density_march: {name} must be contiguous 2-d float32, got {tuple(t.shape)} {t.dtype}")
+    N, P = lengths.shape
+    if origins.shape[0] != N or directions.shape[0] != N:
+        raise ValueError(f"density_march: {origins.shape[0]} origins, {directions.shape[0]} directions, {N} rows of lengths")
+    if P < 1:
+        raise ValueError("density_march: P < 1")
+    thr = float(threshold)
+    if thr != thr:
+        raise ValueError("density_march: threshold is NaN")
+    f32 = dict(dtype=torch.float32, device=dev)
+    points, depth = torch.empty((N, 3), **f32), torch.empty((N,), **f32)
+    hit = torch.empty((N,), dtype=torch.int32, device=dev)
+    dens = torch.empty((N, P), **f32) if want_densities else None
+    wts = torch.empty((N, P), **f32) if want_weights else None
+    pk, nbytes, nh, wp, _keep = _density_field_args(pack, widths)
+    with torch.cuda.device(dev), _timed("density_march", float(N) * P * density_flops(widths, H)):
+        rc = lib().isr_density_march(pk, nbytes, nh, wp, int(H), ptr(origins), ptr(directions), ptr(lengths), N, P, thr,
+                                     ptr(dens), ptr(wts), ptr(depth), ptr(points), ptr(hit), current_stream(dev))
+    check(rc, "isr_density_march")
+    return points, depth, hit, dens, wts
+
+
 def _host_i32(v, B: int, what: str):
     """A HOST (B,) int32 array for the C ABI (None stays None)."""
     if v is None:
