@@ -9,7 +9,10 @@ def __getattr__(name):
     if name in ("sample_farthest_points", "thin_keys"):
         from . import sampling
         return getattr(sampling, name)
-    if name in ("export_keys", "collect_candidates"):
+    if name in ("export_keys", "collect_candidates", "extract_mesh"):
         from . import key_export
         return getattr(key_export, name)
+    if name == "marching_cubes":
+        from . import ops
+        return ops.marching_cubes
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

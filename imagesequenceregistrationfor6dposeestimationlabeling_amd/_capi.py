@@ -161,6 +161,15 @@ DENSITY_SIGNATURES = {
     "isr_density_activations_host": (_i, [_vp, _sz, _f, _vp, _vp]),
 }
 
+# include/isr_mc.h (iso-surface extraction), bound the same way
+MC_SIGNATURES = {
+    "isr_mc_workspace_bytes": (_sz, [_i, _i, _i]),
+    "isr_mc_count": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
+    "isr_mc_emit": (_i, [_vp, _i, _i, _i, _f, _vp, _sz, _vp, _i64, _vp, _i64, _vp]),
+    "isr_mc_count_host": (_i, [_vp, _i, _i, _i, _f, _vp]),
+    "isr_mc_emit_host": (_i, [_vp, _i, _i, _i, _f, _vp, _i64, _vp, _i64]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libisr_hip.so (once).  Raises IsrError when it has not been built."""
@@ -176,7 +185,8 @@ def lib() -> C.CDLL:
         L = C.CDLL(str(LIB_PATH))
     except OSError as e:  # pragma: no cover
         raise IsrError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES, **FPS_SIGNATURES, **DENSITY_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES, **FPS_SIGNATURES, **DENSITY_SIGNATURES,
+                               **MC_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

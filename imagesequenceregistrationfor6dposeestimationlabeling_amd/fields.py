@@ -185,6 +185,30 @@ class DensityField:
         pts = torch.stack(torch.meshgrid(t, t, t, indexing="ij"), dim=-1).reshape(-1, 3).contiguous()
         return ops.density_eval(self.pack, self.widths, self.H, pts).reshape(int(res), int(res), int(res))
 
+    def batched_forward_forPC(self, threshold: float = 0.1, res: int = 128, coords: str = "reference"):
+        """The reference's call of that name (nerf.py:640-703): grid_densities(res), then the iso-surface at `threshold` by
+        ops.marching_cubes (the package's own rule, csrc/mc_extract.hpp; mcubes may triangulate ambiguous cells differently
+        and orders its vertices differently) -> (mvertices (V,3) f64, mtriangles (F,3) int32), NumPy.  coords:
+          "reference": (v - res/2) / (res/2), the reference's own map (v - 64) / 64 (nerf.py:701) for any res.  It is NOT the
+                       grid's geometry: linspace(-1, 1, 128) has spacing 2/127, so index 127, the far face at +1, lands at
+                       0.984 and every distance is scaled by 127/128.  It is what the reference saves and what its later
+                       stages were tuned on;
+          "grid":      -1 + 2 v / (res - 1), where the densities were evaluated;
+          "index":     v, as marching cubes returns it."""
+        if coords not in ("reference", "grid", "index"):
+            raise ValueError(f"DensityField.batched_forward_forPC: coords = {coords!r} (reference, grid or index)")
+        res = int(res)
+        verts, tris = ops.marching_cubes(self.grid_densities(res), float(threshold))
+        return self._pc_coords(verts.cpu().numpy(), res, coords), tris.cpu().numpy()
+
+    @staticmethod
+    def _pc_coords(v: np.ndarray, res: int, coords: str) -> np.ndarray:
+        if coords == "reference":
+            return (v - res / 2) / (res / 2)
+        if coords == "grid":
+            return -1.0 + 2.0 * v / (res - 1)
+        return v
+
     def surface_points(self, origins, directions, lengths, threshold: float = 0.2, return_weights: bool = False,
                        surface_thickness: int = 1):
         """genFeat.py:191-193: origins + directions * max(lengths * weights) per ray -> (points (..., 3), depth (...),
@@ -206,6 +230,12 @@ class DensityField:
         check(lib().isr_density_eval_host(_vp(self.pack_host), self.pack_host.nbytes, len(self.widths), _vp(self._w), self.H,
                                           _vp(pts), pts.shape[0], _vp(out)), "isr_density_eval_host")
         return out
+
+    def grid_densities_host(self, res: int = 128) -> np.ndarray:
+        """grid_densities by eval_host: NumPy (res, res, res) f32, the same points in the same order.  For tests."""
+        t = np.linspace(-1, 1, int(res)).astype(np.float32)
+        pts = np.stack(np.meshgrid(t, t, t, indexing="ij"), axis=-1).reshape(-1, 3)
+        return self.eval_host(pts).reshape(int(res), int(res), int(res))
 
     def march_host(self, origins, directions, lengths, threshold: float = 0.2):
         """isr_density_march_host: NumPy (N,3), (N,3), (N,P) -> dict of points, depth, hit, densities, weights.  For tests."""

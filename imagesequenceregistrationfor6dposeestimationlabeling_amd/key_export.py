@@ -54,6 +54,15 @@ def export_keys(candidates: torch.Tensor, mesh, field, diameter: float, K: int =
     return scaled, feats.detach().to(torch.float32).cpu().numpy(), normals, order.cpu().numpy()
 
 
+def extract_mesh(density_field, threshold: float = 0.05, res: int = 128, coords: str = "reference"):
+    """genFeat.py:206-209: the density field's iso-surface as a render.Mesh, export_keys' `mesh`
+    (fields.DensityField.batched_forward_forPC explains `coords`), so that
+    export_keys(candidates, extract_mesh(df), key_field, diameter) is the whole of genFeat.py:201-224."""
+    from .render import Mesh
+    verts, tris = density_field.batched_forward_forPC(threshold=threshold, res=res, coords=coords)
+    return Mesh(verts, tris)
+
+
 def collect_candidates(field, bundles, threshold: float = 0.2) -> torch.Tensor:
     """genFeat.py:191-198: the surface point of every ray of every bundle (any objects with .origins, .directions (..., 3) and
     .lengths (..., P); field a fields.DensityField), rays whose point did not leave the origin dropped (the reference's

@@ -1263,3 +1263,59 @@ def fps_sample_host(points, K: int, lengths=None, start=None):
     hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
     check(lib().isr_fps_sample_host(hp(p), B, M, hp(lens), hp(st), K, hp(idx), hp(rad)), "isr_fps_sample_host")
     return (idx[0], rad[0]) if single else (idx, rad)
+
+
+def marching_cubes(vol: torch.Tensor, iso: float, check_finite: bool = True):
+    """isr_mc_count + isr_mc_emit: the iso-surface of vol (nx,ny,nz) f32 on the device at level iso (rounded to f32) -> (verts (V,3) f64 in
+    INDEX space, tris (F,3) int32), on the device; an empty surface gives (0,3) arrays.  The rule (csrc/mc_extract.hpp, the
+    table by tools/gen_mc_table.py) is the package's own: a corner is below when v < iso, the vertex of a crossing edge sits
+    at (iso - va) / (vb - va) in f64, vertices in the order of the owning grid point then axis, triangles in cell order,
+    right-hand normals pointing to the below side; a function of (vol, iso) only.  The totals are read between the two calls:
+    the one synchronise.  check_finite (one more) refuses non-finite values, which a meaningful surface takes as a
+    precondition."""
+    dev = require_cuda(vol)
+    v = _f32c(vol)
+    if v.ndim != 3 or min(v.shape) < 2 or max(v.shape) > 1024 or v.numel() > 2 ** 28:
+        raise ValueError(f"marching_cubes: vol must be (nx,ny,nz), every dimension 2..1024, at most 2^28 points, got "
+                         f"{tuple(vol.shape)}")
+    iso = float(iso)
+    if iso != iso:
+        raise ValueError("marching_cubes: iso is NaN")
+    if check_finite and not bool(torch.isfinite(v).all()):
+        raise ValueError("marching_cubes: non-finite values in vol (finite values are a precondition)")
+    nx, ny, nz = v.shape
+    L = lib()
+    ws = workspace(dev, L.isr_mc_workspace_bytes(nx, ny, nz), "mc")
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        with _timed("mc_count", float(v.numel())):
+            rc = L.isr_mc_count(ptr(v), nx, ny, nz, iso, ptr(counts), ptr(ws), ws.numel(), current_stream(dev))
+        check(rc, "isr_mc_count")
+        V, F = (int(c) for c in counts.cpu())
+        verts = torch.empty((V, 3), dtype=torch.float64, device=dev)
+        tris = torch.empty((F, 3), dtype=torch.int32, device=dev)
+        if V or F:
+            with _timed("mc_emit", float(v.numel())):
+                rc = L.isr_mc_emit(ptr(v), nx, ny, nz, iso, ptr(ws), ws.numel(), ptr(verts) if V else None, V,
+                                   ptr(tris) if F else None, F, current_stream(dev))
+            check(rc, "isr_mc_emit")
+    return verts, tris
+
+
+def marching_cubes_host(vol, iso: float, check_finite: bool = True):
+    """isr_mc_count_host + isr_mc_emit_host: the same extraction as host code, NumPy (nx,ny,nz) -> (verts (V,3) f64,
+    tris (F,3) int32).  For tests."""
+    v = np.ascontiguousarray(vol, np.float32)
+    if v.ndim != 3:
+        raise ValueError(f"marching_cubes_host: vol must be (nx,ny,nz), got {v.shape}")
+    if check_finite and not np.isfinite(v).all():
+        raise ValueError("marching_cubes_host: non-finite values in vol (finite values are a precondition)")
+    nx, ny, nz = v.shape
+    hp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    counts = np.empty(2, np.int32)
+    check(lib().isr_mc_count_host(hp(v), nx, ny, nz, float(iso), hp(counts)), "isr_mc_count_host")
+    V, F = int(counts[0]), int(counts[1])
+    verts, tris = np.empty((V, 3), np.float64), np.empty((F, 3), np.int32)
+    check(lib().isr_mc_emit_host(hp(v), nx, ny, nz, float(iso), hp(verts) if V else None, V, hp(tris) if F else None, F),
+          "isr_mc_emit_host")
+    return verts, tris
