@@ -1,13 +1,11 @@
 // field_density.hip — the density field (field_density.hpp) and the ray march on top of it, each ONE launch: the entries of
 // include/isr_density.h.
 //
-// field_mlp.hip's design: a workgroup takes a tile of 64 points through every layer, the tile's activations live in LDS, the
-// weights are streamed from the pack in matrix-core order, the bias sits in the accumulator and the k loop runs in order, so
-// v_mfma_f32_32x32x2_f32 gives the k-ordered fmaf chain bit for bit.  What differs:
+// field_tile.hpp's design with 8 waves per workgroup (512 threads, two per SIMD): wave w takes neuron block w of a 256-wide
+// layer over both point blocks.  What is the density field's own:
 //   * The first layer's input is the harmonic embedding, computed in the kernel into LDS (sincos32, one call per sine /
-//     cosine pair).  The activation buffer holds 384 k's x 64 points = 96 KB, so one workgroup is resident per CU; it has
-//     8 waves (512 threads), two per SIMD, and wave w takes neuron block w of a 256-wide layer over both point blocks.
-//     Neither the (N, 6H) embedding nor a hidden activation is ever in device memory.
+//     cosine pair).  The activation buffer holds 384 k's x 64 points = 96 KB, so one workgroup is resident per CU.  Neither
+//     the (N, 6H) embedding nor a hidden activation is ever in device memory.
 //   * Every hidden layer runs on the matrix cores, also a first layer narrower than 32 (K is padded to 8 with zero weights
 //     and zero activations).
 //   * The output neuron is a dot product on the vector unit: lane p of wave 0 runs the chain of point p.
@@ -18,64 +16,27 @@
 // would give by 0, so no output bit depends on it.
 // Rows past the end of a tile's work are evaluated at the origin and never written.
 #include "field_density.hpp"
+#include "field_tile.hpp"
 #include "isr_common.hpp"
 
 #include "../../include/isr_density.h"
 
-#include <thread>
 #include <vector>
 
 namespace {
 
 using namespace isr::density;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using isr::field::act_index;
+using isr::field::kTP;
 
-constexpr int kTP = 64;            // points per tile
 constexpr int kThreads = 512;
-constexpr int kWaves = kThreads / 64;
 constexpr int kActWords = (6 * kMaxH / 2) * kTP * 2;      // 96 KB
-
-__device__ __forceinline__ int act_index(int k, int p) { return ((k >> 1) * kTP + p) * 2 + (k & 1); }
-
-// One wave's share of a layer: neuron block mb x NNB blocks of 32 points from point block nb0.
-template <int NNB>
-__device__ __forceinline__ void mfma_block(const Layer& L, const float* __restrict__ Wl, const float* __restrict__ bl,
-                                           const float* act, int mb, int nb0, int lane, f32x16 (&acc)[2]) {
-  const int r = lane & 31, hh = lane >> 5;
-  const int S4 = L.kstride >> 3;
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const float bias = bl[mb * 32 + 8 * a + 4 * hh + b];
-#pragma unroll
-      for (int n = 0; n < NNB; ++n) acc[n][4 * a + b] = bias;
-    }
-  const float4* wp = reinterpret_cast<const float4*>(Wl) + (size_t)mb * S4 * 64 + lane;
-  float4 cur = wp[0];
-  const float* bp = act + (nb0 * 32 + r) * 2 + hh;
-  for (int s4 = 0; s4 < S4; ++s4) {
-    const int sn = s4 + 1 < S4 ? s4 + 1 : s4;
-    const float4 nxt = wp[(size_t)sn * 64];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float bv[NNB];
-#pragma unroll
-      for (int n = 0; n < NNB; ++n) bv[n] = bp[((4 * s4 + i) * kTP + n * 32) * 2];
-      const float av = i == 0 ? cur.x : i == 1 ? cur.y : i == 2 ? cur.z : cur.w;
-#pragma unroll
-      for (int n = 0; n < NNB; ++n) acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[n], acc[n], 0, 0, 0);
-    }
-    cur = nxt;
-  }
-}
 
 // The 64 points of ptl (LDS, coordinate-major: ptl[d * 64 + p]) through the field; density of point p -> dens[p] (LDS).
 // Every thread of the workgroup calls it; ptl may be rewritten after the call, dens is complete after the next barrier.
 __device__ __forceinline__ void tile_density(const Layout& lay, const float* __restrict__ pack, float* act, const float* ptl,
                                              float* dens) {
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const int r = lane & 31, hh = lane >> 5;
   const int H = lay.H;
   const float beta = pack[0];
   const float* freqs = pack + kFreqOff;
@@ -93,47 +54,8 @@ __device__ __forceinline__ void tile_density(const Layout& lay, const float* __r
   for (int i = tid; i < (lay.L[0].kstride - 6 * H) * kTP; i += kThreads) act[act_index(6 * H + (i >> 6), i & (kTP - 1))] = 0.f;
   __syncthreads();
 
-  for (int l = 0; l < lay.n_hidden; ++l) {
-    const Layer L = lay.L[l];
-    const float* Wl = pack + L.w_off;
-    const float* bl = pack + L.b_off;
-    const int MB = L.OP >> 5;
-    int mb, nb0, nnb;
-    if (MB > kWaves / 2) {        // a wave: one neuron block, both point blocks
-      mb = w;
-      nb0 = 0;
-      nnb = 2;
-    } else {                      // up to four neuron blocks: a wave takes one 32 x 32 tile
-      mb = w >> 1;
-      nb0 = w & 1;
-      nnb = 1;
-    }
-    const bool active = mb < MB;
-    f32x16 acc[2];
-    if (active) {
-      if (nnb == 2) mfma_block<2>(L, Wl, bl, act, mb, nb0, lane, acc);
-      else mfma_block<1>(L, Wl, bl, act, mb, nb0, lane, acc);
-    }
-    __syncthreads();              // every wave has read the layer's input: the outputs may take its place
-    if (active) {
-#pragma unroll
-      for (int n = 0; n < 2; ++n) {
-        if (n < nnb) {
-          const int p = (nb0 + n) * 32 + r;
-#pragma unroll
-          for (int a = 0; a < 4; ++a) {
-            const int j = mb * 32 + 8 * a + 4 * hh;
-            float v[4];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) v[b] = j + b < L.O ? softplus32(acc[n][4 * a + b], beta) : 0.f;
-            *reinterpret_cast<float2*>(&act[((j >> 1) * kTP + p) * 2]) = make_float2(v[0], v[1]);
-            *reinterpret_cast<float2*>(&act[(((j >> 1) + 1) * kTP + p) * 2]) = make_float2(v[2], v[3]);
-          }
-        }
-      }
-    }
-    __syncthreads();
-  }
+  for (int l = 0; l < lay.n_hidden; ++l)
+    isr::field::mfma_tile_layer<kThreads / 64>(lay.L[l], pack, act, false, [=](float z) { return softplus32(z, beta); });
 
   if (w == 0) {                   // the output neuron: the chain itself, lane = point
     const float* wo = pack + lay.out_w_off;
@@ -217,20 +139,17 @@ __global__ __launch_bounds__(kThreads) void density_march_kernel(Layout lay, con
 
 // the checks every entry shares; on success lay is filled
 int check_field(const char* who, const void* pack, size_t pack_bytes, int n_hidden, const int32_t* widths, int H, Layout& lay) {
-  ISR_REQUIRE(pack && widths, "%s: null pointer", who);
+  if (int rc = isr::check_pack_pointers(who, pack, widths)) return rc;
   ISR_REQUIRE(make_layout(n_hidden, widths, H, lay), "%s: %d hidden layers (1..%d), a width outside 1..%d or H = %d outside 1..%d",
               who, n_hidden, kMaxHidden, kMaxWidth, H, kMaxH);
-  ISR_REQUIRE(pack_bytes == (size_t)lay.total_words * 4, "%s: pack_bytes %zu, this field packs to %zu", who, pack_bytes,
-              (size_t)lay.total_words * 4);
-  return ISR_OK;
+  return isr::check_pack_bytes(who, pack_bytes, lay.total_words);
 }
 
 int check_march(const char* who, const float* origins, const float* directions, const float* lengths, int N, int P,
                 float threshold, const float* depth, const float* points, const int32_t* hit) {
-  ISR_REQUIRE(N >= 0, "%s: N = %d", who, N);
+  if (int rc = isr::check_rows(who, N, origins && directions && lengths && depth && points && hit)) return rc;
   ISR_REQUIRE(P >= 1 && P <= kMaxP, "%s: P = %d (1..%d)", who, P, kMaxP);
   ISR_REQUIRE(threshold == threshold, "%s: threshold is NaN", who);
-  ISR_REQUIRE(N == 0 || (origins && directions && lengths && depth && points && hit), "%s: null pointer", who);
   return ISR_OK;
 }
 
@@ -239,13 +158,10 @@ struct HostField {
   HostWeights hw;
   bool fma;
   HostField(const Layout& lay, const void* pack) {
-    const float* pf = static_cast<const float*>(pack);
     wt.resize(lay.n_hidden);
     for (int l = 0; l < lay.n_hidden; ++l) {
-      const Layer& L = lay.L[l];
-      wt[l].resize((size_t)L.O * L.K);
-      for (int j = 0; j < L.O; ++j)
-        for (int k = 0; k < L.K; ++k) wt[l][(size_t)k * L.O + j] = pf[L.w_off + w_index(L, j, k)];
+      wt[l].resize((size_t)lay.L[l].O * lay.L[l].K);
+      isr::field::unpack_layer(lay.L[l], static_cast<const float*>(pack), wt[l].data(), true);
       hw.Wt[l] = wt[l].data();
     }
 #ifdef ISR_DENSITY_HAVE_FMA_BUILD
@@ -255,24 +171,6 @@ struct HostField {
 #endif
   }
 };
-
-// fn(i) for i in [0, n) over a few threads
-template <class F>
-void parallel_rows(long n, long per_thread_min, F fn) {
-  const int nthreads = n >= 8 * per_thread_min ? 8 : 1;
-  if (nthreads == 1) {
-    for (long i = 0; i < n; ++i) fn(i);
-    return;
-  }
-  std::vector<std::thread> pool;
-  for (int t = 0; t < nthreads; ++t) {
-    const long n0 = n * t / nthreads, n1 = n * (t + 1) / nthreads;
-    pool.emplace_back([=] {
-      for (long i = n0; i < n1; ++i) fn(i);
-    });
-  }
-  for (auto& th : pool) th.join();
-}
 
 float point_host(const Layout& lay, const void* pack, const HostField& hf, const float* x) {
 #ifdef ISR_DENSITY_HAVE_FMA_BUILD
@@ -307,8 +205,7 @@ extern "C" int isr_density_eval(const void* pack, size_t pack_bytes, int n_hidde
                                 int N, float* out, isr_stream_t stream) {
   Layout lay;
   if (int rc = check_field("isr_density_eval", pack, pack_bytes, n_hidden, widths, H, lay)) return rc;
-  ISR_REQUIRE(N >= 0, "isr_density_eval: N = %d", N);
-  ISR_REQUIRE(N == 0 || (pts && out), "isr_density_eval: null pointer");
+  if (int rc = isr::check_rows("isr_density_eval", N, pts && out)) return rc;
   if (N == 0) return ISR_OK;
   const unsigned blocks = (unsigned)(((long)N + kTP - 1) / kTP);
   density_eval_kernel<<<blocks, kThreads, 0, isr::as_stream(stream)>>>(lay, static_cast<const float*>(pack), pts, N, out);
@@ -337,11 +234,10 @@ extern "C" int isr_density_eval_host(const void* pack, size_t pack_bytes, int n_
                                      const float* pts, int N, float* out) {
   Layout lay;
   if (int rc = check_field("isr_density_eval_host", pack, pack_bytes, n_hidden, widths, H, lay)) return rc;
-  ISR_REQUIRE(N >= 0, "isr_density_eval_host: N = %d", N);
-  ISR_REQUIRE(N == 0 || (pts && out), "isr_density_eval_host: null pointer");
+  if (int rc = isr::check_rows("isr_density_eval_host", N, pts && out)) return rc;
   if (N == 0) return ISR_OK;
   const HostField hf(lay, pack);
-  parallel_rows(N, 64, [&](long i) { out[i] = point_host(lay, pack, hf, pts + 3 * i); });
+  isr::parallel_rows(N, 64, [&](long i) { out[i] = point_host(lay, pack, hf, pts + 3 * i); });
   return ISR_OK;
 }
 
@@ -355,7 +251,7 @@ extern "C" int isr_density_march_host(const void* pack, size_t pack_bytes, int n
   if (N == 0) return ISR_OK;
   const HostField hf(lay, pack);
   std::vector<float> rho((size_t)N * P);
-  parallel_rows((long)N * P, 64, [&](long q) {
+  isr::parallel_rows((long)N * P, 64, [&](long q) {
     const long ray = q / P;
     float x[3];
     for (int d = 0; d < 3; ++d) x[d] = origins[3 * ray + d] + directions[3 * ray + d] * lengths[q];

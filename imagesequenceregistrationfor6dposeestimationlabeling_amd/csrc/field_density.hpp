@@ -52,16 +52,7 @@ ISR_FIELD_FN bool make_layout(int n_hidden, const int32_t* widths, int H, Layout
   for (int l = 0; l < n_hidden; ++l) {
     const int O = widths[l];
     if (O < 1 || O > kMaxWidth) return false;
-    Layer& L = lay.L[l];
-    L.K = K;
-    L.O = O;
-    L.OP = (O + 31) / 32 * 32;
-    L.mfma = 1;
-    L.kstride = (K + 7) / 8 * 8;
-    L.w_off = off;
-    off += L.OP * L.kstride;
-    L.b_off = off;
-    off += L.OP;
+    field::add_layer(K, O, 1, off, lay.L[l]);
     K = O;
   }
   lay.n_hidden = n_hidden;
@@ -101,12 +92,12 @@ ISR_FIELD_FN uint32_t two_over_pi_word(int i) {
 }
 
 // sin(a) and cos(a) of an f32 a, each an f64 result (error ~1e-16) rounded once: within 1 ulp of the true values for EVERY
-// finite a (measured 0.5001).  |a| < 2^17: sin32's Cody-Waite reduction (field_mlp.hpp), the same bits as sin32 for the sine.
+// finite a (measured 0.5001).  |a| < 2^17: sin32's reduction (field::reduce_pio2), the same bits as sin32 for the sine.
 // Otherwise Payne-Hanek: |a| = m 2^e with m the 24-bit mantissa as an integer; the bits of 2/pi whose weight times 2^e is 4
 // or more contribute whole turns and are skipped, m times the next 128 bits (integer arithmetic, 32-bit limbs) gives
 // a 2/pi mod 4 as 2 integer and 126 fraction bits, of which 96 fraction bits are kept: the quadrant n and a fraction in
 // [-1/2, 1/2) with at least 60 significant bits even where a is nearest a multiple of pi/2; r = fraction * pi/2, then
-// sin32's f64 kernels on |r| <= pi/4.  The table reaches past the largest finite f32 (e = 104 needs bit 262), so the rule
+// field::sincos_kernel on |r| <= pi/4.  The table reaches past the largest finite f32 (e = 104 needs bit 262), so the rule
 // beyond 2^64 is the same rule and the same accuracy.  NaN and +-Inf give NaN for both; sin(-0) = -0, cos(-0) = 1.
 ISR_FIELD_FN void sincos32(float a, float* sn, float* cs) {
   const uint32_t ab = to_bits32(a);
@@ -116,15 +107,12 @@ ISR_FIELD_FN void sincos32(float a, float* sn, float* cs) {
     *cs = a - a;
     return;
   }
-  double r;
+  double r, s, c;
   int q;
   bool neg = false;
   if (ax < 0x48000000u) {            // |a| < 2^17
-    const double x = (double)a;
-    const double n = rint(x * 6.36619772367581382433e-01);
-    const double r0 = (x - n * 1.57079632673412561417e+00) - n * 6.07710050650619224932e-11;
-    r = (n == 0.0) ? x : r0;
-    r = r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);
+    double n;
+    r = field::reduce_pio2((double)a, &n);
     q = (int)n & 3;
   } else {
     neg = (ab >> 31) != 0;
@@ -151,19 +139,7 @@ ISR_FIELD_FN void sincos32(float a, float* sn, float* cs) {
     r = frac * 1.57079632679489655800e+00;
     q &= 3;
   }
-  const double r2 = r * r;
-  const double ps = -1.66666666666666324348e-01 +
-                    r2 * (8.33333333332248946124e-03 +
-                          r2 * (-1.98412698298579493134e-04 +
-                                r2 * (2.75573137070700676789e-06 +
-                                      r2 * (-2.50507602534068634195e-08 + r2 * 1.58969099521155010221e-10))));
-  const double pc = -0.5 + r2 * (4.16666666666666019037e-02 +
-                                 r2 * (-1.38888888888741095749e-03 +
-                                       r2 * (2.48015872894767294178e-05 +
-                                             r2 * (-2.75573143513906633035e-07 +
-                                                   r2 * (2.08757232129817482790e-09 + r2 * -1.13596475577881948265e-11)))));
-  const double s = r * (1.0 + r2 * ps);
-  const double c = 1.0 + r2 * pc;
+  field::sincos_kernel(r, &s, &c);
   double vs = (q == 0) ? s : (q == 1) ? c : (q == 3) ? -c : -s;
   const double vc = (q == 0) ? c : (q == 1) ? -s : (q == 3) ? s : -c;
   if (neg) vs = -vs;
@@ -294,10 +270,7 @@ inline void pack_host(const Layout& lay, const float* freqs, float beta, const f
   for (int i = 0; i < lay.H; ++i) pf[kFreqOff + i] = freqs[i];
   for (int l = 0; l < lay.n_hidden; ++l) {
     const Layer& L = lay.L[l];
-    for (int j = 0; j < L.O; ++j) {
-      for (int k = 0; k < L.K; ++k) pf[L.w_off + w_index(L, j, k)] = W[(size_t)j * L.K + k];
-      pf[L.b_off + j] = b[j];
-    }
+    field::pack_layer(L, W, b, pf);
     W += (size_t)L.O * L.K;
     b += L.O;
   }
@@ -319,32 +292,34 @@ struct HostWeights {
   const float* Wt[kMaxHidden];
 };
 
-// one point through the field; the k loop is outermost and ascending, each z_j sees its own k-ordered fmaf chain
-#define ISR_DENSITY_POINT_BODY                                                                  \
-  float e[6 * kMaxH], z[kMaxWidth];                                                             \
-  const float* pf = static_cast<const float*>(pack);                                            \
-  const float beta = pf[0];                                                                     \
-  embed_point(x, pf + kFreqOff, lay.H, e);                                                      \
-  const float* h = e;                                                                           \
-  float g[kMaxWidth];                                                                           \
-  for (int l = 0; l < lay.n_hidden; ++l) {                                                      \
-    const Layer& L = lay.L[l];                                                                  \
-    const float* wt = hw.Wt[l];                                                                 \
-    for (int j = 0; j < L.O; ++j) z[j] = pf[L.b_off + j];                                       \
-    for (int k = 0; k < L.K; ++k) {                                                             \
-      const float hk = h[k];                                                                    \
-      const float* wk = wt + (size_t)k * L.O;                                                   \
-      for (int j = 0; j < L.O; ++j) z[j] = __builtin_fmaf(wk[j], hk, z[j]);                     \
-    }                                                                                           \
-    for (int j = 0; j < L.O; ++j) g[j] = softplus32(z[j], beta);                                \
-    h = g;                                                                                      \
-  }                                                                                             \
-  float zo = pf[lay.out_b_off];                                                                 \
-  for (int k = 0; k < lay.out_K; ++k) zo = __builtin_fmaf(pf[lay.out_w_off + k], h[k], zo);     \
+// one point through the field; the k loop is outermost and ascending, each z_j sees its own k-ordered fmaf chain.  Inlined
+// into its two callers below, so that each compiles the loops for its own instruction set.
+__attribute__((always_inline)) inline float point_density_body(const Layout& lay, const void* pack, const HostWeights& hw,
+                                                               const float* x) {
+  float e[6 * kMaxH], z[kMaxWidth], g[kMaxWidth];
+  const float* pf = static_cast<const float*>(pack);
+  const float beta = pf[0];
+  embed_point(x, pf + kFreqOff, lay.H, e);
+  const float* h = e;
+  for (int l = 0; l < lay.n_hidden; ++l) {
+    const Layer& L = lay.L[l];
+    const float* wt = hw.Wt[l];
+    for (int j = 0; j < L.O; ++j) z[j] = pf[L.b_off + j];
+    for (int k = 0; k < L.K; ++k) {
+      const float hk = h[k];
+      const float* wk = wt + (size_t)k * L.O;
+      for (int j = 0; j < L.O; ++j) z[j] = __builtin_fmaf(wk[j], hk, z[j]);
+    }
+    for (int j = 0; j < L.O; ++j) g[j] = softplus32(z[j], beta);
+    h = g;
+  }
+  float zo = pf[lay.out_b_off];
+  for (int k = 0; k < lay.out_K; ++k) zo = __builtin_fmaf(pf[lay.out_w_off + k], h[k], zo);
   return density32(softplus32(zo, beta));
+}
 
 inline float point_density_host(const Layout& lay, const void* pack, const HostWeights& hw, const float* x) {
-  ISR_DENSITY_POINT_BODY
+  return point_density_body(lay, pack, hw, x);
 }
 
 #if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
@@ -352,7 +327,7 @@ inline float point_density_host(const Layout& lay, const void* pack, const HostW
 // bits do not depend on which of the two runs); callers ask __builtin_cpu_supports("fma") first
 __attribute__((target("avx2,fma"))) inline float point_density_host_fma(const Layout& lay, const void* pack,
                                                                         const HostWeights& hw, const float* x) {
-  ISR_DENSITY_POINT_BODY
+  return point_density_body(lay, pack, hw, x);
 }
 #define ISR_DENSITY_HAVE_FMA_BUILD 1
 #endif

@@ -41,6 +41,19 @@ struct Layout {
   Layer L[kMaxLayers];
 };
 
+// Layer `L` of a pack: K inputs, O outputs, in matrix-core order or not, its words from `off` on (which moves past them).
+ISR_FIELD_FN void add_layer(int K, int O, int mfma, int& off, Layer& L) {
+  L.K = K;
+  L.O = O;
+  L.OP = (O + 31) / 32 * 32;
+  L.mfma = mfma;
+  L.kstride = mfma ? (K + 7) / 8 * 8 : (K + 3) / 4 * 4;
+  L.w_off = off;
+  off += L.OP * L.kstride;
+  L.b_off = off;
+  off += L.OP;
+}
+
 // false: a layer count or a width outside the limits (lay is then unspecified)
 ISR_FIELD_FN bool make_layout(int n_layers, const int32_t* widths, Layout& lay) {
   if (n_layers < 1 || n_layers > kMaxLayers || widths[0] != 3) return false;
@@ -48,16 +61,7 @@ ISR_FIELD_FN bool make_layout(int n_layers, const int32_t* widths, Layout& lay) 
   for (int l = 0; l < n_layers; ++l) {
     const int K = widths[l], O = widths[l + 1];
     if (O < 1 || O > kMaxWidth) return false;
-    Layer& L = lay.L[l];
-    L.K = K;
-    L.O = O;
-    L.OP = (O + 31) / 32 * 32;
-    L.mfma = K >= kMfmaMinK ? 1 : 0;
-    L.kstride = L.mfma ? (K + 7) / 8 * 8 : (K + 3) / 4 * 4;
-    L.w_off = off;
-    off += L.OP * L.kstride;
-    L.b_off = off;
-    off += L.OP;
+    add_layer(K, O, K >= kMfmaMinK ? 1 : 0, off, lay.L[l]);
   }
   if (widths[n_layers] > kMaxOut) return false;
   lay.n_layers = n_layers;
@@ -74,17 +78,19 @@ ISR_FIELD_FN int w_index(const Layer& L, int j, int k) {
   return (((j >> 5) * (L.kstride >> 3) + (k >> 3)) * 64 + lane) * 4 + ((k & 7) >> 1);
 }
 
-// sin(a) for an f32 a, correctly rounded up to the rounding of an f64 result whose error is ~1e-16 (within 1 ulp of the true
-// sine for |a| <= 2^17; measured 0.5 ulp).  Cody-Waite reduction in f64: n = rint(a * 2/pi), r = (a - n C1) - n C2 with C1 the
-// leading 33 bits of pi/2 — n C1 and the subtraction are exact for |n| < 2^20 — then the degree-13 / degree-14 kernels of
-// Sun's fdlibm on |r| <= pi/4.  Beyond 2^17 the reduction loses accuracy but r is clamped, so the value stays in [-1, 1] and
-// is the same on every build.  NaN and +-Inf give NaN (every comparison below is false for them); sin32(-0) = -0.
-ISR_FIELD_FN float sin32(float a) {
-  const double x = (double)a;
+// The reduction and the kernels of sin32 below and of sincos32 (field_density.hpp), in f64.
+// Cody-Waite: n = rint(x * 2/pi), r = (x - n C1) - n C2 with C1 the leading 33 bits of pi/2 -- n C1 and the subtraction are
+// exact for |n| < 2^20 -- clamped to [-1, 1] (it is within pi/4 wherever the reduction is accurate).  -> r, n in *n.
+ISR_FIELD_FN double reduce_pio2(double x, double* n_out) {
   const double n = rint(x * 6.36619772367581382433e-01);
   const double r0 = (x - n * 1.57079632673412561417e+00) - n * 6.07710050650619224932e-11;
-  double r = (n == 0.0) ? x : r0;
-  r = r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);
+  const double r = (n == 0.0) ? x : r0;
+  *n_out = n;
+  return r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);
+}
+
+// sin(r) and cos(r) on |r| <= pi/4: the degree-13 / degree-14 kernels of Sun's fdlibm
+ISR_FIELD_FN void sincos_kernel(double r, double* s, double* c) {
   const double r2 = r * r;
   const double ps = -1.66666666666666324348e-01 +
                     r2 * (8.33333333332248946124e-03 +
@@ -96,8 +102,18 @@ ISR_FIELD_FN float sin32(float a) {
                                        r2 * (2.48015872894767294178e-05 +
                                              r2 * (-2.75573143513906633035e-07 +
                                                    r2 * (2.08757232129817482790e-09 + r2 * -1.13596475577881948265e-11)))));
-  const double s = r * (1.0 + r2 * ps);
-  const double c = 1.0 + r2 * pc;
+  *s = r * (1.0 + r2 * ps);
+  *c = 1.0 + r2 * pc;
+}
+
+// sin(a) for an f32 a, correctly rounded up to the rounding of an f64 result whose error is ~1e-16 (within 1 ulp of the true
+// sine for |a| <= 2^17; measured 0.5 ulp).  Beyond 2^17 the reduction loses accuracy but r is clamped, so the value stays in
+// [-1, 1] and is the same on every build; n can reach 2e38 there, so the quadrant is taken in f64.  NaN and +-Inf give NaN
+// (every comparison is false for them); sin32(-0) = -0.
+ISR_FIELD_FN float sin32(float a) {
+  double n, s, c;
+  const double r = reduce_pio2((double)a, &n);
+  sincos_kernel(r, &s, &c);
   const double q = n - 4.0 * rint(n * 0.25);      // n mod 4 in {-2, ..., 2}
   const double v = (q == 0.0) ? s : (q == 1.0) ? c : (q == -1.0) ? -c : -s;
   return (float)v;
@@ -113,6 +129,20 @@ ISR_FIELD_FN float activate(float z, bool sine, float omega) {
 inline float header_omega(const void* pack, int l) { return static_cast<const float*>(pack)[l]; }
 inline bool header_sine(const void* pack, int l) { return static_cast<const uint32_t*>(pack)[8 + l] != 0; }
 
+// Host: one layer's W (O, K) row-major and b (O,) to their places in the pack (the padding is not touched)
+inline void pack_layer(const Layer& L, const float* W, const float* b, float* pack) {
+  for (int j = 0; j < L.O; ++j) {
+    for (int k = 0; k < L.K; ++k) pack[L.w_off + w_index(L, j, k)] = W[(size_t)j * L.K + k];
+    pack[L.b_off + j] = b[j];
+  }
+}
+
+// Host: the layer's weights out of the pack: dst[j * K + k], or transposed dst[k * O + j]
+inline void unpack_layer(const Layer& L, const float* pack, float* dst, bool transposed) {
+  for (int j = 0; j < L.O; ++j)
+    for (int k = 0; k < L.K; ++k) dst[transposed ? (size_t)k * L.O + j : (size_t)j * L.K + k] = pack[L.w_off + w_index(L, j, k)];
+}
+
 // Host: W (row-major, layer after layer), b, omega, sine -> pack (lay.total_words words).
 inline void pack_host(const Layout& lay, const float* W, const float* b, const float* omega, const int32_t* sine, void* pack) {
   float* pf = static_cast<float*>(pack);
@@ -122,17 +152,14 @@ inline void pack_host(const Layout& lay, const float* W, const float* b, const f
     const Layer& L = lay.L[l];
     pf[l] = sine[l] ? omega[l] : 0.f;
     pu[8 + l] = sine[l] ? 1u : 0u;
-    for (int j = 0; j < L.O; ++j) {
-      for (int k = 0; k < L.K; ++k) pf[L.w_off + w_index(L, j, k)] = W[(size_t)j * L.K + k];
-      pf[L.b_off + j] = b[j];
-    }
+    pack_layer(L, W, b, pf);
     W += (size_t)L.O * L.K;
     b += L.O;
   }
 }
 
 // Host: rows [n0, n1) of pts (N, 3) through the packed field into out (N, ld_out), columns < out_last.  dense: the layers'
-// weights unpacked row-major (unpack_host), so that the inner loop is the plain chain.
+// weights unpacked row-major (unpack_layer), so that the inner loop is the plain chain.
 inline void eval_rows_host(const Layout& lay, const void* pack, const float* const* dense, const float* pts, long n0, long n1,
                            float* out, long ld_out) {
   const float* pf = static_cast<const float*>(pack);

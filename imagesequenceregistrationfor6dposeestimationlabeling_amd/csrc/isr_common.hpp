@@ -5,6 +5,8 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <thread>
+#include <vector>
 
 #include "../../include/isr_hip.h"
 
@@ -45,6 +47,41 @@ inline hipStream_t as_stream(isr_stream_t s) { return reinterpret_cast<hipStream
       return ISR_ERR_ARG;                                                       \
     }                                                                           \
   } while (0)
+
+// Argument checks the packed-field entries share (csrc/field_mlp.hip, csrc/field_density.hip); who: the entry's name.
+inline int check_pack_pointers(const char* who, const void* pack, const void* widths) {
+  ISR_REQUIRE(pack && widths, "%s: null pointer", who);
+  return ISR_OK;
+}
+inline int check_pack_bytes(const char* who, size_t pack_bytes, int total_words) {
+  ISR_REQUIRE(pack_bytes == (size_t)total_words * 4, "%s: pack_bytes %zu, this field packs to %zu", who, pack_bytes,
+              (size_t)total_words * 4);
+  return ISR_OK;
+}
+// N rows in, N rows out: the arrays may be null only when there are none
+inline int check_rows(const char* who, int N, bool pointers) {
+  ISR_REQUIRE(N >= 0, "%s: N = %d", who, N);
+  ISR_REQUIRE(N == 0 || pointers, "%s: null pointer", who);
+  return ISR_OK;
+}
+
+// Host builds of the kernels: fn(i) for i in [0, n), over 8 threads from 8 * per_thread_min rows on
+template <class F>
+void parallel_rows(long n, long per_thread_min, F fn) {
+  const int nthreads = n >= 8 * per_thread_min ? 8 : 1;
+  if (nthreads == 1) {
+    for (long i = 0; i < n; ++i) fn(i);
+    return;
+  }
+  std::vector<std::thread> pool;
+  for (int t = 0; t < nthreads; ++t) {
+    const long n0 = n * t / nthreads, n1 = n * (t + 1) / nthreads;
+    pool.emplace_back([=] {
+      for (long i = n0; i < n1; ++i) fn(i);
+    });
+  }
+  for (auto& th : pool) th.join();
+}
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

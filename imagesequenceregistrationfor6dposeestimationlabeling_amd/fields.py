@@ -22,39 +22,68 @@ def _vp(a: np.ndarray):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
-class KeyField:
+class _PackedField:
+    """What the two fields share: layers to contiguous f32 on the host with their chain of widths checked, the pack made by
+    the library and uploaded, and the checks in front of a device call.  `_host_calls` finishes the subclass's refusal."""
+
+    @staticmethod
+    def _host(t) -> np.ndarray:
+        return np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, np.float32)
+
+    def _layers(self, weights, biases, first=None):
+        """-> (Ws, bs, widths): every W (out_l, in_l) with in_l the width before it, `first` (W_0's own when None) at l = 0."""
+        name = type(self).__name__
+        Ws, bs = [self._host(w) for w in weights], [self._host(b).reshape(-1) for b in biases]
+        widths = [(Ws[0].shape[1] if Ws[0].ndim == 2 else -1) if first is None else first]
+        for l, (w, b) in enumerate(zip(Ws, bs)):
+            if w.ndim != 2 or w.shape[1] != widths[-1] or b.shape[0] != w.shape[0]:
+                raise ValueError(f"{name}: layer {l} has W {w.shape} and b {b.shape} after width {widths[-1]}")
+            widths.append(w.shape[0])
+        return Ws, bs, tuple(int(v) for v in widths)
+
+    def _pack_and_upload(self, kind, dims, before, Ws, bs, after, device):
+        """isr_<kind>_pack_bytes(*dims), isr_<kind>_pack(*dims, *before, W, b, *after, pack, bytes) -> pack_host; its copy on
+        `device` -> pack.  device=None: host-only (the _host calls, the tests' reference); there is no CPU fallback."""
+        name, L = type(self).__name__, lib()
+        nbytes = getattr(L, f"isr_{kind}_pack_bytes")(*dims)
+        if nbytes == 0:
+            raise IsrError(f"isr_{kind}_pack_bytes failed: {L.isr_last_error().decode()}")
+        self.pack_host = np.empty(nbytes // 4, np.float32)
+        check(getattr(L, f"isr_{kind}_pack")(*dims, *before, _vp(np.concatenate([w.reshape(-1) for w in Ws])),
+                                             _vp(np.concatenate(bs)), *after, _vp(self.pack_host), nbytes), f"isr_{kind}_pack")
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type != "cuda":
+            raise IsrError(f"{name}: device {self.device} is not a GPU (there is no CPU fallback)")
+        self.pack = None if self.device is None else torch.from_numpy(self.pack_host).to(self.device)
+
+    def _need_device(self, *tensors):
+        if self.pack is None:
+            raise IsrError(f"{type(self).__name__} was built without a device (device=None): only {self._host_calls} available")
+        require_cuda(self.pack, *tensors)
+
+    def _rows(self, points: torch.Tensor) -> torch.Tensor:
+        self._need_device(points)
+        if points.shape[-1] != 3:
+            raise ValueError(f"{type(self).__name__}: points {tuple(points.shape)} must end in 3")
+        return points.to(torch.float32).reshape(-1, 3).contiguous()
+
+
+class KeyField(_PackedField):
     """weights[l] (out_l, in_l), biases[l] (out_l,), omegas[l] a float (sine layer: h <- sin(omega (W h + b))) or None
     (linear layer: h <- W h + b); in_0 = 3, at most 8 layers, widths at most 256, the last at most 32."""
+    _host_calls = "eval_host is"
 
     def __init__(self, weights, biases, omegas, device):
         if not (len(weights) == len(biases) == len(omegas)) or len(weights) == 0:
             raise ValueError(f"KeyField: {len(weights)} weights, {len(biases)} biases, {len(omegas)} omegas")
-        host = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, np.float32)
-        Ws, bs = [host(w) for w in weights], [host(b).reshape(-1) for b in biases]
-        widths = [Ws[0].shape[1] if Ws[0].ndim == 2 else -1]
-        for l, (w, b) in enumerate(zip(Ws, bs)):
-            if w.ndim != 2 or w.shape[1] != widths[-1] or b.shape[0] != w.shape[0]:
-                raise ValueError(f"KeyField: layer {l} has W {w.shape} and b {b.shape} after width {widths[-1]}")
-            widths.append(w.shape[0])
-        self.widths = tuple(int(v) for v in widths)
+        Ws, bs, self.widths = self._layers(weights, biases)
         self.omegas = tuple(None if o is None else float(o) for o in omegas)
         self.n_layers = len(Ws)
         self.out_features = self.widths[-1]
-        L = lib()
         self._w = np.asarray(self.widths, np.int32)
-        nbytes = L.isr_field_pack_bytes(self.n_layers, _vp(self._w))
-        if nbytes == 0:
-            raise IsrError(f"isr_field_pack_bytes failed: {L.isr_last_error().decode()}")
         om = np.asarray([0.0 if o is None else o for o in self.omegas], np.float32)
         sine = np.asarray([o is not None for o in self.omegas], np.int32)
-        self.pack_host = np.empty(nbytes // 4, np.float32)
-        check(L.isr_field_pack(self.n_layers, _vp(self._w), _vp(np.concatenate([w.reshape(-1) for w in Ws])),
-                               _vp(np.concatenate(bs)), _vp(om), _vp(sine), _vp(self.pack_host), nbytes), "isr_field_pack")
-        # device=None: host-only (eval_host, the tests' reference); there is no CPU fallback for the calls below
-        self.device = None if device is None else torch.device(device)
-        if self.device is not None and self.device.type != "cuda":
-            raise IsrError(f"KeyField: device {self.device} is not a GPU (there is no CPU fallback)")
-        self.pack = None if self.device is None else torch.from_numpy(self.pack_host).to(self.device)
+        self._pack_and_upload("field", (self.n_layers, _vp(self._w)), (), Ws, bs, (_vp(om), _vp(sine)), device)
 
     @classmethod
     def from_linears(cls, linears, omegas, device=None):
@@ -65,14 +94,6 @@ class KeyField:
         if device is None:
             device = linears[0].weight.device
         return cls([m.weight for m in linears], [m.bias for m in linears], omegas, device)
-
-    def _rows(self, points: torch.Tensor) -> torch.Tensor:
-        if self.pack is None:
-            raise IsrError("KeyField was built without a device (device=None): only eval_host is available")
-        require_cuda(self.pack, points)
-        if points.shape[-1] != 3:
-            raise ValueError(f"KeyField: points {tuple(points.shape)} must end in 3")
-        return points.to(torch.float32).reshape(-1, 3).contiguous()
 
     def __call__(self, points: torch.Tensor) -> torch.Tensor:
         """points (..., 3) -> keys (..., out), on the device."""
@@ -95,43 +116,28 @@ class KeyField:
         return out
 
 
-class DensityField:
+class DensityField(_PackedField):
     """The density head of the reference's NeuralRadianceFieldFeat as a device-resident field: HarmonicEmbedding(H) ->
     Linear + Softplus(beta) per hidden layer -> Linear(., 1) + Softplus(beta) -> 1 - exp(-x) (nerf.py:106-144, :163-177,
     :206-228), evaluated by one kernel launch, and the ray march that turns it into surface points (pren.py:338-365 as
     genFeat.py:185-198 and generateCors.py:299-334 use it).  weights[l] (out_l, in_l) and biases[l] for the hidden layers
     (in_0 = 6 H, at most 4 layers of at most 256), then the output row (1, in) and its bias; frequencies (H,) f32, H <= 64."""
 
+    _host_calls = "the _host calls are"
+
     def __init__(self, weights, biases, frequencies, beta=10.0, device=None):
-        host = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, np.float32)
         if len(weights) != len(biases) or len(weights) < 2:
             raise ValueError(f"DensityField: {len(weights)} weights, {len(biases)} biases (hidden layers, then the output row)")
-        Ws, bs = [host(w) for w in weights], [host(b).reshape(-1) for b in biases]
-        self.frequencies = host(frequencies).reshape(-1)
+        self.frequencies = self._host(frequencies).reshape(-1)
         self.H = int(self.frequencies.shape[0])
-        prev = 6 * self.H
-        for l, (w, b) in enumerate(zip(Ws, bs)):
-            if w.ndim != 2 or w.shape[1] != prev or b.shape[0] != w.shape[0]:
-                raise ValueError(f"DensityField: layer {l} has W {w.shape} and b {b.shape} after width {prev}")
-            prev = w.shape[0]
-        if prev != 1:
-            raise ValueError(f"DensityField: the last layer has {prev} outputs, the density is one")
-        self.widths = tuple(int(w.shape[0]) for w in Ws[:-1])
+        Ws, bs, widths = self._layers(weights, biases, 6 * self.H)
+        if widths[-1] != 1:
+            raise ValueError(f"DensityField: the last layer has {widths[-1]} outputs, the density is one")
+        self.widths = widths[1:-1]
         self.beta = float(beta)
-        L = lib()
         self._w = np.asarray(self.widths, np.int32)
-        nbytes = L.isr_density_pack_bytes(len(self.widths), _vp(self._w), self.H)
-        if nbytes == 0:
-            raise IsrError(f"isr_density_pack_bytes failed: {L.isr_last_error().decode()}")
-        self.pack_host = np.empty(nbytes // 4, np.float32)
-        check(L.isr_density_pack(len(self.widths), _vp(self._w), self.H, _vp(self.frequencies), self.beta,
-                                 _vp(np.concatenate([w.reshape(-1) for w in Ws])), _vp(np.concatenate(bs)),
-                                 _vp(self.pack_host), nbytes), "isr_density_pack")
-        # device=None: host-only (eval_host / march_host, the tests' reference); there is no CPU fallback for the device calls
-        self.device = None if device is None else torch.device(device)
-        if self.device is not None and self.device.type != "cuda":
-            raise IsrError(f"DensityField: device {self.device} is not a GPU (there is no CPU fallback)")
-        self.pack = None if self.device is None else torch.from_numpy(self.pack_host).to(self.device)
+        self._pack_and_upload("density", (len(self.widths), _vp(self._w), self.H), (_vp(self.frequencies), self.beta), Ws, bs, (),
+                              device)
 
     @classmethod
     def from_linears(cls, hidden_linears, density_linear, n_harmonic=60, omega0=0.1, beta=10.0, device=None):
@@ -144,17 +150,6 @@ class DensityField:
             device = linears[0].weight.device
         freqs = omega0 * (2.0 ** torch.arange(n_harmonic))
         return cls([m.weight for m in linears], [m.bias for m in linears], freqs.to(torch.float32), beta, device)
-
-    def _need_device(self, *tensors):
-        if self.pack is None:
-            raise IsrError("DensityField was built without a device (device=None): only the _host calls are available")
-        require_cuda(self.pack, *tensors)
-
-    def _rows(self, points: torch.Tensor) -> torch.Tensor:
-        self._need_device(points)
-        if points.shape[-1] != 3:
-            raise ValueError(f"DensityField: points {tuple(points.shape)} must end in 3")
-        return points.to(torch.float32).reshape(-1, 3).contiguous()
 
     def customForwardForDensity(self, points: torch.Tensor) -> torch.Tensor:
         """nerf.py:417-432: points (..., 3) -> densities (..., 1), on the device."""

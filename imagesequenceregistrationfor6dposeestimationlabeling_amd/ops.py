@@ -1130,23 +1130,31 @@ def field_flops(widths) -> float:
     return 2.0 * sum(int(a) * int(b) for a, b in zip(widths[:-1], widths[1:]))
 
 
+def _points_n3(name: str, points: torch.Tensor) -> int:
+    if points.dtype != torch.float32 or points.ndim != 2 or points.shape[1] != 3 or not points.is_contiguous():
+        raise ValueError(f"{name}: points must be contiguous (N,3) float32, got {tuple(points.shape)} {points.dtype}")
+    return points.shape[0]
+
+
+def _field_args(pack: torch.Tensor, widths, n_layers: int):
+    w = (ctypes.c_int32 * len(widths))(*[int(v) for v in widths])
+    return ptr(pack), pack.numel() * pack.element_size(), n_layers, ctypes.cast(w, ctypes.c_void_p), w      # w: kept alive by the caller
+
+
 def field_eval(pack: torch.Tensor, widths, points: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """isr_field_eval: points (N,3) f32 through the packed field (`pack`: the device copy of isr_field_pack's bytes for these
     `widths`, fields.KeyField builds it) -> out (N, ld) f32, ld >= widths[-1] (allocated (N, widths[-1]) when None); only
     columns < widths[-1] are written."""
     dev = require_cuda(pack, points, out)
-    if points.dtype != torch.float32 or points.ndim != 2 or points.shape[1] != 3 or not points.is_contiguous():
-        raise ValueError(f"field_eval: points must be contiguous (N,3) float32, got {tuple(points.shape)} {points.dtype}")
-    N, o = points.shape[0], int(widths[-1])
+    N, o = _points_n3("field_eval", points), int(widths[-1])
     if out is None:
         out = torch.empty((N, o), dtype=torch.float32, device=dev)
     elif out.dtype != torch.float32 or out.ndim != 2 or out.shape[0] != N or not out.is_contiguous():
         raise ValueError(f"field_eval: out must be contiguous ({N}, >= {o}) float32, got {tuple(out.shape)} {out.dtype}")
-    w = (ctypes.c_int32 * len(widths))(*[int(v) for v in widths])
+    pk, nbytes, nl, wp, _keep = _field_args(pack, widths, len(widths) - 1)
     with torch.cuda.device(dev), _timed("field_eval", N * field_flops(widths)):
-        rc = lib().isr_field_eval(ptr(pack), pack.numel() * pack.element_size(), len(widths) - 1,
-                                  ctypes.cast(w, ctypes.c_void_p), ptr(points) if N else None, N, ptr(out) if N else None,
-                                  out.shape[1], current_stream(dev))
+        rc = lib().isr_field_eval(pk, nbytes, nl, wp, ptr(points) if N else None, N, ptr(out) if N else None, out.shape[1],
+                                  current_stream(dev))
     check(rc, "isr_field_eval")
     return out
 
@@ -1157,23 +1165,16 @@ def density_flops(widths, H: int) -> float:
     return 2.0 * sum(a * b for a, b in zip(w[:-1], w[1:]))
 
 
-def _density_field_args(pack: torch.Tensor, widths):
-    w = (ctypes.c_int32 * len(widths))(*[int(v) for v in widths])
-    return ptr(pack), pack.numel() * pack.element_size(), len(widths), ctypes.cast(w, ctypes.c_void_p), w
-
-
 def density_eval(pack: torch.Tensor, widths, H: int, points: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """isr_density_eval: points (N,3) f32 through the packed density field (`pack`: the device copy of isr_density_pack's
     bytes for these hidden `widths` and `H` frequencies, fields.DensityField builds it) -> out (N,) f32."""
     dev = require_cuda(pack, points, out)
-    if points.dtype != torch.float32 or points.ndim != 2 or points.shape[1] != 3 or not points.is_contiguous():
-        raise ValueError(f"density_eval: points must be contiguous (N,3) float32, got {tuple(points.shape)} {points.dtype}")
-    N = points.shape[0]
+    N = _points_n3("density_eval", points)
     if out is None:
         out = torch.empty((N,), dtype=torch.float32, device=dev)
     elif out.dtype != torch.float32 or out.shape != (N,) or not out.is_contiguous():
         raise ValueError(f"density_eval: out must be contiguous ({N},) float32, got {tuple(out.shape)} {out.dtype}")
-    pk, nbytes, nh, wp, _keep = _density_field_args(pack, widths)
+    pk, nbytes, nh, wp, _keep = _field_args(pack, widths, len(widths))
     with torch.cuda.device(dev), _timed("density_eval", N * density_flops(widths, H)):
         rc = lib().isr_density_eval(pk, nbytes, nh, wp, int(H), ptr(points) if N else None, N, ptr(out) if N else None,
                                     current_stream(dev))
@@ -1203,7 +1204,7 @@ def density_march(pack: torch.Tensor, widths, H: int, origins: torch.Tensor, dir
     hit = torch.empty((N,), dtype=torch.int32, device=dev)
     dens = torch.empty((N, P), **f32) if want_densities else None
     wts = torch.empty((N, P), **f32) if want_weights else None
-    pk, nbytes, nh, wp, _keep = _density_field_args(pack, widths)
+    pk, nbytes, nh, wp, _keep = _field_args(pack, widths, len(widths))
     with torch.cuda.device(dev), _timed("density_march", float(N) * P * density_flops(widths, H)):
         rc = lib().isr_density_march(pk, nbytes, nh, wp, int(H), ptr(origins), ptr(directions), ptr(lengths), N, P, thr,
                                      ptr(dens), ptr(wts), ptr(depth), ptr(points), ptr(hit), current_stream(dev))

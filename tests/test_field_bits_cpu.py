@@ -1,0 +1,150 @@
+"""CPU: the bits of the host entries of the key field and the density field (isr_field_* / isr_density_*_host), pinned by
+tests/golden/field_host_bits.npz.  The file was written once by tests/golden/make_field_host_bits.py, before the two fields
+came to share their tile core, layout and sine kernels: whatever is moved between those files, every entry must still give
+these bits.  Inputs come from integer arithmetic alone (a 32-bit LCG, values k / 2^15 - 1); the small ones are stored, the
+weights are remade from their seed.  A pack is pinned by one 8-byte digest per 256 words (the reference width packs to
+630 KB), everything else word for word."""
+import ctypes
+import hashlib
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from imagesequenceregistrationfor6dposeestimationlabeling_amd.fields import DensityField, KeyField
+
+GOLDEN = Path(__file__).resolve().parent / "golden" / "field_host_bits.npz"
+f32 = np.float32
+vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+
+# name -> (widths, omegas, seed)
+KEY_FIELDS = {"key_odd": ((3, 5, 40, 33, 7), (30.0, 1.5, None, 2.0), 101), "key_64": ((3, 64, 64, 12), (30.0, 30.0, None), 102)}
+# name -> (H, hidden widths, seed)
+DENSITY_FIELDS = {"density_odd": (4, (33, 100), 203), "density_ref": (60, (256, 256), 202)}
+THRESHOLDS = (0.2, -1.0)
+
+
+def lcg(seed, n):
+    """n values k / 2^15 - 1, k the bits 8..23 of s <- 1664525 s + 1013904223 (mod 2^32): tools/density_host_check.cpp's rnd."""
+    out = np.empty(n, np.float64)
+    s = seed
+    for i in range(n):
+        s = (s * 1664525 + 1013904223) & 0xFFFFFFFF
+        out[i] = ((s >> 8) & 0xFFFF) / 32768.0 - 1.0
+    return out
+
+
+def sine_arguments():
+    """Every finite f32 exponent, both signs, five mantissas; then 4 096 values in +-64."""
+    e = np.arange(255, dtype=np.uint32)[:, None, None] << 23
+    m = np.array([0, 1, 0x400000, 0x7FFFFF, 0x2AAAAA], np.uint32)[None, :, None]
+    sg = np.array([0, 0x80000000], np.uint32)[None, None, :]
+    return np.concatenate([(sg | e | m).reshape(-1).view(f32), (64.0 * lcg(7, 4096)).astype(f32)])
+
+
+def key_field(name):
+    widths, omegas, seed = KEY_FIELDS[name]
+    Ws, bs = [], []
+    for l, (K, O) in enumerate(zip(widths[:-1], widths[1:])):
+        scale = 1.0 if l == 0 else np.sqrt(6.0 / K) / (omegas[l] or 1.0)
+        Ws.append((lcg(seed + 10 * l, O * K) * scale).astype(f32).reshape(O, K))
+        bs.append((lcg(seed + 10 * l + 1, O) * 0.1).astype(f32))
+    return KeyField(Ws, bs, omegas, None)
+
+
+def density_field(name):
+    H, hidden, seed = DENSITY_FIELDS[name]
+    w = (6 * H,) + hidden
+    Ws = [(lcg(seed + 10 * l, O * K) / np.sqrt(K)).astype(f32).reshape(O, K) for l, (K, O) in enumerate(zip(w[:-1], w[1:]))]
+    bs = [(lcg(seed + 10 * l + 1, O) * 0.1).astype(f32) for l, O in enumerate(w[1:])]
+    Ws.append((lcg(seed + 90, w[-1]) * 8.0 / np.sqrt(w[-1])).astype(f32).reshape(1, -1))
+    bs.append(np.array([0.25], f32))
+    return DensityField(Ws, bs, (0.1 * 2.0 ** np.arange(H)).astype(f32), 10.0, None)
+
+
+def small_inputs():
+    """What the .npz stores beside the results: the activations' z, the points and the rays."""
+    return {"z": (32.0 * lcg(8, 2000)).astype(f32), "points": (1.2 * lcg(9, 210)).astype(f32).reshape(70, 3),
+            "origins": (0.5 * lcg(10, 15)).astype(f32).reshape(5, 3), "directions": lcg(11, 15).astype(f32).reshape(5, 3),
+            "lengths": ((np.arange(33)[None, :] + 0.5 * (lcg(12, 165).reshape(5, 33) + 1.0)) * (1.5 / 33)).astype(f32)}
+
+
+def pack_digests(pack):
+    """(ceil(words / 256), 8) uint8: blake2b of every 256-word chunk of the pack's bytes."""
+    raw = np.ascontiguousarray(pack).view(np.uint8)
+    return np.array([np.frombuffer(hashlib.blake2b(raw[i:i + 1024].tobytes(), digest_size=8).digest(), np.uint8)
+                     for i in range(0, raw.size, 1024)])
+
+
+def compute(hip_lib, inp):
+    """Every pinned result, from the stored inputs: name -> array."""
+    out = {}
+    a = sine_arguments()
+    s0, s, c = np.empty_like(a), np.empty_like(a), np.empty_like(a)
+    assert hip_lib.isr_field_sin_host(vp(a), a.size, vp(s0)) == 0
+    assert hip_lib.isr_density_sincos_host(vp(a), a.size, vp(s), vp(c)) == 0
+    # sincos32's sine is sin32's below 2^17: stored as the words in which the two differ (zeros there), which is as strict
+    out["sin32"], out["sincos32_sin_xor_sin32"], out["sincos32_cos"] = s0, s.view(np.uint32) ^ s0.view(np.uint32), c
+    z = inp["z"]
+    for beta in (10.0, 1.0):
+        sp, de = np.empty_like(z), np.empty_like(z)
+        assert hip_lib.isr_density_activations_host(vp(z), z.size, beta, vp(sp), vp(de)) == 0
+        out[f"softplus32_beta{beta:g}"] = sp
+        assert beta == 10.0 or np.array_equal(de.view(np.uint32), out["density32"].view(np.uint32))      # beta plays no part
+        out["density32"] = de
+    for name in KEY_FIELDS:
+        f = key_field(name)
+        out[f"{name}_pack_words"] = np.array([f.pack_host.size], np.int64)
+        out[f"{name}_pack_digests"] = pack_digests(f.pack_host)
+        out[f"{name}_eval"] = f.eval_host(inp["points"])
+    for name in DENSITY_FIELDS:
+        f = density_field(name)
+        out[f"{name}_pack_words"] = np.array([f.pack_host.size], np.int64)
+        out[f"{name}_pack_digests"] = pack_digests(f.pack_host)
+        out[f"{name}_eval"] = f.eval_host(inp["points"])
+        for thr in THRESHOLDS:
+            for k, v in f.march_host(inp["origins"], inp["directions"], inp["lengths"], thr).items():
+                out[f"{name}_march_{thr:g}_{k}"] = v
+    return out
+
+
+def words(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32) if a.dtype == f32 else a
+
+
+@pytest.fixture(scope="module")
+def pinned(hip_lib):
+    gold = dict(np.load(GOLDEN))
+    inp = small_inputs()
+    for k, v in inp.items():
+        assert np.array_equal(words(v), words(gold[k])), f"the input {k} is not the stored one"
+    return gold, compute(hip_lib, inp)
+
+
+def _compare(pinned, select):
+    gold, got = pinned
+    names = [k for k in got if select(k)]
+    assert names
+    for k in names:
+        g, w = words(got[k]), words(gold[k])
+        assert g.shape == w.shape and g.dtype == w.dtype, (k, g.shape, w.shape)
+        if not np.array_equal(g, w):
+            bad = np.argwhere(g != w)
+            print(f"{k}: {len(bad)} of {g.size} differ, first at {bad[:8].tolist()}: got {g[tuple(bad[0])]:#x}, pinned {w[tuple(bad[0])]:#x}")
+        assert np.array_equal(g, w), k
+
+
+def test_every_stored_array_is_recomputed(pinned):
+    gold, got = pinned
+    assert set(gold) == set(got) | set(small_inputs())
+
+
+def test_sines_and_activations_keep_their_bits(pinned):
+    _compare(pinned, lambda k: k.startswith(("sin", "softplus32", "density32")))
+
+
+@pytest.mark.parametrize("name", list(KEY_FIELDS) + list(DENSITY_FIELDS))
+def test_pack_and_host_results_keep_their_bits(pinned, name):
+    """A differing digest row r is a difference inside the pack's words [256 r, 256 r + 256)."""
+    _compare(pinned, lambda k: k.startswith(name + "_"))

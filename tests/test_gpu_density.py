@@ -48,8 +48,11 @@ def _same(got, want, dens=True):
 
 
 @pytest.mark.parametrize("H,hidden,n_layers,N", [(1, 32, 1, 1), (1, 32, 2, 63), (4, 32, 1, 65), (4, 256, 2, 63), (60, 32, 2, 65),
-                                                 (60, 256, 1, 257), (60, 256, 2, 257), (1, 256, 1, 257), (4, 32, 2, 257)])
+                                                 (60, 256, 1, 257), (60, 256, 2, 257), (1, 256, 1, 257), (4, 32, 2, 257),
+                                                 (4, 128, 2, 65), (4, 160, 1, 63), (4, 100, 2, 65), (1, 33, 1, 63)])
 def test_eval_equals_the_host_build(cuda0, H, hidden, n_layers, N):
+    """The last row: 4 blocks of 32 neurons (the most that go one 32 x 32 tile per wave) and 5 (one block per wave, three waves
+    idle); widths that are no multiple of 32 or 8, whose padded neurons feed the next layer as zeros."""
     f = _field(H, hidden, n_layers, cuda0)
     pts = np.random.default_rng(N).uniform(-1.2, 1.2, (N, 3)).astype(np.float32)
     got = f.customForwardForDensity(torch.from_numpy(pts).to(cuda0))

@@ -28,11 +28,14 @@ def _bits(a):
 # (N, hidden width, hidden layers, out, last layer sine, omega): every N of {1, 63, 64, 65, 257, 4099}, every hidden width of
 # {32, 96, 256}, 1-3 hidden layers, every out of {1, 12, 13, 32}, both kinds of last layer, both omegas; then the paths beside
 # them: a hidden width below 32 (a vector-unit layer after layer 0), widths that are no multiple of 8 or 32, no hidden layer.
+# The last row: 5 and 7 blocks of 32 neurons (wave 0, or waves 0-2, take two and the rest one), and 2 blocks on the route of
+# one 32 x 32 tile per wave with every wave busy.
 CASES = [
     (1, 32, 1, 1, False, 1), (63, 96, 2, 12, True, 30), (64, 256, 3, 13, False, 30), (65, 32, 3, 32, True, 1),
     (257, 256, 1, 12, True, 30), (4099, 96, 1, 13, False, 1), (4099, 256, 2, 12, False, 30), (257, 96, 3, 32, False, 30),
     (65, 256, 2, 1, True, 1), (63, 32, 2, 13, True, 30), (1, 256, 3, 32, True, 30), (64, 96, 1, 1, False, 30),
     (257, 16, 2, 12, False, 30), (65, 45, 2, 7, True, 30), (129, 100, 1, 31, False, 1),
+    (65, 160, 2, 12, True, 30), (63, 224, 1, 13, False, 1), (64, 64, 2, 32, False, 30),
 ]
 
 

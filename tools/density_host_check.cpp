@@ -1,10 +1,11 @@
 // density_host_check.cpp — csrc/field_density.hpp as plain host code, for a sanitizer build:
 //     c++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all \
 //         tools/density_host_check.cpp -o density_host_check && ./density_host_check
-// Runs sincos32 over every exponent of f32 (both signs, the extremes of the mantissa) and the non-finite values, softplus32 and
+// Runs sin32 and sincos32 over every exponent of f32 (both signs, the extremes of the mantissa) and the non-finite values, softplus32 and
 // density32 over a sweep that crosses every branch, packs fields at the limits of the layout (H = 1 and 64, widths 1 and 256,
 // 1 and 4 hidden layers) and evaluates points through them, and marches rays in both modes including P = 1 and a partly
-// evaluated ray.  Checks ranges and a few identities; prints one line per case; exit status 0 = all hold.
+// evaluated ray, and takes a key field (csrc/field_mlp.hpp) of odd widths through make_layout / pack_host / eval_rows_host, so that
+// the helpers the two headers share run from both sides.  Checks ranges and a few identities; prints one line per case; exit status 0 = all hold.
 // The log of one such run is profiles/density_host_sanitizers.txt.
 #include <cmath>
 #include <cstdio>
@@ -35,16 +36,19 @@ int check_sincos() {
         std::memcpy(&a, &u, 4);
         sincos32(a, &s, &c);
         if (!(std::fabs(s) <= 1.f) || !(std::fabs(c) <= 1.f)) ++bad;
+        const float s1 = isr::field::sin32(a);
+        if (!(std::fabs(s1) <= 1.f) || (e < 144 && std::memcmp(&s1, &s, 4) != 0)) ++bad;       // |a| < 2^17: the same bits
         if (std::fabs((double)s - std::sin((double)a)) > 1.2e-7 || std::fabs((double)c - std::cos((double)a)) > 1.2e-7) ++bad;
       }
   float s, c;
   for (float a : {INFINITY, -INFINITY, NAN}) {
     sincos32(a, &s, &c);
-    if (s == s || c == c) ++bad;
+    const float s1 = isr::field::sin32(a);
+    if (s == s || c == c || s1 == s1) ++bad;
   }
   sincos32(-0.f, &s, &c);
-  if (!std::signbit(s) || c != 1.f) ++bad;
-  return report("sincos32: every exponent, non-finite, -0", bad);
+  if (!std::signbit(s) || c != 1.f || !std::signbit(isr::field::sin32(-0.f))) ++bad;
+  return report("sin32 / sincos32: every exponent, non-finite, -0", bad);
 }
 
 int check_activations() {
@@ -91,10 +95,8 @@ int check_field(int H, int n_hidden, int width, int N) {
   std::vector<std::vector<float>> wt(n_hidden);
   HostWeights hw;
   for (int l = 0; l < n_hidden; ++l) {
-    const Layer& L = lay.L[l];
-    wt[l].resize((size_t)L.O * L.K);
-    for (int j = 0; j < L.O; ++j)
-      for (int k = 0; k < L.K; ++k) wt[l][(size_t)k * L.O + j] = pack[L.w_off + w_index(L, j, k)];
+    wt[l].resize((size_t)lay.L[l].O * lay.L[l].K);
+    isr::field::unpack_layer(lay.L[l], pack.data(), wt[l].data(), true);
     hw.Wt[l] = wt[l].data();
   }
   int bad = 0;
@@ -143,6 +145,53 @@ int check_field(int H, int n_hidden, int width, int N) {
   return report(name, bad);
 }
 
+// a key field of widths no multiple of 4, 8 or 32 on either side of kMfmaMinK: layout, pack, unpack, host evaluation
+int check_key_field() {
+  namespace kf = isr::field;
+  const int32_t widths[5] = {3, 5, 40, 33, 7};
+  const float omega[4] = {30.f, 1.5f, 0.f, 2.f};
+  const int32_t sine[4] = {1, 1, 0, 1};
+  kf::Layout lay;
+  if (!kf::make_layout(4, widths, lay)) return report("field::make_layout", 1);
+  size_t nw = 0, nb = 0;
+  for (int l = 0; l < 4; ++l) {
+    nw += (size_t)widths[l] * widths[l + 1];
+    nb += widths[l + 1];
+  }
+  std::vector<float> W(nw), b(nb), pack(lay.total_words);
+  unsigned s = 777u;
+  auto rnd = [&] {
+    s = s * 1664525u + 1013904223u;
+    return (float)((s >> 8) & 0xffff) / 32768.f - 1.f;
+  };
+  for (auto& v : W) v = 0.2f * rnd();
+  for (auto& v : b) v = 0.1f * rnd();
+  kf::pack_host(lay, W.data(), b.data(), omega, sine, pack.data());
+  int bad = 0;
+  std::vector<std::vector<float>> dense(4);
+  const float* rows[kf::kMaxLayers];
+  const float* w = W.data();
+  for (int l = 0; l < 4; ++l) {
+    const kf::Layer& L = lay.L[l];
+    dense[l].resize((size_t)L.O * L.K);
+    kf::unpack_layer(L, pack.data(), dense[l].data(), false);
+    if (std::memcmp(dense[l].data(), w, dense[l].size() * 4) != 0) ++bad;            // the round trip
+    if (L.mfma != (L.K >= kf::kMfmaMinK) || L.OP % 32 || L.OP < L.O) ++bad;
+    rows[l] = dense[l].data();
+    w += dense[l].size();
+  }
+  const int N = 70;
+  std::vector<float> pts(3 * N), out((size_t)N * 8, -7.f);
+  for (auto& v : pts) v = rnd();
+  kf::eval_rows_host(lay, pack.data(), rows, pts.data(), 0, N, out.data(), 8);
+  for (int n = 0; n < N; ++n) {
+    for (int j = 0; j < 7; ++j)
+      if (!(std::fabs(out[n * 8 + j]) <= 1.f)) ++bad;                                // the last layer is a sine
+    if (out[n * 8 + 7] != -7.f) ++bad;                                               // the column past the width is not written
+  }
+  return report("key field 3-5-40-33-7: layout, pack, host rows", bad);
+}
+
 }  // namespace
 
 int main() {
@@ -155,6 +204,7 @@ int main() {
   bad += check_field(60, 2, 256, 33);
   bad += check_field(4, 2, 33, 70);
   bad += check_field(64, 4, 1, 4);
+  bad += check_key_field();
   Layout lay;
   const int32_t w5[5] = {8, 8, 8, 8, 8}, w257[1] = {257};
   int refused = 0;
