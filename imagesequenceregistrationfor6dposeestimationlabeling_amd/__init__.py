@@ -12,6 +12,9 @@ def __getattr__(name):
     if name in ("export_keys", "collect_candidates", "extract_mesh"):
         from . import key_export
         return getattr(key_export, name)
+    if name in ("view_correspondences", "clean_mesh_vertices", "ViewCorrespondences"):
+        from . import correspondences
+        return getattr(correspondences, name)
     if name == "marching_cubes":
         from . import ops
         return ops.marching_cubes

@@ -161,6 +161,20 @@ DENSITY_SIGNATURES = {
     "isr_density_activations_host": (_i, [_vp, _sz, _f, _vp, _vp]),
 }
 
+# include/isr_density_dir.h (the march with a direction), bound the same way
+DENSITY_DIR_SIGNATURES = {
+    "isr_density_march_dir": (_i, [_vp, _sz, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "isr_density_march_dir_host": (_i, [_vp, _sz, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "isr_density_march_given_host": (_i, [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp]),
+}
+
+# include/isr_radius.h (the fixed-radius neighbour count), bound the same way
+RADIUS_SIGNATURES = {
+    "isr_radius_workspace_bytes": (_sz, [_i]),
+    "isr_radius_count": (_i, [_vp, _i, _d, _i, _vp, _vp, _sz, _vp]),
+    "isr_radius_count_host": (_i, [_vp, _i, _d, _i, _vp]),
+}
+
 # include/isr_mc.h (iso-surface extraction), bound the same way
 MC_SIGNATURES = {
     "isr_mc_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -186,7 +200,7 @@ def lib() -> C.CDLL:
     except OSError as e:  # pragma: no cover
         raise IsrError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES, **FPS_SIGNATURES, **DENSITY_SIGNATURES,
-                               **MC_SIGNATURES}.items():
+                               **DENSITY_DIR_SIGNATURES, **RADIUS_SIGNATURES, **MC_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -1,0 +1,101 @@
+"""view_correspondences: one view of generateCors.py's loop (generateCors.py:250-361) on the device.
+
+generateCors.py extracts the density field's mesh, removes its radius outliers, and then for every training view marches the
+view's rays to the front surface, keeps the rays that end near the mesh, shoots a second ray from each surface point towards
+the centre, takes the point where that ray LEAVES the surface (the march from the far end, prenBack.py:378-381), keeps the
+ones near the mesh again, and saves the four tensors augment.getNerfSamples loads (augment.py:639-702).  The functions here
+restate those steps in that order; formats.save_view_correspondences writes the result.  The ray sampler stays the caller's
+(pytorch3d's camera conventions are not restated here): `rays` is whatever bundle it made.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import ops
+from ._capi import require_cuda
+
+
+@dataclass
+class ViewCorrespondences:
+    """On the device; n1 rays passed the front filter, n2 of them the back filter."""
+    xys: torch.Tensor             # (1, n1, 2)  sampled_rays.xys[:, idx1]            -> <size>_sampledRayxys
+    pos_vec: torch.Tensor         # (1, n1, 3)  front surface points                 -> <size>_posVec
+    pos_vec_back: torch.Tensor    # (1, n2, 3)  exit points                          -> <size>_posVecBack
+    xys_back: torch.Tensor        # (1, n2, 2)  xys of the rays that kept their exit -> <size>_sampledRayBackxys
+    idx1: torch.Tensor            # (n1,) int64 into the bundle's rays
+    idx2: torch.Tensor            # (n2,) int64 into the n1 kept rays
+
+
+def clean_mesh_vertices(verts, nb_points: int = 20, radius: float = 0.05):
+    """generateCors.py:254-259: the vertices that have more than nb_points vertices within `radius`, themselves included
+    (ops.radius_outlier_mask, which states what is known of Open3D's rule and that it is unpinned) -> (verts[ind], ind).
+    verts (V,3): a device tensor gives device results (ind int64); a NumPy array is counted on device 0 in f32 and gives
+    NumPy results, the kept rows in the array's own dtype."""
+    if isinstance(verts, torch.Tensor):
+        keep = ops.radius_outlier_mask(verts, nb_points, radius)
+        ind = torch.nonzero(keep).reshape(-1)
+        return verts[ind], ind
+    v = np.asarray(verts)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    keep = ops.radius_outlier_mask(torch.from_numpy(np.ascontiguousarray(v, np.float32)).to(dev), nb_points, radius)
+    ind = np.nonzero(keep.cpu().numpy())[0]
+    return v[ind], ind
+
+
+def near_mesh(points: torch.Tensor, verts64: np.ndarray, verts32: torch.Tensor, max_dist: float) -> torch.Tensor:
+    """Indices of the points within max_dist of their nearest mesh vertex, as key_export.export_keys step 3 finds it: the
+    vertex by ops.nn_batched (an f32 search, the lowest index on ties), the distance in f64 to that vertex as the mesh holds
+    it.  points (n,3) f32 on the device -> (m,) int64 on the device."""
+    if points.shape[0] == 0:
+        return torch.zeros(0, dtype=torch.int64, device=points.device)
+    nearest = ops.nn_batched(points, verts32, want_idx=True).nn_idx[0].to(torch.int64).cpu().numpy()
+    dist = np.linalg.norm(points.cpu().numpy().astype(np.float64) - verts64[nearest], axis=1)
+    return torch.from_numpy(np.where(dist < max_dist)[0]).to(points.device)
+
+
+def view_correspondences(field, rays, mesh_verts, threshold: float = 0.2, back_threshold: float = 0.05, max_dist: float = 0.1,
+                         back_scale: float = 3.0) -> ViewCorrespondences:
+    """generateCors.py:299-349 for one view.  field: a fields.DensityField; rays: any object with .origins, .directions
+    (1, n, 3), .lengths (1, n, P) and .xys (1, n, 2) on the device; mesh_verts (V, 3): the cleaned mesh vertices
+    (clean_mesh_vertices), NumPy or a tensor.
+      1. posVec: the front march at `threshold` (:306);
+      2. idx1: the rays whose posVec is within max_dist of its nearest mesh vertex (:308-309, near_mesh);
+      3. the back rays of the kept rays (:323-329), f32 on the device: origin posVec, direction -(o / ||o||) of the RAY's
+         origin with ||o|| = sqrt(x x + y y + z z), lengths (lengths - lengths[..., :1]) / back_scale;
+      4. posVecBack: the march of the back rays from their far end at back_threshold (:331-334): the last sample above it.
+         back_threshold is 0.05 because prenBack.py:367 compares against the literal 0.05 — it ignores the threshold = 0.2
+         the script sets at generateCors.py:182 for the front march;
+      5. idx2: the same mesh-distance filter on posVecBack (:338-341)."""
+    dev = require_cuda(rays.origins, rays.directions, rays.lengths, rays.xys)
+    if rays.origins.ndim != 3 or rays.origins.shape[0] != 1 or rays.xys.shape[:2] != rays.origins.shape[:2]:
+        raise ValueError(f"view_correspondences: origins {tuple(rays.origins.shape)}, xys {tuple(rays.xys.shape)}: expected "
+                         "(1, n, 3) and (1, n, 2)")
+    v64 = np.ascontiguousarray(mesh_verts.detach().cpu().numpy() if isinstance(mesh_verts, torch.Tensor) else mesh_verts,
+                               np.float64)
+    if v64.ndim != 2 or v64.shape[1] != 3 or len(v64) == 0:
+        raise ValueError(f"view_correspondences: mesh_verts {v64.shape} must be (V, 3) with V >= 1")
+    v32 = torch.from_numpy(v64.astype(np.float32)).to(dev)
+    f32 = lambda t: t.to(torch.float32)
+    o, ln, xys = f32(rays.origins)[0], f32(rays.lengths)[0], rays.xys[0]
+
+    pos, _, _ = field.surface_points(rays.origins, rays.directions, rays.lengths, threshold=threshold)
+    pos = pos[0]
+    idx1 = near_mesh(pos.contiguous(), v64, v32, max_dist)
+    pos, o1, ln1, xys1 = pos[idx1].contiguous(), o[idx1], ln[idx1], xys[idx1]
+
+    norm = torch.sqrt(o1[:, 0] * o1[:, 0] + o1[:, 1] * o1[:, 1] + o1[:, 2] * o1[:, 2])
+    back_dirs = -(o1 / norm[:, None])
+    # the reference takes this quotient on CPU tensors (generateCors.py:316-323 moves the bundle to the host first): a true
+    # f32 division.  On the device torch divides by a host scalar as a multiplication by its reciprocal, another rounding;
+    # a 0-d device tensor as the divisor keeps the division
+    back_lengths = (ln1 - ln1[:, :1]) / torch.tensor(float(back_scale), dtype=torch.float32, device=dev)
+    if pos.shape[0]:
+        back, _, _ = field.surface_points(pos, back_dirs, back_lengths, threshold=back_threshold, direction="back")
+    else:
+        back = pos
+    idx2 = near_mesh(back.contiguous(), v64, v32, max_dist)
+    return ViewCorrespondences(xys=xys1[None], pos_vec=pos[None], pos_vec_back=back[idx2][None], xys_back=xys1[idx2][None],
+                               idx1=idx1, idx2=idx2)

@@ -13,13 +13,15 @@
 // A WORKGROUP OWNS WHOLE RAYS: G = max(1, 64 / P) consecutive rays, their G * P points taken 64 at a time; the densities of
 // its rays stay in LDS (P <= 4096), then thread g marches ray g.  In threshold mode with one ray per workgroup and no
 // densities asked for, the tiles after the one holding the first hit are not evaluated: march_ray multiplies whatever they
-// would give by 0, so no output bit depends on it.
+// would give by 0, so no output bit depends on it.  The march from the far end (isr_density_march_dir, march_ray_back) does
+// the same from the other side, and both directions together skip the tiles between the first and the last hit.
 // Rows past the end of a tile's work are evaluated at the origin and never written.
 #include "field_density.hpp"
 #include "field_tile.hpp"
 #include "isr_common.hpp"
 
 #include "../../include/isr_density.h"
+#include "../../include/isr_density_dir.h"
 
 #include <vector>
 
@@ -83,6 +85,14 @@ __global__ __launch_bounds__(kThreads) void density_eval_kernel(Layout lay, cons
   if (tid < kTP && row0 + tid < N) out[row0 + tid] = dens[tid];
 }
 
+// kDir: 0 the march from the near end (march_ray), 1 from the far end (march_ray_back), 2 both.  Outputs of the back march
+// of kDir 2 follow the front march's: depth[N + ray], points[3 (N + ray)], hit[N + ray], and a ray's weights are 2P wide,
+// [front | back].  In threshold mode with one ray per workgroup and no densities asked for, only the tiles an output bit
+// depends on are evaluated: front walks up to the tile of the first hit; back walks down from the far end to the tile of
+// the last hit; both walks forward to the tile tf of the first hit and then from the far end down to, but not into, tf
+// (the last hit is in tf when nothing lies above it).  rho[0 .. n_eval) and rho[lo_eval .. total) are what was evaluated,
+// and all the marches read.
+template <int kDir>
 __global__ __launch_bounds__(kThreads) void density_march_kernel(Layout lay, const float* __restrict__ pack,
                                                                  const float* __restrict__ origins,
                                                                  const float* __restrict__ directions,
@@ -99,8 +109,8 @@ __global__ __launch_bounds__(kThreads) void density_march_kernel(Layout lay, con
   const int total = nr * P;                          // <= max(64, P) <= kMaxP
   const int T = (total + kTP - 1) / kTP;
   const bool early = threshold >= 0.f && dens_out == nullptr && G == 1;
-  int n_eval = total;
-  for (int t = 0; t < T; ++t) {
+  // tile t through the field -> dens[t * 64 ..); with `early`, whether one of its samples is above the threshold
+  auto tile = [&](int t) -> bool {
     const int q = t * kTP + (tid & 63);
     if (tid < 3 * kTP) {
       const int d = tid >> 6;
@@ -115,25 +125,50 @@ __global__ __launch_bounds__(kThreads) void density_march_kernel(Layout lay, con
     __syncthreads();
     tile_density(lay, pack, act, ptl, dens + t * kTP);
     __syncthreads();
-    if (early) {
-      const int found = tid < kTP && q < total && dens[q] > threshold;
-      if (__syncthreads_or(found)) {
-        n_eval = (t + 1) * kTP < total ? (t + 1) * kTP : total;
+    if (!early) return false;
+    const int found = tid < kTP && q < total && dens[q] > threshold;
+    return __syncthreads_or(found) != 0;
+  };
+  int n_eval = total, lo_eval = 0;
+  int tf = kDir == 1 ? 0 : T;                        // the tiles [0, tf) are the forward walk's
+  if (kDir != 1)
+    for (int t = 0; t < T; ++t)
+      if (tile(t)) {
+        tf = t + 1;
+        n_eval = tf * kTP < total ? tf * kTP : total;
         break;
       }
-    }
-  }
+  if (kDir != 0)
+    for (int t = T - 1; t >= tf; --t)
+      if (tile(t)) {
+        lo_eval = t * kTP;
+        break;
+      }
   if (dens_out)
     for (int q = tid; q < total; q += kThreads) dens_out[ray0 * P + q] = dens[q];
+  if (kDir != 0) __syncthreads();                    // march_ray_back overwrites the densities it reads
   if (tid < nr) {
     const long ray = ray0 + tid;
-    const int left = n_eval - tid * P;               // G > 1: every point was evaluated
+    float* rho = dens + tid * P;                     // G > 1: every point was evaluated
     float dep;
     int32_t h;
-    march_ray(P, lengths + ray * P, dens + tid * P, left < P ? left : P, threshold, w_out ? w_out + ray * P : nullptr, &dep, &h);
-    depth[ray] = dep;
-    hit[ray] = h;
-    for (int d = 0; d < 3; ++d) points[3 * ray + d] = origins[3 * ray + d] + directions[3 * ray + d] * dep;
+    if (kDir != 1) {
+      const int left = n_eval - tid * P;
+      float* w = w_out ? w_out + ray * P * (kDir == 2 ? 2 : 1) : nullptr;
+      march_ray(P, lengths + ray * P, rho, left < P ? left : P, threshold, w, &dep, &h);
+      depth[ray] = dep;
+      hit[ray] = h;
+      for (int d = 0; d < 3; ++d) points[3 * ray + d] = origins[3 * ray + d] + directions[3 * ray + d] * dep;
+    }
+    if (kDir != 0) {
+      const long out = kDir == 2 ? (long)N + ray : ray;
+      const int lo = lo_eval - tid * P;
+      float* w = w_out ? (kDir == 2 ? w_out + ray * P * 2 + P : w_out + ray * P) : nullptr;
+      march_ray_back(P, lengths + ray * P, rho, lo > 0 ? lo : 0, threshold, w, &dep, &h);
+      depth[out] = dep;
+      hit[out] = h;
+      for (int d = 0; d < 3; ++d) points[3 * out + d] = origins[3 * ray + d] + directions[3 * ray + d] * dep;
+    }
   }
 }
 
@@ -213,21 +248,85 @@ extern "C" int isr_density_eval(const void* pack, size_t pack_bytes, int n_hidde
   return ISR_OK;
 }
 
+namespace {
+
+int march_device(const char* who, const void* pack, size_t pack_bytes, int n_hidden, const int32_t* widths, int H,
+                 const float* origins, const float* directions, const float* lengths, int N, int P, float threshold, int direction,
+                 float* densities, float* weights, float* depth, float* points, int32_t* hit, isr_stream_t stream) {
+  Layout lay;
+  if (int rc = check_field(who, pack, pack_bytes, n_hidden, widths, H, lay)) return rc;
+  if (int rc = check_march(who, origins, directions, lengths, N, P, threshold, depth, points, hit)) return rc;
+  ISR_REQUIRE(direction >= 0 && direction <= 2, "%s: direction = %d (0 front, 1 back, 2 both)", who, direction);
+  if (N == 0) return ISR_OK;
+  const int G = P >= kTP ? 1 : kTP / P;
+  const unsigned blocks = (unsigned)(((long)N + G - 1) / G);
+  const float* pk = static_cast<const float*>(pack);
+  hipStream_t st = isr::as_stream(stream);
+  if (direction == 0)
+    density_march_kernel<0><<<blocks, kThreads, 0, st>>>(lay, pk, origins, directions, lengths, N, P, G, threshold, densities,
+                                                         weights, depth, points, hit);
+  else if (direction == 1)
+    density_march_kernel<1><<<blocks, kThreads, 0, st>>>(lay, pk, origins, directions, lengths, N, P, G, threshold, densities,
+                                                         weights, depth, points, hit);
+  else
+    density_march_kernel<2><<<blocks, kThreads, 0, st>>>(lay, pk, origins, directions, lengths, N, P, G, threshold, densities,
+                                                         weights, depth, points, hit);
+  ISR_CHECK_LAUNCH("density_march_kernel");
+  return ISR_OK;
+}
+
+int march_host(const char* who, const void* pack, size_t pack_bytes, int n_hidden, const int32_t* widths, int H,
+               const float* origins, const float* directions, const float* lengths, int N, int P, float threshold, int direction,
+               float* densities, float* weights, float* depth, float* points, int32_t* hit) {
+  Layout lay;
+  if (int rc = check_field(who, pack, pack_bytes, n_hidden, widths, H, lay)) return rc;
+  if (int rc = check_march(who, origins, directions, lengths, N, P, threshold, depth, points, hit)) return rc;
+  ISR_REQUIRE(direction >= 0 && direction <= 2, "%s: direction = %d (0 front, 1 back, 2 both)", who, direction);
+  if (N == 0) return ISR_OK;
+  const HostField hf(lay, pack);
+  std::vector<float> rho((size_t)N * P);
+  isr::parallel_rows((long)N * P, 64, [&](long q) {
+    const long ray = q / P;
+    float x[3];
+    for (int d = 0; d < 3; ++d) x[d] = origins[3 * ray + d] + directions[3 * ray + d] * lengths[q];
+    rho[q] = point_host(lay, pack, hf, x);
+  });
+  if (densities)
+    for (size_t q = 0; q < rho.size(); ++q) densities[q] = rho[q];
+  const long wld = direction == 2 ? 2L * P : P;
+  for (long ray = 0; ray < N; ++ray) {
+    const float* len = lengths + ray * P;
+    float* r = rho.data() + ray * P;
+    float* w = weights ? weights + ray * wld : nullptr;
+    if (direction != 1) {
+      march_ray(P, len, r, P, threshold, w, &depth[ray], &hit[ray]);
+      for (int d = 0; d < 3; ++d) points[3 * ray + d] = origins[3 * ray + d] + directions[3 * ray + d] * depth[ray];
+    }
+    if (direction != 0) {
+      const long out = direction == 2 ? (long)N + ray : ray;
+      march_ray_back(P, len, r, 0, threshold, w ? (direction == 2 ? w + P : w) : nullptr, &depth[out], &hit[out]);
+      for (int d = 0; d < 3; ++d) points[3 * out + d] = origins[3 * ray + d] + directions[3 * ray + d] * depth[out];
+    }
+  }
+  return ISR_OK;
+}
+
+}  // namespace
+
 extern "C" int isr_density_march(const void* pack, size_t pack_bytes, int n_hidden, const int32_t* widths, int H,
                                  const float* origins, const float* directions, const float* lengths, int N, int P,
                                  float threshold, float* densities, float* weights, float* depth, float* points, int32_t* hit,
                                  isr_stream_t stream) {
-  Layout lay;
-  if (int rc = check_field("isr_density_march", pack, pack_bytes, n_hidden, widths, H, lay)) return rc;
-  if (int rc = check_march("isr_density_march", origins, directions, lengths, N, P, threshold, depth, points, hit)) return rc;
-  if (N == 0) return ISR_OK;
-  const int G = P >= kTP ? 1 : kTP / P;
-  const unsigned blocks = (unsigned)(((long)N + G - 1) / G);
-  density_march_kernel<<<blocks, kThreads, 0, isr::as_stream(stream)>>>(lay, static_cast<const float*>(pack), origins, directions,
-                                                                        lengths, N, P, G, threshold, densities, weights, depth,
-                                                                        points, hit);
-  ISR_CHECK_LAUNCH("density_march_kernel");
-  return ISR_OK;
+  return march_device("isr_density_march", pack, pack_bytes, n_hidden, widths, H, origins, directions, lengths, N, P, threshold, 0,
+                      densities, weights, depth, points, hit, stream);
+}
+
+extern "C" int isr_density_march_dir(const void* pack, size_t pack_bytes, int n_hidden, const int32_t* widths, int H,
+                                     const float* origins, const float* directions, const float* lengths, int N, int P,
+                                     float threshold, int direction, float* densities, float* weights, float* depth,
+                                     float* points, int32_t* hit, isr_stream_t stream) {
+  return march_device("isr_density_march_dir", pack, pack_bytes, n_hidden, widths, H, origins, directions, lengths, N, P,
+                      threshold, direction, densities, weights, depth, points, hit, stream);
 }
 
 extern "C" int isr_density_eval_host(const void* pack, size_t pack_bytes, int n_hidden, const int32_t* widths, int H,
@@ -245,25 +344,37 @@ extern "C" int isr_density_march_host(const void* pack, size_t pack_bytes, int n
                                       const float* origins, const float* directions, const float* lengths, int N, int P,
                                       float threshold, float* densities, float* weights, float* depth, float* points,
                                       int32_t* hit) {
-  Layout lay;
-  if (int rc = check_field("isr_density_march_host", pack, pack_bytes, n_hidden, widths, H, lay)) return rc;
-  if (int rc = check_march("isr_density_march_host", origins, directions, lengths, N, P, threshold, depth, points, hit)) return rc;
-  if (N == 0) return ISR_OK;
-  const HostField hf(lay, pack);
-  std::vector<float> rho((size_t)N * P);
-  isr::parallel_rows((long)N * P, 64, [&](long q) {
-    const long ray = q / P;
-    float x[3];
-    for (int d = 0; d < 3; ++d) x[d] = origins[3 * ray + d] + directions[3 * ray + d] * lengths[q];
-    rho[q] = point_host(lay, pack, hf, x);
-  });
+  return march_host("isr_density_march_host", pack, pack_bytes, n_hidden, widths, H, origins, directions, lengths, N, P, threshold,
+                    0, densities, weights, depth, points, hit);
+}
+
+extern "C" int isr_density_march_dir_host(const void* pack, size_t pack_bytes, int n_hidden, const int32_t* widths, int H,
+                                          const float* origins, const float* directions, const float* lengths, int N, int P,
+                                          float threshold, int direction, float* densities, float* weights, float* depth,
+                                          float* points, int32_t* hit) {
+  return march_host("isr_density_march_dir_host", pack, pack_bytes, n_hidden, widths, H, origins, directions, lengths, N, P,
+                    threshold, direction, densities, weights, depth, points, hit);
+}
+
+extern "C" int isr_density_march_given_host(const float* lengths, const float* rho, int N, int P, float threshold, int direction,
+                                            float* weights, float* depth, int32_t* hit) {
+  const char* who = "isr_density_march_given_host";
+  if (int rc = isr::check_rows(who, N, lengths && rho && depth && hit)) return rc;
+  ISR_REQUIRE(P >= 1 && P <= kMaxP, "%s: P = %d (1..%d)", who, P, kMaxP);
+  ISR_REQUIRE(threshold == threshold, "%s: threshold is NaN", who);
+  ISR_REQUIRE(direction >= 0 && direction <= 2, "%s: direction = %d (0 front, 1 back, 2 both)", who, direction);
+  std::vector<float> r((size_t)P);
+  const long wld = direction == 2 ? 2L * P : P;
   for (long ray = 0; ray < N; ++ray) {
-    march_ray(P, lengths + ray * P, rho.data() + ray * P, P, threshold, weights ? weights + ray * P : nullptr, &depth[ray],
-              &hit[ray]);
-    for (int d = 0; d < 3; ++d) points[3 * ray + d] = origins[3 * ray + d] + directions[3 * ray + d] * depth[ray];
+    for (int k = 0; k < P; ++k) r[k] = rho[ray * P + k];
+    float* w = weights ? weights + ray * wld : nullptr;
+    if (direction != 1) march_ray(P, lengths + ray * P, r.data(), P, threshold, w, &depth[ray], &hit[ray]);
+    if (direction != 0) {
+      const long out = direction == 2 ? (long)N + ray : ray;
+      march_ray_back(P, lengths + ray * P, r.data(), 0, threshold, w ? (direction == 2 ? w + P : w) : nullptr, &depth[out],
+                     &hit[out]);
+    }
   }
-  if (densities)
-    for (size_t q = 0; q < rho.size(); ++q) densities[q] = rho[q];
   return ISR_OK;
 }
 

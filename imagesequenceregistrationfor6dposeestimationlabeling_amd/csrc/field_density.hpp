@@ -259,6 +259,35 @@ ISR_FIELD_FN void march_ray(int P, const float* len, const float* rho, int n_eva
   *hit = any;
 }
 
+// The march of the same ray taken from its far end (prenBack.py:378-381: weights2 = rho * flip(shifted_cumprod(1 - flip(rho)))).
+//   A_{P-1} = 1, A_k = A_{k+1} * (1 - c_{k+1}) for k descending; c_k as in march_ray (threshold >= 0: rho_k > threshold ? 1 : 0,
+//   a NaN gives 0; threshold < 0: rho_k); w2_k = c_k * A_k: in threshold mode one-hot at the LAST hit, the exit point.
+//   depth = max_k(len_k * w2_k), taken for k ascending from the first product with march_ray's NaN rule; hit = any(w2_k != 0).
+// Only rho[lo_eval .. P) is read: in threshold mode a caller may leave the samples in front of the tile holding the last hit
+// unevaluated, their c_k is multiplied by A_k = 0 whatever it is.  rho[lo_eval .. P) is OVERWRITTEN with the weights (the
+// descending pass leaves them there for the ascending maximum); weights may be null.
+ISR_FIELD_FN void march_ray_back(int P, const float* len, float* rho, int lo_eval, float threshold, float* weights, float* depth,
+                                 int32_t* hit) {
+  float absorb = 1.0f;
+  for (int k = P - 1; k >= lo_eval; --k) {
+    const float c = threshold >= 0.f ? (rho[k] > threshold ? 1.0f : 0.0f) : rho[k];
+    rho[k] = c * absorb;
+    absorb = absorb * (1.0f - c);
+  }
+  float m = 0.f;
+  int32_t any = 0;
+  for (int k = 0; k < P; ++k) {
+    const float w = k >= lo_eval ? rho[k] : 0.0f;      // in front of lo_eval: c_k * A_k with A_k = 0 and c_k 0 or 1
+    if (weights) weights[k] = w;
+    if (w != 0.f) any = 1;
+    const float v = len[k] * w;
+    if (k == 0) m = v;
+    else if (m == m && (v != v || v > m)) m = v;      // a NaN stays
+  }
+  *depth = m;
+  *hit = any;
+}
+
 // Host: W (row-major, hidden layers then the output row), b -> pack (lay.total_words words)
 inline void pack_host(const Layout& lay, const float* freqs, float beta, const float* W, const float* b, void* pack) {
   float* pf = static_cast<float*>(pack);

@@ -205,16 +205,22 @@ class DensityField(_PackedField):
         return v
 
     def surface_points(self, origins, directions, lengths, threshold: float = 0.2, return_weights: bool = False,
-                       surface_thickness: int = 1):
+                       surface_thickness: int = 1, direction: str = "front"):
         """genFeat.py:191-193: origins + directions * max(lengths * weights) per ray -> (points (..., 3), depth (...),
         hit (...) bool), and with return_weights the (..., P) weights of pren.py:365 as a fourth.  threshold >= 0 is the
-        reference's thresholdMode (0.2 there); a negative one gives the emission-absorption weights."""
+        reference's thresholdMode (0.2 there); a negative one gives the emission-absorption weights.
+        direction "back": the same triple for the march from the far end of the ray, the exit point (prenBack.py:378-381 as
+        generateCors.py:334 reads it); "both": (front triple, back triple) from one launch, and with return_weights a third
+        entry, the (..., 2P) weights [front | back] of prenBack.py:385."""
         if surface_thickness != 1:
             raise ValueError("DensityField.surface_points: only surface_thickness = 1 is supported")
         o, d, ln = self._bundle(origins, directions, lengths)
         pts, depth, hit, _, wts = ops.density_march(self.pack, self.widths, self.H, o, d, ln, threshold=threshold,
-                                                    want_weights=return_weights)
+                                                    want_weights=return_weights, direction=direction)
         lead = tuple(lengths.shape[:-1])
+        if direction == "both":
+            res = tuple((pts[s].reshape(*lead, 3), depth[s].reshape(lead), hit[s].reshape(lead) != 0) for s in (0, 1))
+            return res + (wts.reshape(*lead, -1),) if return_weights else res
         res = (pts.reshape(*lead, 3), depth.reshape(lead), hit.reshape(lead) != 0)
         return res + (wts.reshape(lengths.shape),) if return_weights else res
 
@@ -232,16 +238,22 @@ class DensityField(_PackedField):
         pts = np.stack(np.meshgrid(t, t, t, indexing="ij"), axis=-1).reshape(-1, 3)
         return self.eval_host(pts).reshape(int(res), int(res), int(res))
 
-    def march_host(self, origins, directions, lengths, threshold: float = 0.2):
-        """isr_density_march_host: NumPy (N,3), (N,3), (N,P) -> dict of points, depth, hit, densities, weights.  For tests."""
+    def march_host(self, origins, directions, lengths, threshold: float = 0.2, direction: str = "front"):
+        """isr_density_march_host / isr_density_march_dir_host: NumPy (N,3), (N,3), (N,P) -> dict of points, depth, hit,
+        densities, weights, shaped as ops.density_march shapes them for `direction`.  For tests."""
         o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
         ln = np.ascontiguousarray(lengths, np.float32)
         N, P = ln.shape
-        out = dict(points=np.empty((N, 3), np.float32), depth=np.empty(N, np.float32), hit=np.empty(N, np.int32),
-                   densities=np.empty((N, P), np.float32), weights=np.empty((N, P), np.float32))
-        check(lib().isr_density_march_host(_vp(self.pack_host), self.pack_host.nbytes, len(self.widths), _vp(self._w), self.H,
-                                           _vp(o), _vp(d), _vp(ln), N, P, float(threshold), _vp(out["densities"]),
-                                           _vp(out["weights"]), _vp(out["depth"]), _vp(out["points"]), _vp(out["hit"])),
-              "isr_density_march_host")
+        way = ops.march_direction(direction)
+        lead = (2, N) if way == 2 else (N,)
+        out = dict(points=np.empty((*lead, 3), np.float32), depth=np.empty(lead, np.float32), hit=np.empty(lead, np.int32),
+                   densities=np.empty((N, P), np.float32), weights=np.empty((N, 2 * P if way == 2 else P), np.float32))
+        head = (_vp(self.pack_host), self.pack_host.nbytes, len(self.widths), _vp(self._w), self.H, _vp(o), _vp(d), _vp(ln), N, P,
+                float(threshold))
+        tail = (_vp(out["densities"]), _vp(out["weights"]), _vp(out["depth"]), _vp(out["points"]), _vp(out["hit"]))
+        if way == 0:
+            check(lib().isr_density_march_host(*head, *tail), "isr_density_march_host")
+        else:
+            check(lib().isr_density_march_dir_host(*head, way, *tail), "isr_density_march_dir_host")
         return out

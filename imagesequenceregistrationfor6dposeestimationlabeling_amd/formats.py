@@ -43,6 +43,36 @@ def save_model(pts, feats, normals, UH, dataset: str, objid, base: Path | str = 
     return d
 
 
+VIEW_DIRS = ("sampledRayxys", "posVec", "posVecBack", "sampledRayBackxys")      # generateCors.py:358-361, in that order
+VIEW_FIELDS = ("xys", "pos_vec", "pos_vec_back", "xys_back")
+
+
+def save_view_correspondences(nerf_dir: Path | str, render_size: int, view, vc) -> list[Path]:
+    """generateCors.py:358-361: the four files of one view, <nerf_dir>/<render_size>_sampledRayxys/<view>.pt (1, n1, 2),
+    _posVec (1, n1, 3), _posVecBack (1, n2, 3) and _sampledRayBackxys (1, n2, 2), each a CPU tensor written by torch.save —
+    what augment.getNerfSamples loads (augment.py:641-666).  vc: a correspondences.ViewCorrespondences (any object with
+    xys, pos_vec, pos_vec_back, xys_back).  Directories are created as needed."""
+    import torch
+    paths = []
+    for sub, name in zip(VIEW_DIRS, VIEW_FIELDS):
+        d = Path(nerf_dir) / f"{render_size}_{sub}"
+        d.mkdir(parents=True, exist_ok=True)
+        t = getattr(vc, name).detach().cpu().contiguous()
+        want = 2 if name.startswith("xys") else 3
+        if t.ndim != 3 or t.shape[0] != 1 or t.shape[2] != want:
+            raise ValueError(f"save_view_correspondences: {name} {tuple(t.shape)} must be (1, n, {want})")
+        torch.save(t, d / f"{view}.pt")
+        paths.append(d / f"{view}.pt")
+    return paths
+
+
+def load_view_correspondences(nerf_dir: Path | str, render_size: int, view) -> dict:
+    """The four files back as augment.py:641-666 reads them -> dict of xys, pos_vec, pos_vec_back, xys_back (CPU tensors)."""
+    import torch
+    return {name: torch.load(Path(nerf_dir) / f"{render_size}_{sub}" / f"{view}.pt")
+            for sub, name in zip(VIEW_DIRS, VIEW_FIELDS)}
+
+
 def is_failure(R, t=None) -> bool:
     """pnp()'s failure sentinel is the int triple (1, 1, 1) (inference.py:130-134)."""
     return isinstance(R, (int, np.integer)) or np.ndim(R) == 0

@@ -1182,11 +1182,24 @@ def density_eval(pack: torch.Tensor, widths, H: int, points: torch.Tensor, out: 
     return out
 
 
+MARCH_DIRECTIONS = {"front": 0, "back": 1, "both": 2}
+
+
+def march_direction(direction: str) -> int:
+    """ISR_MARCH_* of include/isr_density_dir.h for "front", "back" or "both"."""
+    if direction not in MARCH_DIRECTIONS:
+        raise ValueError(f"density_march: direction = {direction!r} (front, back or both)")
+    return MARCH_DIRECTIONS[direction]
+
+
 def density_march(pack: torch.Tensor, widths, H: int, origins: torch.Tensor, directions: torch.Tensor, lengths: torch.Tensor,
-                  threshold: float = 0.2, want_densities: bool = False, want_weights: bool = False):
+                  threshold: float = 0.2, want_densities: bool = False, want_weights: bool = False, direction: str = "front"):
     """isr_density_march: origins (N,3), directions (N,3), lengths (N,P) f32 -> (points (N,3) f32, depth (N,) f32,
     hit (N,) int32, densities (N,P) f32 or None, weights (N,P) f32 or None).  threshold >= 0: the weight is one at the first
-    density above it (the reference's thresholdMode); threshold < 0: emission-absorption weights."""
+    density above it (the reference's thresholdMode); threshold < 0: emission-absorption weights.
+    direction (isr_density_march_dir): "front" is the above; "back" the same outputs for the march from the far end of the
+    ray (one at the LAST density above the threshold: the exit point, prenBack.py:378-381); "both" gives points (2,N,3),
+    depth (2,N), hit (2,N), front then back, and weights (N,2P), a ray's front weights then its back weights."""
     dev = require_cuda(pack, origins, directions, lengths)
     for name, t, cols in (("origins", origins, 3), ("directions", directions, 3), ("lengths", lengths, None)):
         if t.dtype != torch.float32 or t.ndim != 2 or (cols and t.shape[1] != cols) or not t.is_contiguous():
@@ -1199,17 +1212,42 @@ def density_march(pack: torch.Tensor, widths, H: int, origins: torch.Tensor, dir
     thr = float(threshold)
     if thr != thr:
         raise ValueError("density_march: threshold is NaN")
+    way = march_direction(direction)
+    lead = (2, N) if way == 2 else (N,)
     f32 = dict(dtype=torch.float32, device=dev)
-    points, depth = torch.empty((N, 3), **f32), torch.empty((N,), **f32)
-    hit = torch.empty((N,), dtype=torch.int32, device=dev)
+    points, depth = torch.empty((*lead, 3), **f32), torch.empty(lead, **f32)
+    hit = torch.empty(lead, dtype=torch.int32, device=dev)
     dens = torch.empty((N, P), **f32) if want_densities else None
-    wts = torch.empty((N, P), **f32) if want_weights else None
+    wts = torch.empty((N, 2 * P if way == 2 else P), **f32) if want_weights else None
     pk, nbytes, nh, wp, _keep = _field_args(pack, widths, len(widths))
-    with torch.cuda.device(dev), _timed("density_march", float(N) * P * density_flops(widths, H)):
-        rc = lib().isr_density_march(pk, nbytes, nh, wp, int(H), ptr(origins), ptr(directions), ptr(lengths), N, P, thr,
-                                     ptr(dens), ptr(wts), ptr(depth), ptr(points), ptr(hit), current_stream(dev))
-    check(rc, "isr_density_march")
+    work = float(N) * P * density_flops(widths, H)
+    if way == 0:
+        with torch.cuda.device(dev), _timed("density_march", work):
+            rc = lib().isr_density_march(pk, nbytes, nh, wp, int(H), ptr(origins), ptr(directions), ptr(lengths), N, P, thr,
+                                         ptr(dens), ptr(wts), ptr(depth), ptr(points), ptr(hit), current_stream(dev))
+        check(rc, "isr_density_march")
+    else:
+        with torch.cuda.device(dev), _timed("density_march_" + direction, work):
+            rc = lib().isr_density_march_dir(pk, nbytes, nh, wp, int(H), ptr(origins), ptr(directions), ptr(lengths), N, P, thr,
+                                             way, ptr(dens), ptr(wts), ptr(depth), ptr(points), ptr(hit), current_stream(dev))
+        check(rc, "isr_density_march_dir")
     return points, depth, hit, dens, wts
+
+
+def density_march_given_host(lengths, rho, threshold: float, direction: str = "front"):
+    """isr_density_march_given_host: the march alone of given densities, host code, NumPy (N,P), (N,P) -> (weights, depth,
+    hit) shaped as density_march shapes them for `direction`.  For tests."""
+    ln, r = np.ascontiguousarray(lengths, np.float32), np.ascontiguousarray(rho, np.float32)
+    if ln.ndim != 2 or ln.shape != r.shape:
+        raise ValueError(f"density_march_given_host: lengths {ln.shape}, rho {r.shape}")
+    N, P = ln.shape
+    way = march_direction(direction)
+    lead = (2, N) if way == 2 else (N,)
+    wts, depth, hit = np.empty((N, 2 * P if way == 2 else P), np.float32), np.empty(lead, np.float32), np.empty(lead, np.int32)
+    hp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    check(lib().isr_density_march_given_host(hp(ln), hp(r), N, P, float(threshold), way, hp(wts), hp(depth), hp(hit)),
+          "isr_density_march_given_host")
+    return wts, depth, hit
 
 
 def _host_i32(v, B: int, what: str):
@@ -1320,3 +1358,50 @@ def marching_cubes_host(vol, iso: float, check_finite: bool = True):
     check(lib().isr_mc_emit_host(hp(v), nx, ny, nz, float(iso), hp(verts) if V else None, V, hp(tris) if F else None, F),
           "isr_mc_emit_host")
     return verts, tris
+
+
+def _cloud_n3(name: str, points, radius, check_finite: bool) -> float:
+    if points.ndim != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+        raise ValueError(f"{name}: points must be (N,3) with N >= 1, got {tuple(points.shape)}")
+    r = float(radius)
+    if not (np.isfinite(r) and r > 0):
+        raise ValueError(f"{name}: radius = {radius} must be finite and positive")
+    if check_finite and not bool(torch.isfinite(points).all() if isinstance(points, torch.Tensor) else np.isfinite(points).all()):
+        raise ValueError(f"{name}: non-finite coordinates (finite points are a precondition)")
+    return r
+
+
+def radius_count(points: torch.Tensor, radius: float, cap: int = 0, check_finite: bool = True) -> torch.Tensor:
+    """isr_radius_count: points (N,3) f32 on the device -> counts (N,) int32, counts[i] the number of points j, i itself
+    included, with d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) <= r * r in f32 (r the radius rounded to f32), clamped to cap
+    when cap > 0.  A cell grid and a counting sort on the device (csrc/radius_count.hpp states the rule); exact, a function of
+    (points, radius, cap) only.  Nothing synchronises but check_finite, which refuses non-finite coordinates (a precondition)."""
+    dev = require_cuda(points)
+    pts = _f32c(points)
+    r = _cloud_n3("radius_count", pts, radius, check_finite)
+    N = pts.shape[0]
+    L = lib()
+    counts = torch.empty((N,), dtype=torch.int32, device=dev)
+    ws = workspace(dev, L.isr_radius_workspace_bytes(N), "radius")
+    with torch.cuda.device(dev), _timed("radius_count", float(N)):
+        rc = L.isr_radius_count(ptr(pts), N, r, int(cap), ptr(counts), ptr(ws), ws.numel(), current_stream(dev))
+    check(rc, "isr_radius_count")
+    return counts
+
+
+def radius_count_host(points, radius: float, cap: int = 0, check_finite: bool = True):
+    """isr_radius_count_host: the same count as host code, NumPy (N,3) -> (N,) int32.  For tests."""
+    p = np.ascontiguousarray(points, np.float32)
+    r = _cloud_n3("radius_count_host", p, radius, check_finite)
+    counts = np.empty(p.shape[0], np.int32)
+    hp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    check(lib().isr_radius_count_host(hp(p), p.shape[0], r, int(cap), hp(counts)), "isr_radius_count_host")
+    return counts
+
+
+def radius_outlier_mask(points: torch.Tensor, nb_points: int, radius: float) -> torch.Tensor:
+    """True where a point has more than nb_points points within `radius`, itself included:
+    radius_count(points, radius, cap=nb_points + 1) > nb_points.  This is Open3D's RemoveRadiusOutliers
+    (generateCors.py:257) AS FAR AS IT IS KNOWN FROM MEMORY — it keeps a point whose radius search, which finds the point
+    itself, returns more than nb_points — Open3D is not available to compare against: the rule is unpinned."""
+    return radius_count(points, radius, cap=int(nb_points) + 1) > int(nb_points)

@@ -4,7 +4,8 @@
 // Runs sin32 and sincos32 over every exponent of f32 (both signs, the extremes of the mantissa) and the non-finite values, softplus32 and
 // density32 over a sweep that crosses every branch, packs fields at the limits of the layout (H = 1 and 64, widths 1 and 256,
 // 1 and 4 hidden layers) and evaluates points through them, and marches rays in both modes including P = 1 and a partly
-// evaluated ray, and takes a key field (csrc/field_mlp.hpp) of odd widths through make_layout / pack_host / eval_rows_host, so that
+// evaluated ray, marches the same rays from the far end (march_ray_back: both modes, P = 1, a partly evaluated ray, NaN
+// densities, a null weights pointer) against the flipped forward march, and takes a key field (csrc/field_mlp.hpp) of odd widths through make_layout / pack_host / eval_rows_host, so that
 // the helpers the two headers share run from both sides.  Checks ranges and a few identities; prints one line per case; exit status 0 = all hold.
 // The log of one such run is profiles/density_host_sanitizers.txt.
 #include <cmath>
@@ -192,6 +193,55 @@ int check_key_field() {
   return report("key field 3-5-40-33-7: layout, pack, host rows", bad);
 }
 
+// march_ray_back against march_ray on the flipped ray: the weights are the forward weights of the reversed densities,
+// reversed; a partly evaluated ray in threshold mode gives the bits of the fully evaluated one.
+int check_back_march() {
+  int bad = 0;
+  unsigned s = 99u;
+  auto rnd = [&] {
+    s = s * 1664525u + 1013904223u;
+    return (float)((s >> 8) & 0xffff) / 65536.f;
+  };
+  for (int P : {1, 2, 63, 64, 65, 200, kMaxP})
+    for (float thr : {0.5f, -1.f}) {
+      std::vector<float> len(P), rho(P), rev(P), ones(P, 1.f), w(P), wrev(P), work(P);
+      for (int k = 0; k < P; ++k) {
+        len[k] = 0.01f * (float)k - 0.3f;
+        rho[k] = rnd() * (thr < 0.f ? 0.2f : 1.f);
+        if (P > 2 && k == P / 2) rho[k] = NAN;
+        rev[P - 1 - k] = rho[k];
+      }
+      float dep, drev;
+      int32_t hit, hrev;
+      work = rho;
+      march_ray_back(P, len.data(), work.data(), 0, thr, w.data(), &dep, &hit);
+      march_ray(P, ones.data(), rev.data(), P, thr, wrev.data(), &drev, &hrev);
+      for (int k = 0; k < P; ++k)
+        if (std::memcmp(&w[k], &wrev[P - 1 - k], 4) != 0 && !(w[k] != w[k] && wrev[P - 1 - k] != wrev[P - 1 - k])) ++bad;
+      if (hit != hrev) ++bad;
+      work = rho;
+      float dep0;
+      int32_t hit0;
+      march_ray_back(P, len.data(), work.data(), 0, thr, nullptr, &dep0, &hit0);             // null weights: the same depth
+      if (std::memcmp(&dep, &dep0, 4) != 0 || hit != hit0) ++bad;
+      if (thr >= 0.f && hit) {
+        int last = P - 1;
+        while (!(rho[last] > thr)) --last;
+        const int lo = last / 64 * 64;                                                       // the tile of the last hit
+        std::vector<float> part(rho), w2(P);
+        for (int k = 0; k < lo; ++k) part[k] = 7.f;                                          // in front of lo: above the threshold, never read
+        float dep2;
+        int32_t hit2;
+        march_ray_back(P, len.data(), part.data(), lo, thr, w2.data(), &dep2, &hit2);
+        for (int k = 0; k < lo; ++k)
+          if (part[k] != 7.f) ++bad;                                                         // nor written
+        if (std::memcmp(&dep, &dep2, 4) != 0 || hit2 != 1 || std::memcmp(w.data(), w2.data(), (size_t)P * 4) != 0) ++bad;
+        if (w[last] != 1.f) ++bad;
+      }
+    }
+  return report("march_ray_back: flipped march, partial ray, null", bad);
+}
+
 }  // namespace
 
 int main() {
@@ -205,6 +255,7 @@ int main() {
   bad += check_field(4, 2, 33, 70);
   bad += check_field(64, 4, 1, 4);
   bad += check_key_field();
+  bad += check_back_march();
   Layout lay;
   const int32_t w5[5] = {8, 8, 8, 8, 8}, w257[1] = {257};
   int refused = 0;
