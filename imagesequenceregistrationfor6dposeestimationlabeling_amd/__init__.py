@@ -6,13 +6,13 @@ def __getattr__(name):
     if name in ("KeyField", "DensityField"):
         from . import fields
         return getattr(fields, name)
-    if name in ("sample_farthest_points", "thin_keys"):
+    if name in ("sample_farthest_points", "thin_keys", "estimate_pointcloud_normals", "estimate_pointcloud_local_coord_frames"):
         from . import sampling
         return getattr(sampling, name)
     if name in ("export_keys", "collect_candidates", "extract_mesh"):
         from . import key_export
         return getattr(key_export, name)
-    if name in ("view_correspondences", "clean_mesh_vertices", "ViewCorrespondences"):
+    if name in ("view_correspondences", "clean_mesh_vertices", "ViewCorrespondences", "subsampled_normals"):
         from . import correspondences
         return getattr(correspondences, name)
     if name == "marching_cubes":

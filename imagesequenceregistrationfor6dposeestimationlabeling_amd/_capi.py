@@ -175,6 +175,15 @@ RADIUS_SIGNATURES = {
     "isr_radius_count_host": (_i, [_vp, _i, _d, _i, _vp]),
 }
 
+# include/isr_knn.h (k nearest neighbours and local frames), bound the same way
+KNN_SIGNATURES = {
+    "isr_knn_workspace_bytes": (_sz, [_i, _i, _i]),
+    "isr_knn": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "isr_knn_host": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),
+    "isr_local_frames": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "isr_local_frames_host": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),
+}
+
 # include/isr_mc.h (iso-surface extraction), bound the same way
 MC_SIGNATURES = {
     "isr_mc_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -200,7 +209,7 @@ def lib() -> C.CDLL:
     except OSError as e:  # pragma: no cover
         raise IsrError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES, **FPS_SIGNATURES, **DENSITY_SIGNATURES,
-                               **DENSITY_DIR_SIGNATURES, **RADIUS_SIGNATURES, **MC_SIGNATURES}.items():
+                               **DENSITY_DIR_SIGNATURES, **RADIUS_SIGNATURES, **MC_SIGNATURES, **KNN_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

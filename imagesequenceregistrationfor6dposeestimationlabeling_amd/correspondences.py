@@ -45,6 +45,35 @@ def clean_mesh_vertices(verts, nb_points: int = 20, radius: float = 0.05):
     return v[ind], ind
 
 
+def subsampled_normals(mesh_verts, K: int = 1000, neighborhood_size: int = 400, host: bool = False):
+    """generateCors.py:205-212: the mesh vertices as f32, reduced to K points by farthest-point sampling from index 0
+    (sampling.sample_farthest_points(v[None], K=K)[1][0], pytorch3d's default start), and the NEGATED
+    sampling.estimate_pointcloud_normals(subvert, neighborhood_size) of that subset -> (subvert (K,3) f32, subnormal (K,3)
+    f32): what formats.save_subsampled_normals writes.  mesh_verts (V,3): a device tensor gives device tensors; a NumPy array
+    is worked on device 0 and gives NumPy arrays.  Fewer than K vertices, or neighborhood_size >= K, raises ValueError.
+    host=True runs the same steps through the _host entries on a NumPy array (the tests' reference)."""
+    from . import sampling
+    K, nb = int(K), int(neighborhood_size)
+    if mesh_verts.ndim != 2 or mesh_verts.shape[1] != 3:
+        raise ValueError(f"subsampled_normals: mesh_verts must be (V,3), got {tuple(mesh_verts.shape)}")
+    if K < 1 or mesh_verts.shape[0] < K:
+        raise ValueError(f"subsampled_normals: {mesh_verts.shape[0]} vertices, K = {K}")
+    if nb < 1 or nb >= K:
+        raise ValueError(f"subsampled_normals: neighborhood_size = {nb} must be in 1..K - 1 = {K - 1}")
+    if host:
+        v = np.ascontiguousarray(mesh_verts, np.float32)
+        sub = v[ops.fps_sample_host(v, K)[0].astype(np.int64)]
+        return sub, -sampling.estimate_pointcloud_normals(sub, nb, host=True)
+    as_numpy = not isinstance(mesh_verts, torch.Tensor)
+    if as_numpy:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        mesh_verts = torch.from_numpy(np.ascontiguousarray(mesh_verts, np.float32)).to(dev)
+    v = mesh_verts.to(torch.float32)
+    sub = v[sampling.sample_farthest_points(v[None], K=K)[1][0]]
+    normal = -sampling.estimate_pointcloud_normals(sub, nb)
+    return (sub.cpu().numpy(), normal.cpu().numpy()) if as_numpy else (sub, normal)
+
+
 def near_mesh(points: torch.Tensor, verts64: np.ndarray, verts32: torch.Tensor, max_dist: float) -> torch.Tensor:
     """Indices of the points within max_dist of their nearest mesh vertex, as key_export.export_keys step 3 finds it: the
     vertex by ops.nn_batched (an f32 search, the lowest index on ties), the distance in f64 to that vertex as the mesh holds

@@ -73,6 +73,30 @@ def load_view_correspondences(nerf_dir: Path | str, render_size: int, view) -> d
             for sub, name in zip(VIEW_DIRS, VIEW_FIELDS)}
 
 
+def save_subsampled_normals(nerf_dir: Path | str, subvert, subnormal) -> list[Path]:
+    """generateCors.py:214-215: <nerf_dir>/subvert1.npy and subnormal1.npy, (K, 3) float32 arrays written by np.save
+    (correspondences.subsampled_normals makes them; tensors are copied to the host)."""
+    arrays = []
+    for name, a in (("subvert", subvert), ("subnormal", subnormal)):
+        a = np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, np.float32)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"save_subsampled_normals: {name} {a.shape} must be (K, 3)")
+        arrays.append(a)
+    if arrays[0].shape != arrays[1].shape:
+        raise ValueError(f"save_subsampled_normals: subvert {arrays[0].shape} and subnormal {arrays[1].shape}")
+    Path(nerf_dir).mkdir(parents=True, exist_ok=True)
+    paths = [Path(nerf_dir) / "subvert1.npy", Path(nerf_dir) / "subnormal1.npy"]
+    for path, a in zip(paths, arrays):
+        np.save(path, a)
+    return paths
+
+
+def load_subsampled_normals(nerf_dir: Path | str):
+    """The two files back as trainPose.py:196-198 reads them -> (subvert, subnormal), float32 arrays."""
+    return (np.load(Path(nerf_dir) / "subvert1.npy").astype("float32"),
+            np.load(Path(nerf_dir) / "subnormal1.npy").astype("float32"))
+
+
 def is_failure(R, t=None) -> bool:
     """pnp()'s failure sentinel is the int triple (1, 1, 1) (inference.py:130-134)."""
     return isinstance(R, (int, np.integer)) or np.ndim(R) == 0

@@ -1405,3 +1405,81 @@ def radius_outlier_mask(points: torch.Tensor, nb_points: int, radius: float) -> 
     (generateCors.py:257) AS FAR AS IT IS KNOWN FROM MEMORY — it keeps a point whose radius search, which finds the point
     itself, returns more than nb_points — Open3D is not available to compare against: the rule is unpinned."""
     return radius_count(points, radius, cap=int(nb_points) + 1) > int(nb_points)
+
+
+def _knn_args(name: str, query, target, K, check_finite: bool) -> int:
+    for what, a in (("query", query), ("target", target)):
+        if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < 1:
+            raise ValueError(f"{name}: {what} must be (N,3) with N >= 1, got {tuple(a.shape)}")
+    K = int(K)
+    if not 1 <= K <= min(target.shape[0], 1024):
+        raise ValueError(f"{name}: K = {K} outside 1..min(Nt = {target.shape[0]}, 1024)")
+    if check_finite:
+        fin = (lambda a: bool(torch.isfinite(a).all())) if isinstance(query, torch.Tensor) else (lambda a: bool(np.isfinite(a).all()))
+        if not (fin(query) and fin(target)):
+            raise ValueError(f"{name}: non-finite coordinates (finite points are a precondition)")
+    return K
+
+
+def knn(query: torch.Tensor, target: torch.Tensor, K: int, want_d2: bool = True, check_finite: bool = True):
+    """isr_knn: query (Nq,3), target (Nt,3) f32 on the device -> (idx (Nq,K) int32, d2 (Nq,K) f32 or None): per query the K
+    targets smallest under (d2, index), ascending, d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) in f32; among equal distances the
+    lowest index first (csrc/knn.hpp states the rule).  Brute force over LDS tiles, a radix select per query; exact, a
+    function of (query, target, K) only.  Nothing synchronises but check_finite, which refuses non-finite coordinates."""
+    dev = require_cuda(query, target)
+    q, t = _f32c(query), _f32c(target)
+    K = _knn_args("knn", q, t, K, check_finite)
+    Nq, Nt = q.shape[0], t.shape[0]
+    L = lib()
+    idx = torch.empty((Nq, K), dtype=torch.int32, device=dev)
+    d2 = torch.empty((Nq, K), dtype=torch.float32, device=dev) if want_d2 else None
+    ws = workspace(dev, L.isr_knn_workspace_bytes(Nq, Nt, K), "knn")
+    with torch.cuda.device(dev), _timed("knn", float(Nq) * Nt):
+        rc = L.isr_knn(ptr(q), Nq, ptr(t), Nt, K, ptr(idx), ptr(d2), ptr(ws), ws.numel(), current_stream(dev))
+    check(rc, "isr_knn")
+    return idx, d2
+
+
+def knn_host(query, target, K: int, want_d2: bool = True, check_finite: bool = True):
+    """isr_knn_host: the same search as host code, NumPy (Nq,3), (Nt,3) -> (idx int32, d2 f32 or None).  For tests."""
+    q, t = np.ascontiguousarray(query, np.float32), np.ascontiguousarray(target, np.float32)
+    K = _knn_args("knn_host", q, t, K, check_finite)
+    idx = np.empty((q.shape[0], K), np.int32)
+    d2 = np.empty((q.shape[0], K), np.float32) if want_d2 else None
+    hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    check(lib().isr_knn_host(hp(q), q.shape[0], hp(t), t.shape[0], K, hp(idx), hp(d2)), "isr_knn_host")
+    return idx, d2
+
+
+def _frames_args(name: str, points, idx) -> tuple[int, int]:
+    if points.ndim != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+        raise ValueError(f"{name}: points must be (N,3) with N >= 1, got {tuple(points.shape)}")
+    if idx.ndim != 2 or idx.shape[0] != points.shape[0] or not 1 <= idx.shape[1] <= 1024:
+        raise ValueError(f"{name}: idx must be (N,K) with N = {points.shape[0]} and K in 1..1024, got {tuple(idx.shape)}")
+    return points.shape[0], idx.shape[1]
+
+
+def local_frames(points: torch.Tensor, idx: torch.Tensor, disambiguate: bool = True):
+    """isr_local_frames: points (N,3) f32 and idx (N,K) (knn(points, points, K)[0]) on the device -> (curvatures (N,3) f64
+    ascending, frames (N,3,3) f64, columns = eigenvectors, column 0 the normal): the eigen-decomposition of each
+    neighbourhood's covariance about its own mean in f64 by cyclic Jacobi, and with disambiguate the sign rule
+    include/isr_knn.h states (pytorch3d's as far as it is known: unpinned).  Nothing synchronises."""
+    dev = require_cuda(points, idx)
+    pts, ix = _f32c(points), idx.to(torch.int32).contiguous()
+    N, K = _frames_args("local_frames", pts, ix)
+    curv = torch.empty((N, 3), dtype=torch.float64, device=dev)
+    frames = torch.empty((N, 3, 3), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev), _timed("local_frames", float(N) * K):
+        rc = lib().isr_local_frames(ptr(pts), N, ptr(ix), K, int(bool(disambiguate)), ptr(curv), ptr(frames), current_stream(dev))
+    check(rc, "isr_local_frames")
+    return curv, frames
+
+
+def local_frames_host(points, idx, disambiguate: bool = True):
+    """isr_local_frames_host: the same frames as host code, NumPy (N,3), (N,K) -> (curvatures, frames) f64.  For tests."""
+    p, ix = np.ascontiguousarray(points, np.float32), np.ascontiguousarray(idx, np.int32)
+    N, K = _frames_args("local_frames_host", p, ix)
+    curv, frames = np.empty((N, 3), np.float64), np.empty((N, 3, 3), np.float64)
+    hp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    check(lib().isr_local_frames_host(hp(p), N, hp(ix), K, int(bool(disambiguate)), hp(curv), hp(frames)), "isr_local_frames_host")
+    return curv, frames

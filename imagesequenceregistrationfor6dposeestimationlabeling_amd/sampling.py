@@ -1,12 +1,21 @@
-"""Farthest-point sampling on the device, with pytorch3d's call shape.
+"""Farthest-point sampling and point-cloud normals on the device, with pytorch3d's call shapes.
 
 genFeat.py:199-201 thins the key candidates with pytorch3d.ops.sample_farthest_points(fullNegVec, K=80000) on the CPU;
 sample_farthest_points below keeps that signature and return order, so the script works with the import line changed.
 The sampling is isr_fps_sample (csrc/fps.hpp states the rule: f32 squared distances, the lowest index wins a tie), a
 function of (points, lengths, start, K) only.
+
+generateCors.py:211 calls pytorch3d.ops.estimate_pointcloud_normals(fv, neighborhood_size=400);
+estimate_pointcloud_normals and estimate_pointcloud_local_coord_frames below keep pytorch3d's names and signatures.  They
+are ops.knn of the cloud against itself and ops.local_frames (include/isr_knn.h states both rules).  What pytorch3d does is
+restated FROM MEMORY, the library being unavailable to compare against: the covariance divided by the neighbourhood size,
+the smallest eigenvalue's vector as the normal, the sign rule and the refusal of neighborhood_size >= N are unpinned.  One
+known difference: pytorch3d centres the cloud and works in f32; here the covariance is formed in f64 about each
+neighbourhood's own mean, and the results are rounded to f32 at the end.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import ops
@@ -56,3 +65,41 @@ def thin_keys(pts: torch.Tensor, feats: torch.Tensor, n: int):
         raise ValueError(f"thin_keys: n = {n} outside 1..{pts.shape[0]}")
     sel = ops.fps_sample(pts, int(n)).to(torch.int64)
     return pts[sel], feats[sel], sel
+
+
+def estimate_pointcloud_local_coord_frames(pointclouds, neighborhood_size: int = 50, disambiguate_directions: bool = True,
+                                           host: bool = False):
+    """pointclouds (N,3) or (B,N,3) on the device -> (curvatures (..,N,3) ascending, local_coord_frames (..,N,3,3), columns =
+    eigenvectors, column 0 the normal), f32 on the input's device; one ops.knn + ops.local_frames per cloud.
+    neighborhood_size >= N raises ValueError, as pytorch3d does.  host=True takes NumPy arrays through the _host entries and
+    returns NumPy arrays: the tests' reference, never chosen silently."""
+    K = int(neighborhood_size)
+    single = pointclouds.ndim == 2
+    clouds = pointclouds[None] if single else pointclouds
+    if clouds.ndim != 3 or clouds.shape[2] != 3:
+        raise ValueError(f"estimate_pointcloud_local_coord_frames: pointclouds must be (N,3) or (B,N,3), got "
+                         f"{tuple(pointclouds.shape)}")
+    if K < 1 or K >= clouds.shape[1]:
+        raise ValueError(f"estimate_pointcloud_local_coord_frames: neighborhood_size = {K} must be in 1..N - 1 = "
+                         f"{clouds.shape[1] - 1}")
+    curvs, frames = [], []
+    for cloud in clouds:
+        if host:
+            cloud = np.ascontiguousarray(cloud, np.float32)
+            c, f = ops.local_frames_host(cloud, ops.knn_host(cloud, cloud, K, want_d2=False)[0], disambiguate_directions)
+            c, f = c.astype(np.float32), f.astype(np.float32)
+        else:
+            c, f = ops.local_frames(cloud, ops.knn(cloud, cloud, K, want_d2=False)[0], disambiguate_directions)
+            c, f = c.to(torch.float32), f.to(torch.float32)
+        curvs.append(c)
+        frames.append(f)
+    if single:
+        return curvs[0], frames[0]
+    return (np.stack(curvs), np.stack(frames)) if host else (torch.stack(curvs), torch.stack(frames))
+
+
+def estimate_pointcloud_normals(pointclouds, neighborhood_size: int = 50, disambiguate_directions: bool = True,
+                                host: bool = False):
+    """pointclouds (N,3) or (B,N,3) -> normals of the same shape, f32: column 0 of
+    estimate_pointcloud_local_coord_frames(...)[1], the eigenvector of the smallest eigenvalue."""
+    return estimate_pointcloud_local_coord_frames(pointclouds, neighborhood_size, disambiguate_directions, host)[1][..., 0]
