@@ -84,8 +84,30 @@ extern __shared__ uint4 corr_direct_dyn_lds[];
 #ifndef ISR_K1_PLAIN_WAVES
 #define ISR_K1_PLAIN_WAVES 3      // waves per SIMD the plain-row kernels (D <= 64) are compiled for
 #endif
+// The plain-row kernels leave a SLICE of every SIMD's register file free: three waves of at most ISR_K1_PLAIN_VGPRS = 144
+// registers hold 432 of the 512, and those kernels beside K1 in a step that allocate 80 or fewer (scoring, selection, compaction,
+// grid build: profiles/k1_slice_resources.txt) start in the rest instead of waiting for a K1 workgroup to leave and taking its
+// 168-register slot; the wide ones (searches, refits: 104 to 136) still wait (profiles/README.md).  The
+// source sheds the registers itself — ONE staging offset register instead of one per piece (KO1 below) — and the compiler then
+// allocates what the live state needs: no attribute caps the count, the resource table is the check.
+// ISR_K1_PLAIN_VGPRS = 168 builds the former form for an A/B.
+// With the smaller live state the scheduler sees four waves per SIMD (128 registers) within reach and, to get there, leaves
+// the item blocks in source order — each v_exp_f32 directly in front of the addition that needs it, a wait state between
+// them, the sched_group_barriers ignored: 57 instructions per item for 44.  Four waves are not wanted (128 registers mean spills,
+// and measured slower: profiles/README.md, round 4), so the dieted kernels tell it that three is the most (amdgpu_waves_per_eu's
+// second argument).  Its first argument, one less than the launch bound, only keeps the scheduler from undoing its own work in
+// the item blocks of every second stage (at the minimum number of waves it reverts a schedule that does not lower the register
+// pressure); the register count stays the allocator's, 144 or less, and with it three waves per SIMD as before.
+#ifndef ISR_K1_PLAIN_VGPRS
+#define ISR_K1_PLAIN_VGPRS 144
+#endif
+// (D = 64 rows, DK = 4: the narrower plain-row kernels take 128 registers or fewer as they are, four waves per SIMD)
+constexpr bool plain_diet(int DK, int SP) { return ISR_K1_PLAIN_VGPRS < 168 && DK == 4 && SP == 0; }
+constexpr int direct_min_waves(int DK, int SP) { return (DK <= 4 && SP == 0) ? ISR_K1_PLAIN_WAVES : (DK <= 4 ? 3 : (SP >= 8 ? 1 : 2)); }
 template <int DK, int QB, bool NAT, int DKU = DK, int SP = 0, bool F16 = false, bool LSE = false, int SKIP = 0>
-__global__ __launch_bounds__(kThreads, (DK <= 4 && SP == 0) ? ISR_K1_PLAIN_WAVES : (DK <= 4 ? 3 : (SP >= 8 ? 1 : 2))) void corr_bf16_direct_kernel(
+__global__ __attribute__((amdgpu_waves_per_eu(plain_diet(DK, SP) ? direct_min_waves(DK, SP) - 1 : direct_min_waves(DK, SP),
+                                              plain_diet(DK, SP) ? direct_min_waves(DK, SP) : 0)))
+__launch_bounds__(kThreads, direct_min_waves(DK, SP)) void corr_bf16_direct_kernel(
     const uint16_t* __restrict__ Q, const uint16_t* __restrict__ K, int P, int N, int ldq, int ldk,
     int range_chunks, CorrWs ws, int32_t* __restrict__ idx_out, float* __restrict__ logp_out,
     float* __restrict__ lse_out) {
@@ -268,12 +290,21 @@ __global__ __launch_bounds__(kThreads, (DK <= 4 && SP == 0) ? ISR_K1_PLAIN_WAVES
 #define ISR_DIRECT_DMA 1      // plain rows (power-of-two chunk counts) through the same DMA staging: -1.5 % at D = 64 (profiles/r04_k1_dma_ab.txt); 0: registers + ds_write
 #endif
   constexpr bool DMA = SP != 0 || (ISR_DIRECT_DMA != 0 && POW2);
-  int koff[NLD];
+  // KO1 (D = 64 plain rows on the register diet): piece i of a stage starts kThreads / NCH key rows behind piece 0 and, that being a
+  // multiple of the swizzle's period, in the same slot of its row — koff[i] = koff[0] + i ro with ro wave-uniform: one offset
+  // register, the rest joins the stage's scalar offset.  The asm makes koff[0] opaque: seen through, the sum is re-associated
+  // into one vector induction variable per (piece, buffer) plus their bases — fifteen registers for what one and a scalar
+  // addition do (the same v_add_u32 per piece as before, its scalar operand formed on the scalar unit).
+  constexpr bool KO1 = plain_diet(DK, SP) && DMA;
+  static_assert(!KO1 || (POW2 && (kThreads / NCH) % (RPB * NCH) == 0), "one offset register: the swizzle term repeats every kThreads / NCH rows");
+  int koff[KO1 ? 1 : NLD];
 #pragma unroll
-  for (int i = 0; i < NLD; ++i) {
+  for (int i = 0; i < (KO1 ? 1 : NLD); ++i) {
     const int ci = tid + i * kThreads;
     koff[i] = DMA ? ((ci / NCH) * ldk + 8 * slot(ci / NCH, ci % NCH)) * 2 : ((ci / NCH) * ldk + 8 * (ci % NCH)) * 2;
   }
+  if constexpr (KO1) asm volatile("" : "+v"(koff[0]));
+  const int ro = (kThreads / NCH) * ldk * 2;
   uint4 stg[DMA ? 1 : NLD];
   auto gload = [&](int stage, int dbuf = -1) {       // dbuf: the destination buffer when the caller knows it at compile time
     const int so = stage * TKS * ldk * 2;
@@ -283,7 +314,7 @@ __global__ __launch_bounds__(kThreads, (DK <= 4 && SP == 0) ? ISR_K1_PLAIN_WAVES
 #pragma unroll
       for (int i = 0; i < NLD; ++i)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (__attribute__((address_space(3))) void*)&lds[dbuf * CHUNKS + i * kThreads + wave * 64],
-                                                 16, koff[i] + so, 0, 0, 0);
+                                                 16, KO1 ? koff[0] + (so + i * ro) : koff[i] + so, 0, 0, 0);
 #endif
     } else {
 #pragma unroll
