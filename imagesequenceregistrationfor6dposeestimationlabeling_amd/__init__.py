@@ -15,6 +15,9 @@ def __getattr__(name):
     if name in ("view_correspondences", "clean_mesh_vertices", "ViewCorrespondences", "subsampled_normals"):
         from . import correspondences
         return getattr(correspondences, name)
+    if name in ("PerspectiveCameras", "RayBundle", "NDCMultinomialRaysampler", "MonteCarloRaysampler", "sample_images_at_mc_locs"):
+        from . import rays
+        return getattr(rays, name)
     if name == "marching_cubes":
         from . import ops
         return ops.marching_cubes

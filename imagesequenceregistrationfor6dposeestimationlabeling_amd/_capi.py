@@ -184,6 +184,21 @@ KNN_SIGNATURES = {
     "isr_local_frames_host": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),
 }
 
+# include/isr_rays.h (ray bundles from cameras), bound the same way
+_RAYS_SPEC = [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _u64]      # mode .. seed: the arguments every isr_rays_* entry starts with
+RAYS_SIGNATURES = {
+    "isr_rays_workspace_bytes": (_sz, [_i, _i]),
+    "isr_rays_bundle": (_i, [*_RAYS_SPEC, _vp, _vp, _vp, _vp, _vp]),
+    "isr_rays_bundle_host": (_i, [*_RAYS_SPEC, _vp, _vp, _vp, _vp]),
+    "isr_rays_select_count": (_i, [*_RAYS_SPEC, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "isr_rays_select_emit": (_i, [*_RAYS_SPEC, _vp, _i, _i, _vp, _sz, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "isr_rays_select_count_host": (_i, [*_RAYS_SPEC, _vp, _i, _i, _vp]),
+    "isr_rays_select_emit_host": (_i, [*_RAYS_SPEC, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "isr_sample_nearest": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "isr_sample_nearest_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "isr_rays_philox_host": (_i, [_vp, _vp, _vp, _vp]),
+}
+
 # include/isr_mc.h (iso-surface extraction), bound the same way
 MC_SIGNATURES = {
     "isr_mc_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -209,7 +224,8 @@ def lib() -> C.CDLL:
     except OSError as e:  # pragma: no cover
         raise IsrError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES, **FPS_SIGNATURES, **DENSITY_SIGNATURES,
-                               **DENSITY_DIR_SIGNATURES, **RADIUS_SIGNATURES, **MC_SIGNATURES, **KNN_SIGNATURES}.items():
+                               **DENSITY_DIR_SIGNATURES, **RADIUS_SIGNATURES, **MC_SIGNATURES, **KNN_SIGNATURES,
+                               **RAYS_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

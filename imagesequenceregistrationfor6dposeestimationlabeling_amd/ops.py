@@ -1483,3 +1483,210 @@ def local_frames_host(points, idx, disambiguate: bool = True):
     hp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
     check(lib().isr_local_frames_host(hp(p), N, hp(ix), K, int(bool(disambiguate)), hp(curv), hp(frames)), "isr_local_frames_host")
     return curv, frames
+
+
+RAYS_GRID, RAYS_MC = 0, 1       # ISR_RAYS_GRID / ISR_RAYS_MC of include/isr_rays.h
+
+
+@dataclass(frozen=True)
+class RaySpec:
+    """Which rays a call of the isr_rays_* entries makes (include/isr_rays.h states the rules): host values only.
+    mode RAYS_GRID: W x H rays per camera in raster order; mode RAYS_MC: n rays per camera from Philox under `seed`."""
+    mode: int
+    P: int
+    min_depth: float
+    max_depth: float
+    W: int = 0
+    H: int = 0
+    n: int = 0
+    min_x: float = -1.0
+    max_x: float = 1.0
+    min_y: float = -1.0
+    max_y: float = 1.0
+    stratified: bool = False
+    seed: int = 0
+
+    @property
+    def rays_per_camera(self) -> int:
+        return self.W * self.H if self.mode == RAYS_GRID else self.n
+
+
+def _rays_check(name: str, spec: RaySpec, R, T, intr, camera_ids) -> int:
+    """Shapes of the camera arrays and the limits of include/isr_rays.h; -> B."""
+    if R.ndim != 3 or tuple(R.shape[1:]) != (3, 3) or R.shape[0] < 1:
+        raise ValueError(f"{name}: R must be (B,3,3) with B >= 1, got {tuple(R.shape)}")
+    B = R.shape[0]
+    if tuple(T.shape) != (B, 3) or tuple(intr.shape) != (B, 4):
+        raise ValueError(f"{name}: T must be ({B},3) and intr ({B},4), got {tuple(T.shape)} and {tuple(intr.shape)}")
+    if camera_ids is not None and tuple(camera_ids.shape) != (B,):
+        raise ValueError(f"{name}: camera_ids must be ({B},), got {tuple(camera_ids.shape)}")
+    if spec.mode not in (RAYS_GRID, RAYS_MC):
+        raise ValueError(f"{name}: mode = {spec.mode}")
+    if spec.mode == RAYS_GRID and (spec.W < 1 or spec.H < 1):
+        raise ValueError(f"{name}: grid {spec.W} x {spec.H} (each at least 1)")
+    if spec.mode == RAYS_MC and spec.n < 1:
+        raise ValueError(f"{name}: n = {spec.n} rays per camera (at least 1)")
+    if B * spec.rays_per_camera > 2 ** 28:
+        raise ValueError(f"{name}: {B} cameras x {spec.rays_per_camera} rays is more than 2^28")
+    if not 1 <= spec.P <= 4096:
+        raise ValueError(f"{name}: P = {spec.P} outside 1..4096")
+    vals = (spec.min_x, spec.max_x, spec.min_y, spec.max_y, spec.min_depth, spec.max_depth)
+    if not all(np.isfinite(v) for v in vals) or spec.min_x > spec.max_x or spec.min_y > spec.max_y:
+        raise ValueError(f"{name}: ranges and depths must be finite with min <= max, got {vals}")
+    if not 0 <= int(spec.seed) < 2 ** 64:
+        raise ValueError(f"{name}: seed = {spec.seed} outside 0..2^64-1")
+    return B
+
+
+def _rays_args(spec: RaySpec, B: int, R, T, intr, camera_ids, p):
+    return (spec.mode, p(R), p(T), p(intr), p(camera_ids), B, spec.W, spec.H, spec.n, spec.P, spec.min_x, spec.max_x, spec.min_y,
+            spec.max_y, spec.min_depth, spec.max_depth, int(bool(spec.stratified)), int(spec.seed))
+
+
+def _rays_mask(name: str, mask, B: int):
+    if mask.ndim == 4 and mask.shape[-1] == 1:
+        mask = mask[..., 0]
+    if mask.ndim != 3 or mask.shape[0] != B or min(mask.shape[1:]) < 1:
+        raise ValueError(f"{name}: mask must be ({B},mh,mw) or ({B},mh,mw,1), got {tuple(mask.shape)}")
+    return mask
+
+
+def _i32c(t):
+    return None if t is None else t.to(torch.int32).contiguous()
+
+
+def rays_bundle(spec: RaySpec, R: torch.Tensor, T: torch.Tensor, intr: torch.Tensor, camera_ids: torch.Tensor | None = None):
+    """isr_rays_bundle: cameras R (B,3,3), T (B,3), intr (B,4) = (fx, fy, px, py) in NDC, f32 on the device -> every ray of
+    `spec`: (origins (B,n,3), directions (B,n,3), lengths (B,n,P), xys (B,n,2)) f32 on the device.  Nothing synchronises."""
+    dev = require_cuda(R, T, intr, camera_ids)
+    R, T, intr, ids = _f32c(R), _f32c(T), _f32c(intr), _i32c(camera_ids)
+    B = _rays_check("rays_bundle", spec, R, T, intr, ids)
+    n = spec.rays_per_camera
+    o = torch.empty((B, n, 3), dtype=torch.float32, device=dev)
+    d = torch.empty((B, n, 3), dtype=torch.float32, device=dev)
+    ln = torch.empty((B, n, spec.P), dtype=torch.float32, device=dev)
+    xy = torch.empty((B, n, 2), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timed("rays_bundle", float(B) * n * spec.P):
+        rc = lib().isr_rays_bundle(*_rays_args(spec, B, R, T, intr, ids, ptr), ptr(o), ptr(d), ptr(ln), ptr(xy), current_stream(dev))
+    check(rc, "isr_rays_bundle")
+    return o, d, ln, xy
+
+
+def rays_select(spec: RaySpec, R: torch.Tensor, T: torch.Tensor, intr: torch.Tensor, mask: torch.Tensor,
+                camera_ids: torch.Tensor | None = None, cap: int | None = None):
+    """isr_rays_select_count + isr_rays_select_emit: the rays of `spec` whose xy falls on a non-zero pixel of mask (B,mh,mw[,1])
+    (nutil.sample_images_at_mc_locs' nearest pixel; NaN counts), compacted in (camera, ray) order ->
+    (origins (M,3), directions (M,3), lengths (M,P), xys (M,2), src (M,) int32: b * n + r of each kept ray, count (1,) int32),
+    all on the device.  cap None: M = the count, read between the two calls — the one synchronise.  cap given: M = cap,
+    nothing synchronises, rows from the count on are zeros and rows past cap are lost."""
+    dev = require_cuda(R, T, intr, mask, camera_ids)
+    R, T, intr, ids = _f32c(R), _f32c(T), _f32c(intr), _i32c(camera_ids)
+    B = _rays_check("rays_select", spec, R, T, intr, ids)
+    m = _f32c(_rays_mask("rays_select", mask, B))
+    mh, mw = m.shape[1:]
+    if cap is not None and not 0 <= int(cap) <= 2 ** 28:
+        raise ValueError(f"rays_select: cap = {cap} outside 0..2^28")
+    L = lib()
+    args = _rays_args(spec, B, R, T, intr, ids, ptr)
+    ws = workspace(dev, L.isr_rays_workspace_bytes(B, spec.rays_per_camera), "rays")
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        with _timed("rays_select_count", float(B) * spec.rays_per_camera):
+            rc = L.isr_rays_select_count(*args, ptr(m), mh, mw, ptr(count), ptr(ws), ws.numel(), current_stream(dev))
+        check(rc, "isr_rays_select_count")
+        M = int(count.cpu()[0]) if cap is None else int(cap)
+        o = torch.empty((M, 3), dtype=torch.float32, device=dev)
+        d = torch.empty((M, 3), dtype=torch.float32, device=dev)
+        ln = torch.empty((M, spec.P), dtype=torch.float32, device=dev)
+        xy = torch.empty((M, 2), dtype=torch.float32, device=dev)
+        src = torch.empty((M,), dtype=torch.int32, device=dev)
+        if M:
+            with _timed("rays_select_emit", float(M) * spec.P):
+                rc = L.isr_rays_select_emit(*args, ptr(m), mh, mw, ptr(ws), ws.numel(), M, ptr(o), ptr(d), ptr(ln), ptr(xy), ptr(src),
+                                            current_stream(dev))
+            check(rc, "isr_rays_select_emit")
+    return o, d, ln, xy, src, count
+
+
+def _rays_host_arrays(R, T, intr, camera_ids):
+    c = lambda a: np.ascontiguousarray(a, np.float32)
+    return c(R), c(T), c(intr), None if camera_ids is None else np.ascontiguousarray(camera_ids, np.int32)
+
+
+def _hp(a):
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def rays_bundle_host(spec: RaySpec, R, T, intr, camera_ids=None):
+    """isr_rays_bundle_host: the same bundle as host code over NumPy arrays.  For tests."""
+    R, T, intr, ids = _rays_host_arrays(R, T, intr, camera_ids)
+    B = _rays_check("rays_bundle_host", spec, R, T, intr, ids)
+    n = spec.rays_per_camera
+    o, d = np.empty((B, n, 3), np.float32), np.empty((B, n, 3), np.float32)
+    ln, xy = np.empty((B, n, spec.P), np.float32), np.empty((B, n, 2), np.float32)
+    check(lib().isr_rays_bundle_host(*_rays_args(spec, B, R, T, intr, ids, _hp), _hp(o), _hp(d), _hp(ln), _hp(xy)),
+          "isr_rays_bundle_host")
+    return o, d, ln, xy
+
+
+def rays_select_host(spec: RaySpec, R, T, intr, mask, camera_ids=None, cap: int | None = None):
+    """isr_rays_select_count_host + isr_rays_select_emit_host: rays_select as host code over NumPy arrays; count an int."""
+    R, T, intr, ids = _rays_host_arrays(R, T, intr, camera_ids)
+    B = _rays_check("rays_select_host", spec, R, T, intr, ids)
+    m = np.ascontiguousarray(_rays_mask("rays_select_host", np.asarray(mask), B), np.float32)
+    mh, mw = m.shape[1:]
+    args = _rays_args(spec, B, R, T, intr, ids, _hp)
+    cnt = np.empty(1, np.int32)
+    check(lib().isr_rays_select_count_host(*args, _hp(m), mh, mw, _hp(cnt)), "isr_rays_select_count_host")
+    M = int(cnt[0]) if cap is None else int(cap)
+    o, d = np.empty((M, 3), np.float32), np.empty((M, 3), np.float32)
+    ln, xy, src = np.empty((M, spec.P), np.float32), np.empty((M, 2), np.float32), np.empty((M,), np.int32)
+    if M:
+        check(lib().isr_rays_select_emit_host(*args, _hp(m), mh, mw, M, _hp(o), _hp(d), _hp(ln), _hp(xy), _hp(src)),
+              "isr_rays_select_emit_host")
+    return o, d, ln, xy, src, int(cnt[0])
+
+
+def _sample_shapes(name: str, images, xys) -> tuple[int, int, int, int, int]:
+    if images.ndim != 4 or min(images.shape) < 1 or images.shape[3] > 4096:
+        raise ValueError(f"{name}: images must be (B,H,W,C), every side at least 1 and C at most 4096, got {tuple(images.shape)}")
+    B, H, W, C = images.shape
+    if xys.ndim < 3 or xys.shape[0] != B or xys.shape[-1] != 2 or 0 in tuple(xys.shape):
+        raise ValueError(f"{name}: xys must be ({B},...,2) and not empty, got {tuple(xys.shape)}")
+    n = int(np.prod(xys.shape[1:-1]))
+    if B * n > 2 ** 28 or B * n * C >= 2 ** 31:
+        raise ValueError(f"{name}: {B} x {n} locations x {C} channels is too many (B n <= 2^28, B n C < 2^31)")
+    return B, H, W, C, n
+
+
+def sample_at_rays(images: torch.Tensor, xys: torch.Tensor) -> torch.Tensor:
+    """isr_sample_nearest: images (B,H,W,C) sampled at the NDC locations xys (B,...,2) -> (B,...,C) f32, on the device:
+    grid_sample(images.permute(0,3,1,2), -xys, align_corners=True, mode='nearest') with zero padding (nutil.py:188-193),
+    value for value.  Nothing synchronises."""
+    dev = require_cuda(images, xys)
+    im, xy = _f32c(images), _f32c(xys)
+    B, H, W, C, n = _sample_shapes("sample_at_rays", im, xy)
+    out = torch.empty((*xy.shape[:-1], C), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timed("sample_nearest", float(B) * n * C):
+        rc = lib().isr_sample_nearest(ptr(im), B, H, W, C, ptr(xy), n, ptr(out), current_stream(dev))
+    check(rc, "isr_sample_nearest")
+    return out
+
+
+def sample_at_rays_host(images, xys):
+    """isr_sample_nearest_host: the same sampling as host code over NumPy arrays.  For tests."""
+    im, xy = np.ascontiguousarray(images, np.float32), np.ascontiguousarray(xys, np.float32)
+    B, H, W, C, n = _sample_shapes("sample_at_rays_host", im, xy)
+    out = np.empty((*xy.shape[:-1], C), np.float32)
+    check(lib().isr_sample_nearest_host(_hp(im), B, H, W, C, _hp(xy), n, _hp(out)), "isr_sample_nearest_host")
+    return out
+
+
+def philox_host(counter, key):
+    """isr_rays_philox_host: Philox4x32-10 of counter (4 words) under key (2 words) -> (words (4,) uint32, units (4,) f32)."""
+    c, k = np.ascontiguousarray(counter, np.uint32), np.ascontiguousarray(key, np.uint32)
+    if c.shape != (4,) or k.shape != (2,):
+        raise ValueError(f"philox_host: counter must be 4 words and key 2, got {c.shape} and {k.shape}")
+    words, units = np.empty(4, np.uint32), np.empty(4, np.float32)
+    check(lib().isr_rays_philox_host(_hp(c), _hp(k), _hp(words), _hp(units)), "isr_rays_philox_host")
+    return words, units

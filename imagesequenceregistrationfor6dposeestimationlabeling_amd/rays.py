@@ -1,0 +1,169 @@
+"""Rays from cameras on the device, under pytorch3d's names: PerspectiveCameras, NDCMultinomialRaysampler,
+MonteCarloRaysampler and RayBundle as generateCors.py:125-138, :279-293 and genFeat.py:102-106, :162-189 use them, and the
+silhouette selection of pren.py:229-236 (`sampler(cameras, mask=...)`).  The rays come from the isr_rays_* entries
+(include/isr_rays.h states every rule, and which of them are pytorch3d's only as far as they are known from memory); this
+module holds the camera's bookkeeping and the conversion of screen-space intrinsics to NDC.
+
+Out of scope: the renderer's stratified=True (ProbabilisticRaysampler / sample_pdf), rayFreeze (the caller keeps the
+bundle), unit_directions, K= and FoV cameras."""
+from __future__ import annotations
+
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import ops
+from .ops import RAYS_GRID, RAYS_MC, RaySpec
+
+
+class RayBundle(NamedTuple):
+    origins: torch.Tensor       # (..., 3)
+    directions: torch.Tensor    # (..., 3), not normalised: origins + directions * z is the point at camera depth z
+    lengths: torch.Tensor       # (..., P)
+    xys: torch.Tensor           # (..., 2) NDC, +x left, +y up
+
+
+def _rows(name: str, v, B: int, device, per_camera: bool = False) -> torch.Tensor:
+    """v as a (B, 2) f32 tensor.  A scalar, (B, 1) and (B, 2) broadcast; a 1-D value is one per camera when per_camera
+    (focal_length (B,)), otherwise one row (2,)."""
+    t = torch.as_tensor(v).to(device=device, dtype=torch.float32)
+    if t.ndim == 0:
+        t = t.reshape(1, 1)
+    elif t.ndim == 1:
+        t = t.reshape(-1, 1) if per_camera else t.reshape(1, -1)
+    if t.ndim != 2 or t.shape[0] not in (1, B) or t.shape[1] not in (1, 2) or (t.shape[1] == 1 and not (per_camera or t.shape[0] == 1)):
+        raise ValueError(f"PerspectiveCameras: {name} must broadcast to ({B},2), got {tuple(torch.as_tensor(v).shape)}")
+    return t.expand(B, 2).contiguous()
+
+
+class PerspectiveCameras:
+    """Row-vector cameras: X_cam = X_world R + T, x_ndc = fx X/Z + px; NDC is +x left, +y up.
+
+    R (B,3,3), T (B,3); focal_length (B,) or (B,2) and principal_point (B,2) in pixels unless in_ndc, image_size (H, W) (or
+    (B,2) rows of it).  With in_ndc=False the intrinsics are mapped to NDC with s = min(H, W):
+        f_ndc = f * 2 / s,   px_ndc = -(px - W/2) * 2 / s,   py_ndc = -(py - H/2) * 2 / s
+    — pytorch3d's documented formula AS FAR AS IT IS KNOWN FROM MEMORY (unpinned: pytorch3d is not available); the signs are
+    held by tests/test_rays_cpu.py to BOP poses converted as in generateCors.py:98-102 and their OpenCV pixels.
+    cameras[idx] (an int, a slice, a list or a tensor of indices) and len(cameras) work as in pytorch3d."""
+
+    def __init__(self, R, T, focal_length=1.0, principal_point=((0.0, 0.0),), image_size=None, in_ndc: bool = False, device=None,
+                 K=None):
+        if K is not None:
+            raise ValueError("PerspectiveCameras: K= is not supported; give focal_length and principal_point")
+        R = torch.as_tensor(R)
+        device = torch.device(device) if device is not None else R.device
+        self.R = R.to(device=device, dtype=torch.float32).contiguous()
+        self.T = torch.as_tensor(T).to(device=device, dtype=torch.float32).contiguous()
+        if self.R.ndim != 3 or tuple(self.R.shape[1:]) != (3, 3) or self.R.shape[0] < 1 or tuple(self.T.shape) != (self.R.shape[0], 3):
+            raise ValueError(f"PerspectiveCameras: R must be (B,3,3) and T (B,3), got {tuple(self.R.shape)} and {tuple(self.T.shape)}")
+        B = self.R.shape[0]
+        f = _rows("focal_length", focal_length, B, device, per_camera=True)
+        p = _rows("principal_point", principal_point, B, device)
+        self.in_ndc = bool(in_ndc)
+        self.image_size = None
+        if not self.in_ndc:
+            if image_size is None:
+                raise ValueError("PerspectiveCameras: screen-space intrinsics (in_ndc=False) need image_size = (H, W)")
+            hw = _rows("image_size", image_size, B, device)
+            if not bool((hw >= 1).all()):
+                raise ValueError("PerspectiveCameras: image_size must be at least 1 x 1")
+            self.image_size = hw
+            s = hw.min(dim=1, keepdim=True).values
+            wh = hw.flip(1)                                          # (W, H) beside (px, py)
+            f = f * 2 / s
+            p = -(p - wh / 2) * 2 / s
+        self.intrinsics = torch.cat([f, p], dim=1).contiguous()      # (B, 4): fx, fy, px, py in NDC
+        self.device = device
+
+    def __len__(self) -> int:
+        return self.R.shape[0]
+
+    def __getitem__(self, idx) -> "PerspectiveCameras":
+        if isinstance(idx, int):
+            idx = [idx]
+        if not isinstance(idx, slice):
+            idx = torch.as_tensor(idx, device=self.device)
+            if idx.dtype == torch.bool or idx.ndim != 1:
+                raise IndexError("PerspectiveCameras: index with an int, a slice or a 1-D list / tensor of indices")
+            idx = idx.long()
+        out = object.__new__(PerspectiveCameras)
+        out.R, out.T, out.intrinsics = self.R[idx].contiguous(), self.T[idx].contiguous(), self.intrinsics[idx].contiguous()
+        out.image_size = None if self.image_size is None else self.image_size[idx].contiguous()
+        out.in_ndc, out.device = self.in_ndc, self.device
+        if len(out) < 1:
+            raise IndexError("PerspectiveCameras: the index selects no camera")
+        return out
+
+    def to(self, device) -> "PerspectiveCameras":
+        out = object.__new__(PerspectiveCameras)
+        out.device = torch.device(device)
+        out.R, out.T, out.intrinsics = self.R.to(out.device), self.T.to(out.device), self.intrinsics.to(out.device)
+        out.image_size = None if self.image_size is None else self.image_size.to(out.device)
+        out.in_ndc = self.in_ndc
+        return out
+
+
+def _bundle(spec: RaySpec, cameras: PerspectiveCameras, mask, camera_ids, host: bool, shape) -> RayBundle:
+    """The bundle of `spec`: every ray reshaped to (B, *shape, .) without a mask, the kept rays as (1, M, .) with one."""
+    if not isinstance(cameras, PerspectiveCameras):
+        raise TypeError("a raysampler takes rays.PerspectiveCameras")
+    cams = (cameras.R, cameras.T, cameras.intrinsics)
+    if host:
+        cams = tuple(c.cpu().numpy() for c in cams)
+        ids = None if camera_ids is None else np.asarray(torch.as_tensor(camera_ids).cpu())
+        if mask is None:
+            o, d, ln, xy = (torch.from_numpy(a) for a in ops.rays_bundle_host(spec, *cams, ids))
+        else:
+            o, d, ln, xy = (torch.from_numpy(a) for a in ops.rays_select_host(spec, *cams, torch.as_tensor(mask).cpu().numpy(), ids)[:4])
+    else:
+        ids = None if camera_ids is None else torch.as_tensor(camera_ids, device=cameras.device)
+        if mask is None:
+            o, d, ln, xy = ops.rays_bundle(spec, *cams, ids)
+        else:
+            o, d, ln, xy = ops.rays_select(spec, *cams, torch.as_tensor(mask).to(cameras.device), ids)[:4]
+    if mask is not None:
+        return RayBundle(o[None], d[None], ln[None], xy[None])
+    B = len(cameras)
+    return RayBundle(o.reshape(B, *shape, 3), d.reshape(B, *shape, 3), ln.reshape(B, *shape, spec.P), xy.reshape(B, *shape, 2))
+
+
+class NDCMultinomialRaysampler:
+    """One ray through the centre of every pixel of an image_height x image_width grid, in raster order, with n_pts_per_ray
+    depths linspace(min_depth, max_depth) (generateCors.py:136, genFeat.py:102).
+
+    sampler(cameras) -> RayBundle of (B, H, W, .) on the cameras' device.
+    sampler(cameras, mask=(B, mh, mw[, 1])) -> the (1, M, .) bundle of pren.py:232-235: the rays whose xy falls on a non-zero
+    pixel of their camera's mask, in (camera, ray) order; one host read, of the count.
+    camera_ids is accepted for the samplers' common call and not read: a grid ray does not depend on it."""
+
+    def __init__(self, image_width: int, image_height: int, n_pts_per_ray: int, min_depth: float, max_depth: float):
+        self.spec = RaySpec(RAYS_GRID, int(n_pts_per_ray), float(min_depth), float(max_depth), W=int(image_width), H=int(image_height))
+
+    def __call__(self, cameras: PerspectiveCameras, mask=None, camera_ids=None, host: bool = False) -> RayBundle:
+        return _bundle(self.spec, cameras, mask, None, host, (self.spec.H, self.spec.W))
+
+
+class MonteCarloRaysampler:
+    """n_rays_per_image rays per camera at uniform NDC locations in [min_x, max_x) x [min_y, max_y) (generateCors.py:138,
+    genFeat.py:105), from Philox4x32-10 under `seed`: torch's random stream is not reproduced.  camera_ids (B,) names the
+    cameras (default 0 .. B-1): a ray is a function of (seed, camera_id, ray index) only, so a camera draws the same rays
+    alone and inside a batch.  A caller who wants fresh rays per call (genFeat.py's 19 rounds) changes the seed.
+    stratified_sampling moves every depth inside its stratum (include/isr_rays.h).
+
+    sampler(cameras) -> RayBundle of (B, n, .); sampler(cameras, mask=...) -> (1, M, .) as for the grid sampler."""
+
+    def __init__(self, min_x: float, max_x: float, min_y: float, max_y: float, n_rays_per_image: int, n_pts_per_ray: int,
+                 min_depth: float, max_depth: float, stratified_sampling: bool = False, seed: int = 0):
+        self.spec = RaySpec(RAYS_MC, int(n_pts_per_ray), float(min_depth), float(max_depth), n=int(n_rays_per_image),
+                            min_x=float(min_x), max_x=float(max_x), min_y=float(min_y), max_y=float(max_y),
+                            stratified=bool(stratified_sampling), seed=int(seed))
+
+    def __call__(self, cameras: PerspectiveCameras, mask=None, camera_ids=None, host: bool = False) -> RayBundle:
+        return _bundle(self.spec, cameras, mask, camera_ids, host, (self.spec.n,))
+
+
+def sample_images_at_mc_locs(target_images: torch.Tensor, sampled_rays_xy: torch.Tensor) -> torch.Tensor:
+    """nutil.sample_images_at_mc_locs (nutil.py:167-196): target_images (B,H,W,C) at the NDC locations (B,...,2) -> (B,...,C),
+    the nearest pixel of -xy with zeros outside, on the device (ops.sample_at_rays)."""
+    return ops.sample_at_rays(target_images, sampled_rays_xy)
