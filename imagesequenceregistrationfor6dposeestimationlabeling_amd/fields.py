@@ -148,8 +148,13 @@ class DensityField(_PackedField):
             raise ValueError("DensityField.from_linears: every layer needs a bias")
         if device is None:
             device = linears[0].weight.device
-        freqs = omega0 * (2.0 ** torch.arange(n_harmonic))
-        return cls([m.weight for m in linears], [m.bias for m in linears], freqs.to(torch.float32), beta, device)
+        return cls([m.weight for m in linears], [m.bias for m in linears], cls.harmonic_frequencies(n_harmonic, omega0), beta,
+                   device)
+
+    @staticmethod
+    def harmonic_frequencies(n_harmonic: int = 60, omega0: float = 0.1) -> torch.Tensor:
+        """The `frequencies` buffer as HarmonicEmbedding builds it (nerf.py:131-134), (n_harmonic,) f32 on the host."""
+        return (omega0 * (2.0 ** torch.arange(n_harmonic))).to(torch.float32)
 
     def customForwardForDensity(self, points: torch.Tensor) -> torch.Tensor:
         """nerf.py:417-432: points (..., 3) -> densities (..., 1), on the device."""

@@ -85,6 +85,18 @@ def nearest_f64(points, verts):
     return idx, dist
 
 
+def norm3(v):
+    """torch.norm(v, dim=-1) of f32 triples on the CPU (generateCors.py:326), bit for bit: sqrt(fmaf(z, z, fmaf(y, y, x x)))."""
+    v = np.asarray(v, f32)
+    return np.sqrt(dr.fma32(v[..., 2], v[..., 2], dr.fma32(v[..., 1], v[..., 1], (v[..., 0] * v[..., 0]).astype(f32)))).astype(f32)
+
+
+def back_rays(o1, ln1, back_scale=3.0):
+    """generateCors.py:323-327 in f32 NumPy: -(o / ||o||) and (lengths - lengths[:, :1]) / back_scale, a true f32 division."""
+    o1, ln1 = np.asarray(o1, f32), np.asarray(ln1, f32)
+    return (-(o1 / norm3(o1)[:, None])).astype(f32), ((ln1 - ln1[:, :1]) / f32(back_scale)).astype(f32)
+
+
 def view_host(field, o, d, ln, xys, verts, threshold=0.2, back_threshold=0.05, max_dist=0.1, back_scale=3.0):
     """correspondences.view_correspondences from the host calls: march_host, an f64 nearest vertex, the back rays in f32
     NumPy.  -> dict with the six fields (batch dimension 1) and the two distance arrays the filters compared."""
@@ -94,9 +106,7 @@ def view_host(field, o, d, ln, xys, verts, threshold=0.2, back_threshold=0.05, m
     idx1 = np.where(dist1 < max_dist)[0]
     pos = front["points"][idx1]
     o1 = o[idx1]
-    norm = np.sqrt(o1[:, 0] * o1[:, 0] + o1[:, 1] * o1[:, 1] + o1[:, 2] * o1[:, 2]).astype(f32)      # f32 throughout
-    bdir = (-(o1 / norm[:, None])).astype(f32)
-    bln = ((ln[idx1] - ln[idx1][:, :1]) / f32(back_scale)).astype(f32)
+    bdir, bln = back_rays(o1, ln[idx1], back_scale)
     if len(idx1):
         back = field.march_host(pos, bdir, bln, back_threshold, direction="back")["points"]
         _, dist2 = nearest_f64(back, verts)

@@ -32,6 +32,19 @@ Chamfer / ICP (verfication.py:97-101, icp.py:96-117) — those stay "parity unpi
   ref_estimate_prune.npz (`prune` argument) poseEstSurf.py:119-121, :145, :147-177: gathers, pruning masks, ordered selection
   ref_vote.npz           (`vote` argument) the n x n relative-pose table choosePose.py:98-107 and the ADD-S vote :121-145
 
+Made by scripts of their own that reuse `_tree`, `_stmts_in`, `ref_statements` and `OUT` from here:
+  ref_back_march.npz     (make_ref_back_march.py) prenBack.py:362-385: the two-way marcher's weights on recorded densities
+  ref_density_net.npz    (make_ref_fields.py) the CLASSES HarmonicEmbedding nerf.py:106-144 and NeuralRadianceFieldFeat nerf.py:148-767,
+                         siren=False: customForwardForDensity :417-432 and forwardWithPoints :750-767 in f32, the module after .double()
+  ref_front_march.npz    (make_ref_fields.py) pren.py:338-365 at self.threshold 0.2 and 0.03 and in plain emission-absorption on
+                         recorded densities; the depth and the drop rule genFeat.py:191-198 over two bundles
+  ref_pc_grid.npz        (make_ref_fields.py) nerf.py:676-697 and the argument expression of :700 at gridRes = 128; statement :701
+  ref_view_cors.npz      (make_ref_fields.py) one view of generateCors.py:306-356 on the CPU, every intermediate
+  ref_key_export.npz     (make_ref_fields.py) genFeat.py:204, :212-217, :223
+Still not reproducible (absent, not stood in for): the SIREN key head (dep/siren.py is not in the reference checkout),
+pytorch3d's ray samplers, sample_farthest_points and estimate_pointcloud_normals, mcubes' triangulation, Open3D's
+remove_radius_outlier, sample_images_at_mc_locs' pytorch3d half, trimesh's vertex normals (they enter ref_key_export as data).
+
 Run from the repo root:  python tests/golden/make_golden_from_reference.py
 """
 import ast
