@@ -3,7 +3,7 @@ def __getattr__(name):
     if name in ("ObjCoordRenderer", "Mesh"):
         from . import render
         return getattr(render, name)
-    if name in ("KeyField", "DensityField"):
+    if name in ("KeyField", "DensityField", "RadianceField", "FeatureField"):
         from . import fields
         return getattr(fields, name)
     if name in ("sample_farthest_points", "thin_keys", "estimate_pointcloud_normals", "estimate_pointcloud_local_coord_frames"):
@@ -15,7 +15,8 @@ def __getattr__(name):
     if name in ("view_correspondences", "clean_mesh_vertices", "ViewCorrespondences", "subsampled_normals"):
         from . import correspondences
         return getattr(correspondences, name)
-    if name in ("PerspectiveCameras", "RayBundle", "NDCMultinomialRaysampler", "MonteCarloRaysampler", "sample_images_at_mc_locs"):
+    if name in ("PerspectiveCameras", "RayBundle", "NDCMultinomialRaysampler", "MonteCarloRaysampler", "sample_images_at_mc_locs",
+                "EmissionAbsorptionRaymarcherStratified", "ImplicitRendererStratified"):
         from . import rays
         return getattr(rays, name)
     if name == "marching_cubes":

@@ -199,6 +199,20 @@ RAYS_SIGNATURES = {
     "isr_rays_philox_host": (_i, [_vp, _vp, _vp, _vp]),
 }
 
+# include/isr_radiance.h (the radiance field's render and the emission-absorption march), bound the same way
+_RADIANCE_FIELD = [_vp, _sz, _i, _vp, _i, _i, _i]      # pack .. C: the arguments both render entries start with
+RADIANCE_SIGNATURES = {
+    "isr_radiance_pack_bytes": (_sz, [_i, _vp, _i, _i, _i]),
+    "isr_radiance_pack": (_i, [_i, _vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _sz]),
+    "isr_radiance_workspace_bytes": (_sz, [_i, _i]),
+    "isr_radiance_render": (_i, [*_RADIANCE_FIELD, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "isr_ea_march": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "isr_radiance_render_host": (_i, [*_RADIANCE_FIELD, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "isr_ea_march_host": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "isr_radiance_sigmoid_host": (_i, [_vp, _sz, _vp]),
+    "isr_radiance_normalize_host": (_i, [_vp, _sz, _vp]),
+}
+
 # include/isr_mc.h (iso-surface extraction), bound the same way
 MC_SIGNATURES = {
     "isr_mc_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -225,7 +239,7 @@ def lib() -> C.CDLL:
         raise IsrError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES, **FPS_SIGNATURES, **DENSITY_SIGNATURES,
                                **DENSITY_DIR_SIGNATURES, **RADIUS_SIGNATURES, **MC_SIGNATURES, **KNN_SIGNATURES,
-                               **RAYS_SIGNATURES}.items():
+                               **RAYS_SIGNATURES, **RADIANCE_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -1,5 +1,5 @@
-// field_tile.hpp — the matrix-core layer of a fused field kernel, once, for csrc/field_mlp.hip and csrc/field_density.hip
-// (device only).
+// field_tile.hpp — the matrix-core layer of a fused field kernel, once, for csrc/field_mlp.hip, csrc/field_density.hip and
+// csrc/field_radiance.hip (device only).
 //
 // A workgroup takes a tile of kTP = 64 points through every layer of its field; the tile's activations live in LDS from the
 // first layer to the last.  A layer runs on v_mfma_f32_32x32x2_f32, which is bit for bit the k-ordered fmaf chain: A = the
@@ -58,11 +58,17 @@ __device__ __forceinline__ WaveShare<kMaxWidth / 32 / kWaves> wave_share(int MB,
   return s;
 }
 
+// What a chain starts from: init(j, p) is the accumulator of neuron j (below the layer's OP) and point p of the tile before
+// the first k.  BiasInit is the layer's own bias, the same for every point.
+struct BiasInit {
+  const float* bl;
+  __device__ __forceinline__ float operator()(int j, int) const { return bl[j]; }
+};
+
 // NMB blocks of 32 neurons x NNB blocks of 32 points: the accumulators of the whole k loop.
-template <int NMB, int NNB, int kMaxMb>
-__device__ __forceinline__ void mfma_layer(const Layer& L, const float* __restrict__ Wl, const float* __restrict__ bl,
-                                           const float* act, const int (&mb)[kMaxMb], int nb0, int lane,
-                                           f32x16 (&acc)[kMaxMb][2]) {
+template <int NMB, int NNB, int kMaxMb, class Init>
+__device__ __forceinline__ void mfma_layer(const Layer& L, const float* __restrict__ Wl, Init init, const float* act,
+                                           const int (&mb)[kMaxMb], int nb0, int lane, f32x16 (&acc)[kMaxMb][2]) {
   const int r = lane & 31, hh = lane >> 5;
   const int S4 = L.kstride >> 3;
 #pragma unroll
@@ -71,9 +77,8 @@ __device__ __forceinline__ void mfma_layer(const Layer& L, const float* __restri
     for (int a = 0; a < 4; ++a)
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
-        const float bias = bl[mb[m] * 32 + 8 * a + 4 * hh + b];
 #pragma unroll
-        for (int n = 0; n < NNB; ++n) acc[m][n][4 * a + b] = bias;
+        for (int n = 0; n < NNB; ++n) acc[m][n][4 * a + b] = init(mb[m] * 32 + 8 * a + 4 * hh + b, (nb0 + n) * 32 + r);
       }
   const float4* wp[NMB];
   float4 cur[NMB];
@@ -138,25 +143,31 @@ __device__ __forceinline__ void store_activations(const Layer& L, const f32x16 (
 }
 
 // One matrix-core layer of the tile, in place: act holds the layer's input on entry (k-pair major, K padded to kstride with
-// zeros) and its output after the call.  Every thread of a workgroup of kWaves waves calls it.
-template <int kWaves, class Act>
-__device__ __forceinline__ void mfma_tile_layer(const Layer& L, const float* __restrict__ pack, float* act, bool row_major,
-                                                Act activation) {
+// zeros) and its output after the call.  Every thread of a workgroup of kWaves waves calls it.  The chains start from
+// init(neuron, point) (mfma_tile_layer below: from the layer's bias).
+template <int kWaves, class Act, class Init>
+__device__ __forceinline__ void mfma_tile_layer_from(const Layer& L, const float* __restrict__ pack, float* act, bool row_major,
+                                                     Act activation, Init init) {
   constexpr int kMaxMb = kMaxWidth / 32 / kWaves;
   static_assert(kMaxMb == 1 || kMaxMb == 2, "mfma_tile_layer dispatches one or two neuron blocks per wave");
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const float* Wl = pack + L.w_off;
-  const float* bl = pack + L.b_off;
   const WaveShare<kMaxMb> s = wave_share<kWaves>(L.OP >> 5, w);
   f32x16 acc[kMaxMb][2];
   if constexpr (kMaxMb == 2) {
-    if (s.nmb == 2) mfma_layer<2, 2>(L, Wl, bl, act, s.mb, s.nb0, lane, acc);
+    if (s.nmb == 2) mfma_layer<2, 2>(L, Wl, init, act, s.mb, s.nb0, lane, acc);
   }
-  if (s.nmb == 1 && s.nnb == 2) mfma_layer<1, 2>(L, Wl, bl, act, s.mb, s.nb0, lane, acc);
-  else if (s.nmb == 1) mfma_layer<1, 1>(L, Wl, bl, act, s.mb, s.nb0, lane, acc);
+  if (s.nmb == 1 && s.nnb == 2) mfma_layer<1, 2>(L, Wl, init, act, s.mb, s.nb0, lane, acc);
+  else if (s.nmb == 1) mfma_layer<1, 1>(L, Wl, init, act, s.mb, s.nb0, lane, acc);
   __syncthreads();                // every wave has read the layer's input: the outputs may take its place
   store_activations(L, acc, s, act, lane, row_major, activation);
   __syncthreads();
+}
+
+template <int kWaves, class Act>
+__device__ __forceinline__ void mfma_tile_layer(const Layer& L, const float* __restrict__ pack, float* act, bool row_major,
+                                                Act activation) {
+  mfma_tile_layer_from<kWaves>(L, pack, act, row_major, activation, BiasInit{pack + L.b_off});
 }
 
 }  // namespace field

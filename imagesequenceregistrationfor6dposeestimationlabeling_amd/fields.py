@@ -262,3 +262,112 @@ class DensityField(_PackedField):
         else:
             check(lib().isr_density_march_dir_host(*head, way, *tail), "isr_density_march_dir_host")
         return out
+
+
+class RadianceField(DensityField):
+    """NeuralRadianceFieldFeat in mode="color" (nerf.py:163-218, :230-268, :340-402) as a device-resident field: the
+    DensityField of the same trunk (every call of it keeps working, with the same bits) plus the colour head
+    Linear(Wt + 6H -> Wc), Softplus(beta), Linear(Wc -> C), Sigmoid on the trunk's last activations and the harmonic
+    embedding of the normalised ray direction, and the emission-absorption render of pren.py:298-369, fused into one call
+    (include/isr_radiance.h states every rule).  weights / biases: the hidden layers, then the density row (1, Wt);
+    color_weights / color_biases: W1 (Wc, Wt + 6H) with the trunk's columns first, W2 (C, Wc)."""
+
+    def __init__(self, weights, biases, color_weights, color_biases, frequencies, beta=10.0, device=None):
+        super().__init__(weights, biases, frequencies, beta, device)
+        if len(color_weights) != 2 or len(color_biases) != 2:
+            raise ValueError(f"RadianceField: {len(color_weights)} colour weights, {len(color_biases)} colour biases (two layers)")
+        Wt = self.widths[-1]
+        cW, cb, cw = self._layers(color_weights, color_biases, Wt + 6 * self.H)
+        self.Wc, self.C = cw[1], cw[2]
+        Ws, bs, _ = self._layers(weights, biases, 6 * self.H)
+        density_pack_host, density_pack = self.pack_host, self.pack
+        self._pack_and_upload("radiance", (len(self.widths), _vp(self._w), self.H, self.Wc, self.C),
+                              (_vp(self.frequencies), self.beta), Ws + cW, bs + cb, (), device)
+        self.rpack_host, self.rpack = self.pack_host, self.pack
+        self.pack_host, self.pack = density_pack_host, density_pack
+
+    @classmethod
+    def from_linears(cls, hidden_linears, density_linear, color_linears, n_harmonic=60, omega0=0.1, beta=10.0, device=None):
+        """From the torch.nn.Linear modules of the loaded network: model.mlp[0], model.mlp[2], model.density_layer[0] and
+        (model.color_layer[0], model.color_layer[2])."""
+        trunk, colour = list(hidden_linears) + [density_linear], list(color_linears)
+        if any(m.bias is None for m in trunk + colour):
+            raise ValueError("RadianceField.from_linears: every layer needs a bias")
+        if device is None:
+            device = trunk[0].weight.device
+        return cls([m.weight for m in trunk], [m.bias for m in trunk], [m.weight for m in colour], [m.bias for m in colour],
+                   cls.harmonic_frequencies(n_harmonic, omega0), beta, device)
+
+    @classmethod
+    def from_module(cls, model, beta=10.0, device=None):
+        """From a NeuralRadianceFieldFeat-shaped module: the Linear layers of .mlp, .density_layer and .color_layer and
+        .harmonic_embedding.frequencies."""
+        lin = lambda seq: [m for m in seq if isinstance(m, torch.nn.Linear)]
+        trunk, colour = lin(model.mlp) + lin(model.density_layer), lin(model.color_layer)
+        if device is None:
+            device = trunk[0].weight.device
+        return cls([m.weight for m in trunk], [m.bias for m in trunk], [m.weight for m in colour], [m.bias for m in colour],
+                   model.harmonic_embedding.frequencies, beta, device)
+
+    def _render(self, o, d, ln, **kw):
+        return ops.radiance_render(self.rpack, self.widths, self.H, self.Wc, self.C, o, d, ln, **kw)
+
+    def forward(self, ray_bundle, **kw):
+        """nerf.py:340-402 in mode="color": any object with .origins, .directions (..., 3) and .lengths (..., P) ->
+        (densities (..., P, 1), colours (..., P, C)), on the device."""
+        o, d, ln = self._bundle(ray_bundle.origins, ray_bundle.directions, ray_bundle.lengths)
+        out = self._render(o, d, ln, threshold=-1.0, want_densities=True, want_colours=True)
+        shape = tuple(ray_bundle.lengths.shape)
+        return out["densities"].reshape(*shape, 1), out["colours"].reshape(*shape, self.C)
+
+    __call__ = forward
+
+    def batched_forward(self, ray_bundle, n_batches: int = 16, **kw):
+        """nerf.py:458-521: the same pair.  n_batches is accepted and changes nothing: rows are independent, the bundle is
+        one call."""
+        return self.forward(ray_bundle)
+
+    def render(self, ray_bundle, threshold: float = -1.0, return_weights: bool = True):
+        """The render of the bundle in one fused call: (images (..., C+1) [features | opacity], weights (..., P) or None,
+        depth (...)).  threshold >= 0 is the raymarcher's thresholdMode."""
+        o, d, ln = self._bundle(ray_bundle.origins, ray_bundle.directions, ray_bundle.lengths)
+        out = self._render(o, d, ln, threshold=threshold, want_weights=return_weights)
+        lead = tuple(ray_bundle.lengths.shape[:-1])
+        wts = out["weights"].reshape(ray_bundle.lengths.shape) if return_weights else None
+        return out["image"].reshape(*lead, self.C + 1), wts, out["depth"].reshape(lead)
+
+    def render_host(self, origins, directions, lengths, threshold: float = -1.0):
+        """isr_radiance_render_host: NumPy (N,3), (N,3), (N,P) -> dict of image, depth, points, hit, weights, densities,
+        colours.  For tests."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        ln = np.ascontiguousarray(lengths, np.float32)
+        N, P = ln.shape
+        out = dict(image=np.empty((N, self.C + 1), np.float32), depth=np.empty(N, np.float32), points=np.empty((N, 3), np.float32),
+                   hit=np.empty(N, np.int32), weights=np.empty((N, P), np.float32), densities=np.empty((N, P), np.float32),
+                   colours=np.empty((N, P, self.C), np.float32))
+        check(lib().isr_radiance_render_host(_vp(self.rpack_host), self.rpack_host.nbytes, len(self.widths), _vp(self._w), self.H,
+                                             self.Wc, self.C, _vp(o), _vp(d), _vp(ln), N, P, float(threshold),
+                                             *(_vp(out[k]) for k in ("image", "depth", "points", "hit", "weights", "densities",
+                                                                      "colours"))), "isr_radiance_render_host")
+        return out
+
+
+class FeatureField:
+    """NeuralRadianceFieldFeat in mode="feature" with the SIREN head (nerf.py:388-390; genFeat.py:131, trainPose.py:165,
+    generateCors.py:177 set it): the densities of a DensityField and the keys of a KeyField at the bundle's points
+    origins + lengths * directions, which are materialised as the reference materialises them.  Hand its batched_forward to
+    rays.ImplicitRendererStratified; the images come from ops.ea_march."""
+
+    def __init__(self, density_field: DensityField, key_field: KeyField):
+        self.density_field, self.key_field = density_field, key_field
+
+    def forward(self, ray_bundle, **kw):
+        pts = ray_bundle.origins[..., None, :] + ray_bundle.lengths[..., :, None] * ray_bundle.directions[..., None, :]
+        dens, _ = self.density_field.batched_forward_fordensity(ray_bundle)
+        return dens, self.key_field(pts)
+
+    __call__ = forward
+
+    def batched_forward(self, ray_bundle, n_batches: int = 16, **kw):
+        return self.forward(ray_bundle)

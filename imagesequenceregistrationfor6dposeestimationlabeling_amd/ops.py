@@ -1250,6 +1250,93 @@ def density_march_given_host(lengths, rho, threshold: float, direction: str = "f
     return wts, depth, hit
 
 
+def radiance_flops(widths, H: int, Wc: int, C: int) -> float:
+    """Multiply-adds x 2 of one point through a radiance field: the density field's and the colour head's trunk part
+    (the direction's 6H x Wc block is per ray)."""
+    return density_flops(widths, H) + 2.0 * (int(widths[-1]) * int(Wc) + int(Wc) * int(C))
+
+
+def radiance_workspace_bytes(N: int, Wc: int) -> int:
+    """isr_radiance_workspace_bytes: the device workspace radiance_render needs for N rays."""
+    return int(lib().isr_radiance_workspace_bytes(int(N), int(Wc)))
+
+
+def radiance_render(pack: torch.Tensor, widths, H: int, Wc: int, C: int, origins: torch.Tensor, directions: torch.Tensor,
+                    lengths: torch.Tensor, threshold: float = -1.0, want_weights: bool = False, want_densities: bool = False,
+                    want_colours: bool = False, workspace: torch.Tensor | None = None):
+    """isr_radiance_render: origins (N,3), directions (N,3), lengths (N,P) f32 through the packed radiance field (`pack`:
+    the device copy of isr_radiance_pack's bytes, fields.RadianceField builds it) -> dict of image (N, C+1) [features |
+    opacity], depth (N,), points (N,3), hit (N,) int32 and weights (N,P), densities (N,P), colours (N,P,C) or None.
+    threshold >= 0 is the reference's thresholdMode, a negative one the emission-absorption weights.  workspace: a
+    contiguous device tensor of at least radiance_workspace_bytes(N, Wc) bytes to reuse (allocated when None)."""
+    dev = require_cuda(pack, origins, directions, lengths, workspace)
+    for name, t, cols in (("origins", origins, 3), ("directions", directions, 3), ("lengths", lengths, None)):
+        if t.dtype != torch.float32 or t.ndim != 2 or (cols and t.shape[1] != cols) or not t.is_contiguous():
+            raise ValueError(f"radiance_render: {name} must be contiguous 2-d float32, got {tuple(t.shape)} {t.dtype}")
+    N, P = lengths.shape
+    if origins.shape[0] != N or directions.shape[0] != N:
+        raise ValueError(f"radiance_render: {origins.shape[0]} origins, {directions.shape[0]} directions, {N} rows of lengths")
+    if P < 1:
+        raise ValueError("radiance_render: P < 1")
+    thr = float(threshold)
+    if thr != thr:
+        raise ValueError("radiance_render: threshold is NaN")
+    Wc, C = int(Wc), int(C)
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = dict(image=torch.empty((N, C + 1), **f32), depth=torch.empty((N,), **f32), points=torch.empty((N, 3), **f32),
+               hit=torch.empty((N,), dtype=torch.int32, device=dev),
+               weights=torch.empty((N, P), **f32) if want_weights else None,
+               densities=torch.empty((N, P), **f32) if want_densities else None,
+               colours=torch.empty((N, P, C), **f32) if want_colours else None)
+    need = radiance_workspace_bytes(N, Wc) if N else 0
+    if workspace is None:
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    elif not workspace.is_contiguous():
+        raise ValueError("radiance_render: the workspace must be contiguous")
+    pk, nbytes, nh, wp, _keep = _field_args(pack, widths, len(widths))
+    with torch.cuda.device(dev), _timed("radiance_render", float(N) * P * radiance_flops(widths, H, Wc, C)):
+        rc = lib().isr_radiance_render(pk, nbytes, nh, wp, int(H), Wc, C, ptr(origins), ptr(directions), ptr(lengths), N, P, thr,
+                                       ptr(out["image"]), ptr(out["depth"]), ptr(out["points"]), ptr(out["hit"]),
+                                       ptr(out["weights"]), ptr(out["densities"]), ptr(out["colours"]), ptr(workspace),
+                                       workspace.numel() * workspace.element_size(), current_stream(dev))
+    check(rc, "isr_radiance_render")
+    return out
+
+
+def ea_march(densities: torch.Tensor, features: torch.Tensor, threshold: float = -1.0, want_weights: bool = True):
+    """isr_ea_march: densities (N,P), features (N,P,F) f32 -> (image (N, F+1) [features | opacity], weights (N,P) or None):
+    the emission-absorption march of pren.py:338-369 (threshold >= 0: thresholdMode) over tensors the caller has."""
+    dev = require_cuda(densities, features)
+    if (densities.dtype != torch.float32 or features.dtype != torch.float32 or densities.ndim != 2 or features.ndim != 3
+            or features.shape[:2] != densities.shape or not densities.is_contiguous() or not features.is_contiguous()):
+        raise ValueError(f"ea_march: densities {tuple(densities.shape)} {densities.dtype} and features {tuple(features.shape)} "
+                         f"{features.dtype} must be contiguous float32 (N,P) and (N,P,F)")
+    N, P, F = features.shape
+    if P < 1 or F < 1:
+        raise ValueError("ea_march: P < 1 or F < 1")
+    thr = float(threshold)
+    if thr != thr:
+        raise ValueError("ea_march: threshold is NaN")
+    image = torch.empty((N, F + 1), dtype=torch.float32, device=dev)
+    wts = torch.empty((N, P), dtype=torch.float32, device=dev) if want_weights else None
+    with torch.cuda.device(dev), _timed("ea_march", 2.0 * N * P * F):
+        rc = lib().isr_ea_march(ptr(densities), ptr(features), N, P, F, thr, ptr(image), ptr(wts), current_stream(dev))
+    check(rc, "isr_ea_march")
+    return image, wts
+
+
+def ea_march_host(densities, features, threshold: float = -1.0):
+    """isr_ea_march_host: the same march as host code, NumPy (N,P), (N,P,F) -> (image (N,F+1), weights (N,P)).  For tests."""
+    r, f = np.ascontiguousarray(densities, np.float32), np.ascontiguousarray(features, np.float32)
+    if r.ndim != 2 or f.ndim != 3 or f.shape[:2] != r.shape:
+        raise ValueError(f"ea_march_host: densities {r.shape}, features {f.shape}")
+    N, P, F = f.shape
+    image, wts = np.empty((N, F + 1), np.float32), np.empty((N, P), np.float32)
+    hp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    check(lib().isr_ea_march_host(hp(r), hp(f), N, P, F, float(threshold), hp(image), hp(wts)), "isr_ea_march_host")
+    return image, wts
+
+
 def _host_i32(v, B: int, what: str):
     """A HOST (B,) int32 array for the C ABI (None stays None)."""
     if v is None:

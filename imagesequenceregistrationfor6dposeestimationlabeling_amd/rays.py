@@ -2,10 +2,12 @@
 MonteCarloRaysampler and RayBundle as generateCors.py:125-138, :279-293 and genFeat.py:102-106, :162-189 use them, and the
 silhouette selection of pren.py:229-236 (`sampler(cameras, mask=...)`).  The rays come from the isr_rays_* entries
 (include/isr_rays.h states every rule, and which of them are pytorch3d's only as far as they are known from memory); this
-module holds the camera's bookkeeping and the conversion of screen-space intrinsics to NDC.
+module holds the camera's bookkeeping and the conversion of screen-space intrinsics to NDC.  On top of them the renderer
+of pren.py under its names: EmissionAbsorptionRaymarcherStratified (pren.py:256-369) and ImplicitRendererStratified
+(pren.py:172-253), whose images come from isr_ea_march or, for a fields.RadianceField, from the fused isr_radiance_render.
 
-Out of scope: the renderer's stratified=True (ProbabilisticRaysampler / sample_pdf), rayFreeze (the caller keeps the
-bundle), unit_directions, K= and FoV cameras."""
+Out of scope: the renderer's stratified=True (ProbabilisticRaysampler / sample_pdf), the raymarcher's weightMode,
+unit_directions, K= and FoV cameras."""
 from __future__ import annotations
 
 from typing import NamedTuple
@@ -167,3 +169,87 @@ def sample_images_at_mc_locs(target_images: torch.Tensor, sampled_rays_xy: torch
     """nutil.sample_images_at_mc_locs (nutil.py:167-196): target_images (B,H,W,C) at the NDC locations (B,...,2) -> (B,...,C),
     the nearest pixel of -xy with zeros outside, on the device (ops.sample_at_rays)."""
     return ops.sample_at_rays(target_images, sampled_rays_xy)
+
+
+class EmissionAbsorptionRaymarcherStratified:
+    """pren.py:256-369: rays_densities (..., P, 1) and rays_features (..., P, F) -> (images (..., F+1) [features |
+    opacity], weights (..., P)) by ops.ea_march.  thresholdMode marches the densities above `threshold` as ones.  The
+    attributes stay assignable after construction (genFeat.py:132); weightMode and a surface_thickness other than 1 raise
+    NotImplementedError when the marcher is called."""
+
+    def __init__(self, surface_thickness: int = 1, thresholdMode: bool = False, weightMode: bool = False, threshold: float = 0.03):
+        self.surface_thickness = surface_thickness
+        self.thresholdMode = thresholdMode
+        self.weightMode = weightMode
+        self.threshold = threshold
+
+    def march_threshold(self) -> float:
+        """The threshold argument of the C entries: the marcher's own in thresholdMode, -1 (emission-absorption) otherwise."""
+        if self.surface_thickness != 1:
+            raise NotImplementedError("EmissionAbsorptionRaymarcherStratified: only surface_thickness = 1 is supported")
+        if self.weightMode and not self.thresholdMode:
+            raise NotImplementedError("EmissionAbsorptionRaymarcherStratified: weightMode is not supported")
+        if not self.thresholdMode:
+            return -1.0
+        if not float(self.threshold) >= 0.0:
+            raise ValueError(f"EmissionAbsorptionRaymarcherStratified: threshold = {self.threshold} must be >= 0 in thresholdMode")
+        return float(self.threshold)
+
+    def __call__(self, rays_densities: torch.Tensor, rays_features: torch.Tensor, **kwargs):
+        thr = self.march_threshold()
+        if rays_densities.shape[-1] != 1 or rays_features.shape[:-1] != rays_densities.shape[:-1]:
+            raise ValueError(f"EmissionAbsorptionRaymarcherStratified: densities {tuple(rays_densities.shape)}, features "
+                             f"{tuple(rays_features.shape)}: expected (..., P, 1) and (..., P, F)")
+        lead, P, F = tuple(rays_features.shape[:-2]), rays_features.shape[-2], rays_features.shape[-1]
+        image, wts = ops.ea_march(rays_densities.to(torch.float32).reshape(-1, P).contiguous(),
+                                  rays_features.to(torch.float32).reshape(-1, P, F).contiguous(), thr, want_weights=True)
+        return image.reshape(*lead, F + 1), wts.reshape(*lead, P)
+
+    forward = __call__
+
+
+class ImplicitRendererStratified:
+    """pren.py:57-253 without its stratified branch: renderer(cameras, volumetric_function, maskRays=False, mask=False) ->
+    (images (..., F+1), ray_bundle, weights (..., P)).  The bundle is raysampler(cameras), (B, H, W, .) for a grid sampler,
+    or with maskRays the (1, M, .) rays on non-zero pixels of `mask` (pren.py:230-236).  rayFreeze keeps the first call's
+    bundle for every later call.  When volumetric_function is the bound batched_forward (or forward) of a
+    fields.RadianceField the fused render runs; anything else callable is called as
+    volumetric_function(ray_bundle=..., cameras=..., **kwargs) and its (densities, features) go through the raymarcher."""
+
+    def __init__(self, raysampler, raymarcher, device=None, rayFreeze: bool = False):
+        if not callable(raysampler):
+            raise ValueError('"raysampler" has to be a "Callable" object.')
+        if not callable(raymarcher):
+            raise ValueError('"raymarcher" has to be a "Callable" object.')
+        self.raysampler, self.raymarcher, self.device, self.rayFreeze = raysampler, raymarcher, device, rayFreeze
+        self.rayState = "Empty"
+        self.frozenRays = False
+
+    @staticmethod
+    def _fused_field(volumetric_function):
+        from .fields import RadianceField
+        owner = getattr(volumetric_function, "__self__", None)
+        if isinstance(owner, RadianceField) and getattr(volumetric_function, "__func__", None) in (
+                RadianceField.batched_forward, RadianceField.forward):
+            return owner
+        return None
+
+    def __call__(self, cameras, volumetric_function, stratified: bool = False, maskRays: bool = False, mask=False, **kwargs):
+        if not callable(volumetric_function):
+            raise ValueError('"volumetric_function" has to be a "Callable" object.')
+        if stratified:
+            raise NotImplementedError("ImplicitRendererStratified: stratified=True (ProbabilisticRaysampler) is not supported")
+        if self.rayState == "Empty":
+            if self.rayFreeze:
+                self.rayState = "Occupied"
+            self.frozenRays = self.raysampler(cameras, mask=mask) if maskRays else self.raysampler(cameras)
+        bundle = self.frozenRays
+        field = self._fused_field(volumetric_function)
+        if field is not None and isinstance(self.raymarcher, EmissionAbsorptionRaymarcherStratified):
+            images, weights, _ = field.render(bundle, threshold=self.raymarcher.march_threshold(), return_weights=True)
+        else:
+            rays_densities, rays_features = volumetric_function(ray_bundle=bundle, cameras=cameras, **kwargs)
+            images, weights = self.raymarcher(rays_densities=rays_densities, rays_features=rays_features, ray_bundle=bundle, **kwargs)
+        return images, bundle, weights
+
+    forward = __call__

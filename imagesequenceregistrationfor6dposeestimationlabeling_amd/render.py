@@ -169,3 +169,37 @@ class ObjCoordRenderer:
 
     def denormalize(self, model_coords: np.ndarray, obj_idx: int):
         return model_coords * self.objs[obj_idx].scale + self.objs[obj_idx].offset
+
+
+def get_emb_vis(emb_img: torch.Tensor, mask: torch.Tensor = None, demean=False) -> torch.Tensor:
+    """nutil.get_emb_vis (nutil.py:198-210): an embedding image (..., 3 n) to three channels in [0, 1] for viewing: the
+    optional mean over the mask taken off, groups of n channels averaged, pixels off the mask zeroed, scaled by the
+    largest magnitude."""
+    last = emb_img.shape[-1]
+    if demean is True:
+        demean = emb_img[mask].view(-1, last).mean(dim=0)
+    if demean is not False:
+        emb_img = emb_img - demean
+    emb_img = emb_img.view(*emb_img.shape[:-1], 3, -1).mean(dim=-1)
+    if mask is not None:
+        emb_img[~mask] = 0.
+    emb_img /= torch.abs(emb_img).max() + 1e-9
+    emb_img.mul_(0.5).add_(0.5)
+    return emb_img
+
+
+def normImage(emb_img: torch.Tensor) -> torch.Tensor:
+    """nutil.normImage (nutil.py:345-348): in place, the image over its largest magnitude, then halved around 0.5."""
+    emb_img /= torch.abs(emb_img).max() + 1e-9
+    emb_img.mul_(0.5).add_(0.5)
+    return emb_img
+
+
+def full_render(field, camera, renderer_grid):
+    """The tensor half of nutil.show_full_render1 (nutil.py:233-246): renderer_grid(cameras=camera,
+    volumetric_function=field.batched_forward), the first image split into (rendered_image (H, W, F),
+    rendered_silhouette (H, W, 1)).  Writing image files is the caller's."""
+    with torch.no_grad():
+        rendered, _, _ = renderer_grid(cameras=camera, volumetric_function=field.batched_forward)
+        last = rendered.shape[-1]
+        return rendered[0].split([last - 1, 1], dim=-1)
