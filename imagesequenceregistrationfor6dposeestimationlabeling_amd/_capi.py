@@ -213,6 +213,15 @@ RADIANCE_SIGNATURES = {
     "isr_radiance_normalize_host": (_i, [_vp, _sz, _vp]),
 }
 
+# include/isr_resample.h (the fine pass's ray sampling), bound the same way
+RESAMPLE_SIGNATURES = {
+    "isr_sample_pdf": (_i, [_vp, _vp, _i64, _i, _i, _i, _f, _u64, _vp, _vp, _vp]),
+    "isr_sample_pdf_host": (_i, [_vp, _vp, _i64, _i, _i, _i, _f, _u64, _vp, _vp]),
+    "isr_resample_lengths": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _f, _u64, _vp, _vp, _vp]),
+    "isr_resample_lengths_host": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _f, _u64, _vp, _vp]),
+    "isr_resample_rays_per_group": (_i, [_i, _i, _i, _i]),
+}
+
 # include/isr_mc.h (iso-surface extraction), bound the same way
 MC_SIGNATURES = {
     "isr_mc_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -239,7 +248,7 @@ def lib() -> C.CDLL:
         raise IsrError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES, **FPS_SIGNATURES, **DENSITY_SIGNATURES,
                                **DENSITY_DIR_SIGNATURES, **RADIUS_SIGNATURES, **MC_SIGNATURES, **KNN_SIGNATURES,
-                               **RAYS_SIGNATURES, **RADIANCE_SIGNATURES}.items():
+                               **RAYS_SIGNATURES, **RADIANCE_SIGNATURES, **RESAMPLE_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

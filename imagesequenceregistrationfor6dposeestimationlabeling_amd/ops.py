@@ -1777,3 +1777,102 @@ def philox_host(counter, key):
     words, units = np.empty(4, np.uint32), np.empty(4, np.float32)
     check(lib().isr_rays_philox_host(_hp(c), _hp(k), _hp(words), _hp(units)), "isr_rays_philox_host")
     return words, units
+
+
+def _resample_check(name: str, a, w, a_cols_minus_w: int, n_samples, eps, seed, ray_ids) -> tuple[int, int]:
+    """Shapes and limits of include/isr_resample.h for rows a (N, w_cols + a_cols_minus_w) and w (N, w_cols); -> (N, w_cols)."""
+    if a.ndim != 2 or w.ndim != 2 or a.shape[0] != w.shape[0] or a.shape[1] != w.shape[1] + a_cols_minus_w:
+        raise ValueError(f"{name}: rows of {tuple(a.shape)} and {tuple(w.shape)} do not belong together "
+                         f"(expected (N, {'P' if a_cols_minus_w == 0 else 'nb+1'}) and (N, {'P' if a_cols_minus_w == 0 else 'nb'}))")
+    if a.dtype != w.dtype or str(a.dtype).split(".")[-1] != "float32":
+        raise ValueError(f"{name}: float32 arrays only, got {a.dtype} and {w.dtype}")
+    N, P = a.shape[0], w.shape[1] + 2 * a_cols_minus_w           # P: the lengths the bins came from
+    if not 3 <= P <= 1024:
+        raise ValueError(f"{name}: P = {P} outside 3..1024 (nb = P - 2)")
+    if not 1 <= int(n_samples) <= 1024:
+        raise ValueError(f"{name}: n_samples = {n_samples} outside 1..1024")
+    if N > 2 ** 28:
+        raise ValueError(f"{name}: {N} rays is more than 2^28")
+    if not (float(eps) > 0.0 and np.isfinite(np.float32(eps)) and np.float32(eps) > 0):
+        raise ValueError(f"{name}: eps = {eps} must be positive and finite in float32")
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"{name}: seed = {seed} outside 0..2^64-1")
+    if ray_ids is not None and tuple(ray_ids.shape) != (N,):
+        raise ValueError(f"{name}: ray_ids must be ({N},), got {tuple(ray_ids.shape)}")
+    return N, w.shape[1]
+
+
+def _resample_device(name: str, a: torch.Tensor, w: torch.Tensor, ray_ids):
+    dev = require_cuda(a, w, ray_ids)
+    if not (a.is_contiguous() and w.is_contiguous()):
+        raise ValueError(f"{name}: the arrays must be contiguous")
+    return dev, _i32c(ray_ids)
+
+
+def sample_pdf(bins: torch.Tensor, weights: torch.Tensor, n_samples: int, det: bool = False, eps: float = 1e-5, seed: int = 0,
+               ray_ids: torch.Tensor | None = None) -> torch.Tensor:
+    """isr_sample_pdf: bins (N, nb+1), weights (N, nb) contiguous f32 on the device -> samples (N, n_samples), unsorted, in
+    sample order: pytorch3d's sample_pdf as include/isr_resample.h states it.  det: units linspace(0, 1, n), otherwise Philox
+    under `seed` and ray_ids (N,) int32 (default 0 .. N-1).  One launch; nothing synchronises."""
+    dev, ids = _resample_device("sample_pdf", bins, weights, ray_ids)
+    N, nb = _resample_check("sample_pdf", bins, weights, 1, n_samples, eps, seed, ids)
+    out = torch.empty((N, int(n_samples)), dtype=torch.float32, device=dev)
+    if N:
+        with torch.cuda.device(dev), _timed("sample_pdf", float(N) * (2 * nb + 1 + int(n_samples)) * 4):
+            rc = lib().isr_sample_pdf(ptr(bins), ptr(weights), N, nb, int(n_samples), int(bool(det)), float(eps), int(seed), ptr(ids),
+                                      ptr(out), current_stream(dev))
+        check(rc, "isr_sample_pdf")
+    return out
+
+
+def resample_lengths(lengths: torch.Tensor, ray_weights: torch.Tensor, n_samples: int, add_input_samples: bool = True,
+                     det: bool = False, eps: float = 1e-5, seed: int = 0, ray_ids: torch.Tensor | None = None) -> torch.Tensor:
+    """isr_resample_lengths: lengths (N, P), ray_weights (N, P) contiguous f32 on the device -> the sorted depths of the fine
+    pass (N, n_samples + P) (or (N, n_samples) without add_input_samples): ProbabilisticRaysampler.forward of pren.py:427-457
+    as include/isr_resample.h states it.  One launch; nothing synchronises."""
+    dev, ids = _resample_device("resample_lengths", lengths, ray_weights, ray_ids)
+    N, P = _resample_check("resample_lengths", lengths, ray_weights, 0, n_samples, eps, seed, ids)
+    P_out = int(n_samples) + (P if add_input_samples else 0)
+    out = torch.empty((N, P_out), dtype=torch.float32, device=dev)
+    if N:
+        with torch.cuda.device(dev), _timed("resample_lengths", float(N) * (2 * P + P_out) * 4):
+            rc = lib().isr_resample_lengths(ptr(lengths), ptr(ray_weights), N, P, int(n_samples), int(bool(add_input_samples)),
+                                            int(bool(det)), float(eps), int(seed), ptr(ids), ptr(out), current_stream(dev))
+        check(rc, "isr_resample_lengths")
+    return out
+
+
+def _resample_host(name: str, a, w, ray_ids):
+    if getattr(a, "dtype", None) != np.float32 or getattr(w, "dtype", None) != np.float32:
+        raise ValueError(f"{name}: float32 NumPy arrays only")
+    ids = None if ray_ids is None else np.ascontiguousarray(ray_ids, np.int32)
+    return np.ascontiguousarray(a), np.ascontiguousarray(w), ids
+
+
+def sample_pdf_host(bins, weights, n_samples: int, det: bool = False, eps: float = 1e-5, seed: int = 0, ray_ids=None):
+    """isr_sample_pdf_host: sample_pdf as host code over NumPy arrays.  For tests."""
+    b, w, ids = _resample_host("sample_pdf_host", bins, weights, ray_ids)
+    N, nb = _resample_check("sample_pdf_host", b, w, 1, n_samples, eps, seed, ids)
+    out = np.empty((N, int(n_samples)), np.float32)
+    check(lib().isr_sample_pdf_host(_hp(b), _hp(w), N, nb, int(n_samples), int(bool(det)), float(eps), int(seed), _hp(ids), _hp(out)),
+          "isr_sample_pdf_host")
+    return out
+
+
+def resample_lengths_host(lengths, ray_weights, n_samples: int, add_input_samples: bool = True, det: bool = False,
+                          eps: float = 1e-5, seed: int = 0, ray_ids=None):
+    """isr_resample_lengths_host: resample_lengths as host code over NumPy arrays.  For tests."""
+    ln, w, ids = _resample_host("resample_lengths_host", lengths, ray_weights, ray_ids)
+    N, P = _resample_check("resample_lengths_host", ln, w, 0, n_samples, eps, seed, ids)
+    out = np.empty((N, int(n_samples) + (P if add_input_samples else 0)), np.float32)
+    check(lib().isr_resample_lengths_host(_hp(ln), _hp(w), N, P, int(n_samples), int(bool(add_input_samples)), int(bool(det)),
+                                          float(eps), int(seed), _hp(ids), _hp(out)), "isr_resample_lengths_host")
+    return out
+
+
+def resample_rays_per_group(P: int, n_samples: int, add_input_samples: bool = True, sorted_rows: bool = True) -> int:
+    """isr_resample_rays_per_group: the rays one workgroup of the resample kernel owns for this shape (tests and tools)."""
+    R = lib().isr_resample_rays_per_group(int(P), int(n_samples), int(bool(add_input_samples)), int(bool(sorted_rows)))
+    if R < 1:
+        check(-1, "isr_resample_rays_per_group")
+    return R

@@ -5,9 +5,10 @@ silhouette selection of pren.py:229-236 (`sampler(cameras, mask=...)`).  The ray
 module holds the camera's bookkeeping and the conversion of screen-space intrinsics to NDC.  On top of them the renderer
 of pren.py under its names: EmissionAbsorptionRaymarcherStratified (pren.py:256-369) and ImplicitRendererStratified
 (pren.py:172-253), whose images come from isr_ea_march or, for a fields.RadianceField, from the fused isr_radiance_render.
+The fine pass's depths — sample_pdf and ProbabilisticRaysampler (pren.py:372-457), the renderer's stratified=True — come from
+isr_resample_lengths (include/isr_resample.h; the rule of sample_pdf is pytorch3d's only as far as it is known from memory).
 
-Out of scope: the renderer's stratified=True (ProbabilisticRaysampler / sample_pdf), the raymarcher's weightMode,
-unit_directions, K= and FoV cameras."""
+Out of scope: the raymarcher's weightMode, unit_directions, K= and FoV cameras."""
 from __future__ import annotations
 
 from typing import NamedTuple
@@ -171,6 +172,56 @@ def sample_images_at_mc_locs(target_images: torch.Tensor, sampled_rays_xy: torch
     return ops.sample_at_rays(target_images, sampled_rays_xy)
 
 
+def sample_pdf(bins: torch.Tensor, weights: torch.Tensor, n_samples: int, det: bool = False, eps: float = 1e-5, *,
+               seed: int = 0) -> torch.Tensor:
+    """pytorch3d's sample_pdf: bins (..., nb+1), weights (..., nb) -> samples (..., n_samples) by inverse-CDF sampling, on
+    the device (ops.sample_pdf; include/isr_resample.h states the rule).  det: evenly spaced units, otherwise Philox under
+    `seed` with the flattened row index as the ray id — torch's random stream is not reproduced."""
+    lead = tuple(bins.shape[:-1])
+    if tuple(weights.shape[:-1]) != lead:
+        raise ValueError(f"sample_pdf: bins {tuple(bins.shape)} and weights {tuple(weights.shape)} differ in their leading shape")
+    out = ops.sample_pdf(bins.to(torch.float32).reshape(-1, bins.shape[-1]).contiguous(),
+                         weights.to(torch.float32).reshape(-1, weights.shape[-1]).contiguous(), n_samples, det, eps, seed)
+    return out.reshape(*lead, int(n_samples))
+
+
+class ProbabilisticRaysampler:
+    """pren.py:372-457: sampler(input_ray_bundle, ray_weights) -> the RayBundle whose lengths are n_pts_per_ray depths drawn
+    from the coarse ray_weights (..., P), together with the input lengths when add_input_samples, sorted; origins, directions
+    and xys are passed through.  Any leading shape is taken, so the view() calls of pren.py:216-224 are not needed.
+    The units are evenly spaced unless (stratified and training) or (stratified_test and not training), when they come from
+    Philox under `seed` with the flattened ray index as the ray id; a caller who wants fresh samples changes `seed`."""
+
+    def __init__(self, n_pts_per_ray: int, stratified: bool, stratified_test: bool, add_input_samples: bool = True, seed: int = 0):
+        self._n_pts_per_ray = int(n_pts_per_ray)
+        self._stratified = bool(stratified)
+        self._stratified_test = bool(stratified_test)
+        self._add_input_samples = bool(add_input_samples)
+        self.seed = int(seed)
+        self.training = True
+
+    def train(self, mode: bool = True) -> "ProbabilisticRaysampler":
+        self.training = bool(mode)
+        return self
+
+    def eval(self) -> "ProbabilisticRaysampler":
+        return self.train(False)
+
+    def __call__(self, input_ray_bundle: RayBundle, ray_weights: torch.Tensor, **kwargs) -> RayBundle:
+        z = input_ray_bundle.lengths
+        if tuple(ray_weights.shape) != tuple(z.shape):
+            raise ValueError(f"ProbabilisticRaysampler: ray_weights {tuple(ray_weights.shape)} for lengths {tuple(z.shape)}")
+        det = not ((self._stratified and self.training) or (self._stratified_test and not self.training))
+        P = z.shape[-1]
+        out = ops.resample_lengths(z.to(torch.float32).reshape(-1, P).contiguous(),
+                                   ray_weights.to(torch.float32).reshape(-1, P).contiguous(), self._n_pts_per_ray,
+                                   self._add_input_samples, det, seed=self.seed)
+        return RayBundle(input_ray_bundle.origins, input_ray_bundle.directions, out.reshape(*z.shape[:-1], out.shape[-1]),
+                         input_ray_bundle.xys)
+
+    forward = __call__
+
+
 class EmissionAbsorptionRaymarcherStratified:
     """pren.py:256-369: rays_densities (..., P, 1) and rays_features (..., P, F) -> (images (..., F+1) [features |
     opacity], weights (..., P)) by ops.ea_march.  thresholdMode marches the densities above `threshold` as ones.  The
@@ -209,19 +260,31 @@ class EmissionAbsorptionRaymarcherStratified:
 
 
 class ImplicitRendererStratified:
-    """pren.py:57-253 without its stratified branch: renderer(cameras, volumetric_function, maskRays=False, mask=False) ->
+    """pren.py:57-253: renderer(cameras, volumetric_function, stratified=False, maskRays=False, mask=False) ->
     (images (..., F+1), ray_bundle, weights (..., P)).  The bundle is raysampler(cameras), (B, H, W, .) for a grid sampler,
     or with maskRays the (1, M, .) rays on non-zero pixels of `mask` (pren.py:230-236).  rayFreeze keeps the first call's
     bundle for every later call.  When volumetric_function is the bound batched_forward (or forward) of a
     fields.RadianceField the fused render runs; anything else callable is called as
-    volumetric_function(ray_bundle=..., cameras=..., **kwargs) and its (densities, features) go through the raymarcher."""
+    volumetric_function(ray_bundle=..., cameras=..., **kwargs) and its (densities, features) go through the raymarcher.
 
-    def __init__(self, raysampler, raymarcher, device=None, rayFreeze: bool = False):
+    stratified=True is the fine pass of pren.py:203-226 and needs a renderer built with fine_seed (an int): with the default
+    fine_seed=None it raises NotImplementedError.  The coarse bundle is the one above; the reference selects the mask's rays
+    after the coarse pass, this renderer before it — weights are per ray, so the rays and their weights are the same, for
+    less work.  The coarse weights are emission-absorption weights whatever the marcher's thresholdMode (getWeights,
+    pren.py:159-170): from field.render(threshold=-1) for a fused RadianceField, otherwise from the callable's densities
+    through ops.ea_march(threshold=-1).  The fine bundle is ProbabilisticRaysampler(P, True, False, add_input_samples,
+    seed=fine_seed) of the coarse bundle and weights ((..., 2P) lengths with add_input_samples, (..., P) without); the field
+    and the marcher then run on it as above, and rayFreeze freezes it.  coarse=(bundle, weights) skips the coarse pass
+    (pren2.py:204-217 with trainNerfFine.py:293-300's coarseR / coarseW).  A caller who wants fresh samples per call changes
+    renderer.fine_seed."""
+
+    def __init__(self, raysampler, raymarcher, device=None, rayFreeze: bool = False, fine_seed: int | None = None):
         if not callable(raysampler):
             raise ValueError('"raysampler" has to be a "Callable" object.')
         if not callable(raymarcher):
             raise ValueError('"raymarcher" has to be a "Callable" object.')
         self.raysampler, self.raymarcher, self.device, self.rayFreeze = raysampler, raymarcher, device, rayFreeze
+        self.fine_seed = fine_seed
         self.rayState = "Empty"
         self.frozenRays = False
 
@@ -234,15 +297,37 @@ class ImplicitRendererStratified:
             return owner
         return None
 
-    def __call__(self, cameras, volumetric_function, stratified: bool = False, maskRays: bool = False, mask=False, **kwargs):
+    def _coarse_weights(self, bundle: RayBundle, cameras, volumetric_function, kwargs) -> torch.Tensor:
+        """getWeights (pren.py:159-170): the emission-absorption weights of the field along the coarse bundle."""
+        field = self._fused_field(volumetric_function)
+        if field is not None:
+            return field.render(bundle, threshold=-1.0, return_weights=True)[1]
+        rays_densities, rays_features = volumetric_function(ray_bundle=bundle, cameras=cameras, **kwargs)
+        lead, P, F = tuple(rays_features.shape[:-2]), rays_features.shape[-2], rays_features.shape[-1]
+        _, wts = ops.ea_march(rays_densities.to(torch.float32).reshape(-1, P).contiguous(),
+                              rays_features.to(torch.float32).reshape(-1, P, F).contiguous(), -1.0, want_weights=True)
+        return wts.reshape(*lead, P)
+
+    def __call__(self, cameras, volumetric_function, stratified: bool = False, maskRays: bool = False, mask=False,
+                 add_input_samples: bool = False, coarse=None, **kwargs):
         if not callable(volumetric_function):
             raise ValueError('"volumetric_function" has to be a "Callable" object.')
-        if stratified:
-            raise NotImplementedError("ImplicitRendererStratified: stratified=True (ProbabilisticRaysampler) is not supported")
+        if stratified and self.fine_seed is None:
+            raise NotImplementedError("ImplicitRendererStratified: stratified=True (ProbabilisticRaysampler) is not supported "
+                                      "without fine_seed: build the renderer with fine_seed=<int>")
         if self.rayState == "Empty":
             if self.rayFreeze:
                 self.rayState = "Occupied"
-            self.frozenRays = self.raysampler(cameras, mask=mask) if maskRays else self.raysampler(cameras)
+            if stratified and coarse is not None:
+                bundle, weights = coarse
+            else:
+                bundle = self.raysampler(cameras, mask=mask) if maskRays else self.raysampler(cameras)
+            if stratified:
+                if coarse is None:
+                    weights = self._coarse_weights(bundle, cameras, volumetric_function, kwargs)
+                psampler = ProbabilisticRaysampler(bundle.lengths.shape[-1], True, False, add_input_samples, seed=self.fine_seed)
+                bundle = psampler(bundle, weights)
+            self.frozenRays = bundle
         bundle = self.frozenRays
         field = self._fused_field(volumetric_function)
         if field is not None and isinstance(self.raymarcher, EmissionAbsorptionRaymarcherStratified):
