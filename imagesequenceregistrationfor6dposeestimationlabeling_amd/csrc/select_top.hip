@@ -99,8 +99,8 @@ __global__ void pick_kernel(const int32_t* __restrict__ hist, SelState* __restri
     const int b = t * PER + j;
     if (b < NB) cum[b] = before + loc[j];
   }
+  const int32_t k = st->k;   // read before the barrier: the thread that finds the bin rewrites st->k after it
   __syncthreads();
-  const int32_t k = st->k;
   if (LAST && st->n == 0 && t == 0) {               // empty input: keep nothing
     st->thr_bits = __float_as_uint(__builtin_inff());
     if (thr_out) *thr_out = __builtin_inff();

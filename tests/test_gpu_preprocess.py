@@ -135,3 +135,281 @@ def test_register_frame_runs_the_whole_per_image_loop(cuda0):
     assert torch.equal(res.idx[:n], ref.idx[:n]) and torch.equal(res.pose, ref.pose) and int(res.status.item()) == 1
     pose = res.pose.cpu().numpy()
     assert synth.rot_angle(pose[:, :3], R[0]) < 0.05 and np.linalg.norm(pose[:, 3] - t) < 0.05 * 700
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Batch chunks, general affines, rounding ties and ragged frames.  Small frames throughout: 45 x 61 = 2745 pixels (ten
+# full strides of mask_bbox_kernel's 256 threads and a tail of 185) and a 37 x 37 crop (1369 output pixels = five full
+# workgroups of crop_normalize_kernel and a sixth of 89 threads).
+_H, _W, _R = 45, 61, 37
+
+
+def _sample_positions(M, size=_R):
+    """The crop's sample positions in the frame, by the oracle's own statements (preprocess_oracle.warp_affine)."""
+    M = np.asarray(M, np.float64)
+    det = M[0, 0] * M[1, 1] - M[0, 1] * M[1, 0]
+    i00, i01, i10, i11 = M[1, 1] / det, -M[0, 1] / det, -M[1, 0] / det, M[0, 0] / det
+    i02 = -(i00 * M[0, 2] + i01 * M[1, 2])
+    i12 = -(i10 * M[0, 2] + i11 * M[1, 2])
+    y, x = np.mgrid[0:size, 0:size].astype(np.float64)
+    return (i00 * x + i01 * y) + i02, (i10 * x + i11 * y) + i12
+
+
+def _affine(A, src_centre, size=_R):
+    """M = [A | t] (source -> crop) that sends the frame position src_centre to the middle of the crop."""
+    A = np.asarray(A, np.float64)
+    t = np.array([(size - 1) / 2.0, (size - 1) / 2.0]) - A @ np.asarray(src_centre, np.float64)
+    return np.concatenate([A, t[:, None]], axis=1)
+
+
+def _rot(deg):
+    c, s = np.cos(np.deg2rad(deg)), np.sin(np.deg2rad(deg))
+    return np.array([[c, -s], [s, c]])
+
+
+# The general-affine family: (linear part, frame position under the crop's centre).  Every centre is pushed towards a
+# side of the frame so that part of the crop samples the zero border.  A 37 x 37 crop at an isotropic scale below 0.5
+# would cover more than twice the 45 x 61 frame (more than half of it border), so the minification is 0.45 along x and
+# 0.7 along y (area factor 0.315); it overhangs all four sides at once.
+_AFFINES = {
+    "rotation_aniso": (_rot(33.0) @ np.diag([1.3, 0.8]), (50.0, 12.0)),
+    "shear": (np.array([[0.9, 0.45], [0.0, 0.9]]), (14.0, 36.0)),
+    "reflection": (np.array([[-0.85, 0.1], [0.15, 0.95]]), (49.0, 33.0)),
+    "magnify": (np.diag([2.6, 2.3]), (3.5, 4.0)),
+    "minify": (np.diag([0.45, 0.7]), (30.0, 22.0)),
+}
+
+
+def _frames(rng, B, Cm, H=_H, W=_W):
+    """B frames of their own: random bytes and a mask (values 255, every channel alike) that is a random blob with holes
+    plus scattered pixels outside it, so that a crop of any corner of the frame still sees mask pixels of both kinds."""
+    rgb = rng.integers(0, 256, size=(B, H, W, 3), dtype=np.uint8)
+    yy, xx = np.mgrid[:H, :W]
+    mask = np.zeros((B, H, W, Cm), np.uint8)
+    for b in range(B):
+        cy, cx = rng.uniform(0.3, 0.7) * H, rng.uniform(0.3, 0.7) * W
+        blob = ((yy - cy) / (0.45 * H)) ** 2 + ((xx - cx) / (0.45 * W)) ** 2 < 1.0
+        u = rng.random((H, W))
+        mask[b, np.where(blob, u > 0.15, u < 0.3)] = 255
+    return rgb, mask
+
+
+_CHUNK_CACHE = {}
+
+
+def _chunk_scene(Cm):
+    """33 frames (three chunks of kMaxBatch = 16: 16 + 16 + 1), each with its own content, mask and general affine, and
+    the oracle's outputs for both use_mask values.  Computed once per mask-channel count and never modified."""
+    if Cm not in _CHUNK_CACHE:
+        from oracle import preprocess_oracle as pp
+        rng = np.random.default_rng(100 + Cm)
+        B = 33
+        rgb, mask = _frames(rng, B, Cm)
+        kinds = list(_AFFINES)
+        M = np.empty((B, 2, 3))
+        for b in range(B):
+            A, c = _AFFINES[kinds[b % len(kinds)]]
+            M[b] = _affine(_rot(rng.uniform(-8.0, 8.0)) @ A, np.asarray(c) + rng.uniform(-2.0, 2.0, 2))
+        ref = {um: [pp.crop_inputs(rgb[b], mask[b], M[b], _R, um) for b in range(B)] for um in (True, False)}
+        for a in (rgb, mask, M):
+            a.setflags(write=False)
+        _CHUNK_CACHE[Cm] = rgb, mask, M, ref
+    return _CHUNK_CACHE[Cm]
+
+
+@pytest.mark.parametrize("use_mask", [True, False])
+@pytest.mark.parametrize("Cm", [1, 3])
+@pytest.mark.parametrize("B", [16, 17, 33])
+def test_crop_normalize_chunks_match_oracle(cuda0, B, Cm, use_mask):
+    """The chunk loop of isr_crop_normalize, `for (int b0 = 0; b0 < B; b0 += kMaxBatch)` with kMaxBatch = 16: B = 16 is
+    one full chunk, B = 17 reaches the second chunk with nb = 1 (`rgb + (size_t)b0 * H * W * 3`, `mask + ...`,
+    `out + (size_t)b0 * 3 * r * r`, `crop_mask + (size_t)b0 * r * r` and `M_host + 6 * (size_t)(b0 + ...)` with
+    b0 = 16), B = 33 the third (b0 = 32).  Every image has its own bytes, mask and general affine, and by the oracle
+    alone no two images of the batch share an output — a wrong chunk offset cannot land on an equal image.  Every
+    image is byte-equal to preprocess_oracle.crop_inputs."""
+    from imagesequenceregistrationfor6dposeestimationlabeling_amd import ops
+    rgb, mask, M, ref = _chunk_scene(Cm)
+    want = ref[use_mask][:B]
+    for i in range(B):
+        for j in range(i + 1, B):
+            assert not np.array_equal(want[i][0], want[j][0]) and not np.array_equal(want[i][1], want[j][1]), (i, j)
+    out, cm = ops.crop_normalize(torch.from_numpy(rgb[:B].copy()).to(cuda0), torch.from_numpy(mask[:B].copy()).to(cuda0),
+                                 M[:B], out_size=_R, use_mask=use_mask)
+    out, cm = out.cpu().numpy(), cm.cpu().numpy()
+    assert out.shape == (B, 3, _R, _R) and cm.shape == (B, _R, _R)
+    for b in range(B):
+        assert np.array_equal(cm[b], want[b][1]), f"crop_mask of image {b}"
+        assert np.array_equal(out[b], want[b][0]), f"network input of image {b}"
+
+
+def test_crop_inputs_chunks_equal_single_frames(cuda0):
+    """registration.crop_inputs over 17 frames — isr_mask_bbox with 17 images on blockIdx.z, the host table of M, and
+    the second chunk of isr_crop_normalize (b0 = 16) — against the 17 single-frame calls and the oracle: M, cam,
+    inputIM and cropMask are equal.  Frames of 95 x 127 = 12065 pixels (not a multiple of 256), a different box each."""
+    from imagesequenceregistrationfor6dposeestimationlabeling_amd import formats, registration
+    from oracle import preprocess_oracle as pp
+    rng = np.random.default_rng(17)
+    B, H, W, r = 17, 95, 127, 32
+    rgb = rng.integers(0, 256, size=(B, H, W, 3), dtype=np.uint8)
+    mask = np.zeros((B, H, W, 3), np.uint8)
+    for b in range(B):
+        x, y, w, h = 3 + 5 * b, (7 * b) % 50, 20 + 3 * b, 18 + 2 * (b % 9)
+        mask[b, y:y + h, x:x + w] = 255
+        mask[b, y + 2:y + 5, x + 3:x + 9] = 0                   # a hole: the box is still the rectangle's
+    K = np.array([[300.0, 0, 63.0], [0, 310.0, 47.0], [0, 0, 1]]) + np.arange(B)[:, None, None] * np.array([[1.0, 0, 0.5], [0, 1.0, 0.25], [0, 0, 0]])
+    inB, mB, camB, MB = registration.crop_inputs(rgb, mask, K, out_size=r)
+    assert inB.shape == (B, 3, r, r) and mB.shape == (B, r, r)
+    boxes = set()
+    for b in range(B):
+        in1, m1, cam1, M1 = registration.crop_inputs(rgb[b], mask[b], K[b], out_size=r)
+        assert np.array_equal(M1[0], MB[b]) and np.array_equal(cam1[0], camB[b]), b
+        assert torch.equal(in1[0], inB[b]) and torch.equal(m1[0], mB[b]), b
+        bb = pp.bounding_rect(mask[b, :, :, 0])
+        boxes.add(bb)
+        assert np.array_equal(MB[b], formats.crop_affine(bb, r)) and np.array_equal(camB[b], formats.crop_camera(K[b], bb, r))
+        ref_in, ref_mask = pp.crop_inputs(rgb[b], mask[b], MB[b], r, True)
+        assert np.array_equal(mB[b].cpu().numpy(), ref_mask) and np.array_equal(inB[b].cpu().numpy(), ref_in), b
+    assert len(boxes) == B
+
+
+@pytest.mark.parametrize("use_mask", [True, False])
+def test_crop_normalize_general_affines(cuda0, use_mask):
+    """The kernel inverts a general 2 x 3 affine (`i00 = M[4] / det, i01 = -M[1] / det, i10 = -M[3] / det,
+    i11 = M[0] / det`), the suite so far only fed it formats.crop_affine's axis-aligned scalings (M[1] = M[3] = 0).
+    A rotation with anisotropic scale, a shear, a reflection (det < 0: `const double det = M[0] * M[4] - M[1] * M[3]`
+    negative), a magnification above 2 and a minification below 0.5, each translated so that — by the oracle alone —
+    between 5 % and 50 % of the crop's sample positions lie outside the frame, all four sides being crossed by some
+    member (the `px` lambda's zero border).  Bytes equal the oracle's."""
+    from imagesequenceregistrationfor6dposeestimationlabeling_amd import ops
+    from oracle import preprocess_oracle as pp
+    rng = np.random.default_rng(7)
+    kinds = list(_AFFINES)
+    B = len(kinds)
+    rgb, mask = _frames(rng, B, 3)
+    M = np.stack([_affine(*_AFFINES[k]) for k in kinds])
+    det = M[:, 0, 0] * M[:, 1, 1] - M[:, 0, 1] * M[:, 1, 0]
+    assert det[kinds.index("reflection")] < 0 and (np.delete(det, kinds.index("reflection")) > 0).all()
+    assert M[kinds.index("rotation_aniso"), 0, 1] != 0 and M[kinds.index("shear"), 0, 1] != 0 and M[kinds.index("shear"), 1, 0] == 0
+    sv = np.linalg.svd(M[:, :, :2], compute_uv=False)
+    assert sv[kinds.index("magnify")].min() > 2.0 and sv[kinds.index("minify")].min() < 0.5
+    sides = np.zeros(4, bool)
+    for b, k in enumerate(kinds):
+        sx, sy = _sample_positions(M[b])
+        off = [sx < 0, sx > _W - 1, sy < 0, sy > _H - 1]
+        frac = np.mean(off[0] | off[1] | off[2] | off[3])
+        assert 0.05 <= frac <= 0.50, (k, frac)
+        sides |= np.array([o.any() for o in off])
+    assert sides.all()
+    out, cm = ops.crop_normalize(torch.from_numpy(rgb).to(cuda0), torch.from_numpy(mask).to(cuda0), M, out_size=_R,
+                                 use_mask=use_mask)
+    out, cm = out.cpu().numpy(), cm.cpu().numpy()
+    for b, k in enumerate(kinds):
+        ref_in, ref_mask = pp.crop_inputs(rgb[b], mask[b], M[b], _R, use_mask)
+        assert 0 < np.count_nonzero(ref_mask) < ref_mask.size, k
+        assert np.array_equal(cm[b], ref_mask), k
+        assert np.array_equal(out[b], ref_in), k
+
+
+def _tie_values(img, both_axes):
+    """The exact f64 bilinear sums of the two tie affines on the top-left _R x _R crop: sx = x - 0.5 (and sy = y - 0.5),
+    so every weight is 1/2 (1/4) and the neighbour left of column 0 (above row 0) is the zero border."""
+    P = np.zeros((img.shape[0] + 1, img.shape[1] + 1) + img.shape[2:], np.float64)
+    P[1:, 1:] = img
+    if both_axes:
+        v = ((P[:-1, :-1] * 0.25 + P[:-1, 1:] * 0.25) + P[1:, :-1] * 0.25) + P[1:, 1:] * 0.25
+    else:
+        v = P[1:, :-1] * 0.5 + P[1:, 1:] * 0.5
+    return v[:_R, :_R]
+
+
+@pytest.mark.parametrize("use_mask", [False, True])
+@pytest.mark.parametrize("both_axes", [False, True])
+def test_crop_normalize_rounds_ties_to_even(cuda0, both_axes, use_mask):
+    """sample_u8's `return (uint8_t)rint(v);`: round half to even.  M = [[1, 0, .5], [0, 1, 0]] puts every sample exactly
+    between two source pixels, M = [[1, 0, .5], [0, 1, .5]] at the centre of four; the sums are exact in f64, about half
+    of the two-pixel sums end in .5, and by the oracle alone at least 20 % of the bytes differ from floor(v + 0.5).  (Of
+    four random bytes only one sum in four ends in .5 and half of those have an odd floor, where both rules round up:
+    12.5 %.  So in the four-pixel case the left 20 columns carry constructed low bits — 1 in even columns, 0 in odd ones,
+    below random multiples of 8 — which makes every 2 x 2 sum 8 k + 2, a tie above an even floor; the other columns stay
+    random and keep the ties that round up.)  With use_mask the
+    mask holds 0 and 1: its warped value is 0.5 at many pixels, rint gives 0 there and `if (use_mask && m == 0) v = 0;`
+    blanks the pixel — the blanking is decided by the tie rule.  Bytes equal the oracle's."""
+    from imagesequenceregistrationfor6dposeestimationlabeling_amd import ops
+    from oracle import preprocess_oracle as pp
+    rng = np.random.default_rng(11 + both_axes)
+    rgb = rng.integers(0, 256, size=(_H, _W, 3), dtype=np.uint8)
+    if both_axes:
+        rgb[:, :20] = (rgb[:, :20] & 0xF8) | (np.arange(20) % 2 == 0).astype(np.uint8)[None, :, None]
+    mask = rng.integers(0, 2, size=(_H, _W, 1), dtype=np.uint8)
+    M = np.array([[1.0, 0.0, 0.5], [0.0, 1.0, 0.5 if both_axes else 0.0]])
+    v = _tie_values(rgb, both_axes)
+    even, half_up = pp.warp_affine(rgb, M, _R), np.floor(v + 0.5).astype(np.uint8)
+    assert np.array_equal(even, np.rint(v).astype(np.uint8))
+    assert np.mean(even != half_up) >= 0.20
+    up = (v % 1.0 == 0.5) & (np.floor(v) % 2 == 1)                     # ties that half-to-even rounds up as well
+    assert np.mean(up) >= 0.03
+    vm = _tie_values(mask, both_axes)[:, :, 0]
+    m_even, m_half_up = pp.warp_affine(mask, M, _R)[:, :, 0], np.floor(vm + 0.5).astype(np.uint8)
+    assert set(np.unique(m_even)) == {0, 1} and np.mean((m_even == 0) & (m_half_up == 1)) >= 0.20
+    ref_in, ref_mask = pp.crop_inputs(rgb, mask, M, _R, use_mask)
+    assert np.array_equal(ref_mask, m_even)
+    out, cm = ops.crop_normalize(torch.from_numpy(rgb[None]).to(cuda0), torch.from_numpy(mask[None]).to(cuda0), M[None],
+                                 out_size=_R, use_mask=use_mask)
+    assert np.array_equal(cm[0].cpu().numpy(), ref_mask)
+    assert np.array_equal(out[0].cpu().numpy(), ref_in)
+
+
+@pytest.mark.parametrize("C", [1, 3, 4])
+def test_mask_bbox_ragged_frames(cuda0, C):
+    """mask_bbox_kernel's strided loop `for (int i = threadIdx.x; i < H * W; i += 256)` on 45 x 61 = 2745 pixels: ten
+    full strides and a tail of 185, whose last pixel is index H * W - 1.  40 masks on blockIdx.z with single non-zero
+    pixels at each corner, at the first and the last pixel of the tail, images that are non-zero only in channels other
+    than 0 (`m[(size_t)i * C]` reads channel 0 alone), an empty one, and random sparse ones.  Boxes equal
+    preprocess_oracle.bounding_rect."""
+    from imagesequenceregistrationfor6dposeestimationlabeling_amd import ops
+    from oracle import preprocess_oracle as pp
+    rng = np.random.default_rng(40 + C)
+    B, H, W = 40, _H, _W
+    masks = np.zeros((B, H, W, C), np.uint8)
+    flat = masks.reshape(B, H * W, C)
+    flat[0, 0, 0] = 1                                   # top-left
+    flat[1, W - 1, 0] = 2                               # top-right
+    flat[2, (H - 1) * W, 0] = 3                         # bottom-left
+    flat[3, H * W - 1, 0] = 255                         # bottom-right = the last pixel of the tail
+    flat[4, 2560, 0] = 9                                # the first pixel of the tail (10 * 256)
+    flat[5, [0, W - 1, (H - 1) * W, H * W - 1], 0] = 7  # all four corners
+    # 6 stays empty
+    if C > 1:                                           # non-zero only in the channels the box ignores
+        masks[7, 5:30, 8:50, 1:] = 255
+        masks[8, :, :, C - 1] = 1
+        masks[9, 20, 30, 0] = 1
+        masks[9, 0, 0, 1] = 255
+    for b in range(10, B):
+        masks[b, rng.random((H, W)) < rng.choice([0.001, 0.01, 0.2]), 0] = rng.integers(1, 256)
+        if C > 1:
+            masks[b, rng.random((H, W)) < 0.3, 1] = 255
+    got = ops.mask_bbox(torch.from_numpy(masks).to(cuda0)).cpu().numpy()
+    want = np.array([pp.bounding_rect(masks[b, :, :, 0]) for b in range(B)])
+    assert tuple(want[3]) == (W - 1, H - 1, 1, 1) and tuple(want[5]) == (0, 0, W, H) and tuple(want[6]) == (0, 0, 0, 0)
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("H,W", [(45, 1), (1, 61), (7, 9), (1, 1)])
+def test_mask_bbox_thin_and_tiny_frames(cuda0, H, W):
+    """One-pixel-wide and one-pixel-high frames (`y = i / W, x = i - y * W` with W = 1, H = 1) and frames smaller than
+    one workgroup (7 x 9 = 63 pixels: three of the four waves see nothing and reduce their W / H / -1 start values)."""
+    from imagesequenceregistrationfor6dposeestimationlabeling_amd import ops
+    from oracle import preprocess_oracle as pp
+    rng = np.random.default_rng(H * 100 + W)
+    B, C = 6, 3
+    masks = np.zeros((B, H, W, C), np.uint8)
+    masks[0, 0, 0, 0] = 1
+    masks[1, H - 1, W - 1, 0] = 1
+    masks[2, H // 2, W // 2, 0] = 200
+    masks[3, :, :, 0] = 255
+    masks[4, :, :, 1] = 255                             # empty in channel 0
+    masks[5, rng.random((H, W)) < 0.3, 0] = 1
+    got = ops.mask_bbox(torch.from_numpy(masks).to(cuda0)).cpu().numpy()
+    want = np.array([pp.bounding_rect(masks[b, :, :, 0]) for b in range(B)])
+    assert tuple(want[3]) == (0, 0, W, H) and tuple(want[4]) == (0, 0, 0, 0)
+    assert np.array_equal(got, want)
