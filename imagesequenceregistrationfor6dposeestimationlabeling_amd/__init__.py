@@ -19,6 +19,9 @@ def __getattr__(name):
                 "EmissionAbsorptionRaymarcherStratified", "ImplicitRendererStratified"):
         from . import rays
         return getattr(rays, name)
+    if name in ("contrastive_loss", "returnCrossEntropy", "returnCrossEntropy2", "returnCrossEntropyWithNeg"):
+        from . import losses
+        return getattr(losses, name)
     if name == "marching_cubes":
         from . import ops
         return ops.marching_cubes

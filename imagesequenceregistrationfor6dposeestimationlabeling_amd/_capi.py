@@ -222,6 +222,18 @@ RESAMPLE_SIGNATURES = {
     "isr_resample_rays_per_group": (_i, [_i, _i, _i, _i]),
 }
 
+# include/isr_contrastive.h (the contrastive key loss and its gradient), bound the same way
+_CONTRASTIVE_SHAPE = [_vp, _vp, _vp, _i64, _i64, _i64, _i, _i64, _d]      # q, k, n, B, S, M, D, Bn, scale
+CONTRASTIVE_SIGNATURES = {
+    "isr_contrastive_workspace_bytes": (_sz, [_i64, _i64, _i64, _i, _i64]),
+    "isr_contrastive_forward": (_i, [*_CONTRASTIVE_SHAPE, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "isr_contrastive_backward": (_i, [*_CONTRASTIVE_SHAPE, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "isr_contrastive_forward_host": (_i, [*_CONTRASTIVE_SHAPE, _vp, _vp, _vp, _vp, _vp]),
+    "isr_contrastive_backward_host": (_i, [*_CONTRASTIVE_SHAPE, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "isr_contrastive_geometry": (_i, [_i]),
+    "isr_contrastive_column_splits": (_i64, [_i64, _i64, _i64, _i, _i64]),
+}
+
 # include/isr_mc.h (iso-surface extraction), bound the same way
 MC_SIGNATURES = {
     "isr_mc_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -248,7 +260,8 @@ def lib() -> C.CDLL:
         raise IsrError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES, **FPS_SIGNATURES, **DENSITY_SIGNATURES,
                                **DENSITY_DIR_SIGNATURES, **RADIUS_SIGNATURES, **MC_SIGNATURES, **KNN_SIGNATURES,
-                               **RAYS_SIGNATURES, **RADIANCE_SIGNATURES, **RESAMPLE_SIGNATURES}.items():
+                               **RAYS_SIGNATURES, **RADIANCE_SIGNATURES, **RESAMPLE_SIGNATURES,
+                               **CONTRASTIVE_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -1876,3 +1876,112 @@ def resample_rays_per_group(P: int, n_samples: int, add_input_samples: bool = Tr
     if R < 1:
         check(-1, "isr_resample_rays_per_group")
     return R
+
+
+# ---- the contrastive key loss and its gradient (include/isr_contrastive.h)
+
+def _contrastive_shape(name: str, q, k, n):
+    """-> (B, S, M, D, Bn) of q (B, S, D), k (B, S, D), n (Bn, M, D); the library checks the limits."""
+    if q.ndim != 3 or tuple(k.shape) != tuple(q.shape) or n.ndim != 3 or n.shape[2] != q.shape[2]:
+        raise ValueError(f"{name}: q (B, S, D), k (B, S, D), n (Bn, M, D) expected, got {tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(n.shape)}")
+    return q.shape[0], q.shape[1], n.shape[1], q.shape[2], n.shape[0]
+
+
+def _contrastive_device(name: str, *tensors):
+    dev = require_cuda(*tensors)
+    for t in tensors:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"{name}: contiguous float32 tensors only")
+    return dev
+
+
+def _contrastive_workspace(dev, shape) -> torch.Tensor:
+    nbytes = lib().isr_contrastive_workspace_bytes(*shape)
+    if nbytes == 0:
+        check(-1, "isr_contrastive_workspace_bytes")
+    return workspace(dev, nbytes, "contrastive")
+
+
+def contrastive_forward(q: torch.Tensor, k: torch.Tensor, n: torch.Tensor, scale: float = 1e-3):
+    """isr_contrastive_forward: q (B, S, D), k (B, S, D), n (Bn, M, D) contiguous f32 on the device, Bn in {1, B} ->
+    (m, t, pos, rows) of shape (B, S) and loss (0-d): the cross-entropy of every query against its positive and its negative
+    keys as include/isr_contrastive.h states it, scaled.  No (S, M) array is made; nothing synchronises."""
+    dev = _contrastive_device("contrastive_forward", q, k, n)
+    shape = _contrastive_shape("contrastive_forward", q, k, n)
+    B, S, M, D, Bn = shape
+    ws = _contrastive_workspace(dev, shape)
+    m, t, pos, rows = (torch.empty((B, S), dtype=torch.float32, device=dev) for _ in range(4))
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timed("contrastive_forward", 2.0 * B * S * M * D * 2):
+        rc = lib().isr_contrastive_forward(ptr(q), ptr(k), ptr(n), B, S, M, D, Bn, float(scale), ptr(m), ptr(t), ptr(pos), ptr(rows),
+                                           ptr(loss), ptr(ws), ws.numel(), current_stream(dev))
+    check(rc, "isr_contrastive_forward")
+    return m, t, pos, rows, loss
+
+
+def contrastive_backward(q: torch.Tensor, k: torch.Tensor, n: torch.Tensor, m: torch.Tensor, t: torch.Tensor,
+                         g: torch.Tensor | None = None, scale: float = 1e-3, need=(True, True, True)):
+    """isr_contrastive_backward: the gradients (dq, dk, dn) of contrastive_forward's loss from its saved m and t; g: the
+    upstream gradient as a device tensor of one f32 (read on the device; None for 1); need: which of the three to compute
+    (the others are None).  Nothing synchronises."""
+    dev = _contrastive_device("contrastive_backward", q, k, n, m, t, g)
+    shape = _contrastive_shape("contrastive_backward", q, k, n)
+    B, S, M, D, Bn = shape
+    if m.numel() != B * S or t.numel() != B * S or (g is not None and g.numel() != 1):
+        raise ValueError("contrastive_backward: m and t must hold B S values, g one")
+    ws = _contrastive_workspace(dev, shape)
+    dq = torch.empty_like(q) if need[0] else None
+    dk = torch.empty_like(k) if need[1] else None
+    dn = torch.empty_like(n) if need[2] else None
+    with torch.cuda.device(dev), _timed("contrastive_backward", 2.0 * B * S * M * D * 4):
+        rc = lib().isr_contrastive_backward(ptr(q), ptr(k), ptr(n), B, S, M, D, Bn, float(scale), ptr(m), ptr(t), ptr(g), ptr(dq),
+                                            ptr(dk), ptr(dn), ptr(ws), ws.numel(), current_stream(dev))
+    check(rc, "isr_contrastive_backward")
+    return dq, dk, dn
+
+
+def _contrastive_host(name: str, *arrays):
+    for a in arrays:
+        if a is not None and getattr(a, "dtype", None) != np.float32:
+            raise ValueError(f"{name}: float32 NumPy arrays only")
+    return tuple(None if a is None else np.ascontiguousarray(a) for a in arrays)
+
+
+def contrastive_forward_host(q, k, n, scale: float = 1e-3):
+    """isr_contrastive_forward_host: contrastive_forward as host code over NumPy arrays.  For tests."""
+    q, k, n = _contrastive_host("contrastive_forward_host", q, k, n)
+    B, S, M, D, Bn = _contrastive_shape("contrastive_forward_host", q, k, n)
+    m, t, pos, rows = (np.empty((B, S), np.float32) for _ in range(4))
+    loss = np.empty((), np.float32)
+    check(lib().isr_contrastive_forward_host(_hp(q), _hp(k), _hp(n), B, S, M, D, Bn, float(scale), _hp(m), _hp(t), _hp(pos), _hp(rows),
+                                             _hp(loss)), "isr_contrastive_forward_host")
+    return m, t, pos, rows, loss
+
+
+def contrastive_backward_host(q, k, n, m, t, g=None, scale: float = 1e-3, need=(True, True, True)):
+    """isr_contrastive_backward_host: contrastive_backward as host code over NumPy arrays.  For tests."""
+    q, k, n, m, t = _contrastive_host("contrastive_backward_host", q, k, n, m, t)
+    B, S, M, D, Bn = _contrastive_shape("contrastive_backward_host", q, k, n)
+    if m.size != B * S or t.size != B * S:
+        raise ValueError("contrastive_backward_host: m and t must hold B S values")
+    gp = None if g is None else np.array([g], np.float32)
+    dq = np.empty_like(q) if need[0] else None
+    dk = np.empty_like(k) if need[1] else None
+    dn = np.empty_like(n) if need[2] else None
+    check(lib().isr_contrastive_backward_host(_hp(q), _hp(k), _hp(n), B, S, M, D, Bn, float(scale), _hp(m), _hp(t), _hp(gp), _hp(dq),
+                                              _hp(dk), _hp(dn)), "isr_contrastive_backward_host")
+    return dq, dk, dn
+
+
+def contrastive_geometry() -> dict:
+    """isr_contrastive_geometry: the widths of the contrastive kernels (tests and tools)."""
+    return {name: lib().isr_contrastive_geometry(i) for i, name in enumerate(("group", "tile", "range_rows", "reduce"))}
+
+
+def contrastive_column_splits(B: int, S: int, M: int, D: int, Bn: int) -> int:
+    """isr_contrastive_column_splits: the 1024-row ranges the dn pass is split into for this shape (1: not split)."""
+    r = lib().isr_contrastive_column_splits(int(B), int(S), int(M), int(D), int(Bn))
+    if r < 1:
+        check(-1, "isr_contrastive_column_splits")
+    return r

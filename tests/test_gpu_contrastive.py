@@ -1,0 +1,277 @@
+"""GPU: the contrastive loss kernels against the host build of the same header (which tests/test_contrastive_cpu.py holds to
+the NumPy restatement of include/isr_contrastive.h), bit for bit, for m, t, pos, rows, loss, dq, dk and dn: S and M one below,
+at and above the workgroup and tile width (64), the 1024-row range and the 256-leaf tree; every D path (padded and exact);
+shared negatives with and without the split column pass; then the contracts (a row alone, a NaN row, poisoned outputs, a
+reused workspace, a caller's stream, gradients left out), autograd against the reference formula in torch on the same device
+and against the reference's own recorded results, and the peak memory, which must not grow with M beyond n and dn."""
+import numpy as np
+import pytest
+import torch
+
+from imagesequenceregistrationfor6dposeestimationlabeling_amd import losses, ops
+from tests import contrastive_ref as cr
+from tests import poison
+from tests.contrastive_ref import ROOT, f32, f64, same
+
+pytestmark = pytest.mark.gpu
+NAMES = ("m", "t", "pos", "rows", "loss", "dq", "dk", "dn")
+
+
+def _t(a, dev):
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _device(dev, q, k, n, scale=1e-3, g=None, need=(True, True, True)):
+    tq, tk, tn = _t(q, dev), _t(k, dev), _t(n, dev)
+    fwd = ops.contrastive_forward(tq, tk, tn, scale)
+    tg = None if g is None else torch.tensor(g, dtype=torch.float32, device=dev)
+    bwd = ops.contrastive_backward(tq, tk, tn, fwd[0], fwd[1], tg, scale, need)
+    return [None if x is None else x.cpu().numpy() for x in (*fwd, *bwd)]
+
+
+def _host(q, k, n, scale=1e-3, g=None, need=(True, True, True)):
+    fwd = ops.contrastive_forward_host(q, k, n, scale)
+    return [*fwd, *ops.contrastive_backward_host(q, k, n, fwd[0], fwd[1], g, scale, need)]
+
+
+def _check(dev, B, S, M, D, Bn, sigma=1.0, g=None):
+    rng = np.random.default_rng(B * 7919 + S * 31 + M * 7 + D + Bn)
+    q, k, n = cr.inputs(rng, B, S, M, D, Bn, sigma)
+    got, want = _device(dev, q, k, n, g=g), _host(q, k, n, g=g)
+    for name, a, b in zip(NAMES, got, want):
+        assert same(a, b), (name, B, S, M, D, Bn)
+
+
+@pytest.mark.parametrize("M", [1, 63, 64, 65, 257, 4097])
+def test_device_equals_host_over_M(cuda0, M):
+    geo = ops.contrastive_geometry()
+    assert geo == {"group": 64, "tile": 64, "range_rows": 1024, "reduce": 256}           # the widths the sizes here straddle
+    for S in (1, 63, 64, 65) if M < 4097 else (1, 65):
+        _check(cuda0, 2, S, M, 12, 2)
+    _check(cuda0, 1, 65, M, 13, 1)
+
+
+@pytest.mark.parametrize("S", [1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 1030])
+def test_device_equals_host_over_S(cuda0, S):
+    _check(cuda0, 1, S, 65, 12, 1)
+    _check(cuda0, 2, S, 63, 12, 2, g=-2.5)
+
+
+@pytest.mark.parametrize("D", [1, 2, 4, 5, 12, 13, 16, 17, 32, 33, 64])
+def test_device_equals_host_over_D(cuda0, D):
+    _check(cuda0, 2, 65, 130, D, 2, sigma=3.0 / np.sqrt(D))
+    _check(cuda0, 2, 65, 66, D, 1, sigma=3.0 / np.sqrt(D))
+
+
+@pytest.mark.parametrize("B", [1, 2, 3])
+def test_device_equals_host_over_B(cuda0, B):
+    _check(cuda0, B, 130, 257, 12, B)
+    _check(cuda0, B, 130, 257, 12, 1)
+
+
+def test_shared_negatives_split_and_unsplit(cuda0):
+    assert ops.contrastive_column_splits(3, 1030, 65, 12, 1) == 4                         # the split column pass, a partial last range
+    _check(cuda0, 3, 1030, 65, 12, 1)
+    assert ops.contrastive_column_splits(3, 342, 65, 12, 1) == 2                          # 1026 rows: a range of two rows
+    _check(cuda0, 3, 342, 65, 12, 1)
+    assert ops.contrastive_column_splits(3, 341, 65, 12, 1) == 1                          # 1023 rows: not split
+    _check(cuda0, 3, 341, 65, 12, 1)
+    assert ops.contrastive_column_splits(3, 1030, 65, 12, 3) == 1                         # the same rows, a middle accumulator per item
+    _check(cuda0, 3, 1030, 65, 12, 3)
+    assert ops.contrastive_column_splits(2, 1030, 64 * 512, 1, 1) == 1                    # enough columns: unsplit over three ranges
+    _check(cuda0, 2, 1030, 64 * 512, 1, 1)
+
+
+def test_large_logits(cuda0):
+    for sigma in (0.3, 3.0, 5.0):                                                         # logits to about +-90 at sigma 3, beyond at 5
+        _check(cuda0, 2, 65, 130, 12, 2, sigma=sigma)
+
+
+def test_a_row_alone_against_the_row_among_4097(cuda0):
+    rng = np.random.default_rng(3)
+    q, k, n = cr.inputs(rng, 1, 4097, 70, 12, 1)
+    full = _device(cuda0, q, k, n, g=4097.0, need=(True, True, False))
+    for s in (0, 64, 2049, 4096):
+        one = _device(cuda0, q[:, s:s + 1], k[:, s:s + 1], n, g=1.0, need=(True, True, False))
+        for i in (0, 1, 2, 3):
+            assert same(one[i][0, 0], full[i][0, s])
+        assert same(one[5][0, 0], full[5][0, s]) and same(one[6][0, 0], full[6][0, s])
+
+
+def test_a_nan_row_between_clean_rows(cuda0):
+    rng = np.random.default_rng(4)
+    q, k, n = cr.inputs(rng, 2, 70, 66, 12, 2)
+    clean = _device(cuda0, q, k, n)
+    q[1, 64, 5] = np.nan
+    got, want = _device(cuda0, q, k, n), _host(q, k, n)
+    for name, a, b in zip(NAMES, got, want):
+        assert same(a, b), name
+    nan = np.array([0x7FC00000], np.uint32)
+    keep = np.ones((2, 70), bool)
+    keep[1, 64] = False
+    for i in (0, 1, 2, 3, 5, 6):
+        assert (got[i][1, 64].view(np.uint32) == nan).all() and same(got[i][keep], clean[i][keep])
+    assert got[4].view(np.uint32) == nan and (got[7][1].view(np.uint32) == nan).all() and same(got[7][0], clean[7][0])
+
+
+def test_every_byte_of_every_output_is_written(cuda0, monkeypatch):
+    rng = np.random.default_rng(5)
+    for B, S, M, D, Bn in ((2, 65, 130, 12, 2), (3, 1030, 65, 13, 1), (1, 1, 1, 1, 1)):
+        q, k, n = cr.inputs(rng, B, S, M, D, Bn)
+        def call():
+            x = [_t(q, cuda0), _t(k, cuda0), _t(n, cuda0)]
+            fwd = ops.contrastive_forward(*x)
+            return ops.contrastive_backward(*x, fwd[0], fwd[1]) + fwd
+
+        a, b = poison.run_twice(monkeypatch, call)
+        assert poison.same_bits(a, b)
+        want = _host(q, k, n)
+        for got, w in zip((*a[3:], *a[:3]), want):
+            assert same(got.numpy(), w)
+
+
+def test_second_call_a_reused_workspace_and_a_callers_stream(cuda0):
+    rng = np.random.default_rng(6)
+    q, k, n = cr.inputs(rng, 3, 1030, 65, 12, 1)                                          # forward and the split pass share the workspace
+    want = _host(q, k, n)
+    ops.clear_workspaces()
+    for _ in range(2):
+        for name, a, b in zip(NAMES, _device(cuda0, q, k, n), want):
+            assert same(a, b), name
+    side = torch.cuda.Stream(cuda0)
+    side.wait_stream(torch.cuda.current_stream(cuda0))
+    with torch.cuda.stream(side):
+        got = _device(cuda0, q, k, n)
+    side.synchronize()
+    for name, a, b in zip(NAMES, got, want):
+        assert same(a, b), name
+
+
+def test_each_gradient_left_out_in_turn(cuda0):
+    rng = np.random.default_rng(7)
+    q, k, n = cr.inputs(rng, 2, 65, 130, 12, 2)
+    full = _device(cuda0, q, k, n)
+    for skip in range(3):
+        need = tuple(i != skip for i in range(3))
+        got = _device(cuda0, q, k, n, need=need)
+        for i in range(3):
+            assert (got[5 + i] is None) if i == skip else same(got[5 + i], full[5 + i])
+    assert _device(cuda0, q, k, n, need=(False, False, False))[5:] == [None, None, None]
+
+
+# ---- autograd
+
+@pytest.fixture(scope="module")
+def golden():
+    return np.load(ROOT / "tests" / "golden" / "ref_contrastive.npz")
+
+
+def _bound_check(tag, golden, loss, grads):
+    l64, e = float(golden[f"{tag}_loss_f64"]), float(golden[f"{tag}_loss_eref"])
+    dev = abs(float(loss) - l64)
+    print(f"{tag}: loss deviation {dev:.3e}, reference f32 {e:.3e}, ulp {cr.ulp32(l64):.3e}")
+    assert dev <= max(cr.PARITY_MARGIN * e, cr.ulp32(l64))
+    for name, got in grads.items():
+        want, e = golden[f"{tag}_d{name}_f64"], float(golden[f"{tag}_d{name}_eref"])
+        dev = np.abs(got.detach().cpu().numpy().astype(f64) - want).max()
+        print(f"{tag}: d{name} deviation {dev:.3e}, reference f32 {e:.3e}, ratio {dev / e:.2f}")
+        assert got.dtype == torch.float32 and tuple(got.shape) == want.shape and dev <= cr.PARITY_MARGIN * e
+
+
+def _leaves(golden, tag, names, dev):
+    return [_t(golden[f"{tag}_{x}"], dev).requires_grad_(True) for x in names]
+
+
+@pytest.mark.parametrize("tag", ["a03", "a1", "a3", "b1", "c1", "d32"])
+def test_with_neg_against_the_fixture_and_torch_on_the_device(cuda0, golden, tag):
+    q, k, n = _leaves(golden, tag, "qkn", cuda0)
+    loss = losses.returnCrossEntropyWithNeg(q, k, n)
+    loss.backward()
+    _bound_check(tag, golden, loss, {"q": q.grad, "k": k.grad, "n": n.grad})
+    # the reference formula under autograd on the same device, f64: the same bound, the tolerance from its own f32 run
+    q64, k64, n64 = (x.detach().double().requires_grad_(True) for x in (q, k, n))
+    cr.torch_loss(q64, k64, n64).backward()
+    q32, k32, n32 = (x.detach().clone().requires_grad_(True) for x in (q, k, n))
+    cr.torch_loss(q32, k32, n32).backward()
+    for name, ours, r32, r64 in (("q", q, q32, q64), ("k", k, k32, k64), ("n", n, n32, n64)):
+        e = (r32.grad.double() - r64.grad).abs().max().item()
+        dev = (ours.grad.double() - r64.grad).abs().max().item()
+        print(f"{tag}: d{name} against torch on the device: deviation {dev:.3e}, torch f32 {e:.3e}")
+        assert e > 0 and dev <= cr.PARITY_MARGIN * e
+
+
+def test_own_keys_wrappers_against_the_fixture(cuda0, golden):
+    for tag in ("e05", "e1"):
+        q, k = _leaves(golden, tag, "qk", cuda0)
+        torch.manual_seed(int(golden["seed"][0]))
+        loss = losses.returnCrossEntropy(q, k, negFrac=float(golden[f"{tag}_negFrac"][0]))
+        loss.backward()
+        _bound_check(tag, golden, loss, {"q": q.grad, "k": k.grad})
+    q, k = _leaves(golden, "f2", "qk", cuda0)
+    loss = losses.returnCrossEntropy2(q, k, negKeys=_t(golden["f2_negKeys"], cuda0))
+    loss.backward()
+    _bound_check("f2", golden, loss, {"q": q.grad, "k": k.grad})
+
+
+def test_randperm_is_drawn_as_the_reference_draws_it(cuda0, golden):
+    q, k, n = (x.detach() for x in _leaves(golden, "a1", "qkn", cuda0))
+    torch.manual_seed(1)
+    losses.returnCrossEntropyWithNeg(q, k, n)
+    after = torch.randperm(5)
+    torch.manual_seed(1)
+    torch.randperm(k.shape[1], dtype=torch.int64)
+    assert torch.equal(after, torch.randperm(5))
+
+
+def test_upstream_gradient_and_one_input_only(cuda0, golden):
+    q, k, n = _leaves(golden, "a1", "qkn", cuda0)
+    losses.contrastive_loss(q, k, n).backward()
+    base = [x.grad.clone() for x in (q, k, n)]
+    host = _host(*(golden[f"a1_{x}"] for x in "qkn"), g=3.0)
+    q3, k3, n3 = _leaves(golden, "a1", "qkn", cuda0)
+    (3 * losses.contrastive_loss(q3, k3, n3)).backward()
+    for x, w, b in zip((q3, k3, n3), host[5:], base):
+        assert same(x.grad.cpu().numpy(), w) and not torch.equal(x.grad, b)               # g = 3 read on the device, the host's bits
+    for only in range(3):
+        xs = [x.detach().clone().requires_grad_(i == only) for i, x in enumerate((q, k, n))]
+        losses.contrastive_loss(*xs).backward()
+        for i, x in enumerate(xs):
+            assert (x.grad is None) if i != only else torch.equal(x.grad, base[i])
+
+
+def test_shared_negatives_are_not_copied_and_inputs_are_converted(cuda0, golden):
+    q, k, n = _leaves(golden, "b1", "qkn", cuda0)                                          # B = 1: (1, M, D) is both forms
+    losses.returnCrossEntropyWithNeg(q, k, n).backward()
+    q2 = torch.cat([q.detach(), q.detach()]).requires_grad_(True)                         # B = 2 over the shared (1, M, D)
+    k2 = torch.cat([k.detach(), k.detach()])
+    n2 = n.detach().clone().requires_grad_(True)
+    l2 = losses.returnCrossEntropyWithNeg(q2, k2, n2)
+    l2.backward()
+    assert n2.grad.shape == n.shape
+    exp = cr.torch_loss(q2.detach().double(), k2.double(), n2.detach().double())
+    assert abs(l2.item() - exp.item()) <= 4 * cr.ulp32(exp.item())
+    # not f32, not contiguous: converted as the other wrappers do; the gradient comes back through the conversion
+    qd = q.detach().double().requires_grad_(True)
+    kt = k.detach().transpose(1, 2).contiguous().transpose(1, 2)
+    assert not kt.is_contiguous()
+    l3 = losses.contrastive_loss(qd, kt, n.detach(), 1 / 1000)
+    l3.backward()
+    assert qd.grad.dtype == torch.float64 and torch.equal(qd.grad.float(), q.grad)
+
+
+def test_peak_memory_does_not_grow_with_M(cuda0):
+    """Forward plus backward at B = 2, S = 256: after subtracting the bytes of n and dn the peaks at M = 256 and M = 4096 are
+    equal, so nothing sized S x M is allocated (the torch formula allocates several (B, 1 + M, S) arrays)."""
+    rng = np.random.default_rng(8)
+    peaks = []
+    for M in (4096, 256, 4096):                                                           # the first run warms the cached workspace
+        q, k, n = (_t(x, cuda0).requires_grad_(True) for x in cr.inputs(rng, 2, 256, M, 12, 2))
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(cuda0)
+        before = torch.cuda.memory_allocated(cuda0)
+        losses.contrastive_loss(q, k, n).backward()
+        torch.cuda.synchronize()
+        peaks.append(torch.cuda.max_memory_allocated(cuda0) - before - n.grad.numel() * 4)
+        del q, k, n
+    print("peak bytes beyond the inputs and dn:", peaks[1:])
+    assert peaks[1] == peaks[2] and peaks[1] < 2 * 256 * 4096 * 4

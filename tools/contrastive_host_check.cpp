@@ -1,0 +1,167 @@
+// contrastive_host_check.cpp — csrc/contrastive.hpp as plain host code, for a sanitizer build:
+//     c++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all \
+//         tools/contrastive_host_check.cpp -o contrastive_host_check && ./contrastive_host_check
+// Drives forward_row, backward_row, backward_column and sum_rows over the shapes of the tests, with arrays of exactly the
+// sizes the header asks for, and over the value cases: equal logits, a dominating positive, logits beyond the exponential's
+// cut, a NaN and an infinity.  Checks what can be checked without a second implementation: the softmax of a clean row sums
+// to 1 (ppos + sum_j p_ij, to 1e-5), t and row are not negative, dq + the k-term and dk follow the formulas to f32 accuracy
+// against an f64 evaluation, a NaN row is canonical NaN, sum_rows equals a plain f64 sum to 1e-12 relative, check_shape
+// refuses what the header says.  Then measures exp32 against the f64 exponential over [-104, 0]: every 997th f32 bit pattern
+// of the range, the error in units of the f32 ulp of the true value for results that are normal numbers (x >= -87), the
+// absolute error below.  Prints one line per case; exit status 0 = all hold.  The log of one such run is
+// profiles/contrastive_host_sanitizers.txt.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#define __host__
+#define __device__
+#include "../imagesequenceregistrationfor6dposeestimationlabeling_amd/csrc/contrastive.hpp"
+
+using namespace isr::contrastive;
+
+namespace {
+
+unsigned seed = 97531u;
+float rnd() {                                        // roughly N(0, 1): the sum of four uniforms, centred and scaled
+  float s = 0.f;
+  for (int i = 0; i < 4; ++i) {
+    seed = seed * 1664525u + 1013904223u;
+    s += (float)((seed >> 8) & 0xffff) / 65536.f;
+  }
+  return (s - 2.f) * 1.7320508f;
+}
+
+uint32_t bits_of(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  return u;
+}
+
+int fails = 0;
+
+enum Kind { kRandom, kEqual, kDominant, kFar, kNan, kPosInf, kNegInf, kKinds };
+const char* kNames[kKinds] = {"random", "equal logits", "a dominating positive", "logits beyond the cut", "a NaN", "a +Inf logit", "a -Inf logit"};
+
+void run(int S, int M, int D, float sigma, Kind kind) {
+  std::vector<float> q((size_t)S * D), k((size_t)S * D), n((size_t)M * D), m((size_t)S), t((size_t)S), pos((size_t)S), row((size_t)S);
+  std::vector<float> dq((size_t)S * D), dk((size_t)S * D), dn((size_t)M * D);
+  for (auto& v : q) v = rnd() * sigma;
+  for (auto& v : k) v = rnd() * sigma;
+  for (auto& v : n) v = rnd() * sigma;
+  if (kind == kEqual) {
+    for (auto& v : q) v = 0.f;
+  } else if (kind == kDominant || kind == kFar) {
+    for (auto& v : q) v = 3.f;
+    for (auto& v : k) v = kind == kDominant ? 3.f : -3.f;
+    for (auto& v : n) v = kind == kDominant ? -3.f : 3.f;
+    if (kind == kFar) n[0] = -3.f;
+  } else if (kind == kNan) {
+    q[(size_t)(S / 2) * D] = std::numeric_limits<float>::quiet_NaN();
+  } else if (kind == kPosInf || kind == kNegInf) {
+    for (int s = 0; s < S; ++s) q[(size_t)s * D] = std::fabs(q[(size_t)s * D]) + 0.1f;
+    n[(size_t)(M / 2) * D] = kind == kPosInf ? std::numeric_limits<float>::infinity() : -std::numeric_limits<float>::infinity();
+  }
+  for (int s = 0; s < S; ++s)
+    forward_row(&q[(size_t)s * D], &k[(size_t)s * D], n.data(), M, D, &m[s], &t[s], &pos[s], &row[s]);
+  std::vector<double> scratch((size_t)(S + kReduce - 1) / kReduce);
+  const double R = sum_rows(row.data(), S, scratch.data());
+  double plain = 0.0;
+  for (int s = 0; s < S; ++s) plain += (double)row[s];
+  const float c = grad_scale(-2.5f, 1e-3, S);
+  for (int s = 0; s < S; ++s)
+    backward_row(&q[(size_t)s * D], &k[(size_t)s * D], n.data(), M, D, m[s], t[s], c, &dq[(size_t)s * D], &dk[(size_t)s * D]);
+  for (int j = 0; j < M; ++j) backward_column(q.data(), m.data(), t.data(), S, &n[(size_t)j * D], D, c, &dn[(size_t)j * D]);
+  backward_row(q.data(), k.data(), n.data(), M, D, m[0], t[0], c, nullptr, dk.data());        // either gradient may be left out
+  backward_row(q.data(), k.data(), n.data(), M, D, m[0], t[0], c, dq.data(), nullptr);
+
+  bool ok = true;
+  const bool clean = kind <= kFar;
+  int nans = 0;
+  for (int s = 0; s < S; ++s) nans += bits_of(row[s]) == kNanBits;
+  if (clean) {
+    ok = ok && nans == 0 && (R == plain || std::fabs(R - plain) <= 1e-12 * std::fabs(plain));
+    for (int s = 0; s < S; ++s) {
+      ok = ok && t[s] >= 0.f && row[s] >= 0.f;
+      double total = (double)exp32((pos[s] - m[s]) - t[s]);
+      std::vector<double> acc((size_t)D, 0.0), mass((size_t)D, 0.0);
+      for (int j = 0; j < M; ++j) {
+        const double p = (double)exp32((dot(&q[(size_t)s * D], &n[(size_t)j * D], D) - m[s]) - t[s]);
+        total += p;
+        for (int d = 0; d < D; ++d) acc[d] += p * (double)n[(size_t)j * D + d], mass[d] += p * std::fabs((double)n[(size_t)j * D + d]);
+      }
+      ok = ok && std::fabs(total - 1.0) <= 1e-5;
+      const double a = (double)exp32((pos[s] - m[s]) - t[s]) - 1.0;
+      for (int d = 0; d < D; ++d) {
+        const double want = (double)c * (a * (double)k[(size_t)s * D + d] + acc[d]);
+        double mag = std::fabs((double)c) * (std::fabs(a * (double)k[(size_t)s * D + d]) + mass[d]) + 1e-30;
+        ok = ok && std::fabs((double)dq[(size_t)s * D + d] - want) <= 2e-5 * mag + 1e-12 * std::fabs((double)c);
+      }
+    }
+    if (kind == kEqual) ok = ok && std::fabs((double)row[0] - std::log(1.0 + M)) <= 1e-6 * std::log(1.0 + M);
+    if (kind == kDominant) ok = ok && row[0] == 0.f && t[0] == 0.f;
+  }
+  if (kind == kNan) {
+    ok = ok && nans == 1 && bits_of(row[S / 2]) == kNanBits && bits_of(m[S / 2]) == kNanBits && bits_of(dq[(size_t)(S / 2) * D]) == kNanBits;
+    for (int j = 0; j < M; ++j) ok = ok && bits_of(dn[(size_t)j * D]) == kNanBits;
+    ok = ok && bits_of(loss_value(R, 1e-3, S)) == kNanBits;
+  }
+  if (kind == kPosInf) ok = ok && nans == S;
+  if (kind == kNegInf) ok = ok && nans == 0;
+  std::printf("S %-5d M %-5d D %-3d sigma %-4g %-24s NaN rows %-5d loss %-14.8g %s\n", S, M, D, (double)sigma, kNames[kind], nans,
+              (double)loss_value(R, 1e-3, S), ok ? "ok" : "FAILED");
+  fails += !ok;
+}
+
+void measure_exp() {
+  double worst = 0.0, worst_at = 0.0, worst_abs = 0.0;
+  long count = 0, below = 0;
+  const uint32_t last = bits_of(104.0f);
+  for (uint32_t u = 0; u <= last; u += 997u) {
+    float x;
+    const uint32_t neg = u | 0x80000000u;
+    std::memcpy(&x, &neg, 4);
+    const double want = std::exp((double)x);
+    const double got = (double)exp32(x);
+    if (x >= -87.0f) {
+      int e;
+      std::frexp(want, &e);
+      const double ulp = std::ldexp(1.0, e - 24);
+      const double err = std::fabs(got - want) / ulp;
+      if (err > worst) worst = err, worst_at = x;
+      ++count;
+    } else {
+      if (std::fabs(got - want) > worst_abs) worst_abs = std::fabs(got - want);
+      ++below;
+    }
+  }
+  const bool ok = worst < 1.0 && exp32(0.f) == 1.f && exp32(-0.f) == 1.f && worst_abs < 1.7e-38 &&
+                  exp32(-std::numeric_limits<float>::infinity()) == 0.f &&
+                  bits_of(exp32(std::numeric_limits<float>::quiet_NaN())) == kNanBits;
+  std::printf("exp32 over [-87, 0]: %ld arguments, largest error %.4f f32 ulp of the f64 exponential (at x = %.9g)\n", count, worst, worst_at);
+  std::printf("exp32 over [-104, -87): %ld arguments, result 0 by the rule, largest absolute error %.3e   %s\n", below, worst_abs,
+              ok ? "ok" : "FAILED");
+  fails += !ok;
+}
+
+}  // namespace
+
+int main() {
+  const bool refusals = check_shape(1, 1, 1, 0, 1) && check_shape(1, 1, 1, 65, 1) && check_shape(0, 1, 1, 4, 1) && check_shape(1, 0, 1, 4, 1) &&
+                        check_shape(1, 1, 0, 4, 1) && check_shape(1, 1, (1 << 24) + 1, 4, 1) && check_shape(1 << 14, (1 << 14) + 1, 1, 4, 1) &&
+                        check_shape(3, 1, 1, 4, 2) && !check_shape(3, 1, 1, 4, 3) && !check_shape(3, 1, 1, 4, 1) &&
+                        !check_shape(1 << 14, 1 << 14, 1 << 24, 64, 1);
+  std::printf("check_shape refuses what the header says                 %s\n", refusals ? "ok" : "FAILED");
+  fails += !refusals;
+  const int shapes[][3] = {{1, 1, 1}, {65, 130, 12}, {64, 63, 13}, {130, 4097, 12}, {257, 64, 64}, {1030, 64, 12}, {2049, 65, 4}};
+  for (auto& sh : shapes)
+    for (float sigma : {0.3f, 1.f, 3.f}) run(sh[0], sh[1], sh[2], sigma / (sh[2] > 12 ? std::sqrt((float)sh[2] / 12.f) : 1.f), kRandom);
+  for (int kind = kEqual; kind < kKinds; ++kind)
+    for (auto& sh : {shapes[1], shapes[2], shapes[5]}) run(sh[0], sh[1], sh[2], 1.f, (Kind)kind);
+  measure_exp();
+  std::printf("%s\n", fails ? "FAILED" : "all hold");
+  return fails ? 1 : 0;
+}
