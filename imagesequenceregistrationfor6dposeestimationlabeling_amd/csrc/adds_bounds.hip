@@ -12,10 +12,17 @@
 // isr_nn_batched, everything else is decided here — the same booleans as evaluating every item (tests compare the error
 // matrices), at ~40 VALU operations and one 4-byte gather per vertex instead of a nearest-neighbour search.
 //
-// Tt need not be exactly orthonormal (the reference loads f32-born poses from pred_R.npy): with A its 3 x 3 part and
-// eta >= ||A^T A - I||_2,  | |A^T w - s| - |w - A s| | <= eta (|s| + |w - A s|)  for every surface point s, so each vertex's
-// bracket is widened by eta (max|s| + its upper bound) — 1e-5 mm at eta = 1e-7 and object scale, nothing for f64 rotations;
-// a Tt that is far from rigid only makes the brackets useless (everything is searched), never wrong.
+// Tt need not be exactly orthonormal (the reference loads f32-born poses from pred_R.npy).  With A its 3 x 3 part,
+// eta >= ||A^T A - I||_2 < 1, w a query in Tt's frame less its translation and k(s) = |A^T w - s| what the field measures
+// where the truth is d(s) = |w - A s|:  A^T w - s = A^T (w - A s) + (A^T A - I) s, and the singular values of A lie in
+// [sqrt(1 - eta), sqrt(1 + eta)], so
+//     (1 - eta) d(s) - eta |s|  <=  k(s)  <=  (1 + eta) d(s) + eta |s|      for every surface point s.
+// At the minimisers this gives  min d >= min k - eta (max|s| + min k)  and  min d <= min k + eta (max|s| + min k) / (1 - eta):
+// the lower side is widened by eta (max|s| + upper bound), the upper side needs the factor 1 / (1 - eta) on top.  The kernel
+// multiplies both by 1.01, which covers 1 / (1 - eta) only while eta <= 0.0099; it is used up to kEtaMax = 0.009
+// (1 / (1 - 0.009) = 1.00909 < 1.01, and three orders of magnitude above anything a rounded rotation produces: 1e-5 mm of
+// widening at eta = 1e-7 and object scale, nothing for f64 rotations).  Beyond kEtaMax — a scaled, sheared, collapsed or
+// non-finite Tt — no bracket is claimed: lb_sum = 0, ub_sum = +inf, which decides nothing, so the caller searches the item.
 //
 // The field is built once per surface cloud by the caller (cell centres through isr_nn_batched: exact distances).
 #include "isr_common.hpp"
@@ -23,6 +30,7 @@
 namespace {
 
 constexpr int kBThreads = 256;
+constexpr double kEtaMax = 0.009;      // the largest eta the 1.01 of the widening is valid for is 0.0099 (header)
 
 __global__ __launch_bounds__(kBThreads) void adds_bounds_kernel(const float* __restrict__ verts, int V, const double* __restrict__ Tq,
                                                                 const double* __restrict__ Tt, const float* __restrict__ field,
@@ -85,8 +93,9 @@ __global__ __launch_bounds__(kBThreads) void adds_bounds_kernel(const float* __r
     const double sx = fmax(fabs((double)b0), fabs((double)b3)), sy = fmax(fabs((double)b1), fabs((double)b4)),
                  sz = fmax(fabs((double)b2), fabs((double)b5));
     const double widen = eta_s * ((double)V * sqrt(sx * sx + sy * sy + sz * sz) + u) * 1.01;
-    lb_sum[b] = l - widen;
-    ub_sum[b] = u + widen;
+    const bool claimed = eta_s <= kEtaMax;      // false for a NaN as well
+    lb_sum[b] = claimed ? l - widen : 0.0;
+    ub_sum[b] = claimed ? u + widen : (double)INFINITY;
   }
 }
 

@@ -230,7 +230,8 @@ def dist_field(cloud: torch.Tensor, cells: int = 128, margin: float | None = Non
 
 def adds_bounds(verts: torch.Tensor, Tq: torch.Tensor, Tt: torch.Tensor | None, fld: DistField):
     """isr_adds_bounds: per batch item b bounds of sum_v dist(Tt[b]^-1 Tq[b] v, cloud) — isr_nn_batched's sum_d for queries
-    `verts` against the field's cloud — as (lb_sum, ub_sum) f64 device tensors (wider, still finite, for vertices off the grid)."""
+    `verts` against the field's cloud — as (lb_sum, ub_sum) f64 device tensors: wider, still finite, for vertices off the grid;
+    (0, +inf) — a bracket that decides nothing — for an item whose Tt is not rigid to within eta = 3 max|R^T R - I| <= 0.009."""
     import ctypes
     dev = require_cuda(verts, Tq, Tt, fld.field)
     v, Tq, Tt = _f32c(verts), _f64c(Tq), _f64c(Tt)

@@ -387,10 +387,13 @@ int isr_nn_batched(const float* qry, int Nq, const float* tgt, int Nt, const dou
  * grid (origin grid_min, edge h; the caller builds it once per cloud, e.g. through isr_nn_batched on the centres) — dist(., S)
  * is 1-Lipschitz, so a vertex x lies within |x - centre(c)| of field[c] for the cell c that holds it (or, outside the grid, the
  * nearest cell of the grid; its distance to surface_bbox (lo xyz, hi xyz) is then a second lower bound): both sums are
- * finite for every pose.  verts (V,3) f32, Tq / Tt (B,12) f64
+ * finite for every pose with a (nearly) rigid Tt.  verts (V,3) f32, Tq / Tt (B,12) f64
  * [R|t] (Tt nullable = identity), field on the device.  Tt is inverted as a rigid motion (R^T, -R^T t); where it is only
  * nearly one (f32-born rotations, ||R^T R - I|| = eta ~ 1e-7) every vertex's bracket is widened by eta (max|s| + its upper
- * bound), so the sums stay rigorous bounds of isr_nn_batched's sum_d for the matrix AS GIVEN; grid_min (3 doubles) and surface_bbox (6 floats) on the HOST.
+ * bound) x 1.01, so the sums stay rigorous bounds of isr_nn_batched's sum_d for the matrix AS GIVEN while eta <= 0.009 (eta =
+ * 3 max|R^T R - I|_ij; the widening is valid up to 0.0099).  A Tt beyond that (scaled, sheared, singular, non-finite) gets no
+ * bracket at all: lb_sum = 0, ub_sum = +inf, which no threshold test can decide.  grid_min (3 doubles) and surface_bbox
+ * (6 floats) on the HOST.
  * lb_sum, ub_sum (B) f64 on the device.  An item whose bounds straddle the threshold is evaluated exactly by the caller. */
 int isr_adds_bounds(const float* verts, int V, const double* Tq, const double* Tt, int B, const float* field,
                     const double* grid_min, double h, int nx, int ny, int nz, const float* surface_bbox,

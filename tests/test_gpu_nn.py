@@ -79,6 +79,70 @@ def test_nn_large_batch_vote_shape(cuda0, oracle_lib):
     np.testing.assert_allclose(g["sum_d"][sel], o["sum_d"], rtol=1e-12)
 
 
+def _al(n):
+    return (n + 255) // 256 * 256          # the workspace's carve-outs are 256-byte aligned
+
+
+def _run_chunked(cuda0, q, t, Tq, Tt, sel):
+    """sum_d, nn_idx and nn_d of the whole batch; the items `sel` brought to the host."""
+    from imagesequenceregistrationfor6dposeestimationlabeling_amd import ops
+    r = ops.nn_batched(torch.from_numpy(q).to(cuda0), torch.from_numpy(t).to(cuda0), torch.from_numpy(Tq).to(cuda0),
+                       torch.from_numpy(Tt).to(cuda0), want_idx=True, want_dist=True)
+    torch.cuda.synchronize()
+    return r, {k: getattr(r, k)[sel].cpu().numpy() for k in ("sum_d", "nn_idx", "nn_d")}
+
+
+def _compare_sample(g, o):
+    assert np.array_equal(g["nn_idx"], o["nn_idx"])
+    assert np.array_equal(g["nn_d"], o["nn_d"])
+    np.testing.assert_allclose(g["sum_d"], o["sum_d"], rtol=1e-12)
+
+
+def test_nn_batch_chunks_at_the_grid_dimension_cap(cuda0, oracle_lib, hip_lib):
+    """More batch items than a grid dimension holds: Nq = Nt = 64, B = 65 600.  make_plan: one query block, no target split,
+    per_b = nsplit * Nq * 8 = 512 bytes, kPartBudget / per_b = (192 << 20) / 512 = 393 216 > B, then the cap: bchunk =
+    65 535 — the b0 loop runs twice, 65 535 + 65 items, and nn_finalize_kernel writes the second chunk at its b0 offset."""
+    Nq, Nt, B, bchunk = 64, 64, 65600, 65535
+    assert hip_lib.isr_nn_batched_workspace_bytes(Nq, Nt, B) == 2 * _al(bchunk * 1 * Nq * 4) + _al(B * 1 * 18 * 8) + 256
+    rng = np.random.default_rng(65)
+    q = rng.normal(0, 40, (Nq, 3)).astype(np.float32)
+    t = rng.normal(0, 40, (Nt, 3)).astype(np.float32)
+    Tq, Tt = _poses(rng, B), _poses(rng, B)
+    sel = [0, 1, bchunk - 1, bchunk, B - 1]
+    _, g = _run_chunked(cuda0, q, t, Tq, Tt, sel)
+    _compare_sample(g, oracle_lib.nn_batched(q, t, Tq[sel], Tt[sel], -1.0))
+
+
+@pytest.mark.parametrize("Nt", [64, 4096])
+def test_nn_batch_chunks_at_the_partial_budget(cuda0, oracle_lib, hip_lib, Nt):
+    """More per-query partials than kPartBudget holds: Nq = 1 024, B = 24 600.  make_plan: rq = 4, one query block, nsplit = 1
+    (brute force with B query blocks >= the 4 096 wanted; the block-cooperative grid at Nt = 4 096, which never splits),
+    per_b = 1 * 1 024 * 8 = 8 192 bytes, bchunk = (192 << 20) / 8 192 = 24 576 < B — two chunks, 24 576 + 24 items.
+    Nt = 64 is brute force; at Nt = 4 096 the default is the block-cooperative grid, compared with brute force bit for bit."""
+    from imagesequenceregistrationfor6dposeestimationlabeling_amd import ops
+    Nq, B, bchunk, fblocks = 1024, 24600, 24576, 4
+    ws = hip_lib.isr_nn_batched_workspace_bytes(Nq, Nt, B)
+    parts = lambda bc, b: 2 * _al(bc * 1 * Nq * 4) + _al(b * fblocks * 18 * 8)
+    if Nt == 64:
+        assert ws == parts(bchunk, B) + 256
+    else:       # plus the search grid's own space, which depends on (Nq, Nt) only: compare with a batch of one chunk
+        assert ws - hip_lib.isr_nn_batched_workspace_bytes(Nq, Nt, 128) == parts(bchunk, B) - parts(128, 128)
+    rng = np.random.default_rng(24 + Nt)
+    q = rng.normal(0, 40, (Nq, 3)).astype(np.float32)
+    t = rng.normal(0, 40, (Nt, 3)).astype(np.float32)
+    Tq = _poses(rng, B)
+    Tt = Tq.copy()                        # the pick's shape: pairs of nearby poses
+    Tt[:, :, 3] += rng.normal(0, 2.0, (B, 3))
+    sel = [0, 1, bchunk - 1, bchunk, B - 1]
+    r, g = _run_chunked(cuda0, q, t, Tq, Tt, sel)
+    _compare_sample(g, oracle_lib.nn_batched(q, t, Tq[sel], Tt[sel], -1.0))
+    if Nt == 4096:
+        with ops.tuning(nn_path=0):
+            b, _ = _run_chunked(cuda0, q, t, Tq, Tt, sel)
+        for k in ("sum_d", "nn_idx", "nn_d"):
+            assert torch.equal(getattr(r, k), getattr(b, k)), k
+
+
 def _both_paths(cuda0, q, t, Tq, Tt, radius):
     """The same call through both grid searches and through brute force (the ISR_TUNE_NN_PATH knob
     forces the path): everything must agree bit for bit."""
