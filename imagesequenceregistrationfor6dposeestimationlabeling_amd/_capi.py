@@ -234,6 +234,17 @@ CONTRASTIVE_SIGNATURES = {
     "isr_contrastive_column_splits": (_i64, [_i64, _i64, _i64, _i, _i64]),
 }
 
+# include/isr_field_grad.h (the key field's backward and the device-side packing), bound the same way
+FIELD_GRAD_SIGNATURES = {
+    "isr_field_grad_pack_bytes": (_sz, [_i, _vp]),
+    "isr_field_pack_device": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "isr_field_grad_workspace_bytes": (_sz, [_i, _vp, _i]),
+    "isr_field_backward": (_i, [_vp, _sz, _vp, _sz, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "isr_field_backward_host": (_i, [_vp, _sz, _i, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "isr_field_cos_host": (_i, [_vp, _sz, _vp]),
+    "isr_field_grad_geometry": (_i, [_i]),
+}
+
 # include/isr_mc.h (iso-surface extraction), bound the same way
 MC_SIGNATURES = {
     "isr_mc_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -261,7 +272,7 @@ def lib() -> C.CDLL:
     for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES, **FPS_SIGNATURES, **DENSITY_SIGNATURES,
                                **DENSITY_DIR_SIGNATURES, **RADIUS_SIGNATURES, **MC_SIGNATURES, **KNN_SIGNATURES,
                                **RAYS_SIGNATURES, **RADIANCE_SIGNATURES, **RESAMPLE_SIGNATURES,
-                               **CONTRASTIVE_SIGNATURES}.items():
+                               **CONTRASTIVE_SIGNATURES, **FIELD_GRAD_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -1,0 +1,166 @@
+// field_grad.hpp — the backward of field_mlp.hpp's coordinate MLP with respect to its weights and biases, defined once and
+// compiled for host and device.  csrc/field_grad.hip holds the kernels and the C entries (include/isr_field_grad.h).
+//
+// One point, with the forward's z_j (the fmaf chain), a_j = omega * z_j and h'_j = sin32(a_j), and u_l the gradient arriving at
+// layer l's output (u of the last layer: the columns below O of the upstream row), from the last layer down:
+//     sine layer:    s_j = omega * cos32(a_j) (one f32 multiply),  g_j = u_j * s_j (one f32 multiply)
+//     linear layer:  g_j = u_j
+//     u_{l-1}[k] = acc after  acc = fmaf(W_l[j,k], g_j, acc)  for j ascending from acc = +0      (not below layer 0)
+// and over the N points   dW_l[j,k] = sum_n g_l[n,j] h_{l-1}[n,k],   db_l[j] = sum_n g_l[n,j]   in THIS order (blocked_sum):
+// the points are cut into consecutive blocks of kGradChain; inside a block the sum is the f32 chain acc = fmaf(g, h, acc) for n
+// ascending from +0 (db: h = 1); the block sums are added in block order in f64 and rounded to f32 once.  So a gradient is a
+// function of the inputs and N alone: no float atomics, nothing depends on a grid, a slab or a stream.
+// v_mfma_f32_32x32x2_f32 is the k-ordered fmaf chain (field_tile.hpp), so u_{l-1} is a tile layer over the TRANSPOSED weights
+// from a zero accumulator, and a block sum of dW is a matrix-core product whose k index is the point.
+//
+// The transposed pack: 64 zero header words, then for every layer l >= 1 the weights W_l^T as a layer with in = O_l rounded up
+// to 32 (matrix-core order; a layer with K_l < 32 is row-major with in = O_l) and out = K_l, zero padded, and a zero bias.
+#pragma once
+#include "field_mlp.hpp"
+
+namespace isr {
+namespace field {
+
+// Points per f32 chain of a weight sum: the tile.  Against torch autograd in f64 at 4 096 points the worst dW_l / db_l of the
+// tests' fields lies at 2.5 x torch-f32's own deviation with chains of 64, 3.2 x with 128 and 4.9 x with 256 (a db of seven
+// entries, which torch sums pairwise): 64 keeps the project's 4 x margin with room.
+constexpr int kGradChain = 64;
+// Points whose activations the workspace holds at a time, at most: 256 tiles, a workgroup for every CU (measured: two slabs
+// of 16 384 take 0.69 ms where one of 32 768, two workgroups a CU, takes 0.74 ms and four of 8 192 take 1.02 ms).  Their block
+// sums are formed and added kGradBatch points at a time.
+constexpr int kGradSlab = 16384;
+constexpr int kGradBatch = 8192;
+
+// cos(a) for an f32 a: sin32's reduction and kernels, the quadrant taken in f64, one rounding to f32.  cos32(+-0) = 1; NaN
+// and +-Inf give NaN.
+ISR_FIELD_FN float cos32(float a) {
+  double n, s, c;
+  const double r = reduce_pio2((double)a, &n);
+  sincos_kernel(r, &s, &c);
+  const double q = n - 4.0 * rint(n * 0.25);      // n mod 4 in {-2, ..., 2}
+  const double v = (q == 0.0) ? c : (q == 1.0) ? -s : (q == -1.0) ? s : -c;
+  return (float)v;
+}
+
+// sin32(a) and cos32(a) from one reduction: the same bits as the two calls.
+ISR_FIELD_FN void sin_cos32(float a, float* sn, float* cs) {
+  double n, s, c;
+  const double r = reduce_pio2((double)a, &n);
+  sincos_kernel(r, &s, &c);
+  const double q = n - 4.0 * rint(n * 0.25);
+  *sn = (float)((q == 0.0) ? s : (q == 1.0) ? c : (q == -1.0) ? -c : -s);
+  *cs = (float)((q == 0.0) ? c : (q == 1.0) ? -s : (q == -1.0) ? s : -c);
+}
+
+// The layers of the transposed pack (L[0] is empty: nothing flows below layer 0).
+ISR_FIELD_FN void make_layout_t(const Layout& lay, Layout& t) {
+  int off = kHeaderWords;
+  t.n_layers = lay.n_layers;
+  t.L[0] = Layer{0, 0, 0, 0, 0, off, off};
+  for (int l = 1; l < lay.n_layers; ++l) {
+    const Layer& L = lay.L[l];
+    add_layer(L.mfma ? L.OP : L.O, L.K, L.mfma, off, t.L[l]);
+  }
+  t.total_words = off;
+}
+
+// Where the real entries of layer l sit in the standard layout (every W (out, in) row-major, layer after layer; every b).
+ISR_FIELD_FN void std_offsets(const Layout& lay, int* w_off, int* b_off, int* w_total, int* b_total) {
+  int w = 0, b = 0;
+  for (int l = 0; l < lay.n_layers; ++l) {
+    w_off[l] = w;
+    b_off[l] = b;
+    w += lay.L[l].O * lay.L[l].K;
+    b += lay.L[l].O;
+  }
+  *w_total = w;
+  *b_total = b;
+}
+
+// Host: the transposed pack of W (standard layout).
+inline void pack_t_host(const Layout& lay, const Layout& t, const float* W, float* packT) {
+  for (int i = 0; i < t.total_words; ++i) packT[i] = 0.f;
+  for (int l = 0; l < lay.n_layers; ++l) {
+    const Layer& L = lay.L[l];
+    if (l > 0)
+      for (int j = 0; j < L.O; ++j)
+        for (int k = 0; k < L.K; ++k) packT[t.L[l].w_off + w_index(t.L[l], k, j)] = W[(size_t)j * L.K + k];
+    W += (size_t)L.O * L.K;
+  }
+}
+
+// One point: the forward from pt, keeping every layer's input (H[l], K_l floats) and slope, then the rule above from the
+// upstream row `up` (O_last floats; nullptr: zeros) down: G[l] (O_l floats).  dense[l]: W_l row-major.
+inline void point_grads(const Layout& lay, const void* pack, const float* const* dense, const float* pt, const float* up,
+                        float* const* H, float* const* G) {
+  const float* pf = static_cast<const float*>(pack);
+  float h[kMaxWidth], u[kMaxWidth], v[kMaxWidth];
+  for (int k = 0; k < 3; ++k) h[k] = pt[k];
+  for (int l = 0; l < lay.n_layers; ++l) {
+    const Layer& L = lay.L[l];
+    const bool sine = header_sine(pack, l);
+    const float omega = header_omega(pack, l);
+    for (int k = 0; k < L.K; ++k) H[l][k] = h[k];
+    for (int j = 0; j < L.O; ++j) {
+      const float* w = dense[l] + (size_t)j * L.K;
+      float z = pf[L.b_off + j];
+      for (int k = 0; k < L.K; ++k) z = fmaf(w[k], H[l][k], z);
+      if (sine) {
+        const float a = omega * z;
+        float sn, cs;
+        sin_cos32(a, &sn, &cs);
+        h[j] = sn;
+        G[l][j] = omega * cs;          // the slope, until the way down replaces it by g
+      } else {
+        h[j] = z;
+      }
+    }
+  }
+  const Layer& last = lay.L[lay.n_layers - 1];
+  for (int j = 0; j < last.O; ++j) u[j] = up ? up[j] : 0.f;
+  for (int l = lay.n_layers - 1; l >= 0; --l) {
+    const Layer& L = lay.L[l];
+    const bool sine = header_sine(pack, l);
+    for (int j = 0; j < L.O; ++j) G[l][j] = sine ? u[j] * G[l][j] : u[j];
+    if (l == 0) break;
+    for (int k = 0; k < L.K; ++k) {
+      float acc = 0.f;
+      for (int j = 0; j < L.O; ++j) acc = fmaf(dense[l][(size_t)j * L.K + k], G[l][j], acc);
+      v[k] = acc;
+    }
+    for (int k = 0; k < L.K; ++k) u[k] = v[k];
+  }
+}
+
+// sum_n g[n gs] * h[n hs] over N points in the order of the rule (h == nullptr: every h is 1).
+ISR_FIELD_FN float blocked_sum(const float* g, long gs, const float* h, long hs, long N) {
+  double total = 0.0;
+  for (long n0 = 0; n0 < N; n0 += kGradChain) {
+    const long n1 = n0 + kGradChain < N ? n0 + kGradChain : N;
+    float acc = 0.f;
+    for (long n = n0; n < n1; ++n) acc = fmaf(g[n * gs], h ? h[n * hs] : 1.f, acc);
+    total += (double)acc;
+  }
+  return (float)total;
+}
+
+// Host: out[k] = blocked_sum(g, gs, H + k, K, N) for every k < K (K <= kMaxWidth), the points walked once: the same chains.
+inline void blocked_row(const float* g, long gs, const float* H, int K, long N, float* out) {
+  double total[kMaxWidth];
+  float acc[kMaxWidth];
+  for (int k = 0; k < K; ++k) total[k] = 0.0;
+  for (long n0 = 0; n0 < N; n0 += kGradChain) {
+    const long n1 = n0 + kGradChain < N ? n0 + kGradChain : N;
+    for (int k = 0; k < K; ++k) acc[k] = 0.f;
+    for (long n = n0; n < n1; ++n) {
+      const float gv = g[n * gs];
+      const float* h = H + (size_t)n * K;
+      for (int k = 0; k < K; ++k) acc[k] = fmaf(gv, h[k], acc[k]);
+    }
+    for (int k = 0; k < K; ++k) total[k] += (double)acc[k];
+  }
+  for (int k = 0; k < K; ++k) out[k] = (float)total[k];
+}
+
+}  // namespace field
+}  // namespace isr

@@ -371,3 +371,142 @@ class FeatureField:
 
     def batched_forward(self, ray_bundle, n_batches: int = 16, **kw):
         return self.forward(ray_bundle)
+
+
+class _KeyFieldFunction(torch.autograd.Function):
+    """rows (N, 3) -> (N, ld) through a TrainableKeyField's packs: isr_field_eval forward, isr_field_backward backward.  Only
+    the points are saved; the backward recomputes the forward.  params: every W, then every b."""
+
+    @staticmethod
+    def forward(ctx, field, rows, ld, *params):
+        pack, packT = field._packs()
+        out = (torch.empty if ld == field.out_features else torch.zeros)((rows.shape[0], ld), dtype=torch.float32, device=rows.device)
+        ops.field_eval(pack, field.widths, rows, out=out)
+        ctx.widths, ctx.packs = field.widths, (pack, packT)
+        ctx.save_for_backward(rows)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        rows, = ctx.saved_tensors
+        nl = len(ctx.widths) - 1
+        need = ctx.needs_input_grad[3:]
+        dW, db = ops.field_backward(*ctx.packs, ctx.widths, rows, dout.to(torch.float32).contiguous(),
+                                    need=(any(need[:nl]), any(need[nl:])))
+        shapes = list(zip(ctx.widths[1:], ctx.widths[:-1]))
+        gW = torch.split(dW, [o * i for o, i in shapes]) if dW is not None else [None] * nl
+        gb = torch.split(db, [o for o, _ in shapes]) if db is not None else [None] * nl
+        grads = [g.view(o, i) if g is not None and n else None for g, (o, i), n in zip(gW, shapes, need[:nl])]
+        grads += [g if g is not None and n else None for g, n in zip(gb, need[nl:])]
+        return (None, None, None, *grads)
+
+
+class TrainableKeyField(torch.nn.Module):
+    """KeyField with parameters: the SIREN feature head trainPose.py trains (feature_layer.requires_grad_(True)), evaluated
+    by KeyField's kernel with the same bits and differentiated by isr_field_backward with respect to its weights and
+    biases.  weights[l] (out_l, in_l) and biases[l] (out_l,) are ParameterLists in the standard layout, so optimizers,
+    per-layer learning rates and state_dict work as usual; omegas[l] is a float (sine layer) or None (linear layer).  The
+    packs the kernels read are rebuilt on the device (isr_field_pack_device) whenever gradients are enabled or a parameter
+    changed.  Points get no gradient: a point tensor that requires one is refused."""
+
+    def __init__(self, weights, biases, omegas, device=None):
+        super().__init__()
+        if not (len(weights) == len(biases) == len(omegas)) or len(weights) == 0:
+            raise ValueError(f"TrainableKeyField: {len(weights)} weights, {len(biases)} biases, {len(omegas)} omegas")
+        f = lambda t: torch.as_tensor(t, dtype=torch.float32).detach().to(device).clone().contiguous()
+        Ws, bs = [f(w) for w in weights], [f(b).reshape(-1) for b in biases]
+        widths = [Ws[0].shape[1] if Ws[0].ndim == 2 else -1]
+        for l, (w, b) in enumerate(zip(Ws, bs)):
+            if w.ndim != 2 or w.shape[1] != widths[-1] or b.shape[0] != w.shape[0]:
+                raise ValueError(f"TrainableKeyField: layer {l} has W {tuple(w.shape)} and b {tuple(b.shape)} after width {widths[-1]}")
+            widths.append(w.shape[0])
+        self.widths = tuple(int(v) for v in widths)
+        if lib().isr_field_pack_bytes(len(Ws), _vp(np.asarray(self.widths, np.int32))) == 0:
+            raise IsrError(f"TrainableKeyField: {lib().isr_last_error().decode()}")
+        self.omegas = tuple(None if o is None else float(o) for o in omegas)
+        self.n_layers, self.out_features = len(Ws), self.widths[-1]
+        self.weights = torch.nn.ParameterList([torch.nn.Parameter(w) for w in Ws])
+        self.biases = torch.nn.ParameterList([torch.nn.Parameter(b) for b in bs])
+        self._packed, self._packed_at = None, None
+
+    @classmethod
+    def from_linears(cls, linears, omegas, device=None):
+        """From torch.nn.Linear modules (each with a bias); their values are copied."""
+        linears = list(linears)
+        if any(m.bias is None for m in linears):
+            raise ValueError("TrainableKeyField.from_linears: every layer needs a bias")
+        return cls([m.weight for m in linears], [m.bias for m in linears], omegas, linears[0].weight.device if device is None else device)
+
+    @classmethod
+    def from_key_field(cls, key_field: KeyField, device=None):
+        """From a KeyField's packed weights (read back out of its host pack)."""
+        pack, Ws, bs, off = key_field.pack_host, [], [], 64
+        for K, O in zip(key_field.widths[:-1], key_field.widths[1:]):
+            OP, mfma = (O + 31) // 32 * 32, K >= 32
+            ks = (K + 7) // 8 * 8 if mfma else (K + 3) // 4 * 4
+            j, k = np.meshgrid(np.arange(O), np.arange(K), indexing="ij")
+            lane = (k & 1) * 32 + (j & 31)
+            idx = ((((j >> 5) * (ks >> 3) + (k >> 3)) * 64 + lane) * 4 + ((k & 7) >> 1)) if mfma else j * ks + k
+            Ws.append(pack[off + idx])
+            bs.append(pack[off + OP * ks: off + OP * ks + O].copy())
+            off += OP * ks + OP
+        return cls(Ws, bs, key_field.omegas, key_field.device if device is None else device)
+
+    @classmethod
+    def siren(cls, hidden=256, hidden_layers=2, out=12, first_omega=30.0, hidden_omega=30.0, outermost_linear=False, seed=None,
+              device=None):
+        """Siren(in_features=3, hidden_features=hidden, hidden_layers=hidden_layers, out_features=out) with the initialisation
+        of Sitzmann et al. 2020, sec. 3.2: first layer U(-1/in, 1/in), the others U(-sqrt(6/in)/omega, sqrt(6/in)/omega),
+        biases torch.nn.Linear's U(-1/sqrt(in), 1/sqrt(in)).  The reference's dep/siren.py is not part of it, so this follows
+        the paper, not a pinned file."""
+        gen = torch.Generator().manual_seed(int(seed)) if seed is not None else None
+        widths = [3] + [int(hidden)] * (int(hidden_layers) + 1) + [int(out)]
+        n = len(widths) - 1
+        omegas = [float(first_omega)] + [float(hidden_omega)] * (n - 1)
+        if outermost_linear:
+            omegas[-1] = None
+        Ws, bs = [], []
+        for l, (i, o) in enumerate(zip(widths[:-1], widths[1:])):
+            lim = 1.0 / i if l == 0 else (6.0 / i) ** 0.5 / float(hidden_omega)
+            Ws.append((torch.rand((o, i), generator=gen) * 2 - 1) * lim)
+            bs.append((torch.rand((o,), generator=gen) * 2 - 1) / i ** 0.5)
+        return cls(Ws, bs, omegas, device)
+
+    def to_key_field(self, device="parameters") -> KeyField:
+        """A frozen KeyField from the current weights, on the parameters' device by default (host-only, as KeyField's
+        device=None, while they are on the CPU)."""
+        if device == "parameters":
+            device = self.weights[0].device if self.weights[0].is_cuda else None
+        return KeyField([w.detach() for w in self.weights], [b.detach() for b in self.biases], self.omegas, device)
+
+    def _params(self):
+        return [*self.weights, *self.biases]
+
+    def _packs(self):
+        """(pack, packT) of the current parameters, fresh buffers whenever they are rebuilt (a saved backward keeps its own)."""
+        at = tuple((p.data_ptr(), p._version) for p in self._params())
+        if self._packed is None or torch.is_grad_enabled() or at != self._packed_at:
+            with torch.no_grad():
+                W = torch.cat([w.reshape(-1) for w in self.weights])
+                b = torch.cat([v.reshape(-1) for v in self.biases])
+                self._packed, self._packed_at = ops.field_pack_device(self.widths, W, b, self.omegas), at
+        return self._packed
+
+    def _eval(self, points: torch.Tensor, ld: int) -> torch.Tensor:
+        if points.requires_grad:
+            raise NotImplementedError("TrainableKeyField: points get no gradient (detach them)")
+        require_cuda(points, *self._params())
+        if points.shape[-1] != 3:
+            raise ValueError(f"TrainableKeyField: points {tuple(points.shape)} must end in 3")
+        rows = points.to(torch.float32).reshape(-1, 3).contiguous()
+        return _KeyFieldFunction.apply(self, rows, ld, *self._params()).reshape(*points.shape[:-1], ld)
+
+    def forward(self, points: torch.Tensor) -> torch.Tensor:
+        """points (..., 3) -> keys (..., out), on the device, differentiable with respect to the parameters."""
+        return self._eval(points, self.out_features)
+
+    def batched_customForward(self, points: torch.Tensor, n_batches: int = 16) -> torch.Tensor:
+        """nerf.py:404-457: (..., 3) -> (..., out + 1), the last channel zeros (nerf.py:415), which takes no gradient.
+        n_batches is accepted and changes nothing: rows are independent, the whole input is one launch."""
+        return self._eval(points, self.out_features + 1)

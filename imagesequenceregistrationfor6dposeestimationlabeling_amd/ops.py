@@ -1986,3 +1986,128 @@ def contrastive_column_splits(B: int, S: int, M: int, D: int, Bn: int) -> int:
     if r < 1:
         check(-1, "isr_contrastive_column_splits")
     return r
+
+
+# ---- the key field's backward and the device-side packing (include/isr_field_grad.h)
+
+def field_grad_geometry() -> dict:
+    """isr_field_grad_geometry: the widths of the backward (tests and tools): the chain length of a weight sum, the tile of
+    points a workgroup takes, the largest slab of points whose activations the workspace holds at a time, and the batch of
+    points whose block sums it holds."""
+    return {name: lib().isr_field_grad_geometry(i) for i, name in enumerate(("chain", "tile", "slab", "batch"))}
+
+
+def field_param_sizes(widths) -> tuple[int, int]:
+    """-> (entries of every W, entries of every b) of a field of these widths, the lengths of the standard layout."""
+    w = [int(v) for v in widths]
+    return sum(a * b for a, b in zip(w[:-1], w[1:])), sum(w[1:])
+
+
+def _field_header(widths, omegas):
+    """-> (n_layers, widths pointer, its array, omega array, sine array) for the entries that take the field's shape."""
+    nl = len(widths) - 1
+    if len(omegas) != nl:
+        raise ValueError(f"{nl} layers but {len(omegas)} omegas")
+    w = (ctypes.c_int32 * len(widths))(*[int(v) for v in widths])
+    om = (ctypes.c_float * nl)(*[0.0 if o is None else float(o) for o in omegas])
+    sine = (ctypes.c_int32 * nl)(*[0 if o is None else 1 for o in omegas])
+    return nl, ctypes.cast(w, ctypes.c_void_p), w, om, sine
+
+
+def _flat_f32(name: str, what: str, t: torch.Tensor, numel: int) -> None:
+    if t.dtype != torch.float32 or t.ndim != 1 or t.numel() != numel or not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be contiguous ({numel},) float32, got {tuple(t.shape)} {t.dtype}")
+
+
+def field_pack_device(widths, W: torch.Tensor, b: torch.Tensor, omegas, pack: torch.Tensor | None = None,
+                      packT: torch.Tensor | None = None):
+    """isr_field_pack_device: W and b in the standard layout (every layer's (out, in) matrix row-major, layer after layer, flat;
+    the biases likewise) on the device -> (pack, packT): the forward pack, byte for byte isr_field_pack's, and the transposed
+    pack of the backward.  Every word of both is written (into `pack` / `packT` when given); nothing synchronises."""
+    dev = require_cuda(W, b, pack, packT)
+    nw, nb = field_param_sizes(widths)
+    _flat_f32("field_pack_device", "W", W, nw)
+    _flat_f32("field_pack_device", "b", b, nb)
+    nl, wp, _keep, om, sine = _field_header(widths, omegas)
+    L = lib()
+    words, wordsT = L.isr_field_pack_bytes(nl, wp) // 4, L.isr_field_grad_pack_bytes(nl, wp) // 4
+    if words == 0 or wordsT == 0:
+        check(-1, "isr_field_pack_bytes")
+    if pack is None:
+        pack = torch.empty(words, dtype=torch.float32, device=dev)
+    if packT is None:
+        packT = torch.empty(wordsT, dtype=torch.float32, device=dev)
+    _flat_f32("field_pack_device", "pack", pack, words)
+    _flat_f32("field_pack_device", "packT", packT, wordsT)
+    with torch.cuda.device(dev), _timed("field_pack_device", 0.0):
+        rc = L.isr_field_pack_device(nl, wp, ptr(W), ptr(b), ctypes.cast(om, ctypes.c_void_p), ctypes.cast(sine, ctypes.c_void_p),
+                                     ptr(pack), words * 4, ptr(packT), wordsT * 4, current_stream(dev))
+    check(rc, "isr_field_pack_device")
+    return pack, packT
+
+
+def field_backward_flops(widths) -> float:
+    """Multiply-adds x 2 of one point through the backward as issued: the forward again, the u pass (every layer but the
+    first) and the dW pass."""
+    w = [int(v) for v in widths]
+    return 2.0 * field_flops(w) + 2.0 * sum(a * b for a, b in zip(w[1:-1], w[2:]))
+
+
+def field_backward(pack: torch.Tensor, packT: torch.Tensor, widths, points: torch.Tensor, dout: torch.Tensor,
+                   need=(True, True), slab: int | None = None):
+    """isr_field_backward: points (N,3) f32 and the upstream gradient dout (N, ld) f32, ld >= widths[-1] (only columns below
+    widths[-1] are read) -> (dW, db) flat in the standard layout (field_param_sizes), every entry written; need: which of the
+    two to compute (the other is None).  The forward is recomputed from the points; pack and packT are field_pack_device's.
+    slab: work through N this many points at a time (a multiple of the chain length; tests) instead of the default.  Nothing
+    synchronises."""
+    dev = require_cuda(pack, packT, points, dout)
+    N, o = _points_n3("field_backward", points), int(widths[-1])
+    if dout.dtype != torch.float32 or dout.ndim != 2 or dout.shape[0] != N or dout.shape[1] < o or not dout.is_contiguous():
+        raise ValueError(f"field_backward: dout must be contiguous ({N}, >= {o}) float32, got {tuple(dout.shape)} {dout.dtype}")
+    nw, nb = field_param_sizes(widths)
+    pk, nbytes, nl, wp, _keep = _field_args(pack, widths, len(widths) - 1)
+    L = lib()
+    if slab is None:
+        ws_bytes = L.isr_field_grad_workspace_bytes(nl, wp, N)
+        ws = workspace(dev, ws_bytes, "field_grad") if ws_bytes else None
+    else:
+        chain = L.isr_field_grad_geometry(0)
+        if slab < chain or slab % chain:
+            raise ValueError(f"field_backward: slab {slab} is not a multiple of the chain length {chain}")
+        ws_bytes = L.isr_field_grad_workspace_bytes(nl, wp, int(slab))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    if ws_bytes == 0:
+        check(-1, "isr_field_grad_workspace_bytes")
+    dW = torch.empty(nw, dtype=torch.float32, device=dev) if need[0] else None
+    db = torch.empty(nb, dtype=torch.float32, device=dev) if need[1] else None
+    with torch.cuda.device(dev), _timed("field_backward", N * field_backward_flops(widths)):
+        rc = L.isr_field_backward(pk, nbytes, ptr(packT), packT.numel() * packT.element_size(), nl, wp, ptr(points) if N else None,
+                                  N, ptr(dout) if N else None, dout.shape[1], ptr(dW), ptr(db), ptr(ws), ws_bytes,
+                                  current_stream(dev))
+    check(rc, "isr_field_backward")
+    return dW, db
+
+
+def field_backward_host(pack_host, widths, points, dout, need=(True, True)):
+    """isr_field_backward_host: field_backward as host code over NumPy arrays (pack_host: isr_field_pack's words, e.g.
+    KeyField.pack_host).  For tests."""
+    pack_host = np.ascontiguousarray(pack_host, np.float32)
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    dout = np.ascontiguousarray(dout, np.float32)
+    if dout.ndim != 2 or dout.shape[0] != pts.shape[0]:
+        raise ValueError(f"field_backward_host: dout {dout.shape} for {pts.shape[0]} points")
+    nw, nb = field_param_sizes(widths)
+    w = np.asarray(widths, np.int32)
+    dW = np.empty(nw, np.float32) if need[0] else None
+    db = np.empty(nb, np.float32) if need[1] else None
+    check(lib().isr_field_backward_host(_hp(pack_host), pack_host.nbytes, len(w) - 1, _hp(w), _hp(pts), pts.shape[0], _hp(dout),
+                                        dout.shape[1], _hp(dW), _hp(db)), "isr_field_backward_host")
+    return dW, db
+
+
+def field_cos_host(a):
+    """isr_field_cos_host: cos32 of every element of a NumPy f32 array.  For tests."""
+    a = np.ascontiguousarray(a, np.float32)
+    out = np.empty_like(a)
+    check(lib().isr_field_cos_host(_hp(a), a.size, _hp(out)), "isr_field_cos_host")
+    return out

@@ -1,0 +1,237 @@
+// field_grad_host_check.cpp — csrc/field_grad.hpp (over csrc/field_mlp.hpp) as plain host code, for a sanitizer build:
+//     c++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all \
+//         tools/field_grad_host_check.cpp -o field_grad_host_check && ./field_grad_host_check
+// Drives make_layout / make_layout_t, pack_host / pack_t_host, point_grads, blocked_sum and blocked_row over the fields and
+// point counts of the tests, with arrays of exactly the sizes the header asks for.  Checks what can be checked without a
+// second f32 implementation: the transposed pack holds W_l[j, k] at w_index(T_l, k, j) and zeros elsewhere, blocked_row equals
+// blocked_sum entry for entry, the gradients follow an f64 evaluation of the same network (within 2e-3 of the magnitude the
+// same backward carries when every term is replaced by its absolute value and every slope by omega: the worst case of
+// 2^-24 x omega 30 x 256 inputs x 4 layers of roundings, angles included), N = 0 gives zeros, a NaN point gives NaNs.  Then
+// measures cos32 against the f64 cosine: every 499th f32 bit pattern of [-2^17, 2^17] and a grid of 4 000 001 points in
+// [-110, 110], in f32 ulp of the true value.  Prints one line per case; exit status 0 = all hold.  The log of one such run is
+// profiles/field_grad_host_sanitizers.txt.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#define __host__
+#define __device__
+#include "../imagesequenceregistrationfor6dposeestimationlabeling_amd/csrc/field_grad.hpp"
+
+using namespace isr::field;
+
+namespace {
+
+unsigned seed = 24680u;
+float uni() {                                        // U(-1, 1)
+  seed = seed * 1664525u + 1013904223u;
+  return (float)((seed >> 8) & 0xffff) / 32768.f - 1.f;
+}
+
+int fails = 0;
+
+void run(int n_layers, const int32_t* widths, const float* omega, const int32_t* sine, long N, bool nan_point) {
+  Layout lay, layT;
+  if (!make_layout(n_layers, widths, lay)) {
+    std::printf("make_layout refused a field of the tests FAILED\n");
+    ++fails;
+    return;
+  }
+  make_layout_t(lay, layT);
+  int w_std[kMaxLayers], b_std[kMaxLayers], w_total, b_total;
+  std_offsets(lay, w_std, b_std, &w_total, &b_total);
+  std::vector<float> W((size_t)w_total), b((size_t)b_total), pack((size_t)lay.total_words), packT((size_t)layT.total_words);
+  for (int l = 0; l < n_layers; ++l) {
+    const float lim = l == 0 ? 1.f / 3.f : std::sqrt(6.f / (float)lay.L[l].K) / (sine[l] ? omega[l] : 30.f);
+    for (int i = 0; i < lay.L[l].O * lay.L[l].K; ++i) W[(size_t)w_std[l] + i] = uni() * lim;
+    for (int j = 0; j < lay.L[l].O; ++j) b[(size_t)b_std[l] + j] = uni() / std::sqrt((float)lay.L[l].K);
+  }
+  pack_host(lay, W.data(), b.data(), omega, sine, pack.data());
+  pack_t_host(lay, layT, W.data(), packT.data());
+  bool ok = true;
+  {                                                  // the transposed pack: every real entry in its place, zeros elsewhere
+    std::vector<char> seen((size_t)layT.total_words, 0);
+    for (int l = 1; l < n_layers; ++l)
+      for (int j = 0; j < lay.L[l].O; ++j)
+        for (int k = 0; k < lay.L[l].K; ++k) {
+          const int at = layT.L[l].w_off + w_index(layT.L[l], k, j);
+          ok = ok && at >= kHeaderWords && at < layT.L[l].b_off && !seen[(size_t)at] && packT[(size_t)at] == W[(size_t)w_std[l] + (size_t)j * lay.L[l].K + k];
+          seen[(size_t)at] = 1;
+        }
+    for (int i = 0; i < layT.total_words; ++i) ok = ok && (seen[(size_t)i] || packT[(size_t)i] == 0.f);
+  }
+  std::vector<std::vector<float>> dense((size_t)n_layers), H((size_t)n_layers), G((size_t)n_layers);
+  const float* rows[kMaxLayers];
+  for (int l = 0; l < n_layers; ++l) {
+    dense[(size_t)l].resize((size_t)lay.L[l].O * lay.L[l].K);
+    unpack_layer(lay.L[l], pack.data(), dense[(size_t)l].data(), false);
+    rows[l] = dense[(size_t)l].data();
+    H[(size_t)l].resize((size_t)N * lay.L[l].K);
+    G[(size_t)l].resize((size_t)N * lay.L[l].O);
+  }
+  const int O = lay.L[n_layers - 1].O;
+  std::vector<float> pts((size_t)N * 3), up((size_t)N * O);
+  for (auto& v : pts) v = uni();
+  for (auto& v : up) v = uni() * 2.f;
+  if (nan_point) pts[(size_t)(N / 2) * 3 + 1] = std::numeric_limits<float>::quiet_NaN();
+  for (long n = 0; n < N; ++n) {
+    float *hp[kMaxLayers], *gp[kMaxLayers];
+    for (int l = 0; l < n_layers; ++l) {
+      hp[l] = H[(size_t)l].data() + (size_t)n * lay.L[l].K;
+      gp[l] = G[(size_t)l].data() + (size_t)n * lay.L[l].O;
+    }
+    point_grads(lay, pack.data(), rows, &pts[(size_t)n * 3], &up[(size_t)n * O], hp, gp);
+  }
+  if (N > 0) {                                       // a null upstream row stands for zeros
+    std::vector<std::vector<float>> h1((size_t)n_layers), g1((size_t)n_layers);
+    float *hp[kMaxLayers], *gp[kMaxLayers];
+    for (int l = 0; l < n_layers; ++l) {
+      h1[(size_t)l].resize((size_t)lay.L[l].K);
+      g1[(size_t)l].resize((size_t)lay.L[l].O);
+      hp[l] = h1[(size_t)l].data();
+      gp[l] = g1[(size_t)l].data();
+    }
+    point_grads(lay, pack.data(), rows, pts.data(), nullptr, hp, gp);
+    if (!nan_point)
+      for (int l = 0; l < n_layers; ++l)
+        for (float v : g1[(size_t)l]) ok = ok && v == 0.f;
+  }
+  // the sums, and the same network in f64
+  std::vector<float> dW((size_t)w_total), db((size_t)b_total);
+  for (int l = 0; l < n_layers; ++l) {
+    const Layer& L = lay.L[l];
+    for (int j = 0; j < L.O; ++j) {
+      blocked_row(G[(size_t)l].data() + j, L.O, H[(size_t)l].data(), L.K, N, &dW[(size_t)w_std[l] + (size_t)j * L.K]);
+      db[(size_t)b_std[l] + j] = blocked_sum(G[(size_t)l].data() + j, L.O, nullptr, 0, N);
+      for (int k = 0; k < L.K; ++k) {
+        const float one = blocked_sum(G[(size_t)l].data() + j, L.O, H[(size_t)l].data() + k, L.K, N);
+        const float row = dW[(size_t)w_std[l] + (size_t)j * L.K + k];
+        ok = ok && (std::memcmp(&one, &row, 4) == 0 || (one != one && row != row));
+      }
+    }
+  }
+  std::vector<double> rW((size_t)w_total, 0.0), rb((size_t)b_total, 0.0), mW((size_t)w_total, 0.0), mb((size_t)b_total, 0.0);
+  for (long n = 0; n < N && !nan_point; ++n) {
+    std::vector<std::vector<double>> h((size_t)n_layers + 1), s((size_t)n_layers);
+    h[0] = {(double)pts[(size_t)n * 3], (double)pts[(size_t)n * 3 + 1], (double)pts[(size_t)n * 3 + 2]};
+    for (int l = 0; l < n_layers; ++l) {
+      const Layer& L = lay.L[l];
+      h[(size_t)l + 1].resize((size_t)L.O);
+      s[(size_t)l].resize((size_t)L.O);
+      for (int j = 0; j < L.O; ++j) {
+        double z = (double)b[(size_t)b_std[l] + j];
+        for (int k = 0; k < L.K; ++k) z += (double)W[(size_t)w_std[l] + (size_t)j * L.K + k] * h[(size_t)l][(size_t)k];
+        h[(size_t)l + 1][(size_t)j] = sine[l] ? std::sin((double)omega[l] * z) : z;
+        s[(size_t)l][(size_t)j] = sine[l] ? (double)omega[l] * std::cos((double)omega[l] * z) : 1.0;
+      }
+    }
+    std::vector<double> u((size_t)O), mu((size_t)O);
+    for (int j = 0; j < O; ++j) u[(size_t)j] = (double)up[(size_t)n * O + j], mu[(size_t)j] = std::fabs(u[(size_t)j]);
+    for (int l = n_layers - 1; l >= 0; --l) {
+      const Layer& L = lay.L[l];
+      std::vector<double> g((size_t)L.O), v((size_t)L.K, 0.0), mv((size_t)L.K, 0.0);
+      for (int j = 0; j < L.O; ++j) {
+        g[(size_t)j] = u[(size_t)j] * s[(size_t)l][(size_t)j];
+        const double mg = mu[(size_t)j] * (sine[l] ? std::fabs((double)omega[l]) : 1.0);
+        rb[(size_t)b_std[l] + j] += g[(size_t)j];
+        mb[(size_t)b_std[l] + j] += mg;
+        for (int k = 0; k < L.K; ++k) {
+          const double w = (double)W[(size_t)w_std[l] + (size_t)j * L.K + k];
+          rW[(size_t)w_std[l] + (size_t)j * L.K + k] += g[(size_t)j] * h[(size_t)l][(size_t)k];
+          mW[(size_t)w_std[l] + (size_t)j * L.K + k] += mg * std::fabs(h[(size_t)l][(size_t)k]);
+          v[(size_t)k] += w * g[(size_t)j];
+          mv[(size_t)k] += std::fabs(w) * mg;
+        }
+      }
+      u = v;
+      mu = mv;
+    }
+  }
+  double worst = 0.0;
+  int nans = 0;
+  for (int i = 0; i < w_total; ++i) {
+    nans += dW[(size_t)i] != dW[(size_t)i];
+    if (!nan_point) worst = std::fmax(worst, std::fabs((double)dW[(size_t)i] - rW[(size_t)i]) / (mW[(size_t)i] + 1e-30));
+  }
+  for (int i = 0; i < b_total; ++i) {
+    nans += db[(size_t)i] != db[(size_t)i];
+    if (!nan_point) worst = std::fmax(worst, std::fabs((double)db[(size_t)i] - rb[(size_t)i]) / (mb[(size_t)i] + 1e-30));
+  }
+  if (N == 0)
+    for (float v : dW) ok = ok && v == 0.f;
+  ok = ok && (nan_point ? nans > 0 : (nans == 0 && worst <= 2e-3));
+  std::printf("widths 3");
+  for (int l = 1; l <= n_layers; ++l) std::printf("-%d", (int)widths[l]);
+  std::printf(" N %-5ld %-12s NaN entries %-6d worst error / magnitude %.3e  %s\n", N, nan_point ? "a NaN point" : "random", nans,
+              worst, ok ? "ok" : "FAILED");
+  fails += !ok;
+}
+
+double ulp_error(float a) {
+  const double want = std::cos((double)a), got = (double)cos32(a);
+  int e;
+  std::frexp(want, &e);
+  return std::fabs(got - want) / std::ldexp(1.0, e - 24);
+}
+
+void measure_cos() {
+  double worst = 0.0, at = 0.0;
+  long count = 0;
+  uint32_t last;
+  const float lim = 131072.f;
+  std::memcpy(&last, &lim, 4);
+  for (uint32_t u = 0; u <= last; u += 499u)
+    for (uint32_t sign : {0u, 0x80000000u}) {
+      float x;
+      const uint32_t v = u | sign;
+      std::memcpy(&x, &v, 4);
+      const double err = ulp_error(x);
+      if (err > worst) worst = err, at = x;
+      ++count;
+    }
+  std::printf("cos32 over [-2^17, 2^17]: %ld arguments, largest error %.4f f32 ulp of the f64 cosine (at a = %.9g)\n", count, worst, at);
+  double dense = 0.0, dense_at = 0.0;
+  for (long i = 0; i <= 4000000; ++i) {
+    const float x = (float)(-110.0 + 220.0 * (double)i / 4000000.0);
+    const double err = ulp_error(x);
+    if (err > dense) dense = err, dense_at = x;
+  }
+  std::printf("cos32 over [-110, 110]: 4000001 arguments, largest error %.4f f32 ulp (at a = %.9g)\n", dense, dense_at);
+  const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
+  float sn, cs;
+  sin_cos32(1.25f, &sn, &cs);
+  const bool ok = worst < 1.0 && dense < 1.0 && cos32(0.f) == 1.f && cos32(-0.f) == 1.f && cos32(nan) != cos32(nan) && cos32(inf) != cos32(inf) &&
+                  cos32(-inf) != cos32(-inf) && std::fabs(cos32(3e38f)) <= 1.f && sn == sin32(1.25f) && cs == cos32(1.25f);
+  std::printf("cos32(+-0) = 1, NaN for NaN and +-Inf, sin_cos32 is sin32 and cos32   %s\n", ok ? "ok" : "FAILED");
+  fails += !ok;
+}
+
+}  // namespace
+
+int main() {
+  const float om4[] = {30.f, 30.f, 30.f, 30.f}, om3[] = {30.f, 1.5f, 2.f};
+  const int32_t s4[] = {1, 1, 1, 1}, lin_hidden[] = {1, 0, 1}, lin_last[] = {1, 1, 0};
+  const int32_t w1[] = {3, 12}, w2[] = {3, 32, 12}, w3[] = {3, 40, 33, 5}, w4[] = {3, 256, 256, 256, 12}, w5[] = {3, 40, 33, 7}, w6[] = {3, 5, 40, 7};
+  for (long N : {0L, 1L, 63L, 64L, 65L, 129L}) {
+    run(1, w1, om4, s4, N, false);
+    run(3, w3, om3, s4, N, false);
+  }
+  run(2, w2, om4, s4, 321, false);
+  run(4, w4, om4, s4, 130, false);
+  run(3, w5, om3, lin_hidden, 321, false);
+  run(3, w6, om3, lin_last, 321, false);
+  run(3, w3, om3, s4, 321, true);
+  run(3, w6, om3, lin_last, 130, true);
+  const int32_t bad0[] = {4, 12}, bad1[] = {3, 257, 12}, bad2[] = {3, 64, 33}, bad3[] = {3, 0, 12};
+  Layout lay;
+  const bool refusals = !make_layout(1, bad0, lay) && !make_layout(2, bad1, lay) && !make_layout(2, bad2, lay) && !make_layout(2, bad3, lay) &&
+                        !make_layout(0, w1, lay) && !make_layout(9, w4, lay);
+  std::printf("make_layout refuses what the header says                 %s\n", refusals ? "ok" : "FAILED");
+  fails += !refusals;
+  measure_cos();
+  std::printf("%s\n", fails ? "FAILED" : "all hold");
+  return fails ? 1 : 0;
+}
