@@ -41,6 +41,26 @@ def objective(t, R, coord_masked, keys_masked, query_img, denom_img, K_crop, ret
     return score.item()
 
 
+def objective_full(Rt, coord_masked, keys_masked, query_img, denom_img, K_crop, interpolation="bilinear", dtype=torch.float64):
+    """The statements of `objective` with the whole 3x4 [R|t] as the autograd leaf (no Rodrigues): the layout of
+    isr_refine_objective_full's out13.  Returns (score, d/dt (3,), d/dR (9,) row-major) as f64."""
+    res = query_img.shape[0]
+    coord_masked, keys_masked, query_img, denom_img = (x.to(dtype) for x in (coord_masked, keys_masked, query_img, denom_img))
+    Rt = torch.tensor(np.asarray(Rt, np.float64).reshape(3, 4), dtype=dtype, requires_grad=True)
+    P = torch.from_numpy(np.asarray(K_crop, np.float64)).to(dtype) @ Rt
+    X = torch.cat((coord_masked, torch.ones(len(coord_masked), 1, dtype=dtype)), dim=1)
+    p_img = X @ P.T
+    p_img = p_img[..., :2] / p_img[..., 2:]
+    p_norm = (p_img + 0.5) * (2 / res) - 1
+    q = sample(query_img, p_norm, interpolation)
+    log_nom = (keys_masked * q).sum(dim=-1)
+    log_den = sample(denom_img, p_norm, interpolation)[:, 0]
+    score = -(log_nom.mean() - log_den.mean()) / 2
+    score.backward()
+    g = (Rt.grad if Rt.grad is not None else torch.zeros(3, 4)).detach().numpy().astype(np.float64)
+    return score.item(), g[:, 3].copy(), g[:, :3].reshape(9).copy()
+
+
 def rodrigues_torch(rvec: torch.Tensor) -> torch.Tensor:
     """Rotation matrix of a rotation vector, differentiable (what cv2.Rodrigues computes; the reference wraps it in
     an autograd Function, pose_refine.py:7-18)."""

@@ -100,10 +100,17 @@ def test_refine_objective_vs_reference_statements(cuda0):
     q, den = torch.from_numpy(g["query_img"]).to(cuda0), torch.from_numpy(g["denom_img"]).to(cuda0)
     obj = pose_refine.RefineObjective(torch.from_numpy(g["X"]).to(cuda0), torch.from_numpy(g["keys"]).to(cuda0), q, den,
                                       g["K_crop"], g["R"])
+    from oracle import refine_pose_oracle as rpo
+    qh, dh = torch.from_numpy(g["query_img"]), torch.from_numpy(g["denom_img"])[..., None]
+    kh, Xh = torch.from_numpy(g["keys"]), torch.from_numpy(g["X"])
     for t, s, gr in zip(g["t"], g["score"], g["grad_t"]):
         pose = np.concatenate([np.zeros(3), t])
         assert abs(obj(pose) - s) <= 2e-5 * max(1.0, abs(s))
         np.testing.assert_allclose(obj(pose, return_grad=True)[3:], gr, rtol=2e-3, atol=1e-6)
+        # the same statements evaluated in f64 (torch autograd): the kernel's f64 value and gradient agree tightly
+        v64, g64 = rpo.objective(t, g["R"], Xh, kh, qh, dh, g["K_crop"], return_grad=True, dtype=torch.float64)
+        assert abs(obj(pose) - v64) <= 1e-9 * max(1.0, abs(v64))
+        np.testing.assert_allclose(obj(pose, return_grad=True)[3:], g64, rtol=1e-7, atol=1e-9)
 
 
 @pytest.mark.parametrize("mode", ["nearest", "bicubic"])
