@@ -22,6 +22,9 @@ def __getattr__(name):
     if name in ("contrastive_loss", "returnCrossEntropy", "returnCrossEntropy2", "returnCrossEntropyWithNeg"):
         from . import losses
         return getattr(losses, name)
+    if name == "pose_train_step":
+        from . import training
+        return training.pose_train_step
     if name == "marching_cubes":
         from . import ops
         return ops.marching_cubes

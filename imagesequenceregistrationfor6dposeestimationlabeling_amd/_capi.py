@@ -245,6 +245,14 @@ FIELD_GRAD_SIGNATURES = {
     "isr_field_grad_geometry": (_i, [_i]),
 }
 
+# include/isr_sample_grad.h (the backward of isr_sample_nearest), bound the same way
+SAMPLE_GRAD_SIGNATURES = {
+    "isr_sample_grad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "isr_sample_nearest_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "isr_sample_nearest_backward_host": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "isr_sample_grad_geometry": (_i, [_i]),
+}
+
 # include/isr_mc.h (iso-surface extraction), bound the same way
 MC_SIGNATURES = {
     "isr_mc_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -272,7 +280,7 @@ def lib() -> C.CDLL:
     for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES, **FPS_SIGNATURES, **DENSITY_SIGNATURES,
                                **DENSITY_DIR_SIGNATURES, **RADIUS_SIGNATURES, **MC_SIGNATURES, **KNN_SIGNATURES,
                                **RAYS_SIGNATURES, **RADIANCE_SIGNATURES, **RESAMPLE_SIGNATURES,
-                               **CONTRASTIVE_SIGNATURES, **FIELD_GRAD_SIGNATURES}.items():
+                               **CONTRASTIVE_SIGNATURES, **FIELD_GRAD_SIGNATURES, **SAMPLE_GRAD_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -1750,7 +1750,8 @@ def _sample_shapes(name: str, images, xys) -> tuple[int, int, int, int, int]:
 def sample_at_rays(images: torch.Tensor, xys: torch.Tensor) -> torch.Tensor:
     """isr_sample_nearest: images (B,H,W,C) sampled at the NDC locations xys (B,...,2) -> (B,...,C) f32, on the device:
     grid_sample(images.permute(0,3,1,2), -xys, align_corners=True, mode='nearest') with zero padding (nutil.py:188-193),
-    value for value.  Nothing synchronises."""
+    value for value.  Nothing synchronises.  Not differentiable: the result carries no grad_fn; the route with a gradient
+    is rays.sample_images_at_mc_locs, whose backward is sample_at_rays_backward."""
     dev = require_cuda(images, xys)
     im, xy = _f32c(images), _f32c(xys)
     B, H, W, C, n = _sample_shapes("sample_at_rays", im, xy)
@@ -1767,6 +1768,59 @@ def sample_at_rays_host(images, xys):
     B, H, W, C, n = _sample_shapes("sample_at_rays_host", im, xy)
     out = np.empty((*xy.shape[:-1], C), np.float32)
     check(lib().isr_sample_nearest_host(_hp(im), B, H, W, C, _hp(xy), n, _hp(out)), "isr_sample_nearest_host")
+    return out
+
+
+# ---- the backward of sample_at_rays (include/isr_sample_grad.h)
+def sample_grad_geometry() -> dict:
+    """isr_sample_grad_geometry: the largest n sorted in LDS, the radix sort's keys per block and the bits of its digit."""
+    L = lib()
+    return {"lds_rays": L.isr_sample_grad_geometry(0), "block_keys": L.isr_sample_grad_geometry(1),
+            "digit_bits": L.isr_sample_grad_geometry(2)}
+
+
+def _sample_grad_shapes(name: str, dout, xys, H: int, W: int) -> tuple[int, int, int]:
+    if xys.ndim < 3 or xys.shape[-1] != 2 or 0 in tuple(xys.shape):
+        raise ValueError(f"{name}: xys must be (B,...,2) and not empty, got {tuple(xys.shape)}")
+    if dout.ndim != xys.ndim or tuple(dout.shape[:-1]) != tuple(xys.shape[:-1]) or not 1 <= dout.shape[-1] <= 4096:
+        raise ValueError(f"{name}: dout must be {tuple(xys.shape[:-1])} + (C,) with C in 1..4096, got {tuple(dout.shape)}")
+    B, C = int(xys.shape[0]), int(dout.shape[-1])
+    n = int(np.prod(xys.shape[1:-1]))
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or H * W >= 2 ** 31 - 1 or B * H * W * C >= 2 ** 40:
+        raise ValueError(f"{name}: an image of {H} x {W} pixels, {B} of them with {C} channels (H W < 2^31 - 1, B H W C < 2^40)")
+    if B * n > 2 ** 28 or B * n * C >= 2 ** 31:
+        raise ValueError(f"{name}: {B} x {n} locations x {C} channels is too many (B n <= 2^28, B n C < 2^31)")
+    return B, C, n
+
+
+def sample_at_rays_backward(dout: torch.Tensor, xys: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """isr_sample_nearest_backward: the gradient of sample_at_rays with respect to its images.  dout (B,...,C) at the NDC
+    locations xys (B,...,2) -> dimages (B,H,W,C) f32 on the device: per (pixel, channel) the f32 sum of the pixel's rays in
+    ray order from +0, a function of the arguments only (no float atomics).  Nothing synchronises."""
+    dev = require_cuda(dout, xys)
+    g, xy = _f32c(dout), _f32c(xys)
+    B, C, n = _sample_grad_shapes("sample_at_rays_backward", g, xy, H, W)
+    out = torch.empty((B, int(H), int(W), C), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        nbytes = lib().isr_sample_grad_workspace_bytes(B, int(H), int(W), n)
+        if nbytes == 0:
+            check(-1, "isr_sample_grad_workspace_bytes")
+        ws = workspace(dev, nbytes, tag="sample_grad")
+        with _timed("sample_nearest_backward", float(B) * n * C):
+            rc = lib().isr_sample_nearest_backward(ptr(g), B, int(H), int(W), C, ptr(xy), n, ptr(out), ptr(ws), ws.numel(),
+                                                   current_stream(dev))
+    check(rc, "isr_sample_nearest_backward")
+    return out
+
+
+def sample_at_rays_backward_host(dout, xys, H: int, W: int):
+    """isr_sample_nearest_backward_host: the same gradient as host code over NumPy arrays.  For tests."""
+    g, xy = np.ascontiguousarray(dout, np.float32), np.ascontiguousarray(xys, np.float32)
+    B, C, n = _sample_grad_shapes("sample_at_rays_backward_host", g, xy, H, W)
+    out = np.empty((B, int(H), int(W), C), np.float32)
+    check(lib().isr_sample_nearest_backward_host(_hp(g), B, int(H), int(W), C, _hp(xy), n, _hp(out)),
+          "isr_sample_nearest_backward_host")
     return out
 
 

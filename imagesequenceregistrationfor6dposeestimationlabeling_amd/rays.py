@@ -168,8 +168,34 @@ class MonteCarloRaysampler:
 
 def sample_images_at_mc_locs(target_images: torch.Tensor, sampled_rays_xy: torch.Tensor) -> torch.Tensor:
     """nutil.sample_images_at_mc_locs (nutil.py:167-196): target_images (B,H,W,C) at the NDC locations (B,...,2) -> (B,...,C),
-    the nearest pixel of -xy with zeros outside, on the device (ops.sample_at_rays)."""
+    the nearest pixel of -xy with zeros outside, on the device (ops.sample_at_rays).
+    When gradients are enabled and target_images requires one, the result carries it back (trainPose.py:397-400 trains the
+    encoder through this call): the values are the same bits, and the backward is ops.sample_at_rays_backward, per pixel the
+    f32 sum of its rays in ray order with no float atomics (include/isr_sample_grad.h), once differentiable.  A
+    non-contiguous or non-f32 target_images is copied by a torch op first, which carries the gradient on to the original.
+    sampled_rays_xy, if it requires a gradient, gets zeros, as torch's nearest-mode grid_sample gives it."""
+    if torch.is_grad_enabled() and target_images.requires_grad:
+        return _SampleAtRays.apply(ops._f32c(target_images), sampled_rays_xy)
     return ops.sample_at_rays(target_images, sampled_rays_xy)
+
+
+class _SampleAtRays(torch.autograd.Function):
+    """images (B,H,W,C) f32 contiguous, xys (B,...,2) -> (B,...,C): ops.sample_at_rays forward, ops.sample_at_rays_backward
+    backward.  Only xys and the image size are saved."""
+
+    @staticmethod
+    def forward(ctx, images, xys):
+        out = ops.sample_at_rays(images.detach(), xys.detach())
+        ctx.save_for_backward(xys.detach())
+        ctx.size = (int(images.shape[1]), int(images.shape[2]))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        xys, = ctx.saved_tensors
+        dimages = ops.sample_at_rays_backward(dout.contiguous(), xys, *ctx.size) if ctx.needs_input_grad[0] else None
+        return dimages, torch.zeros_like(xys) if ctx.needs_input_grad[1] else None
 
 
 def sample_pdf(bins: torch.Tensor, weights: torch.Tensor, n_samples: int, det: bool = False, eps: float = 1e-5, *,
