@@ -535,17 +535,25 @@ __device__ void gn_solve(const double* __restrict__ partial, int nblocks, double
   for (int i = 0; i < 6; ++i)
     for (int j = i; j < 6; ++j) { A[i][j] = s[k]; A[j][i] = s[k]; ++k; }
   for (int i = 0; i < 6; ++i) g[i] = -s[21 + i];
-  // Cholesky A = L L^T (tiny relative damping keeps a rank-deficient system finite)
-  double tr = 0.0;
-  for (int i = 0; i < 6; ++i) tr += A[i][i];
-  for (int i = 0; i < 6; ++i) A[i][i] += 1e-14 * tr;
+  // Cholesky A = L L^T, undamped.  A pivot that is not above kGnPivotRel of its own diagonal entry means the system is
+  // not positive definite to working precision (collinear object points: the rotation about their line is free; NaN
+  // sums fail the comparison too): keep the pose.  The test is relative to the pivot's OWN entry, so it does not depend
+  // on the units of the unknowns.  1e-8: rounding leaves ~20 eps / sqrt(r) of the entry in a pivot that should be zero,
+  // r the smallest ratio before it (measured: 6e-11 behind a pivot of 7e-10), so while every earlier pivot passed, noise
+  // stays below 1e-10 and cannot pass for a pivot; well-posed systems are far above (>= 1e-4 for an object at 700 mm,
+  // 4e-6 at 6 m, 2e-7 for 4 correspondences at 6 m).
+  // (Until the refit had an f64 reference at every iteration count the diagonal was damped by 1e-14 * trace instead.
+  // The trace is the rotation block's, z_c^2 (in mm^2) times the translation block's: the damping was 1e-5 of the
+  // smallest eigenvalue for an object at 700 mm and a tenth of it at 6 m — a Levenberg step, linearly convergent there,
+  // that the stopping rule cut off up to 1e-10 rad short of the optimum.)
+  constexpr double kGnPivotRel = 1e-8;
   double L[6][6];
   for (int i = 0; i < 6; ++i)
     for (int j = 0; j < 6; ++j) L[i][j] = 0.0;
   for (int j = 0; j < 6; ++j) {
     double d = A[j][j];
     for (int p = 0; p < j; ++p) d -= L[j][p] * L[j][p];
-    if (!(d > 0.0)) { state[0] = 1; return; }  // not positive definite: keep the pose
+    if (!(d > kGnPivotRel * A[j][j])) { state[0] = 1; return; }  // not positive definite: keep the pose
     L[j][j] = sqrt(d);
     for (int i = j + 1; i < 6; ++i) {
       double v = A[i][j];
