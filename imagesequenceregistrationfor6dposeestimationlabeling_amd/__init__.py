@@ -19,12 +19,12 @@ def __getattr__(name):
                 "EmissionAbsorptionRaymarcherStratified", "ImplicitRendererStratified"):
         from . import rays
         return getattr(rays, name)
-    if name in ("contrastive_loss", "returnCrossEntropy", "returnCrossEntropy2", "returnCrossEntropyWithNeg"):
+    if name in ("contrastive_loss", "huber", "returnCrossEntropy", "returnCrossEntropy2", "returnCrossEntropyWithNeg"):
         from . import losses
         return getattr(losses, name)
-    if name == "pose_train_step":
+    if name in ("pose_train_step", "nerf_train_step"):
         from . import training
-        return training.pose_train_step
+        return getattr(training, name)
     if name == "marching_cubes":
         from . import ops
         return ops.marching_cubes

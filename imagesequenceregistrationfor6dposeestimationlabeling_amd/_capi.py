@@ -253,6 +253,14 @@ SAMPLE_GRAD_SIGNATURES = {
     "isr_sample_grad_geometry": (_i, [_i]),
 }
 
+# include/isr_ea_grad.h (the backward of isr_ea_march), bound the same way
+EA_GRAD_SIGNATURES = {
+    "isr_ea_march_backward": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "isr_ea_march_backward_host": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "isr_ea_grad_geometry": (_i, [_i]),
+    "isr_ea_grad_rays_per_group": (_i, [_i]),
+}
+
 # include/isr_mc.h (iso-surface extraction), bound the same way
 MC_SIGNATURES = {
     "isr_mc_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -280,7 +288,8 @@ def lib() -> C.CDLL:
     for name, (res, args) in {**SIGNATURES, **FIELD_SIGNATURES, **FPS_SIGNATURES, **DENSITY_SIGNATURES,
                                **DENSITY_DIR_SIGNATURES, **RADIUS_SIGNATURES, **MC_SIGNATURES, **KNN_SIGNATURES,
                                **RAYS_SIGNATURES, **RADIANCE_SIGNATURES, **RESAMPLE_SIGNATURES,
-                               **CONTRASTIVE_SIGNATURES, **FIELD_GRAD_SIGNATURES, **SAMPLE_GRAD_SIGNATURES}.items():
+                               **CONTRASTIVE_SIGNATURES, **FIELD_GRAD_SIGNATURES, **SAMPLE_GRAD_SIGNATURES,
+                               **EA_GRAD_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -4,7 +4,9 @@ kernels of include/isr_contrastive.h.  The (B, 1 + M, S) logits, their softmax a
 forward and backward recompute them tile by tile, so every negative of a key set is affordable, not a sample of them.
 
 `contrastive_loss` is the torch.autograd.Function underneath; the three wrappers carry the reference's names and arguments.
-Device tensors only: a CPU tensor raises IsrError, there is no CPU fallback.  Second derivatives are not provided."""
+Device tensors only: a CPU tensor raises IsrError, there is no CPU fallback.  Second derivatives are not provided.
+
+`huber` is trainNerfFine.py's smooth L1 term (nutil.py:157-164): elementwise torch ops, on any device."""
 from __future__ import annotations
 
 import torch
@@ -12,7 +14,7 @@ from torch.autograd.function import once_differentiable
 
 from . import ops
 
-__all__ = ["contrastive_loss", "returnCrossEntropy", "returnCrossEntropy2", "returnCrossEntropyWithNeg"]
+__all__ = ["contrastive_loss", "huber", "returnCrossEntropy", "returnCrossEntropy2", "returnCrossEntropyWithNeg"]
 
 
 class _ContrastiveLoss(torch.autograd.Function):
@@ -61,3 +63,10 @@ def returnCrossEntropy(q1, k1, negFrac=1, device=False):
 def returnCrossEntropy2(q1, k1, negFrac=1, negKeys=1, device=False):
     """nutil.returnCrossEntropy2 (nutil.py:386-403): as returnCrossEntropy with the caller's negKeys (an index tensor)."""
     return contrastive_loss(q1, k1, k1[:, negKeys, :], 1 / 1000)
+
+
+def huber(x: torch.Tensor, y: torch.Tensor, scaling: float = 0.1) -> torch.Tensor:
+    """nutil.huber (nutil.py:157-164): (sqrt(max(1 + (x - y)^2 / scaling^2, 1e-4)) - 1) * scaling, elementwise.  Torch's own
+    kernels, forward and backward."""
+    diff_sq = (x - y) ** 2
+    return ((1 + diff_sq / (scaling ** 2)).clamp(1e-4).sqrt() - 1) * float(scaling)

@@ -1338,6 +1338,72 @@ def ea_march_host(densities, features, threshold: float = -1.0):
     return image, wts
 
 
+# ---- the backward of ea_march (include/isr_ea_grad.h)
+def ea_grad_geometry() -> dict:
+    """isr_ea_grad_geometry: the threads of a workgroup, the most rays one workgroup owns and the floats of LDS per array."""
+    L = lib()
+    return {"threads": L.isr_ea_grad_geometry(0), "max_group_rays": L.isr_ea_grad_geometry(1),
+            "row_floats": L.isr_ea_grad_geometry(2)}
+
+
+def ea_grad_rays_per_group(P: int) -> int:
+    """isr_ea_grad_rays_per_group: the rays one workgroup of ea_march_backward owns at P samples per ray."""
+    r = lib().isr_ea_grad_rays_per_group(int(P))
+    if r < 1:
+        raise ValueError(f"ea_grad_rays_per_group: P = {P} (1..4096)")
+    return r
+
+
+def _ea_grad_shapes(name: str, densities, features, dimage, dweights, threshold, need) -> tuple[int, int, int, float]:
+    if densities.ndim != 2 or features.ndim != 3 or tuple(features.shape[:2]) != tuple(densities.shape):
+        raise ValueError(f"{name}: densities {tuple(densities.shape)} and features {tuple(features.shape)} must be (N,P) and (N,P,F)")
+    N, P, F = (int(v) for v in features.shape)
+    if P < 1 or F < 1:
+        raise ValueError(f"{name}: P < 1 or F < 1")
+    if tuple(dimage.shape) != (N, F + 1):
+        raise ValueError(f"{name}: dimage must be ({N},{F + 1}), got {tuple(dimage.shape)}")
+    if dweights is not None and tuple(dweights.shape) != (N, P):
+        raise ValueError(f"{name}: dweights must be ({N},{P}), got {tuple(dweights.shape)}")
+    thr = float(threshold)
+    if thr != thr:
+        raise ValueError(f"{name}: threshold is NaN")
+    if not (need[0] or need[1]):
+        raise ValueError(f"{name}: neither gradient is asked for")
+    return N, P, F, thr
+
+
+def ea_march_backward(densities: torch.Tensor, features: torch.Tensor, dimage: torch.Tensor, dweights: torch.Tensor | None = None,
+                      threshold: float = -1.0, need=(True, True)):
+    """isr_ea_march_backward: the gradient of ea_march.  densities (N,P), features (N,P,F), dimage (N,F+1) [features |
+    opacity] and dweights (N,P) or None (zeros), contiguous f32 on the device -> (ddensities (N,P), dfeatures (N,P,F)), None
+    where need[i] is false: an adjoint recurrence per ray with no division and no float atomics, a function of the
+    arguments only (include/isr_ea_grad.h).  In threshold mode ddensities is +0.  Nothing synchronises."""
+    dev = require_cuda(densities, features, dimage, dweights)
+    for t in (densities, features, dimage, dweights):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError("ea_march_backward: every tensor must be contiguous float32")
+    N, P, F, thr = _ea_grad_shapes("ea_march_backward", densities, features, dimage, dweights, threshold, need)
+    dd = torch.empty((N, P), dtype=torch.float32, device=dev) if need[0] else None
+    df = torch.empty((N, P, F), dtype=torch.float32, device=dev) if need[1] else None
+    with torch.cuda.device(dev), _timed("ea_march_backward", 4.0 * N * P * F):
+        rc = lib().isr_ea_march_backward(ptr(densities), ptr(features), N, P, F, thr, ptr(dimage), ptr(dweights), ptr(dd), ptr(df),
+                                         current_stream(dev))
+    check(rc, "isr_ea_march_backward")
+    return dd, df
+
+
+def ea_march_backward_host(densities, features, dimage, dweights=None, threshold: float = -1.0, need=(True, True)):
+    """isr_ea_march_backward_host: the same gradient as host code over NumPy arrays.  For tests."""
+    r, f, g = (np.ascontiguousarray(a, np.float32) for a in (densities, features, dimage))
+    w = None if dweights is None else np.ascontiguousarray(dweights, np.float32)
+    N, P, F, thr = _ea_grad_shapes("ea_march_backward_host", r, f, g, w, threshold, need)
+    dd = np.empty((N, P), np.float32) if need[0] else None
+    df = np.empty((N, P, F), np.float32) if need[1] else None
+    hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    check(lib().isr_ea_march_backward_host(hp(r), hp(f), N, P, F, thr, hp(g), hp(w), hp(dd), hp(df)), "isr_ea_march_backward_host")
+    return dd, df
+
+
 def _host_i32(v, B: int, what: str):
     """A HOST (B,) int32 array for the C ABI (None stays None)."""
     if v is None:

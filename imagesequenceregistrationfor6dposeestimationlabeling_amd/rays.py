@@ -248,11 +248,53 @@ class ProbabilisticRaysampler:
     forward = __call__
 
 
+def ea_march(rays_densities: torch.Tensor, rays_features: torch.Tensor, threshold: float = -1.0):
+    """rays_densities (..., P, 1) and rays_features (..., P, F) -> (images (..., F+1) [features | opacity], weights (..., P))
+    by ops.ea_march; threshold >= 0 is thresholdMode.  Inputs that are not f32 are cast first.
+    When gradients are enabled and an input requires one, the results carry it back (trainNerfFine.py:353 trains the fields
+    through this call): the values are the same bits, and the backward is ops.ea_march_backward, per ray an adjoint
+    recurrence with no division and no float atomics (include/isr_ea_grad.h), once differentiable.  The casts and reshapes
+    are torch ops, so a gradient arrives in its input's dtype and shape.  In thresholdMode the densities get zeros."""
+    lead, P, F = tuple(rays_features.shape[:-2]), rays_features.shape[-2], rays_features.shape[-1]
+    dens, feat = rays_densities.to(torch.float32).reshape(-1, P), rays_features.to(torch.float32).reshape(-1, P, F)
+    if torch.is_grad_enabled() and (dens.requires_grad or feat.requires_grad):
+        image, wts = _EaMarch.apply(dens, feat, float(threshold))
+    else:
+        image, wts = ops.ea_march(dens.contiguous(), feat.contiguous(), threshold, want_weights=True)
+    return image.reshape(*lead, F + 1), wts.reshape(*lead, P)
+
+
+class _EaMarch(torch.autograd.Function):
+    """densities (N,P), features (N,P,F) f32 -> image (N,F+1), weights (N,P): ops.ea_march forward, ops.ea_march_backward
+    backward.  An output nobody used arrives as None: a null dweights, or zeros for dimage."""
+
+    @staticmethod
+    def forward(ctx, densities, features, threshold):
+        dens, feat = densities.detach().contiguous(), features.detach().contiguous()
+        image, wts = ops.ea_march(dens, feat, threshold, want_weights=True)
+        ctx.save_for_backward(dens, feat)
+        ctx.threshold = threshold
+        ctx.set_materialize_grads(False)
+        return image, wts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dimage, dweights):
+        dens, feat = ctx.saved_tensors
+        if dimage is None and dweights is None:
+            return None, None, None
+        if dimage is None:
+            dimage = torch.zeros((feat.shape[0], feat.shape[2] + 1), dtype=torch.float32, device=feat.device)
+        dd, df = ops.ea_march_backward(dens, feat, ops._f32c(dimage), None if dweights is None else ops._f32c(dweights),
+                                       ctx.threshold, need=ctx.needs_input_grad[:2])
+        return dd, df, None
+
+
 class EmissionAbsorptionRaymarcherStratified:
     """pren.py:256-369: rays_densities (..., P, 1) and rays_features (..., P, F) -> (images (..., F+1) [features |
-    opacity], weights (..., P)) by ops.ea_march.  thresholdMode marches the densities above `threshold` as ones.  The
-    attributes stay assignable after construction (genFeat.py:132); weightMode and a surface_thickness other than 1 raise
-    NotImplementedError when the marcher is called."""
+    opacity], weights (..., P)) by ea_march above, which carries gradients to both inputs when they require one.
+    thresholdMode marches the densities above `threshold` as ones.  The attributes stay assignable after construction
+    (genFeat.py:132); weightMode and a surface_thickness other than 1 raise NotImplementedError when the marcher is called."""
 
     def __init__(self, surface_thickness: int = 1, thresholdMode: bool = False, weightMode: bool = False, threshold: float = 0.03):
         self.surface_thickness = surface_thickness
@@ -277,10 +319,7 @@ class EmissionAbsorptionRaymarcherStratified:
         if rays_densities.shape[-1] != 1 or rays_features.shape[:-1] != rays_densities.shape[:-1]:
             raise ValueError(f"EmissionAbsorptionRaymarcherStratified: densities {tuple(rays_densities.shape)}, features "
                              f"{tuple(rays_features.shape)}: expected (..., P, 1) and (..., P, F)")
-        lead, P, F = tuple(rays_features.shape[:-2]), rays_features.shape[-2], rays_features.shape[-1]
-        image, wts = ops.ea_march(rays_densities.to(torch.float32).reshape(-1, P).contiguous(),
-                                  rays_features.to(torch.float32).reshape(-1, P, F).contiguous(), thr, want_weights=True)
-        return image.reshape(*lead, F + 1), wts.reshape(*lead, P)
+        return ea_march(rays_densities, rays_features, thr)
 
     forward = __call__
 
@@ -329,10 +368,7 @@ class ImplicitRendererStratified:
         if field is not None:
             return field.render(bundle, threshold=-1.0, return_weights=True)[1]
         rays_densities, rays_features = volumetric_function(ray_bundle=bundle, cameras=cameras, **kwargs)
-        lead, P, F = tuple(rays_features.shape[:-2]), rays_features.shape[-2], rays_features.shape[-1]
-        _, wts = ops.ea_march(rays_densities.to(torch.float32).reshape(-1, P).contiguous(),
-                              rays_features.to(torch.float32).reshape(-1, P, F).contiguous(), -1.0, want_weights=True)
-        return wts.reshape(*lead, P)
+        return ea_march(rays_densities, rays_features, -1.0)[1]
 
     def __call__(self, cameras, volumetric_function, stratified: bool = False, maskRays: bool = False, mask=False,
                  add_input_samples: bool = False, coarse=None, **kwargs):

@@ -6,14 +6,20 @@ encoder and the key field are trained together, and every gradient the package c
 The encoder is unpinned: the reference's UNet (dep/unet.py) is not part of it, so `encoder` is any torch.nn.Module that maps
 (B, 3, H, W) to (B, 13, H, W), and its own layers, forward and backward, are torch's.  Out of scope: the data loader, the
 learning-rate ramp of trainPose.py:229-236, checkpoints, the back-face keys (computed by trainPose.py:380, unused by its
-loss) and the maskRays=False branch."""
+loss) and the maskRays=False branch.
+
+nerf_train_step is one optimisation step of trainNerfFine.py:238-354 the same way: a coarse and a fine render through
+rays.ImplicitRendererStratified, whose march carries gradients to the fields' densities and features (isr_ea_march_backward),
+the targets sampled at the rays, and losses.huber.  The two fields are unpinned: any callables that map a ray bundle to
+(densities, features), differentiated by torch.  Out of scope: the loader, checkpoints, visualisation and trainNerfFine.py's
+batch_idx bookkeeping (the caller passes the batch's cameras and targets)."""
 from __future__ import annotations
 
 import torch
 
 from . import losses, rays
 
-__all__ = ["pose_train_step"]
+__all__ = ["nerf_train_step", "pose_train_step"]
 
 
 def pose_train_step(encoder: torch.nn.Module, field, optimizer: torch.optim.Optimizer, rgb: torch.Tensor, mask: torch.Tensor,
@@ -41,3 +47,31 @@ def pose_train_step(encoder: torch.nn.Module, field, optimizer: torch.optim.Opti
     loss.backward()                                                                   # :449
     optimizer.step()                                                                  # :450
     return {"loss": loss.detach(), "feature_loss": feature_loss.detach(), "mask_loss": mask_loss.detach()}
+
+
+def nerf_train_step(coarse_field, fine_field, renderer_coarse, renderer_fine, optimizer: torch.optim.Optimizer, cameras,
+                    target_images: torch.Tensor, target_silhouettes: torch.Tensor) -> dict:
+    """cameras: the batch's B rays.PerspectiveCameras; target_images (B, H, W, F) and target_silhouettes (B, H, W) on the
+    device -> dict(loss, color_err, sil_err) of detached 0-d tensors, after one optimizer step.  The fields are callables
+    (ray_bundle=..., cameras=...) -> (densities (..., P, 1), features (..., P, F)); renderer_coarse and renderer_fine are
+    rays.ImplicitRendererStratified over a Monte-Carlo sampler, renderer_fine built with fine_seed."""
+    optimizer.zero_grad()                                                             # trainNerfFine.py:238
+    rendered, sampled_rays, weights = renderer_coarse(cameras=cameras, volumetric_function=coarse_field,
+                                                      add_input_samples=False, stratified=False)      # :288-291
+    rendered_fine, sampled_rays2, _ = renderer_fine(cameras=cameras, volumetric_function=fine_field, add_input_samples=True,
+                                                    stratified=True, coarse=(sampled_rays, weights.detach()))      # :294-300
+    xys = sampled_rays2.xys                                                           # :301
+    last = rendered.shape[-1]
+    images, silhouettes = rendered.split([last - 1, 1], dim=-1)                       # :306-308
+    images_fine, silhouettes_fine = rendered_fine.split([last - 1, 1], dim=-1)        # :310-312
+    silhouettes_at_rays = rays.sample_images_at_mc_locs(target_silhouettes[..., None], xys)      # :314-317
+    colors_at_rays = rays.sample_images_at_mc_locs(target_images, xys)                # :320-323
+    sil_err = losses.huber(silhouettes, silhouettes_at_rays).abs().mean()             # :324
+    color_err = losses.huber(images, colors_at_rays).abs().mean()                     # :326
+    sil_err = sil_err + losses.huber(silhouettes_fine, silhouettes_at_rays).abs().mean()      # :328
+    color_err = color_err + losses.huber(images_fine, colors_at_rays).abs().mean()    # :329
+    sil_err, color_err = 500 * sil_err, 500 * color_err                               # :334-335
+    loss = color_err + sil_err                                                        # :336
+    loss.backward()                                                                   # :353
+    optimizer.step()                                                                  # :354
+    return {"loss": loss.detach(), "color_err": color_err.detach(), "sil_err": sil_err.detach()}
