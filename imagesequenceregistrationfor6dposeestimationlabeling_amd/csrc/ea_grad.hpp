@@ -7,18 +7,15 @@
 // backward of cumprod, which divides by 1 - c and takes a special path where that is exactly 0, and a few dozen launches
 // over (N, P) and (N, P, F) temporaries.  Here the adjoint of the transmittance is a recurrence with no division.
 //
-// The forward chain is RayState::step's (csrc/field_radiance.hpp) restated: w_k = c_k * T_k, T_{k+1} = T_k * (1 - c_k).
-// tests/test_ea_grad_cpu.py holds the two to the same bits.
+// The forward chain is csrc/ea_chain.hpp's, w_k = c_k * T_k, T_{k+1} = T_k * (1 - c_k) with its absorbance; transmittance
+// below keeps every T_k, which the backward needs and the forward's running state does not.  tests/test_ea_grad_cpu.py holds
+// the two to the same bits.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <vector>
 
-#if defined(__HIPCC__)
-#define ISR_EA_FN __host__ __device__ inline
-#else
-#define ISR_EA_FN inline
-#endif
+#include "ea_chain.hpp"
 
 namespace isr {
 namespace ea_grad {
@@ -50,11 +47,7 @@ inline const char* check_call(const void* densities, const void* features, int N
   return nullptr;
 }
 
-// c_k: the density itself, or in threshold mode a step function of it
-ISR_EA_FN float absorbance(float rho, float threshold) {
-  if (threshold >= 0.f) return rho > threshold ? 1.0f : 0.0f;
-  return rho;
-}
+using ea::absorbance;      // c_k: the density itself, or in threshold mode a step function of it
 
 // g_k, everything that reaches w_k from above: dweights[k], then the image's channels in ascending order
 ISR_EA_FN float upstream(const float* dimage, const float* feat, int F, float dweight) {

@@ -1,24 +1,16 @@
 // field_density.hip — the density field (field_density.hpp) and the ray march on top of it, each ONE launch: the entries of
 // include/isr_density.h.
 //
-// field_tile.hpp's design with 8 waves per workgroup (512 threads, two per SIMD): wave w takes neuron block w of a 256-wide
-// layer over both point blocks.  What is the density field's own:
-//   * The first layer's input is the harmonic embedding, computed in the kernel into LDS (sincos32, one call per sine /
-//     cosine pair).  The activation buffer holds 384 k's x 64 points = 96 KB, so one workgroup is resident per CU.  Neither
-//     the (N, 6H) embedding nor a hidden activation is ever in device memory.
-//   * Every hidden layer runs on the matrix cores, also a first layer narrower than 32 (K is padded to 8 with zero weights
-//     and zero activations).
-//   * The output neuron is a dot product on the vector unit: lane p of wave 0 runs the chain of point p.
+// field_trunk.hpp's scheme: a workgroup of 8 waves takes 64 points at a time through the trunk in LDS, so that neither the
+// (N, 6H) embedding nor a hidden activation is ever in device memory, and owns whole rays.
 //   * density_march_kernel makes its points from (origin, direction, length) in the kernel, o + d * len.
-// A WORKGROUP OWNS WHOLE RAYS: G = max(1, 64 / P) consecutive rays, their G * P points taken 64 at a time; the densities of
-// its rays stay in LDS (P <= 4096), then thread g marches ray g.  In threshold mode with one ray per workgroup and no
-// densities asked for, the tiles after the one holding the first hit are not evaluated: march_ray multiplies whatever they
-// would give by 0, so no output bit depends on it.  The march from the far end (isr_density_march_dir, march_ray_back) does
-// the same from the other side, and both directions together skip the tiles between the first and the last hit.
+//   * The densities of a workgroup's rays stay in LDS (P <= 4096), then thread g marches ray g.  In threshold mode with one
+//     ray per workgroup and no densities asked for, the tiles after the one holding the first hit are not evaluated:
+//     march_ray multiplies whatever they would give by 0, so no output bit depends on it.  The march from the far end
+//     (isr_density_march_dir, march_ray_back) does the same from the other side, and both directions together skip the tiles
+//     between the first and the last hit.
 // Rows past the end of a tile's work are evaluated at the origin and never written.
-#include "field_density.hpp"
-#include "field_tile.hpp"
-#include "isr_common.hpp"
+#include "field_trunk.hpp"
 
 #include "../../include/isr_density.h"
 #include "../../include/isr_density_dir.h"
@@ -28,44 +20,6 @@
 namespace {
 
 using namespace isr::density;
-using isr::field::act_index;
-using isr::field::kTP;
-
-constexpr int kThreads = 512;
-constexpr int kActWords = (6 * kMaxH / 2) * kTP * 2;      // 96 KB
-
-// The 64 points of ptl (LDS, coordinate-major: ptl[d * 64 + p]) through the field; density of point p -> dens[p] (LDS).
-// Every thread of the workgroup calls it; ptl may be rewritten after the call, dens is complete after the next barrier.
-__device__ __forceinline__ void tile_density(const Layout& lay, const float* __restrict__ pack, float* act, const float* ptl,
-                                             float* dens) {
-  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const int H = lay.H;
-  const float beta = pack[0];
-  const float* freqs = pack + kFreqOff;
-
-  // the embedding: k = d * H + i holds the sine, 3H + k the cosine; k in [6H, kstride) zeros
-  for (int i = tid; i < 3 * H * kTP; i += kThreads) {
-    const int p = i & (kTP - 1), kk = i >> 6;
-    const int d = kk / H, fi = kk - d * H;
-    const float a = ptl[d * kTP + p] * freqs[fi];
-    float s, c;
-    sincos32(a, &s, &c);
-    act[act_index(kk, p)] = s;
-    act[act_index(3 * H + kk, p)] = c;
-  }
-  for (int i = tid; i < (lay.L[0].kstride - 6 * H) * kTP; i += kThreads) act[act_index(6 * H + (i >> 6), i & (kTP - 1))] = 0.f;
-  __syncthreads();
-
-  for (int l = 0; l < lay.n_hidden; ++l)
-    isr::field::mfma_tile_layer<kThreads / 64>(lay.L[l], pack, act, false, [=](float z) { return softplus32(z, beta); });
-
-  if (w == 0) {                   // the output neuron: the chain itself, lane = point
-    const float* wo = pack + lay.out_w_off;
-    float z = pack[lay.out_b_off];
-    for (int k = 0; k < lay.out_K; ++k) z = fmaf(wo[k], act[act_index(k, lane)], z);
-    dens[lane] = density32(softplus32(z, beta));
-  }
-}
 
 __global__ __launch_bounds__(kThreads) void density_eval_kernel(Layout lay, const float* __restrict__ pack,
                                                                 const float* __restrict__ pts, int N, float* __restrict__ out) {
@@ -80,7 +34,7 @@ __global__ __launch_bounds__(kThreads) void density_eval_kernel(Layout lay, cons
     ptl[tid] = row < N ? pts[3 * row + d] : 0.f;
   }
   __syncthreads();
-  tile_density(lay, pack, act, ptl, dens);
+  tile_trunk(lay, pack, act, ptl, dens);
   __syncthreads();
   if (tid < kTP && row0 + tid < N) out[row0 + tid] = dens[tid];
 }
@@ -104,28 +58,18 @@ __global__ __launch_bounds__(kThreads) void density_march_kernel(Layout lay, con
   __shared__ float ptl[3 * kTP];
   __shared__ float dens[kMaxP];
   const int tid = threadIdx.x;
-  const long ray0 = (long)blockIdx.x * G;
-  const int nr = (long)N - ray0 < G ? (int)((long)N - ray0) : G;
-  const int total = nr * P;                          // <= max(64, P) <= kMaxP
-  const int T = (total + kTP - 1) / kTP;
+  const RayGroup rg(N, P, G);
+  const long ray0 = rg.ray0;
+  const int total = rg.total, T = rg.tiles;
   const bool early = threshold >= 0.f && dens_out == nullptr && G == 1;
   // tile t through the field -> dens[t * 64 ..); with `early`, whether one of its samples is above the threshold
   auto tile = [&](int t) -> bool {
-    const int q = t * kTP + (tid & 63);
-    if (tid < 3 * kTP) {
-      const int d = tid >> 6;
-      float v = 0.f;
-      if (q < total) {
-        const int g = q / P, k = q - g * P;
-        const long ray = ray0 + g;
-        v = origins[3 * ray + d] + directions[3 * ray + d] * lengths[ray * P + k];
-      }
-      ptl[tid] = v;
-    }
+    tile_points_from_rays(rg, P, t, origins, directions, lengths, ptl);
     __syncthreads();
-    tile_density(lay, pack, act, ptl, dens + t * kTP);
+    tile_trunk(lay, pack, act, ptl, dens + t * kTP);
     __syncthreads();
     if (!early) return false;
+    const int q = t * kTP + (tid & 63);
     const int found = tid < kTP && q < total && dens[q] > threshold;
     return __syncthreads_or(found) != 0;
   };
@@ -147,7 +91,7 @@ __global__ __launch_bounds__(kThreads) void density_march_kernel(Layout lay, con
   if (dens_out)
     for (int q = tid; q < total; q += kThreads) dens_out[ray0 * P + q] = dens[q];
   if (kDir != 0) __syncthreads();                    // march_ray_back overwrites the densities it reads
-  if (tid < nr) {
+  if (tid < rg.nr) {
     const long ray = ray0 + tid;
     float* rho = dens + tid * P;                     // G > 1: every point was evaluated
     float dep;
@@ -179,33 +123,6 @@ int check_field(const char* who, const void* pack, size_t pack_bytes, int n_hidd
               who, n_hidden, kMaxHidden, kMaxWidth, H, kMaxH);
   return isr::check_pack_bytes(who, pack_bytes, lay.total_words);
 }
-
-int check_march(const char* who, const float* origins, const float* directions, const float* lengths, int N, int P,
-                float threshold, const float* depth, const float* points, const int32_t* hit) {
-  if (int rc = isr::check_rows(who, N, origins && directions && lengths && depth && points && hit)) return rc;
-  ISR_REQUIRE(P >= 1 && P <= kMaxP, "%s: P = %d (1..%d)", who, P, kMaxP);
-  ISR_REQUIRE(threshold == threshold, "%s: threshold is NaN", who);
-  return ISR_OK;
-}
-
-struct HostField {
-  std::vector<std::vector<float>> wt;
-  HostWeights hw;
-  bool fma;
-  HostField(const Layout& lay, const void* pack) {
-    wt.resize(lay.n_hidden);
-    for (int l = 0; l < lay.n_hidden; ++l) {
-      wt[l].resize((size_t)lay.L[l].O * lay.L[l].K);
-      isr::field::unpack_layer(lay.L[l], static_cast<const float*>(pack), wt[l].data(), true);
-      hw.Wt[l] = wt[l].data();
-    }
-#ifdef ISR_DENSITY_HAVE_FMA_BUILD
-    fma = __builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2");
-#else
-    fma = false;
-#endif
-  }
-};
 
 float point_host(const Layout& lay, const void* pack, const HostField& hf, const float* x) {
 #ifdef ISR_DENSITY_HAVE_FMA_BUILD
@@ -255,10 +172,10 @@ int march_device(const char* who, const void* pack, size_t pack_bytes, int n_hid
                  float* densities, float* weights, float* depth, float* points, int32_t* hit, isr_stream_t stream) {
   Layout lay;
   if (int rc = check_field(who, pack, pack_bytes, n_hidden, widths, H, lay)) return rc;
-  if (int rc = check_march(who, origins, directions, lengths, N, P, threshold, depth, points, hit)) return rc;
+  if (int rc = check_march(who, N, origins && directions && lengths && depth && points && hit, P, threshold)) return rc;
   ISR_REQUIRE(direction >= 0 && direction <= 2, "%s: direction = %d (0 front, 1 back, 2 both)", who, direction);
   if (N == 0) return ISR_OK;
-  const int G = P >= kTP ? 1 : kTP / P;
+  const int G = rays_per_group(P);
   const unsigned blocks = (unsigned)(((long)N + G - 1) / G);
   const float* pk = static_cast<const float*>(pack);
   hipStream_t st = isr::as_stream(stream);
@@ -275,12 +192,25 @@ int march_device(const char* who, const void* pack, size_t pack_bytes, int n_hid
   return ISR_OK;
 }
 
+// The marches of ray `ray` of N for `direction`, as the entries lay their outputs out: the back march of "both" follows the
+// front march's N rows, and a ray's weights are then 2P wide.  rho: the ray's P densities, which the back march overwrites.
+void march_ray_host(long ray, int N, int P, const float* lengths, float* rho, float threshold, int direction, float* weights,
+                    float* depth, int32_t* hit) {
+  const float* len = lengths + ray * P;
+  float* w = weights ? weights + ray * (direction == 2 ? 2L * P : P) : nullptr;
+  if (direction != 1) march_ray(P, len, rho, P, threshold, w, &depth[ray], &hit[ray]);
+  if (direction != 0) {
+    const long out = direction == 2 ? (long)N + ray : ray;
+    march_ray_back(P, len, rho, 0, threshold, w ? (direction == 2 ? w + P : w) : nullptr, &depth[out], &hit[out]);
+  }
+}
+
 int march_host(const char* who, const void* pack, size_t pack_bytes, int n_hidden, const int32_t* widths, int H,
                const float* origins, const float* directions, const float* lengths, int N, int P, float threshold, int direction,
                float* densities, float* weights, float* depth, float* points, int32_t* hit) {
   Layout lay;
   if (int rc = check_field(who, pack, pack_bytes, n_hidden, widths, H, lay)) return rc;
-  if (int rc = check_march(who, origins, directions, lengths, N, P, threshold, depth, points, hit)) return rc;
+  if (int rc = check_march(who, N, origins && directions && lengths && depth && points && hit, P, threshold)) return rc;
   ISR_REQUIRE(direction >= 0 && direction <= 2, "%s: direction = %d (0 front, 1 back, 2 both)", who, direction);
   if (N == 0) return ISR_OK;
   const HostField hf(lay, pack);
@@ -293,20 +223,10 @@ int march_host(const char* who, const void* pack, size_t pack_bytes, int n_hidde
   });
   if (densities)
     for (size_t q = 0; q < rho.size(); ++q) densities[q] = rho[q];
-  const long wld = direction == 2 ? 2L * P : P;
   for (long ray = 0; ray < N; ++ray) {
-    const float* len = lengths + ray * P;
-    float* r = rho.data() + ray * P;
-    float* w = weights ? weights + ray * wld : nullptr;
-    if (direction != 1) {
-      march_ray(P, len, r, P, threshold, w, &depth[ray], &hit[ray]);
-      for (int d = 0; d < 3; ++d) points[3 * ray + d] = origins[3 * ray + d] + directions[3 * ray + d] * depth[ray];
-    }
-    if (direction != 0) {
-      const long out = direction == 2 ? (long)N + ray : ray;
-      march_ray_back(P, len, r, 0, threshold, w ? (direction == 2 ? w + P : w) : nullptr, &depth[out], &hit[out]);
+    march_ray_host(ray, N, P, lengths, rho.data() + ray * P, threshold, direction, weights, depth, hit);
+    for (long out = ray; out < (direction == 2 ? 2L : 1L) * N; out += N)
       for (int d = 0; d < 3; ++d) points[3 * out + d] = origins[3 * ray + d] + directions[3 * ray + d] * depth[out];
-    }
   }
   return ISR_OK;
 }
@@ -359,21 +279,12 @@ extern "C" int isr_density_march_dir_host(const void* pack, size_t pack_bytes, i
 extern "C" int isr_density_march_given_host(const float* lengths, const float* rho, int N, int P, float threshold, int direction,
                                             float* weights, float* depth, int32_t* hit) {
   const char* who = "isr_density_march_given_host";
-  if (int rc = isr::check_rows(who, N, lengths && rho && depth && hit)) return rc;
-  ISR_REQUIRE(P >= 1 && P <= kMaxP, "%s: P = %d (1..%d)", who, P, kMaxP);
-  ISR_REQUIRE(threshold == threshold, "%s: threshold is NaN", who);
+  if (int rc = check_march(who, N, lengths && rho && depth && hit, P, threshold)) return rc;
   ISR_REQUIRE(direction >= 0 && direction <= 2, "%s: direction = %d (0 front, 1 back, 2 both)", who, direction);
   std::vector<float> r((size_t)P);
-  const long wld = direction == 2 ? 2L * P : P;
   for (long ray = 0; ray < N; ++ray) {
     for (int k = 0; k < P; ++k) r[k] = rho[ray * P + k];
-    float* w = weights ? weights + ray * wld : nullptr;
-    if (direction != 1) march_ray(P, lengths + ray * P, r.data(), P, threshold, w, &depth[ray], &hit[ray]);
-    if (direction != 0) {
-      const long out = direction == 2 ? (long)N + ray : ray;
-      march_ray_back(P, lengths + ray * P, r.data(), 0, threshold, w ? (direction == 2 ? w + P : w) : nullptr, &depth[out],
-                     &hit[out]);
-    }
+    march_ray_host(ray, N, P, lengths, r.data(), threshold, direction, weights, depth, hit);
   }
   return ISR_OK;
 }

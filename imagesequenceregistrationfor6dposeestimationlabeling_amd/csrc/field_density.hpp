@@ -23,6 +23,9 @@
 // field_mlp.hpp's matrix-core order (w_index, every layer, kstride = in rounded up to 8) and the bias, zero padded to 32 rows;
 // then the output neuron's weights (row-major, padded to 4) and its bias (4 words).
 #pragma once
+#include <vector>
+
+#include "ea_chain.hpp"
 #include "field_mlp.hpp"
 
 namespace isr {
@@ -226,42 +229,24 @@ ISR_FIELD_FN float density32(float s) {
   return (float)(-(tk * p + (tk - 1.0)));
 }
 
-// The march of one ray (pren.py:338-365 with surface_thickness = 1, _shifted_cumprod's default shift).
-//   threshold >= 0 (thresholdMode): c_k = rho_k > threshold ? 1 : 0 (NaN: 0), w_k = c_k * prod_{j<k} (1 - c_j): one-hot at
-//       the first hit.  The reference writes (1.0 + 1e-10) - c, which is 1 - c in f32: the f64 scalar rounds to 1.0f.
-//   threshold < 0: w_k = rho_k * prod_{j<k} (1 - rho_j), the product taken sequentially in f32 for k ascending.
-//   depth = max_k(len_k * w_k), the maximum of the PRODUCTS starting from the first one (torch.max: a NaN product makes the
-//       depth NaN; with negative lengths the depth can be negative or -0); hit = any(w_k != 0).
-// Only rho[0 .. n_eval) is read: in threshold mode a caller may stop evaluating a ray after its first hit, the later c_k
+// The march of one ray: ea_chain.hpp's chain, threshold >= 0 (thresholdMode) or the emission-absorption weights.
+// Only rho[0 .. n_eval) counts: in threshold mode a caller may stop evaluating a ray after its first hit, the later c_k
 // are multiplied by 0 whatever they are.  weights may be null.
 ISR_FIELD_FN void march_ray(int P, const float* len, const float* rho, int n_eval, float threshold, float* weights, float* depth,
                             int32_t* hit) {
-  float absorb = 1.0f, m = 0.f;
-  int32_t any = 0;
+  ea::WeightChain ch;
+  ch.start();
   for (int k = 0; k < P; ++k) {
-    float w;
-    if (threshold >= 0.f) {
-      const float c = (k < n_eval && rho[k] > threshold) ? 1.0f : 0.0f;
-      w = c * absorb;
-      absorb = absorb * (1.0f - c);
-    } else {
-      const float d = rho[k];
-      w = d * absorb;
-      absorb = absorb * (1.0f - d);
-    }
+    const float w = ch.step(k, len[k], ea::absorbance(rho[k], threshold, k < n_eval));
     if (weights) weights[k] = w;
-    if (w != 0.f) any = 1;
-    const float v = len[k] * w;
-    if (k == 0) m = v;
-    else if (m == m && (v != v || v > m)) m = v;      // a NaN stays
   }
-  *depth = m;
-  *hit = any;
+  *depth = ch.m;
+  *hit = ch.any;
 }
 
 // The march of the same ray taken from its far end (prenBack.py:378-381: weights2 = rho * flip(shifted_cumprod(1 - flip(rho)))).
-//   A_{P-1} = 1, A_k = A_{k+1} * (1 - c_{k+1}) for k descending; c_k as in march_ray (threshold >= 0: rho_k > threshold ? 1 : 0,
-//   a NaN gives 0; threshold < 0: rho_k); w2_k = c_k * A_k: in threshold mode one-hot at the LAST hit, the exit point.
+//   A_{P-1} = 1, A_k = A_{k+1} * (1 - c_{k+1}) for k descending; c_k as in march_ray (ea::absorbance); w2_k = c_k * A_k: in
+//   threshold mode one-hot at the LAST hit, the exit point.
 //   depth = max_k(len_k * w2_k), taken for k ascending from the first product with march_ray's NaN rule; hit = any(w2_k != 0).
 // Only rho[lo_eval .. P) is read: in threshold mode a caller may leave the samples in front of the tile holding the last hit
 // unevaluated, their c_k is multiplied by A_k = 0 whatever it is.  rho[lo_eval .. P) is OVERWRITTEN with the weights (the
@@ -270,22 +255,19 @@ ISR_FIELD_FN void march_ray_back(int P, const float* len, float* rho, int lo_eva
                                  int32_t* hit) {
   float absorb = 1.0f;
   for (int k = P - 1; k >= lo_eval; --k) {
-    const float c = threshold >= 0.f ? (rho[k] > threshold ? 1.0f : 0.0f) : rho[k];
+    const float c = ea::absorbance(rho[k], threshold);
     rho[k] = c * absorb;
     absorb = absorb * (1.0f - c);
   }
-  float m = 0.f;
-  int32_t any = 0;
+  ea::WeightChain ch;
+  ch.start();
   for (int k = 0; k < P; ++k) {
     const float w = k >= lo_eval ? rho[k] : 0.0f;      // in front of lo_eval: c_k * A_k with A_k = 0 and c_k 0 or 1
     if (weights) weights[k] = w;
-    if (w != 0.f) any = 1;
-    const float v = len[k] * w;
-    if (k == 0) m = v;
-    else if (m == m && (v != v || v > m)) m = v;      // a NaN stays
+    ch.take(k, len[k], w);
   }
-  *depth = m;
-  *hit = any;
+  *depth = ch.m;
+  *hit = ch.any;
 }
 
 // Host: W (row-major, hidden layers then the output row), b -> pack (lay.total_words words)
@@ -321,16 +303,17 @@ struct HostWeights {
   const float* Wt[kMaxHidden];
 };
 
-// one point through the field; the k loop is outermost and ascending, each z_j sees its own k-ordered fmaf chain.  Inlined
-// into its two callers below, so that each compiles the loops for its own instruction set.
-__attribute__((always_inline)) inline float point_density_body(const Layout& lay, const void* pack, const HostWeights& hw,
-                                                               const float* x) {
-  float e[6 * kMaxH], z[kMaxWidth], g[kMaxWidth];
+// one point through the trunk: the embedding, the hidden layers, the output neuron -> the last hidden activations (in z or
+// g, lay.out_K of them) and *dens.  The k loop is outermost and ascending, each z_j sees its own k-ordered fmaf chain.
+// Inlined into its callers, so that each compiles the loops for its own instruction set.
+__attribute__((always_inline)) inline const float* trunk_body(const Layout& lay, const void* pack, const HostWeights& hw,
+                                                              const float* x, float* z, float* g, float* dens) {
+  float e[6 * kMaxH];
   const float* pf = static_cast<const float*>(pack);
   const float beta = pf[0];
   embed_point(x, pf + kFreqOff, lay.H, e);
   const float* h = e;
-  for (int l = 0; l < lay.n_hidden; ++l) {
+  for (int l = 0; l < lay.n_hidden; ++l) {              // n_hidden >= 1: e does not outlive the call
     const Layer& L = lay.L[l];
     const float* wt = hw.Wt[l];
     for (int j = 0; j < L.O; ++j) z[j] = pf[L.b_off + j];
@@ -339,12 +322,20 @@ __attribute__((always_inline)) inline float point_density_body(const Layout& lay
       const float* wk = wt + (size_t)k * L.O;
       for (int j = 0; j < L.O; ++j) z[j] = __builtin_fmaf(wk[j], hk, z[j]);
     }
-    for (int j = 0; j < L.O; ++j) g[j] = softplus32(z[j], beta);
+    for (int j = 0; j < L.O; ++j) g[j] = softplus32(z[j], beta);      // every z is complete: h may be g
     h = g;
   }
   float zo = pf[lay.out_b_off];
   for (int k = 0; k < lay.out_K; ++k) zo = __builtin_fmaf(pf[lay.out_w_off + k], h[k], zo);
-  return density32(softplus32(zo, beta));
+  *dens = density32(softplus32(zo, beta));
+  return h;
+}
+
+__attribute__((always_inline)) inline float point_density_body(const Layout& lay, const void* pack, const HostWeights& hw,
+                                                               const float* x) {
+  float z[kMaxWidth], g[kMaxWidth], dens;
+  trunk_body(lay, pack, hw, x, z, g, &dens);
+  return dens;
 }
 
 inline float point_density_host(const Layout& lay, const void* pack, const HostWeights& hw, const float* x) {
@@ -360,6 +351,26 @@ __attribute__((target("avx2,fma"))) inline float point_density_host_fma(const La
 }
 #define ISR_DENSITY_HAVE_FMA_BUILD 1
 #endif
+
+// Host: a pack's hidden layers unpacked and transposed, and whether this CPU runs the _fma builds
+struct HostField {
+  std::vector<std::vector<float>> wt;
+  HostWeights hw;
+  bool fma;
+  HostField(const Layout& lay, const void* pack) {
+    wt.resize(lay.n_hidden);
+    for (int l = 0; l < lay.n_hidden; ++l) {
+      wt[l].resize((size_t)lay.L[l].O * lay.L[l].K);
+      field::unpack_layer(lay.L[l], static_cast<const float*>(pack), wt[l].data(), true);
+      hw.Wt[l] = wt[l].data();
+    }
+#ifdef ISR_DENSITY_HAVE_FMA_BUILD
+    fma = __builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2");
+#else
+    fma = false;
+#endif
+  }
+};
 
 }  // namespace density
 }  // namespace isr

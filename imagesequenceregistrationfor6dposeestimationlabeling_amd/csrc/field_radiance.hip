@@ -1,9 +1,9 @@
 // field_radiance.hip — the radiance field (field_radiance.hpp) rendered into per-ray images, and the emission-absorption
 // march alone: the entries of include/isr_radiance.h.
 //
-// field_density.hip's scheme: 8 waves per workgroup, a workgroup owns G = max(1, 64 / P) consecutive rays and takes their
-// G * P points 64 at a time through the field in LDS (field_tile.hpp).  Per tile: the embedding, the hidden layers on the
-// matrix cores, the density neuron on h (wave 0, lane = point), colour layer 1 in place over h, softplus, colour layer 2
+// field_trunk.hpp's scheme: 8 waves per workgroup, a workgroup owns G = max(1, 64 / P) consecutive rays and takes their
+// G * P points 64 at a time through the field in LDS.  Per tile: the density trunk (tile_trunk: the embedding, the hidden
+// layers on the matrix cores, the density neuron on h), colour layer 1 in place over h, softplus, colour layer 2
 // and the sigmoid into the tile's (64, C) colours at the front of the activation buffer; then thread g advances the render
 // of ray g (RayState: T, feat_c, depth, hit in registers) over the tile's samples of its ray in k order.  Nothing per point
 // reaches device memory unless densities, colours or weights is asked for.
@@ -18,8 +18,7 @@
 //     poisons the features as the full evaluation does.
 // Rows past the end of a tile's work are evaluated at the origin with the workgroup's first ray's term and never written.
 #include "field_radiance.hpp"
-#include "field_tile.hpp"
-#include "isr_common.hpp"
+#include "field_trunk.hpp"
 
 #include "../../include/isr_radiance.h"
 
@@ -28,33 +27,15 @@
 namespace {
 
 using namespace isr::radiance;
-using isr::density::embed_point;
-using isr::density::density32;
-using isr::density::kFreqOff;
-using isr::density::sincos32;
+using isr::density::check_march;
+using isr::density::kActWords;
+using isr::density::kThreads;
+using isr::density::RayGroup;
 using isr::density::softplus32;
-using isr::field::act_index;
+using isr::density::tile_embed;
+using isr::density::tile_points_from_rays;
+using isr::density::tile_trunk;
 using isr::field::kTP;
-
-constexpr int kThreads = 512;
-constexpr int kActWords = (6 * kMaxH / 2) * kTP * 2;      // 96 KB
-
-// e (6H) of the 64 points of ptl (coordinate-major) into act, k in [6H, kstride) zeros; a barrier behind it
-__device__ __forceinline__ void tile_embed(int H, int kstride, const float* __restrict__ pack, float* act, const float* ptl) {
-  const int tid = threadIdx.x;
-  const float* freqs = pack + kFreqOff;
-  for (int i = tid; i < 3 * H * kTP; i += kThreads) {
-    const int p = i & (kTP - 1), kk = i >> 6;
-    const int d = kk / H, fi = kk - d * H;
-    const float a = ptl[d * kTP + p] * freqs[fi];
-    float s, c;
-    sincos32(a, &s, &c);
-    act[act_index(kk, p)] = s;
-    act[act_index(3 * H + kk, p)] = c;
-  }
-  for (int i = tid; i < (kstride - 6 * H) * kTP; i += kThreads) act[act_index(6 * H + (i >> 6), i & (kTP - 1))] = 0.f;
-  __syncthreads();
-}
 
 // u (N, WcP): 64 rays per workgroup
 __global__ __launch_bounds__(kThreads) void radiance_dir_kernel(Layout lay, const float* __restrict__ pack,
@@ -105,42 +86,23 @@ __global__ __launch_bounds__(kThreads) void radiance_render_kernel(Layout lay, c
   __shared__ float act[kActWords];
   __shared__ float ptl[3 * kTP];
   __shared__ float dens[kTP];
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int C = lay.C;
   const float beta = pack[0];
-  const long ray0 = (long)blockIdx.x * G;
-  const int nr = (long)N - ray0 < G ? (int)((long)N - ray0) : G;
-  const int total = nr * P;                          // <= max(64, P)
-  const int T = (total + kTP - 1) / kTP;
+  const RayGroup rg(N, P, G);
+  const long ray0 = rg.ray0;
+  const int total = rg.total, T = rg.tiles;
   const bool early = threshold >= 0.f && dens_out == nullptr && col_out == nullptr && G == 1;
-  const bool owner = tid < nr;
+  const bool owner = tid < rg.nr;
   const long ray = ray0 + (owner ? tid : 0);
   const float* len = lengths + ray * P;
   RayState<kMaxC> st;
   st.start();
   int k_done = 0;                                    // the owner's samples [0, k_done) are rendered
   for (int t = 0; t < T; ++t) {
-    const int q = t * kTP + lane;
-    if (tid < 3 * kTP) {
-      const int d = tid >> 6;
-      float v = 0.f;
-      if (q < total) {
-        const int g = q / P, k = q - g * P;
-        const long r = ray0 + g;
-        v = origins[3 * r + d] + directions[3 * r + d] * lengths[r * P + k];
-      }
-      ptl[tid] = v;
-    }
+    tile_points_from_rays(rg, P, t, origins, directions, lengths, ptl);
     __syncthreads();                                 // also: the owners are done with the previous tile's colours
-    tile_embed(lay.d.H, lay.d.L[0].kstride, pack, act, ptl);
-    for (int l = 0; l < lay.d.n_hidden; ++l)
-      isr::field::mfma_tile_layer<kThreads / 64>(lay.d.L[l], pack, act, false, [=](float z) { return softplus32(z, beta); });
-    if (wv == 0) {                                   // the density neuron: the chain itself, lane = point
-      const float* wo = pack + lay.d.out_w_off;
-      float z = pack[lay.d.out_b_off];
-      for (int k = 0; k < lay.d.out_K; ++k) z = fmaf(wo[k], act[act_index(k, lane)], z);
-      dens[lane] = density32(softplus32(z, beta));
-    }
+    tile_trunk(lay.d, pack, act, ptl, dens);         // no barrier behind the density neuron: the next layer reads act first
     isr::field::mfma_tile_layer_from<kThreads / 64>(lay.trunk, pack, act, false, [=](float z) { return softplus32(z, beta); },
                                                     RayTermInit{u, ray0, P, total, t * kTP, lay.WcP});
     isr::field::mfma_tile_layer<kThreads / 64>(lay.out, pack, act, true, [](float z) { return sigmoid32(z); });
@@ -160,7 +122,7 @@ __global__ __launch_bounds__(kThreads) void radiance_render_kernel(Layout lay, c
       k_done = k1 > k_done ? k1 : k_done;
     }
     if (early) {
-      const int found = tid < kTP && q < total && dens[lane] > threshold;
+      const int found = tid < kTP && t * kTP + lane < total && dens[lane] > threshold;
       if (__syncthreads_or(found)) break;
     }
   }
@@ -206,14 +168,6 @@ int check_field(const char* who, const void* pack, size_t pack_bytes, int n_hidd
   return isr::check_pack_bytes(who, pack_bytes, lay.total_words);
 }
 
-int check_render(const char* who, const float* origins, const float* directions, const float* lengths, int N, int P,
-                 float threshold, const float* image, const float* depth, const float* points, const int32_t* hit) {
-  if (int rc = isr::check_rows(who, N, origins && directions && lengths && image && depth && points && hit)) return rc;
-  ISR_REQUIRE(P >= 1 && P <= kMaxP, "%s: P = %d (1..%d)", who, P, kMaxP);
-  ISR_REQUIRE(threshold == threshold, "%s: threshold is NaN", who);
-  return ISR_OK;
-}
-
 int check_ea(const char* who, const float* densities, const float* features, int N, int P, int F, float threshold,
              const float* image) {
   if (int rc = isr::check_rows(who, N, densities && features && image)) return rc;
@@ -224,35 +178,6 @@ int check_ea(const char* who, const float* densities, const float* features, int
 }
 
 size_t ws_bytes_for(int N, int Wc) { return (size_t)N * (size_t)((Wc + 31) / 32 * 32) * 4; }
-
-struct HostField {
-  std::vector<std::vector<float>> wt;
-  std::vector<float> dir, trunk, out;
-  HostWeights hw;
-  bool fma;
-  HostField(const Layout& lay, const void* pack) {
-    const float* pf = static_cast<const float*>(pack);
-    wt.resize(lay.d.n_hidden);
-    for (int l = 0; l < lay.d.n_hidden; ++l) {
-      wt[l].resize((size_t)lay.d.L[l].O * lay.d.L[l].K);
-      isr::field::unpack_layer(lay.d.L[l], pf, wt[l].data(), true);
-      hw.d.Wt[l] = wt[l].data();
-    }
-    auto take = [&](const Layer& L, std::vector<float>& dst) {
-      dst.resize((size_t)L.O * L.K);
-      isr::field::unpack_layer(L, pf, dst.data(), true);
-      return dst.data();
-    };
-    hw.dir = take(lay.dir, dir);
-    hw.trunk = take(lay.trunk, trunk);
-    hw.out = take(lay.out, out);
-#ifdef ISR_RADIANCE_HAVE_FMA_BUILD
-    fma = __builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2");
-#else
-    fma = false;
-#endif
-  }
-};
 
 }  // namespace
 
@@ -292,7 +217,7 @@ extern "C" int isr_radiance_render(const void* pack, size_t pack_bytes, int n_hi
   const char* who = "isr_radiance_render";
   Layout lay;
   if (int rc = check_field(who, pack, pack_bytes, n_hidden, widths, H, Wc, C, lay)) return rc;
-  if (int rc = check_render(who, origins, directions, lengths, N, P, threshold, image, depth, points, hit)) return rc;
+  if (int rc = check_march(who, N, origins && directions && lengths && image && depth && points && hit, P, threshold)) return rc;
   if (N == 0) return ISR_OK;
   ISR_REQUIRE(ws && ws_bytes >= ws_bytes_for(N, Wc), "%s: workspace of %zu bytes, %zu needed", who, ws ? ws_bytes : (size_t)0,
               ws_bytes_for(N, Wc));
@@ -302,7 +227,7 @@ extern "C" int isr_radiance_render(const void* pack, size_t pack_bytes, int n_hi
   hipStream_t st = isr::as_stream(stream);
   radiance_dir_kernel<<<(unsigned)(((long)N + kTP - 1) / kTP), kThreads, 0, st>>>(lay, pk, directions, N, u);
   ISR_CHECK_LAUNCH("radiance_dir_kernel");
-  const int G = P >= kTP ? 1 : kTP / P;
+  const int G = isr::density::rays_per_group(P);
   radiance_render_kernel<<<(unsigned)(((long)N + G - 1) / G), kThreads, 0, st>>>(lay, pk, origins, directions, lengths, N, P, G,
                                                                                  threshold, u, image, depth, points, hit, weights,
                                                                                  densities, colours);
@@ -327,7 +252,7 @@ extern "C" int isr_radiance_render_host(const void* pack, size_t pack_bytes, int
   const char* who = "isr_radiance_render_host";
   Layout lay;
   if (int rc = check_field(who, pack, pack_bytes, n_hidden, widths, H, Wc, C, lay)) return rc;
-  if (int rc = check_render(who, origins, directions, lengths, N, P, threshold, image, depth, points, hit)) return rc;
+  if (int rc = check_march(who, N, origins && directions && lengths && image && depth && points && hit, P, threshold)) return rc;
   if (N == 0) return ISR_OK;
   const HostField hf(lay, pack);
   std::vector<float> u((size_t)N * Wc), rho((size_t)N * P), col((size_t)N * P * C);

@@ -59,30 +59,20 @@ ISR_FIELD_FN void normalize3(const float* d, float* out) {
   for (int i = 0; i < 3; ++i) out[i] = (float)((double)d[i] / (double)m);
 }
 
-// The running state of one ray's render; step() takes the samples in k order.
+// The running state of one ray's render: ea_chain.hpp's weight chain (T, m, any) and the features; step() takes the samples
+// in k order.
 template <int kChannels>
-struct RayState {
-  float absorb, m, feat[kChannels];
-  int32_t any;
+struct RayState : ea::WeightChain {
+  float feat[kChannels];
   ISR_FIELD_FN void start() {
-    absorb = 1.0f;
-    m = 0.f;
-    any = 0;
+    ea::WeightChain::start();
 #pragma unroll
     for (int c = 0; c < kChannels; ++c) feat[c] = 0.f;
   }
   // sample k: its length, its density (evaluated == false: a sample behind the first hit of thresholdMode, c_k * 0) and its
   // colours col[0 .. C) (nan_colour: the sample's point is not finite, every colour is NaN).  -> w_k
   ISR_FIELD_FN float step(int k, float len, float rho, bool evaluated, float threshold, const float* col, int C, bool nan_colour) {
-    float c;
-    if (threshold >= 0.f) c = (evaluated && rho > threshold) ? 1.0f : 0.0f;
-    else c = rho;
-    const float w = c * absorb;
-    absorb = absorb * (1.0f - c);
-    if (w != 0.f) any = 1;
-    const float v = len * w;
-    if (k == 0) m = v;
-    else if (m == m && (v != v || v > m)) m = v;       // a NaN stays (field_density.hpp's march_ray)
+    const float w = ea::WeightChain::step(k, len, ea::absorbance(rho, threshold, evaluated));
     if (col) {
 #pragma unroll
       for (int ch = 0; ch < kChannels; ++ch)
@@ -94,7 +84,7 @@ struct RayState {
     }
     return w;
   }
-  ISR_FIELD_FN float opacity() const { return 1.0f - absorb; }
+  ISR_FIELD_FN float opacity() const { return 1.0f - T; }
 };
 
 ISR_FIELD_FN bool finite3(const float* x) {
@@ -166,29 +156,13 @@ __attribute__((always_inline)) inline void ray_term_body(const Layout& lay, cons
 }
 
 // Host: one point through the field -> its density and its C colours; u is its ray's direction term.  The k loops are
-// outermost and ascending (field_density.hpp's point_density_body, whose chains the trunk's are).
+// outermost and ascending; the trunk is field_density.hpp's trunk_body, whose last activations the colour head reads.
 __attribute__((always_inline)) inline void point_radiance_body(const Layout& lay, const void* pack, const HostWeights& hw,
                                                                const float* x, const float* u, float* dens, float* colours) {
-  float e[6 * kMaxH], z[kMaxWidth], g[kMaxWidth];
+  float z[kMaxWidth], g[kMaxWidth];
   const float* pf = static_cast<const float*>(pack);
   const float beta = pf[0];
-  density::embed_point(x, pf + density::kFreqOff, lay.d.H, e);
-  const float* h = e;
-  for (int l = 0; l < lay.d.n_hidden; ++l) {
-    const Layer& L = lay.d.L[l];
-    const float* wt = hw.d.Wt[l];
-    for (int j = 0; j < L.O; ++j) z[j] = pf[L.b_off + j];
-    for (int k = 0; k < L.K; ++k) {
-      const float hk = h[k];
-      const float* wk = wt + (size_t)k * L.O;
-      for (int j = 0; j < L.O; ++j) z[j] = __builtin_fmaf(wk[j], hk, z[j]);
-    }
-    for (int j = 0; j < L.O; ++j) g[j] = density::softplus32(z[j], beta);      // every z is complete: h may be g
-    h = g;
-  }
-  float zo = pf[lay.d.out_b_off];
-  for (int k = 0; k < lay.d.out_K; ++k) zo = __builtin_fmaf(pf[lay.d.out_w_off + k], h[k], zo);
-  *dens = density::density32(density::softplus32(zo, beta));
+  const float* h = density::trunk_body(lay.d, pack, hw.d, x, z, g, dens);
   for (int j = 0; j < lay.Wc; ++j) z[j] = u[j];
   for (int k = 0; k < lay.trunk.K; ++k) {
     const float hk = h[k];
@@ -226,6 +200,25 @@ __attribute__((target("avx2,fma"))) inline void point_radiance_host_fma(const La
 }
 #define ISR_RADIANCE_HAVE_FMA_BUILD 1
 #endif
+
+// Host: field_density.hpp's HostField of the trunk and the three colour layers unpacked and transposed
+struct HostField {
+  density::HostField d;
+  std::vector<float> dir, trunk, out;
+  HostWeights hw;
+  bool fma;
+  HostField(const Layout& lay, const void* pack) : d(lay.d, pack), fma(d.fma) {
+    auto take = [&](const Layer& L, std::vector<float>& dst) {
+      dst.resize((size_t)L.O * L.K);
+      field::unpack_layer(L, static_cast<const float*>(pack), dst.data(), true);
+      return dst.data();
+    };
+    hw.d = d.hw;
+    hw.dir = take(lay.dir, dir);
+    hw.trunk = take(lay.trunk, trunk);
+    hw.out = take(lay.out, out);
+  }
+};
 
 }  // namespace radiance
 }  // namespace isr

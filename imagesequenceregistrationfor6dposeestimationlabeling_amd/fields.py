@@ -22,6 +22,25 @@ def _vp(a: np.ndarray):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _host_bundle(origins, directions, lengths):
+    """-> contiguous f32 NumPy origins (N,3), directions (N,3), lengths (N,P) for a _host call, and N, P."""
+    o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+    ln = np.ascontiguousarray(lengths, np.float32)
+    return o, d, ln, *ln.shape
+
+
+def _width_chain(name: str, Ws, bs, first=None) -> tuple:
+    """The widths of a chain of layers, checked: every W (out_l, in_l) with in_l the width before it (`first`, or W_0's own
+    when None, at l = 0) and b (out_l,)."""
+    widths = [(Ws[0].shape[1] if Ws[0].ndim == 2 else -1) if first is None else first]
+    for l, (w, b) in enumerate(zip(Ws, bs)):
+        if w.ndim != 2 or w.shape[1] != widths[-1] or b.shape[0] != w.shape[0]:
+            raise ValueError(f"{name}: layer {l} has W {tuple(w.shape)} and b {tuple(b.shape)} after width {widths[-1]}")
+        widths.append(w.shape[0])
+    return tuple(int(v) for v in widths)
+
+
 class _PackedField:
     """What the two fields share: layers to contiguous f32 on the host with their chain of widths checked, the pack made by
     the library and uploaded, and the checks in front of a device call.  `_host_calls` finishes the subclass's refusal."""
@@ -32,29 +51,24 @@ class _PackedField:
 
     def _layers(self, weights, biases, first=None):
         """-> (Ws, bs, widths): every W (out_l, in_l) with in_l the width before it, `first` (W_0's own when None) at l = 0."""
-        name = type(self).__name__
         Ws, bs = [self._host(w) for w in weights], [self._host(b).reshape(-1) for b in biases]
-        widths = [(Ws[0].shape[1] if Ws[0].ndim == 2 else -1) if first is None else first]
-        for l, (w, b) in enumerate(zip(Ws, bs)):
-            if w.ndim != 2 or w.shape[1] != widths[-1] or b.shape[0] != w.shape[0]:
-                raise ValueError(f"{name}: layer {l} has W {w.shape} and b {b.shape} after width {widths[-1]}")
-            widths.append(w.shape[0])
-        return Ws, bs, tuple(int(v) for v in widths)
+        return Ws, bs, _width_chain(type(self).__name__, Ws, bs, first)
 
     def _pack_and_upload(self, kind, dims, before, Ws, bs, after, device):
-        """isr_<kind>_pack_bytes(*dims), isr_<kind>_pack(*dims, *before, W, b, *after, pack, bytes) -> pack_host; its copy on
-        `device` -> pack.  device=None: host-only (the _host calls, the tests' reference); there is no CPU fallback."""
+        """isr_<kind>_pack_bytes(*dims), isr_<kind>_pack(*dims, *before, W, b, *after, pack, bytes) -> (pack_host, pack): the
+        pack and its copy on `device`, which is set.  device=None: host-only (the _host calls, the tests' reference), pack is
+        None; there is no CPU fallback."""
         name, L = type(self).__name__, lib()
         nbytes = getattr(L, f"isr_{kind}_pack_bytes")(*dims)
         if nbytes == 0:
             raise IsrError(f"isr_{kind}_pack_bytes failed: {L.isr_last_error().decode()}")
-        self.pack_host = np.empty(nbytes // 4, np.float32)
+        pack_host = np.empty(nbytes // 4, np.float32)
         check(getattr(L, f"isr_{kind}_pack")(*dims, *before, _vp(np.concatenate([w.reshape(-1) for w in Ws])),
-                                             _vp(np.concatenate(bs)), *after, _vp(self.pack_host), nbytes), f"isr_{kind}_pack")
+                                             _vp(np.concatenate(bs)), *after, _vp(pack_host), nbytes), f"isr_{kind}_pack")
         self.device = None if device is None else torch.device(device)
         if self.device is not None and self.device.type != "cuda":
             raise IsrError(f"{name}: device {self.device} is not a GPU (there is no CPU fallback)")
-        self.pack = None if self.device is None else torch.from_numpy(self.pack_host).to(self.device)
+        return pack_host, None if self.device is None else torch.from_numpy(pack_host).to(self.device)
 
     def _need_device(self, *tensors):
         if self.pack is None:
@@ -83,7 +97,8 @@ class KeyField(_PackedField):
         self._w = np.asarray(self.widths, np.int32)
         om = np.asarray([0.0 if o is None else o for o in self.omegas], np.float32)
         sine = np.asarray([o is not None for o in self.omegas], np.int32)
-        self._pack_and_upload("field", (self.n_layers, _vp(self._w)), (), Ws, bs, (_vp(om), _vp(sine)), device)
+        self.pack_host, self.pack = self._pack_and_upload("field", (self.n_layers, _vp(self._w)), (), Ws, bs, (_vp(om), _vp(sine)),
+                                                          device)
 
     @classmethod
     def from_linears(cls, linears, omegas, device=None):
@@ -136,8 +151,8 @@ class DensityField(_PackedField):
         self.widths = widths[1:-1]
         self.beta = float(beta)
         self._w = np.asarray(self.widths, np.int32)
-        self._pack_and_upload("density", (len(self.widths), _vp(self._w), self.H), (_vp(self.frequencies), self.beta), Ws, bs, (),
-                              device)
+        self.pack_host, self.pack = self._pack_and_upload("density", (len(self.widths), _vp(self._w), self.H),
+                                                          (_vp(self.frequencies), self.beta), Ws, bs, (), device)
 
     @classmethod
     def from_linears(cls, hidden_linears, density_linear, n_harmonic=60, omega0=0.1, beta=10.0, device=None):
@@ -246,10 +261,7 @@ class DensityField(_PackedField):
     def march_host(self, origins, directions, lengths, threshold: float = 0.2, direction: str = "front"):
         """isr_density_march_host / isr_density_march_dir_host: NumPy (N,3), (N,3), (N,P) -> dict of points, depth, hit,
         densities, weights, shaped as ops.density_march shapes them for `direction`.  For tests."""
-        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
-        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
-        ln = np.ascontiguousarray(lengths, np.float32)
-        N, P = ln.shape
+        o, d, ln, N, P = _host_bundle(origins, directions, lengths)
         way = ops.march_direction(direction)
         lead = (2, N) if way == 2 else (N,)
         out = dict(points=np.empty((*lead, 3), np.float32), depth=np.empty(lead, np.float32), hit=np.empty(lead, np.int32),
@@ -280,11 +292,8 @@ class RadianceField(DensityField):
         cW, cb, cw = self._layers(color_weights, color_biases, Wt + 6 * self.H)
         self.Wc, self.C = cw[1], cw[2]
         Ws, bs, _ = self._layers(weights, biases, 6 * self.H)
-        density_pack_host, density_pack = self.pack_host, self.pack
-        self._pack_and_upload("radiance", (len(self.widths), _vp(self._w), self.H, self.Wc, self.C),
-                              (_vp(self.frequencies), self.beta), Ws + cW, bs + cb, (), device)
-        self.rpack_host, self.rpack = self.pack_host, self.pack
-        self.pack_host, self.pack = density_pack_host, density_pack
+        self.rpack_host, self.rpack = self._pack_and_upload("radiance", (len(self.widths), _vp(self._w), self.H, self.Wc, self.C),
+                                                            (_vp(self.frequencies), self.beta), Ws + cW, bs + cb, (), device)
 
     @classmethod
     def from_linears(cls, hidden_linears, density_linear, color_linears, n_harmonic=60, omega0=0.1, beta=10.0, device=None):
@@ -339,10 +348,7 @@ class RadianceField(DensityField):
     def render_host(self, origins, directions, lengths, threshold: float = -1.0):
         """isr_radiance_render_host: NumPy (N,3), (N,3), (N,P) -> dict of image, depth, points, hit, weights, densities,
         colours.  For tests."""
-        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
-        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
-        ln = np.ascontiguousarray(lengths, np.float32)
-        N, P = ln.shape
+        o, d, ln, N, P = _host_bundle(origins, directions, lengths)
         out = dict(image=np.empty((N, self.C + 1), np.float32), depth=np.empty(N, np.float32), points=np.empty((N, 3), np.float32),
                    hit=np.empty(N, np.int32), weights=np.empty((N, P), np.float32), densities=np.empty((N, P), np.float32),
                    colours=np.empty((N, P, self.C), np.float32))
@@ -416,12 +422,7 @@ class TrainableKeyField(torch.nn.Module):
             raise ValueError(f"TrainableKeyField: {len(weights)} weights, {len(biases)} biases, {len(omegas)} omegas")
         f = lambda t: torch.as_tensor(t, dtype=torch.float32).detach().to(device).clone().contiguous()
         Ws, bs = [f(w) for w in weights], [f(b).reshape(-1) for b in biases]
-        widths = [Ws[0].shape[1] if Ws[0].ndim == 2 else -1]
-        for l, (w, b) in enumerate(zip(Ws, bs)):
-            if w.ndim != 2 or w.shape[1] != widths[-1] or b.shape[0] != w.shape[0]:
-                raise ValueError(f"TrainableKeyField: layer {l} has W {tuple(w.shape)} and b {tuple(b.shape)} after width {widths[-1]}")
-            widths.append(w.shape[0])
-        self.widths = tuple(int(v) for v in widths)
+        self.widths = _width_chain("TrainableKeyField", Ws, bs)
         if lib().isr_field_pack_bytes(len(Ws), _vp(np.asarray(self.widths, np.int32))) == 0:
             raise IsrError(f"TrainableKeyField: {lib().isr_last_error().decode()}")
         self.omegas = tuple(None if o is None else float(o) for o in omegas)

@@ -1193,6 +1193,22 @@ def march_direction(direction: str) -> int:
     return MARCH_DIRECTIONS[direction]
 
 
+def _ray_bundle(name: str, origins, directions, lengths, threshold) -> tuple[int, int, float]:
+    """The checks of a bundle origins (N,3), directions (N,3), lengths (N,P) and its threshold -> (N, P, threshold)."""
+    for what, t, cols in (("origins", origins, 3), ("directions", directions, 3), ("lengths", lengths, None)):
+        if t.dtype != torch.float32 or t.ndim != 2 or (cols and t.shape[1] != cols) or not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be contiguous 2-d float32, got {tuple(t.shape)} {t.dtype}")
+    N, P = lengths.shape
+    if origins.shape[0] != N or directions.shape[0] != N:
+        raise ValueError(f"{name}: {origins.shape[0]} origins, {directions.shape[0]} directions, {N} rows of lengths")
+    if P < 1:
+        raise ValueError(f"{name}: P < 1")
+    thr = float(threshold)
+    if thr != thr:
+        raise ValueError(f"{name}: threshold is NaN")
+    return N, P, thr
+
+
 def density_march(pack: torch.Tensor, widths, H: int, origins: torch.Tensor, directions: torch.Tensor, lengths: torch.Tensor,
                   threshold: float = 0.2, want_densities: bool = False, want_weights: bool = False, direction: str = "front"):
     """isr_density_march: origins (N,3), directions (N,3), lengths (N,P) f32 -> (points (N,3) f32, depth (N,) f32,
@@ -1202,17 +1218,7 @@ def density_march(pack: torch.Tensor, widths, H: int, origins: torch.Tensor, dir
     ray (one at the LAST density above the threshold: the exit point, prenBack.py:378-381); "both" gives points (2,N,3),
     depth (2,N), hit (2,N), front then back, and weights (N,2P), a ray's front weights then its back weights."""
     dev = require_cuda(pack, origins, directions, lengths)
-    for name, t, cols in (("origins", origins, 3), ("directions", directions, 3), ("lengths", lengths, None)):
-        if t.dtype != torch.float32 or t.ndim != 2 or (cols and t.shape[1] != cols) or not t.is_contiguous():
-            raise ValueError(f"density_march: {name} must be contiguous 2-d float32, got {tuple(t.shape)} {t.dtype}")
-    N, P = lengths.shape
-    if origins.shape[0] != N or directions.shape[0] != N:
-        raise ValueError(f"density_march: {origins.shape[0]} origins, {directions.shape[0]} directions, {N} rows of lengths")
-    if P < 1:
-        raise ValueError("density_march: P < 1")
-    thr = float(threshold)
-    if thr != thr:
-        raise ValueError("density_march: threshold is NaN")
+    N, P, thr = _ray_bundle("density_march", origins, directions, lengths, threshold)
     way = march_direction(direction)
     lead = (2, N) if way == 2 else (N,)
     f32 = dict(dtype=torch.float32, device=dev)
@@ -1271,17 +1277,7 @@ def radiance_render(pack: torch.Tensor, widths, H: int, Wc: int, C: int, origins
     threshold >= 0 is the reference's thresholdMode, a negative one the emission-absorption weights.  workspace: a
     contiguous device tensor of at least radiance_workspace_bytes(N, Wc) bytes to reuse (allocated when None)."""
     dev = require_cuda(pack, origins, directions, lengths, workspace)
-    for name, t, cols in (("origins", origins, 3), ("directions", directions, 3), ("lengths", lengths, None)):
-        if t.dtype != torch.float32 or t.ndim != 2 or (cols and t.shape[1] != cols) or not t.is_contiguous():
-            raise ValueError(f"radiance_render: {name} must be contiguous 2-d float32, got {tuple(t.shape)} {t.dtype}")
-    N, P = lengths.shape
-    if origins.shape[0] != N or directions.shape[0] != N:
-        raise ValueError(f"radiance_render: {origins.shape[0]} origins, {directions.shape[0]} directions, {N} rows of lengths")
-    if P < 1:
-        raise ValueError("radiance_render: P < 1")
-    thr = float(threshold)
-    if thr != thr:
-        raise ValueError("radiance_render: threshold is NaN")
+    N, P, thr = _ray_bundle("radiance_render", origins, directions, lengths, threshold)
     Wc, C = int(Wc), int(C)
     f32 = dict(dtype=torch.float32, device=dev)
     out = dict(image=torch.empty((N, C + 1), **f32), depth=torch.empty((N,), **f32), points=torch.empty((N, 3), **f32),

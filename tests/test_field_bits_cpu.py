@@ -52,14 +52,20 @@ def key_field(name):
     return KeyField(Ws, bs, omegas, None)
 
 
-def density_field(name):
+def density_weights(name):
+    """-> (Ws, bs, frequencies) of a density field: the hidden layers, then the output row."""
     H, hidden, seed = DENSITY_FIELDS[name]
     w = (6 * H,) + hidden
     Ws = [(lcg(seed + 10 * l, O * K) / np.sqrt(K)).astype(f32).reshape(O, K) for l, (K, O) in enumerate(zip(w[:-1], w[1:]))]
     bs = [(lcg(seed + 10 * l + 1, O) * 0.1).astype(f32) for l, O in enumerate(w[1:])]
     Ws.append((lcg(seed + 90, w[-1]) * 8.0 / np.sqrt(w[-1])).astype(f32).reshape(1, -1))
     bs.append(np.array([0.25], f32))
-    return DensityField(Ws, bs, (0.1 * 2.0 ** np.arange(H)).astype(f32), 10.0, None)
+    return Ws, bs, (0.1 * 2.0 ** np.arange(H)).astype(f32)
+
+
+def density_field(name):
+    Ws, bs, freqs = density_weights(name)
+    return DensityField(Ws, bs, freqs, 10.0, None)
 
 
 def small_inputs():

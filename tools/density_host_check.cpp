@@ -93,13 +93,9 @@ int check_field(int H, int n_hidden, int width, int N) {
   for (auto& v : b) v = 0.1f * rnd();
   for (int i = 0; i < H; ++i) freqs[i] = 0.1f * std::ldexp(1.f, i);
   pack_host(lay, freqs.data(), 10.f, W.data(), b.data(), pack.data());
-  std::vector<std::vector<float>> wt(n_hidden);
-  HostWeights hw;
-  for (int l = 0; l < n_hidden; ++l) {
-    wt[l].resize((size_t)lay.L[l].O * lay.L[l].K);
-    isr::field::unpack_layer(lay.L[l], pack.data(), wt[l].data(), true);
-    hw.Wt[l] = wt[l].data();
-  }
+  const HostField hf(lay, pack.data());      // the library's own unpacking of the pack
+  const HostWeights& hw = hf.hw;
+  const std::vector<std::vector<float>>& wt = hf.wt;
   int bad = 0;
   // the pack round trip: every weight where w_index says
   {

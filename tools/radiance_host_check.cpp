@@ -101,20 +101,8 @@ int check_field(int H, int n_hidden, int width, int Wc, int C, int N, int P) {
   std::vector<float> dpack(lay.d.total_words);
   isr::density::pack_host(lay.d, freqs.data(), 10.f, W.data(), b.data(), dpack.data());
   if (std::memcmp(pack.data(), dpack.data(), dpack.size() * 4) != 0) ++bad;
-  std::vector<std::vector<float>> wt(n_hidden);
-  HostWeights hw;
-  for (int l = 0; l < n_hidden; ++l) {
-    wt[l].resize((size_t)lay.d.L[l].O * lay.d.L[l].K);
-    isr::field::unpack_layer(lay.d.L[l], pack.data(), wt[l].data(), true);
-    hw.d.Wt[l] = wt[l].data();
-  }
-  std::vector<float> wd((size_t)Wc * 6 * H), wk((size_t)Wc * width), wo((size_t)C * Wc);
-  isr::field::unpack_layer(lay.dir, pack.data(), wd.data(), true);
-  isr::field::unpack_layer(lay.trunk, pack.data(), wk.data(), true);
-  isr::field::unpack_layer(lay.out, pack.data(), wo.data(), true);
-  hw.dir = wd.data();
-  hw.trunk = wk.data();
-  hw.out = wo.data();
+  const HostField hf(lay, pack.data());      // the library's own unpacking of the pack
+  const HostWeights& hw = hf.hw;
   std::vector<float> u(Wc), rho(P), col((size_t)P * C), len(P), wts(P), image(C + 1);
   for (int ray = 0; ray < N; ++ray) {
     float o[3] = {rnd(s), rnd(s), rnd(s)}, d[3] = {rnd(s) * 2.f, rnd(s) * 2.f, rnd(s) * 2.f};
