@@ -165,7 +165,9 @@ __global__ __launch_bounds__(kThreads) void nn_search_kernel(
   constexpr float kU0 = 5.9604645e-8f;    // 2^-24
   auto nearthr = [&](int r, float D) {    // D + 2.5 tol(D), inf for D = inf
     const float tol = __builtin_fmaf(6.f * kU0, D, __builtin_fmaf(2.f * __builtin_sqrtf(D), dlt[r], dlt[r] * dlt[r]));
-    return __builtin_fmaf(2.5f, tol, D);
+    // D = inf outright: with delta = 0 (query and every target at the origin) the fma chain above is inf * 0 = NaN, and a
+    // lane whose bound is NaN never finds its neighbour; every other input keeps its bits
+    return D < __builtin_inff() ? __builtin_fmaf(2.5f, tol, D) : D;
   };
 #pragma unroll
   for (int r = 0; r < RQ; ++r) {
