@@ -3,7 +3,7 @@ def __getattr__(name):
     if name in ("ObjCoordRenderer", "Mesh"):
         from . import render
         return getattr(render, name)
-    if name in ("KeyField", "TrainableKeyField", "DensityField", "RadianceField", "FeatureField"):
+    if name in ("KeyField", "TrainableKeyField", "DensityField", "RadianceField", "TrainableRadianceField", "FeatureField"):
         from . import fields
         return getattr(fields, name)
     if name in ("sample_farthest_points", "thin_keys", "estimate_pointcloud_normals", "estimate_pointcloud_local_coord_frames"):

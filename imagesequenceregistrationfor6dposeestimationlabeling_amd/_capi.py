@@ -261,6 +261,19 @@ EA_GRAD_SIGNATURES = {
     "isr_ea_grad_rays_per_group": (_i, [_i]),
 }
 
+# include/isr_radiance_grad.h (the radiance field's backward and the device-side packing), bound the same way
+_RADIANCE_SHAPE = [_i, _vp, _i, _i, _i]      # n_hidden, widths, H, Wc, C
+_RADIANCE_RAYS = [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]      # origins, directions, lengths, N, P, d_densities, d_colours, dW, db
+RADIANCE_GRAD_SIGNATURES = {
+    "isr_radiance_grad_pack_bytes": (_sz, [*_RADIANCE_SHAPE]),
+    "isr_radiance_pack_device": (_i, [*_RADIANCE_SHAPE, _vp, _f, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "isr_radiance_grad_workspace_bytes": (_sz, [*_RADIANCE_SHAPE, _i, _i]),
+    "isr_radiance_backward": (_i, [_vp, _sz, _vp, _sz, *_RADIANCE_SHAPE, *_RADIANCE_RAYS, _vp, _sz, _vp]),
+    "isr_radiance_backward_host": (_i, [_vp, _sz, *_RADIANCE_SHAPE, *_RADIANCE_RAYS]),
+    "isr_radiance_grad_slopes_host": (_i, [_vp, _sz, _f, _vp, _vp]),
+    "isr_radiance_grad_geometry": (_i, [_i]),
+}
+
 # include/isr_mc.h (iso-surface extraction), bound the same way
 MC_SIGNATURES = {
     "isr_mc_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -289,7 +302,7 @@ def lib() -> C.CDLL:
                                **DENSITY_DIR_SIGNATURES, **RADIUS_SIGNATURES, **MC_SIGNATURES, **KNN_SIGNATURES,
                                **RAYS_SIGNATURES, **RADIANCE_SIGNATURES, **RESAMPLE_SIGNATURES,
                                **CONTRASTIVE_SIGNATURES, **FIELD_GRAD_SIGNATURES, **SAMPLE_GRAD_SIGNATURES,
-                               **EA_GRAD_SIGNATURES}.items():
+                               **EA_GRAD_SIGNATURES, **RADIANCE_GRAD_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

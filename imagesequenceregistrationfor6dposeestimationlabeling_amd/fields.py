@@ -292,6 +292,7 @@ class RadianceField(DensityField):
         cW, cb, cw = self._layers(color_weights, color_biases, Wt + 6 * self.H)
         self.Wc, self.C = cw[1], cw[2]
         Ws, bs, _ = self._layers(weights, biases, 6 * self.H)
+        self._source = (Ws, bs, cW, cb)      # host copies of the weights as given (TrainableRadianceField.from_radiance_field)
         self.rpack_host, self.rpack = self._pack_and_upload("radiance", (len(self.widths), _vp(self._w), self.H, self.Wc, self.C),
                                                             (_vp(self.frequencies), self.beta), Ws + cW, bs + cb, (), device)
 
@@ -511,3 +512,182 @@ class TrainableKeyField(torch.nn.Module):
         """nerf.py:404-457: (..., 3) -> (..., out + 1), the last channel zeros (nerf.py:415), which takes no gradient.
         n_batches is accepted and changes nothing: rows are independent, the whole input is one launch."""
         return self._eval(points, self.out_features + 1)
+
+
+class _RadianceFieldFunction(torch.autograd.Function):
+    """The bundle (N,3), (N,3), (N,P) -> (densities (N,P), colours (N,P,C)) through a TrainableRadianceField's packs:
+    isr_radiance_render forward (threshold -1, densities and colours asked for), isr_radiance_backward backward.  Only the
+    rays are saved; the backward recomputes the forward.  params: every W, then every b, in isr_radiance_pack's order."""
+
+    @staticmethod
+    def forward(ctx, field, o, d, ln, *params):
+        pack, packT = field._packs()
+        out = ops.radiance_render(pack, field.widths, field.H, field.Wc, field.C, o, d, ln, threshold=-1.0, want_densities=True,
+                                  want_colours=True)
+        ctx.shape, ctx.packs = (field.widths, field.H, field.Wc, field.C), (pack, packT)
+        ctx.save_for_backward(o, d, ln)
+        return out["densities"], out["colours"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_dens, d_col):
+        o, d, ln = ctx.saved_tensors
+        shapes = ops.radiance_param_shapes(*ctx.shape)
+        nl = len(shapes)
+        need = ctx.needs_input_grad[4:]
+        f = lambda t: None if t is None else t.to(torch.float32).contiguous()
+        dW, db = ops.radiance_backward(*ctx.packs, *ctx.shape, o, d, ln, f(d_dens), f(d_col),
+                                       need=(any(need[:nl]), any(need[nl:])))
+        gW = torch.split(dW, [a * b for a, b in shapes]) if dW is not None else [None] * nl
+        gb = torch.split(db, [a for a, _ in shapes]) if db is not None else [None] * nl
+        grads = [g.view(a, b) if g is not None and n else None for g, (a, b), n in zip(gW, shapes, need[:nl])]
+        grads += [g if g is not None and n else None for g, n in zip(gb, need[nl:])]
+        return (None, None, None, None, *grads)
+
+
+class TrainableRadianceField(torch.nn.Module):
+    """RadianceField with parameters: NeuralRadianceFieldFeat in mode="color" as trainNerfFine.py:174-186 trains it (mlp,
+    density_layer and color_layer; feature_layer stays frozen and is not part of this field), evaluated by RadianceField's
+    kernel with the same bits and differentiated by isr_radiance_backward with respect to its weights and biases.
+    weights / biases: ParameterLists of the hidden layers, then the density row (1, Wt); color_weights / color_biases:
+    W1 (Wc, Wt + 6H) with the trunk's columns first, W2 (C, Wc); `frequencies` (H,) is a buffer, as in the reference.  The packs
+    the kernels read are rebuilt on the device (isr_radiance_pack_device) whenever gradients are enabled or a parameter
+    changed.  The rays get no gradient: a bundle tensor that requires one is refused.  Not a RadianceField:
+    rays.ImplicitRendererStratified sends it down its generic, differentiable route."""
+
+    def __init__(self, weights, biases, color_weights, color_biases, frequencies, beta=10.0, device=None):
+        super().__init__()
+        if len(weights) != len(biases) or len(weights) < 2:
+            raise ValueError(f"TrainableRadianceField: {len(weights)} weights, {len(biases)} biases (hidden layers, then the density row)")
+        if len(color_weights) != 2 or len(color_biases) != 2:
+            raise ValueError(f"TrainableRadianceField: {len(color_weights)} colour weights, {len(color_biases)} colour biases (two layers)")
+        f = lambda t: torch.as_tensor(t, dtype=torch.float32).detach().to(device).clone().contiguous()
+        fr = f(frequencies).reshape(-1)
+        self.H = int(fr.shape[0])
+        Ws, bs = [f(w) for w in weights], [f(b).reshape(-1) for b in biases]
+        widths = _width_chain("TrainableRadianceField", Ws, bs, 6 * self.H)
+        if widths[-1] != 1:
+            raise ValueError(f"TrainableRadianceField: the last trunk layer has {widths[-1]} outputs, the density is one")
+        self.widths = widths[1:-1]
+        cW, cb = [f(w) for w in color_weights], [f(b).reshape(-1) for b in color_biases]
+        cw = _width_chain("TrainableRadianceField", cW, cb, self.widths[-1] + 6 * self.H)
+        self.Wc, self.C = cw[1], cw[2]
+        self.beta = float(beta)
+        if lib().isr_radiance_pack_bytes(len(self.widths), _vp(np.asarray(self.widths, np.int32)), self.H, self.Wc, self.C) == 0:
+            raise IsrError(f"TrainableRadianceField: {lib().isr_last_error().decode()}")
+        if not (self.beta > 0.0 and self.beta <= 3.0e38):
+            raise ValueError(f"TrainableRadianceField: beta = {beta} must be positive and finite")
+        self.weights = torch.nn.ParameterList([torch.nn.Parameter(w) for w in Ws])
+        self.biases = torch.nn.ParameterList([torch.nn.Parameter(b) for b in bs])
+        self.color_weights = torch.nn.ParameterList([torch.nn.Parameter(w) for w in cW])
+        self.color_biases = torch.nn.ParameterList([torch.nn.Parameter(b) for b in cb])
+        self.register_buffer("frequencies", fr)
+        self._packed, self._packed_at = None, None
+
+    @classmethod
+    def from_linears(cls, hidden_linears, density_linear, color_linears, n_harmonic=60, omega0=0.1, beta=10.0, device=None):
+        """From the torch.nn.Linear modules of the loaded network (RadianceField.from_linears' signature); values are copied."""
+        trunk, colour = list(hidden_linears) + [density_linear], list(color_linears)
+        if any(m.bias is None for m in trunk + colour):
+            raise ValueError("TrainableRadianceField.from_linears: every layer needs a bias")
+        if device is None:
+            device = trunk[0].weight.device
+        return cls([m.weight for m in trunk], [m.bias for m in trunk], [m.weight for m in colour], [m.bias for m in colour],
+                   DensityField.harmonic_frequencies(n_harmonic, omega0), beta, device)
+
+    @classmethod
+    def from_module(cls, model, beta=10.0, device=None):
+        """From a NeuralRadianceFieldFeat-shaped module (RadianceField.from_module's signature); values are copied."""
+        lin = lambda seq: [m for m in seq if isinstance(m, torch.nn.Linear)]
+        trunk, colour = lin(model.mlp) + lin(model.density_layer), lin(model.color_layer)
+        if device is None:
+            device = trunk[0].weight.device
+        return cls([m.weight for m in trunk], [m.bias for m in trunk], [m.weight for m in colour], [m.bias for m in colour],
+                   model.harmonic_embedding.frequencies, beta, device)
+
+    @classmethod
+    def from_radiance_field(cls, field: RadianceField, device=None):
+        """From a RadianceField's weights (the copies its constructor kept on the host)."""
+        return cls(*field._source, field.frequencies, field.beta, field.device if device is None else device)
+
+    def to_radiance_field(self, device="parameters") -> RadianceField:
+        """The frozen RadianceField of the current weights, on the parameters' device by default (host-only, as
+        RadianceField's device=None, while they are on the CPU)."""
+        if device == "parameters":
+            device = self.weights[0].device if self.weights[0].is_cuda else None
+        det = lambda ps: [p.detach() for p in ps]
+        return RadianceField(det(self.weights), det(self.biases), det(self.color_weights), det(self.color_biases),
+                             self.frequencies, self.beta, device)
+
+    # NeuralRadianceFieldFeat's state_dict names (nerf.py:163-218): Sequential(Linear, Softplus, ...) numbers its Linears 0, 2, ...
+    def _reference_names(self):
+        names = [f"mlp.{2 * l}" for l in range(len(self.widths))] + ["density_layer.0", "color_layer.0", "color_layer.2"]
+        return list(zip(names, [*self.weights, *self.color_weights], [*self.biases, *self.color_biases]))
+
+    def reference_state_dict(self) -> dict:
+        """The parameters under NeuralRadianceFieldFeat's key names (mlp.0.weight, ..., density_layer.0.*, color_layer.0.*,
+        color_layer.2.*, harmonic_embedding.frequencies), detached copies: what trainNerfFine.py:228-235 stores as
+        "model_state_dict"."""
+        sd = {}
+        for name, w, b in self._reference_names():
+            sd[name + ".weight"], sd[name + ".bias"] = w.detach().clone(), b.detach().clone()
+        sd["harmonic_embedding.frequencies"] = self.frequencies.detach().clone()
+        return sd
+
+    def load_reference_state_dict(self, sd) -> None:
+        """Copy the values of a NeuralRadianceFieldFeat state_dict (or of a {"epoch", "model_state_dict"} checkpoint) into the
+        parameters.  feature_layer.* keys are ignored; a missing key or another shape is an error."""
+        if "model_state_dict" in sd:
+            sd = sd["model_state_dict"]
+        with torch.no_grad():
+            for name, w, b in self._reference_names():
+                for key, p in ((name + ".weight", w), (name + ".bias", b)):
+                    if key not in sd:
+                        raise KeyError(f"TrainableRadianceField.load_reference_state_dict: {key} is missing")
+                    v = torch.as_tensor(sd[key])
+                    if tuple(v.shape) != tuple(p.shape):
+                        raise ValueError(f"TrainableRadianceField.load_reference_state_dict: {key} is {tuple(v.shape)}, "
+                                         f"expected {tuple(p.shape)}")
+                    p.copy_(v.to(p.device, torch.float32))
+            key = "harmonic_embedding.frequencies"
+            if key in sd:
+                v = torch.as_tensor(sd[key]).reshape(-1)
+                if v.shape[0] != self.H:
+                    raise ValueError(f"TrainableRadianceField.load_reference_state_dict: {v.shape[0]} frequencies, H = {self.H}")
+                self.frequencies.copy_(v.to(self.frequencies.device, torch.float32))
+        self._packed = None
+
+    def _params(self):
+        return [*self.weights, *self.color_weights, *self.biases, *self.color_biases]
+
+    def _packs(self):
+        """(pack, packT) of the current parameters, fresh buffers whenever they are rebuilt (a saved backward keeps its own)."""
+        at = tuple((p.data_ptr(), p._version) for p in [*self._params(), self.frequencies])
+        if self._packed is None or torch.is_grad_enabled() or at != self._packed_at:
+            with torch.no_grad():
+                W = torch.cat([w.reshape(-1) for w in [*self.weights, *self.color_weights]])
+                b = torch.cat([v.reshape(-1) for v in [*self.biases, *self.color_biases]])
+                self._packed = ops.radiance_pack_device(self.widths, self.H, self.Wc, self.C, self.frequencies, self.beta, W, b)
+                self._packed_at = at
+        return self._packed
+
+    def forward(self, ray_bundle, **kw):
+        """nerf.py:340-402 in mode="color": any object with .origins, .directions (..., 3) and .lengths (..., P) ->
+        (densities (..., P, 1), colours (..., P, C)), on the device, differentiable with respect to the parameters.  Keywords
+        (the renderer's cameras=) are accepted and ignored."""
+        o, d, ln = ray_bundle.origins, ray_bundle.directions, ray_bundle.lengths
+        if o.requires_grad or d.requires_grad or ln.requires_grad:
+            raise NotImplementedError("TrainableRadianceField: the rays get no gradient (detach the bundle)")
+        require_cuda(o, d, ln, *self._params())
+        if o.shape[-1] != 3 or d.shape != o.shape or ln.shape[:-1] != o.shape[:-1]:
+            raise ValueError(f"TrainableRadianceField: origins {tuple(o.shape)}, directions {tuple(d.shape)}, lengths "
+                             f"{tuple(ln.shape)}: expected (..., 3), (..., 3), (..., P)")
+        f = lambda t, c: t.to(torch.float32).reshape(-1, c).contiguous()
+        dens, col = _RadianceFieldFunction.apply(self, f(o, 3), f(d, 3), f(ln, ln.shape[-1]), *self._params())
+        shape = tuple(ln.shape)
+        return dens.reshape(*shape, 1), col.reshape(*shape, self.C)
+
+    def batched_forward(self, ray_bundle, n_batches: int = 16, **kw):
+        """nerf.py:458-521: the same pair.  n_batches is accepted and changes nothing: rows are independent, the bundle is
+        one call."""
+        return self.forward(ray_bundle, **kw)

@@ -2227,3 +2227,143 @@ def field_cos_host(a):
     out = np.empty_like(a)
     check(lib().isr_field_cos_host(_hp(a), a.size, _hp(out)), "isr_field_cos_host")
     return out
+
+
+# ---- the radiance field's backward and the device-side packing (include/isr_radiance_grad.h)
+
+def radiance_grad_geometry() -> dict:
+    """isr_radiance_grad_geometry: the chain length of a weight sum, the tile of points a workgroup takes, the largest slab of
+    points whose per-layer inputs the workspace holds at a time, and the batch of points whose block sums it holds."""
+    return {name: lib().isr_radiance_grad_geometry(i) for i, name in enumerate(("chain", "tile", "slab", "batch"))}
+
+
+def radiance_param_sizes(widths, H: int, Wc: int, C: int) -> tuple[int, int]:
+    """-> (entries of every W, entries of every b) of isr_radiance_pack's layout: the hidden matrices, the density row,
+    W1 (Wc, Wt + 6H), W2 (C, Wc); the biases likewise."""
+    w = [6 * int(H)] + [int(v) for v in widths]
+    Wt = w[-1]
+    return (sum(a * b for a, b in zip(w[:-1], w[1:])) + Wt + int(Wc) * (Wt + 6 * int(H)) + int(C) * int(Wc),
+            sum(w[1:]) + 1 + int(Wc) + int(C))
+
+
+def radiance_param_shapes(widths, H: int, Wc: int, C: int) -> list[tuple[int, int]]:
+    """The (out, in) of every matrix of that layout, in its order."""
+    w = [6 * int(H)] + [int(v) for v in widths]
+    return [(o, i) for i, o in zip(w[:-1], w[1:])] + [(1, w[-1]), (int(Wc), w[-1] + 6 * int(H)), (int(C), int(Wc))]
+
+
+def _radiance_shape(widths, H, Wc, C):
+    w = (ctypes.c_int32 * len(widths))(*[int(v) for v in widths])
+    return (len(widths), ctypes.cast(w, ctypes.c_void_p), int(H), int(Wc), int(C)), w      # w: kept alive by the caller
+
+
+def radiance_pack_device(widths, H: int, Wc: int, C: int, frequencies, beta: float, W: torch.Tensor, b: torch.Tensor,
+                         pack: torch.Tensor | None = None, packT: torch.Tensor | None = None):
+    """isr_radiance_pack_device: W and b flat in isr_radiance_pack's layout (radiance_param_sizes) on the device, the H
+    frequencies on the host -> (pack, packT): the forward pack, byte for byte isr_radiance_pack's, and the transposed pack of
+    the backward.  Every word of both is written (into `pack` / `packT` when given); nothing synchronises."""
+    dev = require_cuda(W, b, pack, packT)
+    nw, nb = radiance_param_sizes(widths, H, Wc, C)
+    _flat_f32("radiance_pack_device", "W", W, nw)
+    _flat_f32("radiance_pack_device", "b", b, nb)
+    fr = np.ascontiguousarray(frequencies.detach().cpu().numpy() if isinstance(frequencies, torch.Tensor) else frequencies,
+                              np.float32).reshape(-1)
+    if fr.shape[0] != int(H):
+        raise ValueError(f"radiance_pack_device: {fr.shape[0]} frequencies, H = {H}")
+    shape, _keep = _radiance_shape(widths, H, Wc, C)
+    L = lib()
+    words, wordsT = L.isr_radiance_pack_bytes(*shape) // 4, L.isr_radiance_grad_pack_bytes(*shape) // 4
+    if words == 0 or wordsT == 0:
+        check(-1, "isr_radiance_pack_bytes")
+    if pack is None:
+        pack = torch.empty(words, dtype=torch.float32, device=dev)
+    if packT is None:
+        packT = torch.empty(wordsT, dtype=torch.float32, device=dev)
+    _flat_f32("radiance_pack_device", "pack", pack, words)
+    _flat_f32("radiance_pack_device", "packT", packT, wordsT)
+    with torch.cuda.device(dev), _timed("radiance_pack_device", 0.0):
+        rc = L.isr_radiance_pack_device(*shape, _hp(fr), float(beta), ptr(W), ptr(b), ptr(pack), words * 4, ptr(packT), wordsT * 4,
+                                        current_stream(dev))
+    check(rc, "isr_radiance_pack_device")
+    return pack, packT
+
+
+def radiance_backward_flops(widths, H: int, Wc: int, C: int) -> float:
+    """Multiply-adds x 2 of one point through the backward as issued: the forward again, the u pass (every trunk layer but
+    the first, W1's trunk columns and W2) and the dW pass (W1's direction columns included)."""
+    w = [int(v) for v in widths]
+    f = radiance_flops(w, H, Wc, C)
+    u = 2.0 * (sum(a * b for a, b in zip(w[:-1], w[1:])) + w[-1] * int(Wc) + int(Wc) * int(C) + w[-1])
+    return 2.0 * f + u + 2.0 * int(Wc) * 6 * int(H)
+
+
+def radiance_backward(pack: torch.Tensor, packT: torch.Tensor, widths, H: int, Wc: int, C: int, origins: torch.Tensor,
+                      directions: torch.Tensor, lengths: torch.Tensor, d_densities: torch.Tensor | None,
+                      d_colours: torch.Tensor | None, need=(True, True), slab: int | None = None,
+                      workspace_buf: torch.Tensor | None = None):
+    """isr_radiance_backward: the bundle origins (N,3), directions (N,3), lengths (N,P) and the upstream gradients
+    d_densities (N,P) and d_colours (N,P,C) f32 (either None: zeros) -> (dW, db) flat in isr_radiance_pack's layout
+    (radiance_param_sizes), every entry written; need: which of the two to compute (the other is None).  The forward is
+    recomputed from the rays; pack and packT are radiance_pack_device's.  slab: work through the points this many at a time
+    (a multiple of the chain length; tests) instead of the default; workspace_buf: a contiguous device buffer to use instead
+    of the cached one (tests).  Nothing synchronises."""
+    dev = require_cuda(pack, packT, origins, directions, lengths, d_densities, d_colours, workspace_buf)
+    N, P, _ = _ray_bundle("radiance_backward", origins, directions, lengths, 0.0)
+    C = int(C)
+    for what, t, shape in (("d_densities", d_densities, (N, P)), ("d_colours", d_colours, (N, P, C))):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError(f"radiance_backward: {what} must be contiguous {shape} float32, got {tuple(t.shape)} {t.dtype}")
+    nw, nb = radiance_param_sizes(widths, H, Wc, C)
+    shape, _keep = _radiance_shape(widths, H, Wc, C)
+    L = lib()
+    if workspace_buf is not None:
+        ws, ws_bytes = workspace_buf, workspace_buf.numel() * workspace_buf.element_size()
+    elif slab is None:
+        ws_bytes = L.isr_radiance_grad_workspace_bytes(*shape, N, P)
+        ws = workspace(dev, ws_bytes, "radiance_grad") if ws_bytes else None
+    else:
+        chain = L.isr_radiance_grad_geometry(0)
+        if slab < chain or slab % chain:
+            raise ValueError(f"radiance_backward: slab {slab} is not a multiple of the chain length {chain}")
+        ws_bytes = L.isr_radiance_grad_workspace_bytes(*shape, int(slab), 1)      # `slab` points, a ray each: the most rays
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    if ws_bytes == 0:
+        check(-1, "isr_radiance_grad_workspace_bytes")
+    dW = torch.empty(nw, dtype=torch.float32, device=dev) if need[0] else None
+    db = torch.empty(nb, dtype=torch.float32, device=dev) if need[1] else None
+    with torch.cuda.device(dev), _timed("radiance_backward", float(N) * P * radiance_backward_flops(widths, H, Wc, C)):
+        rc = L.isr_radiance_backward(ptr(pack), pack.numel() * pack.element_size(), ptr(packT), packT.numel() * packT.element_size(),
+                                     *shape, ptr(origins), ptr(directions), ptr(lengths), N, P, ptr(d_densities), ptr(d_colours),
+                                     ptr(dW), ptr(db), ptr(ws), ws_bytes, current_stream(dev))
+    check(rc, "isr_radiance_backward")
+    return dW, db
+
+
+def radiance_backward_host(pack_host, widths, H: int, Wc: int, C: int, origins, directions, lengths, d_densities=None,
+                           d_colours=None, need=(True, True)):
+    """isr_radiance_backward_host: radiance_backward as host code over NumPy arrays (pack_host: isr_radiance_pack's words, e.g.
+    RadianceField.rpack_host).  For tests."""
+    pack_host = np.ascontiguousarray(pack_host, np.float32)
+    o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+    ln = np.ascontiguousarray(lengths, np.float32)
+    N, P = ln.shape
+    dd = None if d_densities is None else np.ascontiguousarray(d_densities, np.float32)
+    dc = None if d_colours is None else np.ascontiguousarray(d_colours, np.float32)
+    if o.shape[0] != N or d.shape[0] != N or (dd is not None and dd.shape != (N, P)) or (dc is not None and dc.shape != (N, P, int(C))):
+        raise ValueError("radiance_backward_host: the shapes of the bundle and the upstream gradients do not agree")
+    nw, nb = radiance_param_sizes(widths, H, Wc, C)
+    shape, _keep = _radiance_shape(widths, H, Wc, C)
+    dW = np.empty(nw, np.float32) if need[0] else None
+    db = np.empty(nb, np.float32) if need[1] else None
+    check(lib().isr_radiance_backward_host(_hp(pack_host), pack_host.nbytes, *shape, _hp(o), _hp(d), _hp(ln), N, P, _hp(dd), _hp(dc),
+                                           _hp(dW), _hp(db)), "isr_radiance_backward_host")
+    return dW, db
+
+
+def radiance_grad_slopes_host(z, beta: float):
+    """isr_radiance_grad_slopes_host: (slope32(z, beta), dexp32(z)) of every element of a NumPy f32 array.  For tests."""
+    z = np.ascontiguousarray(z, np.float32)
+    sl, de = np.empty_like(z), np.empty_like(z)
+    check(lib().isr_radiance_grad_slopes_host(_hp(z), z.size, float(beta), _hp(sl), _hp(de)), "isr_radiance_grad_slopes_host")
+    return sl, de

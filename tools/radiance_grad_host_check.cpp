@@ -1,0 +1,183 @@
+// radiance_grad_host_check.cpp — csrc/radiance_grad.hpp (over csrc/field_radiance.hpp) as plain host code, for a sanitizer build:
+//     c++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all \
+//         tools/radiance_grad_host_check.cpp -o radiance_grad_host_check && ./radiance_grad_host_check
+// Drives make_layout / make_layout_t / std_offsets, pack_host, HostNet, ray_grad_term, point_grads, blocked_row and
+// backward_host over the fields and shapes of the tests, with arrays of exactly the sizes the header asks for.  Checks what
+// can be checked without a second implementation: the transposed layout's blocks follow one another without overlap and
+// hold every W_l^T; N = 0 and a zero upstream give exactly +0 everywhere; doubling the upstream doubles every gradient bit
+// for bit (every operation is linear in it and a factor of 2 is exact); a null upstream is the same as zeros; dW or db left out
+// changes nothing of the other; a NaN sample makes NaNs and nothing else does.  Then measures slope32 and dexp32 against
+// the f64 library over a grid of 2 200 001 arguments in [-110, 110], in f32 ulp of the f64 value.  Prints one line per case;
+// exit status 0 = all hold.  The log of one such run is profiles/radiance_grad_host_sanitizers.txt.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#define __host__
+#define __device__
+#include "../imagesequenceregistrationfor6dposeestimationlabeling_amd/csrc/radiance_grad.hpp"
+
+using namespace isr::radiance;
+
+namespace {
+
+unsigned seed = 13579u;
+float uni() {                                        // U(-1, 1)
+  seed = seed * 1664525u + 1013904223u;
+  return (float)((seed >> 8) & 0xffff) / 32768.f - 1.f;
+}
+
+int fails = 0;
+const auto serial = [](long n, long, auto fn) {
+  for (long i = 0; i < n; ++i) fn(i);
+};
+
+bool same_bits(const std::vector<float>& a, const std::vector<float>& b) {
+  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * 4) == 0);
+}
+
+void run(int H, int n_hidden, const int32_t* widths, int Wc, int C, int N, int P, bool nan_point) {
+  Layout lay;
+  GradLayout T;
+  if (!make_layout(n_hidden, widths, H, Wc, C, lay)) {
+    std::printf("make_layout refused a field of the tests FAILED\n");
+    ++fails;
+    return;
+  }
+  make_layout_t(lay, T);
+  StdOffsets so;
+  std_offsets(lay, so);
+  bool ok = true;
+  {                                                  // the transposed layout: consecutive blocks of the stated shapes
+    int off = isr::field::kHeaderWords;
+    for (int l = 1; l <= n_hidden + 1; ++l) {
+      const Layer& t = l < n_hidden ? T.T[l] : l == n_hidden ? T.trunkT : T.outT;
+      ok = ok && t.w_off == off && t.b_off == off + t.OP * t.kstride && t.kstride % 32 == 0 && t.OP % 32 == 0;
+      off = t.b_off + t.OP;
+    }
+    ok = ok && off == T.total_words && T.trunkT.O == lay.d.out_K && T.trunkT.K == lay.WcP && T.outT.O == Wc && T.outT.K == 32;
+  }
+  std::vector<float> W((size_t)so.w_total), b((size_t)so.b_total), pack((size_t)lay.total_words), freqs((size_t)H);
+  for (int i = 0; i < H; ++i) freqs[(size_t)i] = 0.1f * std::ldexp(1.f, i);
+  {
+    int l = 0, w0 = 0;
+    auto fill = [&](int O, int K, float scale) {
+      for (int i = 0; i < O * K; ++i) W[(size_t)w0 + i] = uni() * scale / std::sqrt((float)K);
+      w0 += O * K;
+      ++l;
+    };
+    for (int i = 0; i < n_hidden; ++i) fill(lay.d.L[i].O, lay.d.L[i].K, 1.f);
+    fill(1, lay.d.out_K, 3.f);
+    fill(Wc, lay.d.out_K + 6 * H, 1.f);
+    fill(C, Wc, 4.f);
+    for (float& v : b) v = 0.1f * uni();
+  }
+  pack_host(lay, freqs.data(), 10.f, W.data(), b.data(), pack.data());
+  const size_t NP = (size_t)N * P;
+  std::vector<float> o((size_t)N * 3), d((size_t)N * 3), ln(NP), dd(NP), dc(NP * C);
+  for (float& v : o) v = 1.5f * uni();
+  for (float& v : d) v = 2.f * uni();
+  if (N > 1) d[3] = d[4] = d[5] = 0.f;               // a zero direction
+  for (size_t i = 0; i < NP; ++i) ln[i] = 1.f + uni();
+  for (float& v : dd) v = uni();
+  for (float& v : dc) v = uni();
+  if (nan_point && NP) ln[NP / 2] = NAN;
+  auto grads = [&](const float* pd, const float* pc, bool wW, bool wb, std::vector<float>& dW, std::vector<float>& db) {
+    dW.assign((size_t)so.w_total, 7.f);
+    db.assign((size_t)so.b_total, 7.f);
+    backward_host(serial, lay, pack.data(), o.data(), d.data(), ln.data(), N, P, pd, pc, wW ? dW.data() : nullptr, wb ? db.data() : nullptr);
+  };
+  std::vector<float> dW, db, dW2, db2, z1, z2;
+  grads(dd.data(), dc.data(), true, true, dW, db);
+  size_t nans = 0;
+  for (float v : dW) nans += v != v;
+  for (float v : db) nans += v != v;
+  ok = ok && (nan_point && NP ? nans > 0 : nans == 0);
+  if (N == 0)
+    for (size_t i = 0; i < dW.size() + db.size(); ++i) {
+      const float v = i < dW.size() ? dW[i] : db[i - dW.size()];
+      ok = ok && v == 0.f && !std::signbit(v);
+    }
+  if (!nan_point) {
+    std::vector<float> dd2(dd), dc2(dc);             // twice the upstream: twice the gradient, bit for bit
+    for (float& v : dd2) v *= 2.f;
+    for (float& v : dc2) v *= 2.f;
+    grads(dd2.data(), dc2.data(), true, true, dW2, db2);
+    for (size_t i = 0; i < dW.size(); ++i) ok = ok && dW2[i] == 2.f * dW[i];
+    for (size_t i = 0; i < db.size(); ++i) ok = ok && db2[i] == 2.f * db[i];
+    std::vector<float> zd(NP, 0.f), zc(NP * C, 0.f);  // zeros, and null upstreams: exactly +0 and the same
+    grads(zd.data(), zc.data(), true, true, z1, z2);
+    for (float v : z1) ok = ok && v == 0.f && !std::signbit(v);
+    for (float v : z2) ok = ok && v == 0.f && !std::signbit(v);
+    grads(nullptr, nullptr, true, true, dW2, db2);
+    ok = ok && same_bits(dW2, z1) && same_bits(db2, z2);
+    grads(dd.data(), nullptr, true, true, dW2, db2);
+    grads(dd.data(), zc.data(), true, true, z1, z2);
+    ok = ok && same_bits(dW2, z1) && same_bits(db2, z2);
+  }
+  grads(dd.data(), dc.data(), true, false, dW2, db2);  // an output left out: the other unchanged, the missing one untouched
+  ok = ok && (nan_point || same_bits(dW2, dW)) && db2[0] == 7.f;
+  grads(dd.data(), dc.data(), false, true, dW2, db2);
+  ok = ok && (nan_point || same_bits(db2, db)) && dW2[0] == 7.f;
+  std::printf("H %-2d widths", H);
+  for (int l = 0; l < n_hidden; ++l) std::printf(" %d", widths[l]);
+  std::printf(" Wc %d C %d  N %d P %d %s NaN entries %zu  %s\n", Wc, C, N, P, nan_point ? "a NaN sample" : "random      ", nans,
+              ok ? "ok" : "FAILED");
+  if (!ok) ++fails;
+}
+
+void slopes() {
+  double worst_s = 0.0, worst_d = 0.0;
+  float at_s = 0.f, at_d = 0.f;
+  long count = 0;
+  for (long i = -1100000; i <= 1100000; ++i, ++count) {
+    const float z = (float)((double)i * 1e-4);
+    const double t = 10.0 * (double)z;
+    const double rs = t > 20.0 ? 1.0 : 1.0 / (1.0 + std::exp(-t)), rd = std::exp(-(double)z);
+    const float s = slope32(z, 10.f), e = dexp32(z);
+    if (rs > 1.2e-38) {
+      const double u = std::fabs((double)s - rs) / (double)(std::nextafter((float)rs, INFINITY) - (float)rs);
+      if (u > worst_s) worst_s = u, at_s = z;
+    }
+    if (rd > 1.2e-38 && rd < 3.4e38) {
+      const double u = std::fabs((double)e - rd) / (double)(std::nextafter((float)rd, INFINITY) - (float)rd);
+      if (u > worst_d) worst_d = u, at_d = z;
+    }
+  }
+  const bool ok = worst_s <= 1.0 && worst_d <= 1.0 && slope32(2.0000002f, 10.f) == 1.f && slope32(NAN, 10.f) != slope32(NAN, 10.f) &&
+                  dexp32(NAN) != dexp32(NAN) && slope32(-INFINITY, 10.f) == 0.f && slope32(INFINITY, 10.f) == 1.f && dexp32(INFINITY) == 0.f &&
+                  dexp32(0.f) == 1.f && slope32(0.f, 10.f) == 0.5f;
+  std::printf("slope32 over [-110, 110]: %ld arguments, largest error %.4f f32 ulp of the f64 value (at z = %.7g)\n", count, worst_s, at_s);
+  std::printf("dexp32 over [-110, 110]: %ld arguments, largest error %.4f f32 ulp (at s = %.7g)\n", count, worst_d, at_d);
+  std::printf("slope32 is 1 past the seam, the limits and NaN of both                %s\n", ok ? "ok" : "FAILED");
+  if (!ok) ++fails;
+}
+
+}  // namespace
+
+int main() {
+  const int32_t w1[] = {1}, w5[] = {5}, w3233[] = {32, 33}, w40[] = {40}, wref[] = {256, 256}, w4[] = {7, 256, 1, 40};
+  const int shapes[][2] = {{0, 3}, {1, 1}, {21, 3}, {4, 16}, {5, 13}, {43, 3}, {64, 1}, {65, 1}, {2, 65}, {22, 3}};
+  for (const auto& s : shapes) {
+    run(1, 1, w1, 1, 1, s[0], s[1], false);
+    run(4, 1, w5, 5, 3, s[0], s[1], false);
+    run(4, 2, w3233, 40, 3, s[0], s[1], false);
+  }
+  run(60, 1, w40, 33, 32, 5, 13, false);
+  run(60, 1, w40, 33, 32, 2, 65, false);
+  run(60, 2, wref, 256, 3, 3, 2, false);
+  run(64, 4, w4, 256, 32, 3, 5, false);              // the limits of the layout: H = 64, four hidden layers, Wc = 256, C = 32
+  run(4, 2, w3233, 40, 3, 43, 3, true);
+  run(4, 1, w5, 5, 3, 2, 65, true);
+  slopes();
+  Layout lay;
+  const int32_t bad[] = {32, 257};
+  const bool refused = !make_layout(0, w1, 4, 8, 3, lay) && !make_layout(5, w4, 4, 8, 3, lay) && !make_layout(2, bad, 4, 8, 3, lay) &&
+                       !make_layout(1, w1, 65, 8, 3, lay) && !make_layout(1, w1, 4, 0, 3, lay) && !make_layout(1, w1, 4, 8, 33, lay);
+  std::printf("make_layout refuses what the header says                              %s\n", refused ? "ok" : "FAILED");
+  if (!refused) ++fails;
+  std::printf(fails ? "%d FAILED\n" : "all hold\n", fails);
+  return fails ? 1 : 0;
+}
