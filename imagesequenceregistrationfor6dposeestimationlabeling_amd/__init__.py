@@ -25,6 +25,9 @@ def __getattr__(name):
     if name in ("pose_train_step", "nerf_train_step"):
         from . import training
         return getattr(training, name)
+    if name in ("PoseBatches", "CorrespondenceBank", "AugmentParams", "draw_params", "rotation_matrix_2d"):
+        from . import augment
+        return getattr(augment, name)
     if name == "marching_cubes":
         from . import ops
         return ops.marching_cubes

@@ -283,6 +283,16 @@ MC_SIGNATURES = {
     "isr_mc_emit_host": (_i, [_vp, _i, _i, _i, _f, _vp, _i64, _vp, _i64]),
 }
 
+# include/isr_augment.h (training batches: the image warps and the ray remap and sample), bound the same way
+_AUGMENT_IMAGES = [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]      # rgb .. mask_out
+_AUGMENT_RAYS = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+AUGMENT_SIGNATURES = {
+    "isr_augment_images": (_i, [*_AUGMENT_IMAGES, _vp]),
+    "isr_augment_images_host": (_i, _AUGMENT_IMAGES),
+    "isr_augment_rays": (_i, [*_AUGMENT_RAYS, _vp]),
+    "isr_augment_rays_host": (_i, _AUGMENT_RAYS),
+}
+
 
 def lib() -> C.CDLL:
     """Load libisr_hip.so (once).  Raises IsrError when it has not been built."""
@@ -302,7 +312,7 @@ def lib() -> C.CDLL:
                                **DENSITY_DIR_SIGNATURES, **RADIUS_SIGNATURES, **MC_SIGNATURES, **KNN_SIGNATURES,
                                **RAYS_SIGNATURES, **RADIANCE_SIGNATURES, **RESAMPLE_SIGNATURES,
                                **CONTRASTIVE_SIGNATURES, **FIELD_GRAD_SIGNATURES, **SAMPLE_GRAD_SIGNATURES,
-                               **EA_GRAD_SIGNATURES, **RADIANCE_GRAD_SIGNATURES}.items():
+                               **EA_GRAD_SIGNATURES, **RADIANCE_GRAD_SIGNATURES, **AUGMENT_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

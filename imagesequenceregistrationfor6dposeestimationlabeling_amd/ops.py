@@ -2367,3 +2367,178 @@ def radiance_grad_slopes_host(z, beta: float):
     sl, de = np.empty_like(z), np.empty_like(z)
     check(lib().isr_radiance_grad_slopes_host(_hp(z), z.size, float(beta), _hp(sl), _hp(de)), "isr_radiance_grad_slopes_host")
     return sl, de
+
+
+# ---- training batches (include/isr_augment.h)
+AUGMENT_MAX_SAMPLE = 4096
+AUGMENT_MAX_VIEW_ROWS = 1 << 20
+
+
+def _augment_image_params(name: str, B: int, M, rect, tra, tra1, border, mean, std):
+    """The host arrays of isr_augment_images: M (B, 2, 3) f64; rect (B, 4), tra, tra1, border (B, 2) i32 or None; mean, std (3,) f32."""
+    Mh = np.ascontiguousarray(np.asarray(M, np.float64).reshape(-1))
+    if Mh.size != 6 * B:
+        raise ValueError(f"{name}: M must be ({B}, 2, 3), got {np.shape(M)}")
+
+    def ints(a, cols, what):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(a, np.int64).reshape(-1))
+        if a.size != cols * B or (np.abs(a) >= 2 ** 31).any():
+            raise ValueError(f"{name}: {what} must be ({B}, {cols}) and fit int32")
+        return a.astype(np.int32)
+
+    mu, sd = np.ascontiguousarray(mean, np.float32).reshape(-1), np.ascontiguousarray(std, np.float32).reshape(-1)
+    if mu.size != 3 or sd.size != 3:
+        raise ValueError(f"{name}: mean and std must hold 3 values")
+    return Mh, ints(rect, 4, "rect"), ints(tra, 2, "tra"), ints(tra1, 2, "tra1"), ints(border, 2, "border"), mu, sd
+
+
+def _augment_image_shapes(name: str, rgb, mask, orig_mask, canvas) -> tuple[int, int, int]:
+    if rgb.ndim != 4 or rgb.shape[3] != 3 or min(rgb.shape) < 1:
+        raise ValueError(f"{name}: rgb must be (B, H, W, 3) and not empty, got {tuple(rgb.shape)}")
+    B, H, W, _ = rgb.shape
+    for what, m in (("mask", mask), ("orig_mask", orig_mask)):
+        if m is not None and tuple(m.shape) != (B, H, W):
+            raise ValueError(f"{name}: {what} must be ({B}, {H}, {W}), got {tuple(m.shape)}")
+    if canvas is not None and tuple(canvas.shape) != (B, H, W, 3):
+        raise ValueError(f"{name}: canvas must be ({B}, {H}, {W}, 3), got {tuple(canvas.shape)}")
+    return int(B), int(H), int(W)
+
+
+def augment_images(rgb: torch.Tensor, mask: torch.Tensor, M, *, orig_mask: torch.Tensor | None = None,
+                   canvas: torch.Tensor | None = None, rect=None, tra=None, tra1=None, border=None, mean=IMAGENET_MEAN,
+                   std=IMAGENET_STD):
+    """isr_augment_images: rgb (B, H, W, 3) f32, mask (B, H, W) u8 holding 0/1, orig_mask likewise (None: mask), canvas
+    (B, H, W, 3) f32 or None (zeros) on the device; M (B, 2, 3) f64, rect (B, 4) = (x, y, w, h), tra, tra1 (B, 2) and border
+    (B, 2) = (kh, kw) on the host (None: no rectangle, zero shifts, no border) -> (rgb_out (B, H, W, 3), mask_orig_out (B, H, W),
+    mask_out (B, H, W)) f32 on the device: generateImages' two warps, paste and border blanking, then dataGen.normalize.
+    Nothing synchronises."""
+    dev = require_cuda(rgb, mask, orig_mask, canvas)
+    if rgb.dtype != torch.float32 or mask.dtype != torch.uint8 or (orig_mask is not None and orig_mask.dtype != torch.uint8) \
+            or (canvas is not None and canvas.dtype != torch.float32):
+        raise ValueError("augment_images: rgb and canvas must be float32, the masks uint8")
+    B, H, W = _augment_image_shapes("augment_images", rgb, mask, orig_mask, canvas)
+    rgb, mask = rgb.contiguous(), mask.contiguous()
+    orig = mask if orig_mask is None else orig_mask.contiguous()
+    canvas = None if canvas is None else canvas.contiguous()
+    Mh, rc_, t_, t1_, bd_, mu, sd = _augment_image_params("augment_images", B, M, rect, tra, tra1, border, mean, std)
+    rgb_out = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+    mask_orig_out = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    mask_out = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timed("augment_images", float(B) * H * W):
+        rc = lib().isr_augment_images(ptr(rgb), ptr(mask), ptr(orig), ptr(canvas), B, H, W, _hp(rc_), _hp(Mh), _hp(t_), _hp(t1_),
+                                      _hp(bd_), _hp(mu), _hp(sd), ptr(rgb_out), ptr(mask_orig_out), ptr(mask_out),
+                                      current_stream(dev))
+    check(rc, "isr_augment_images")
+    return rgb_out, mask_orig_out, mask_out
+
+
+def augment_images_host(rgb, mask, M, *, orig_mask=None, canvas=None, rect=None, tra=None, tra1=None, border=None,
+                        mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """isr_augment_images_host: the same images as host code over NumPy arrays.  For tests."""
+    rgb, mask = np.ascontiguousarray(rgb, np.float32), np.ascontiguousarray(mask, np.uint8)
+    orig = mask if orig_mask is None else np.ascontiguousarray(orig_mask, np.uint8)
+    canvas = None if canvas is None else np.ascontiguousarray(canvas, np.float32)
+    B, H, W = _augment_image_shapes("augment_images_host", rgb, mask, orig, canvas)
+    Mh, rc_, t_, t1_, bd_, mu, sd = _augment_image_params("augment_images_host", B, M, rect, tra, tra1, border, mean, std)
+    rgb_out, mask_orig_out, mask_out = np.empty((B, H, W, 3), np.float32), np.empty((B, H, W), np.float32), np.empty((B, H, W), np.float32)
+    check(lib().isr_augment_images_host(_hp(rgb), _hp(mask), _hp(orig), _hp(canvas), B, H, W, _hp(rc_), _hp(Mh), _hp(t_), _hp(t1_),
+                                        _hp(bd_), _hp(mu), _hp(sd), _hp(rgb_out), _hp(mask_orig_out), _hp(mask_out)),
+          "isr_augment_images_host")
+    return rgb_out, mask_orig_out, mask_out
+
+
+@dataclass
+class AugmentedRays:
+    """One set's sample: xys (B, S, 2) the remapped locations, pos (B, S, 3), index (B, S) i32 (the row in the view, -1 past the
+    count), count (B,) i32; rows past the count are zeros."""
+    xys: "torch.Tensor | np.ndarray"
+    pos: "torch.Tensor | np.ndarray"
+    index: "torch.Tensor | np.ndarray"
+    count: "torch.Tensor | np.ndarray"
+
+
+def _augment_ray_params(name: str, front, back, view_ids, rot, t, S: int):
+    """Checks of isr_augment_rays -> (B, V, host arrays offsets_front, offsets_back or None, view_ids, rot, t).  front / back:
+    (xys (n, 2), pos (n, 3), offsets (V + 1))."""
+    ids = np.ascontiguousarray(np.asarray(view_ids, np.int64).reshape(-1))
+    B = ids.size
+    rot_, t_ = np.ascontiguousarray(rot, np.float32).reshape(-1), np.ascontiguousarray(t, np.float32).reshape(-1)
+    if B < 1 or rot_.size != 4 * B or t_.size != 2 * B:
+        raise ValueError(f"{name}: view_ids (B,), rot (B, 4) and t (B, 2) with B >= 1, got {ids.shape}, {np.shape(rot)}, {np.shape(t)}")
+    if not 1 <= int(S) <= AUGMENT_MAX_SAMPLE:
+        raise ValueError(f"{name}: S = {S} outside 1..{AUGMENT_MAX_SAMPLE}")
+    offs, V = [], None
+    for what, bank in (("front", front), ("back", back)):
+        if bank is None:
+            offs.append(None)
+            continue
+        xys, pos, off = bank
+        off = np.ascontiguousarray(np.asarray(off, np.int64).reshape(-1))
+        if V is None:
+            V = off.size - 1
+        if off.size - 1 != V or V < 1 or off[0] != 0 or (np.diff(off) < 0).any():
+            raise ValueError(f"{name}: the {what} offsets must be (V + 1,) from 0 and non-decreasing, the same V for both sets")
+        n = int(off[-1])
+        if xys.ndim != 2 or xys.shape[1] != 2 or pos.ndim != 2 or pos.shape[1] != 3 or xys.shape[0] != n or pos.shape[0] != n:
+            raise ValueError(f"{name}: the {what} bank must be xys ({n}, 2) and pos ({n}, 3), got {tuple(xys.shape)} and {tuple(pos.shape)}")
+        offs.append(off)
+    if (ids < 0).any() or (ids >= V).any():
+        raise ValueError(f"{name}: view ids outside 0..{V - 1}")
+    return B, V, offs[0], offs[1], ids.astype(np.int32), rot_, t_
+
+
+def augment_rays(front, view_ids, rot, t, S: int, seed: int, back=None):
+    """isr_augment_rays: front = (xys (sum n, 2) f32, pos (sum n, 3) f32 on the device, offsets (V + 1) on the host), back
+    likewise or None; view_ids (B,), rot (B, 4) = (m00, m01, m10, m11) f32 and t (B, 2) f32 on the host -> AugmentedRays of the
+    front set, or (front, back): getNerfSamples' remap and inside filter, and the min(S, m) candidates with the smallest
+    Philox keys of (seed, view id, set, row), in key order.  Nothing synchronises."""
+    dev = require_cuda(front[0], front[1], *(back[:2] if back is not None else ()))
+    B, V, off_f, off_b, ids, rot_, t_ = _augment_ray_params("augment_rays", front, back, view_ids, rot, t, S)
+    S = int(S)
+    sets, outs, args = [], [], []
+    for bank in (front, back):
+        if bank is None:
+            args += [None, None, None, None]
+            sets.append((None, None))
+            continue
+        xys, pos = bank[0], bank[1]
+        if xys.dtype != torch.float32 or pos.dtype != torch.float32:
+            raise ValueError("augment_rays: float32 banks only")
+        if xys.shape[0] == 0:                                                         # an empty bank still needs an address
+            xys, pos = torch.zeros((1, 2), dtype=torch.float32, device=dev), torch.zeros((1, 3), dtype=torch.float32, device=dev)
+        sets.append((xys.contiguous(), pos.contiguous()))
+        o = AugmentedRays(torch.empty((B, S, 2), dtype=torch.float32, device=dev), torch.empty((B, S, 3), dtype=torch.float32, device=dev),
+                          torch.empty((B, S), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+        outs.append(o)
+        args += [ptr(o.xys), ptr(o.pos), ptr(o.index), ptr(o.count)]
+    with torch.cuda.device(dev), _timed("augment_rays", float(B) * S):
+        rc = lib().isr_augment_rays(ptr(sets[0][0]), ptr(sets[0][1]), _hp(off_f), ptr(sets[1][0]), ptr(sets[1][1]), _hp(off_b), V,
+                                    _hp(ids), _hp(rot_), _hp(t_), B, S, int(seed) & 0xFFFFFFFFFFFFFFFF, *args, current_stream(dev))
+    check(rc, "isr_augment_rays")
+    return outs[0] if back is None else (outs[0], outs[1])
+
+
+def augment_rays_host(front, view_ids, rot, t, S: int, seed: int, back=None):
+    """isr_augment_rays_host: the same samples as host code over NumPy arrays.  For tests."""
+    B, V, off_f, off_b, ids, rot_, t_ = _augment_ray_params("augment_rays_host", front, back, view_ids, rot, t, S)
+    S = int(S)
+    sets, outs, args = [], [], []
+    for bank in (front, back):
+        if bank is None:
+            args += [None, None, None, None]
+            sets.append((None, None))
+            continue
+        xys, pos = np.ascontiguousarray(bank[0], np.float32), np.ascontiguousarray(bank[1], np.float32)
+        if xys.shape[0] == 0:
+            xys, pos = np.zeros((1, 2), np.float32), np.zeros((1, 3), np.float32)
+        sets.append((xys, pos))
+        o = AugmentedRays(np.empty((B, S, 2), np.float32), np.empty((B, S, 3), np.float32), np.empty((B, S), np.int32),
+                          np.empty(B, np.int32))
+        outs.append(o)
+        args += [_hp(o.xys), _hp(o.pos), _hp(o.index), _hp(o.count)]
+    check(lib().isr_augment_rays_host(_hp(sets[0][0]), _hp(sets[0][1]), _hp(off_f), _hp(sets[1][0]), _hp(sets[1][1]), _hp(off_b), V,
+                                      _hp(ids), _hp(rot_), _hp(t_), B, S, int(seed) & 0xFFFFFFFFFFFFFFFF, *args),
+          "isr_augment_rays_host")
+    return outs[0] if back is None else (outs[0], outs[1])

@@ -4,7 +4,9 @@ fields.TrainableKeyField (isr_field_backward) and the loss by losses.returnCross
 encoder and the key field are trained together, and every gradient the package computes is a function of its inputs only.
 
 The encoder is unpinned: the reference's UNet (dep/unet.py) is not part of it, so `encoder` is any torch.nn.Module that maps
-(B, 3, H, W) to (B, 13, H, W), and its own layers, forward and backward, are torch's.  Out of scope: the data loader, the
+(B, 3, H, W) to (B, 13, H, W), and its own layers, forward and backward, are torch's.  Its arguments come from
+augment.PoseBatches, the loader of dataGen.AugmentedSamples on the device (the warps, the paste and the ray remap of
+augment.py; include/isr_augment.h).  Out of scope: the loader's colour augmentations (albumentations), the
 learning-rate ramp of trainPose.py:229-236, checkpoints, the back-face keys (computed by trainPose.py:380, unused by its
 loss) and the maskRays=False branch.
 
