@@ -28,6 +28,9 @@ def __getattr__(name):
     if name in ("PoseBatches", "CorrespondenceBank", "AugmentParams", "draw_params", "rotation_matrix_2d"):
         from . import augment
         return getattr(augment, name)
+    if name in ("Adam", "pose_optimizer", "nerf_optimizer"):
+        from . import optim
+        return getattr(optim, name)
     if name == "marching_cubes":
         from . import ops
         return ops.marching_cubes

@@ -293,6 +293,16 @@ AUGMENT_SIGNATURES = {
     "isr_augment_rays_host": (_i, _AUGMENT_RAYS),
 }
 
+# include/isr_adam.h (the fused multi-tensor Adam), bound the same way
+ADAM_SIGNATURES = {
+    "isr_adam_geometry": (_i, [_i]),
+    "isr_adam_table_host": (_i, [_vp, _i, _i, _i64, _vp, _vp]),
+    "isr_adam_step": (_i, [_vp, _vp, _i, _i64, _vp, _i, _vp, _i, _vp]),
+    "isr_adam_zero_grads": (_i, [_vp, _vp, _i, _i64, _vp]),
+    "isr_adam_step_host": (_i, [_vp, _i, _vp, _i, _vp, _i64, _i]),
+    "isr_adam_scalars_host": (_i, [_vp, _i64, _vp, _vp]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libisr_hip.so (once).  Raises IsrError when it has not been built."""
@@ -312,7 +322,8 @@ def lib() -> C.CDLL:
                                **DENSITY_DIR_SIGNATURES, **RADIUS_SIGNATURES, **MC_SIGNATURES, **KNN_SIGNATURES,
                                **RAYS_SIGNATURES, **RADIANCE_SIGNATURES, **RESAMPLE_SIGNATURES,
                                **CONTRASTIVE_SIGNATURES, **FIELD_GRAD_SIGNATURES, **SAMPLE_GRAD_SIGNATURES,
-                               **EA_GRAD_SIGNATURES, **RADIANCE_GRAD_SIGNATURES, **AUGMENT_SIGNATURES}.items():
+                               **EA_GRAD_SIGNATURES, **RADIANCE_GRAD_SIGNATURES, **AUGMENT_SIGNATURES,
+                               **ADAM_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

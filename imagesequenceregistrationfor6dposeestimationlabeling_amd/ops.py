@@ -2542,3 +2542,92 @@ def augment_rays_host(front, view_ids, rot, t, S: int, seed: int, back=None):
                                       _hp(ids), _hp(rot_), _hp(t_), B, S, int(seed) & 0xFFFFFFFFFFFFFFFF, *args),
           "isr_augment_rays_host")
     return outs[0] if back is None else (outs[0], outs[1])
+
+
+# ---- the fused multi-tensor Adam (include/isr_adam.h)
+ADAM_MAX_GROUPS = 8
+ADAM_CHUNK = 4096
+# isr_adam_tensor, 48 bytes: the addresses of p, g, m, v, the element count, the group and the step slot
+ADAM_TENSOR = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("group", "<i4"), ("slot", "<i4")])
+
+
+def adam_geometry() -> dict:
+    """isr_adam_geometry: the descriptor's bytes, the chunk's elements, the workgroup's threads and the most groups, as built."""
+    L = lib()
+    return {k: int(L.isr_adam_geometry(i)) for i, k in enumerate(("tensor_bytes", "chunk", "threads", "max_groups"))}
+
+
+def adam_groups(groups) -> np.ndarray:
+    """(G, 6) f64 rows of (lr, beta1, beta2, eps, weight_decay, ramp) from a sequence of such rows."""
+    g = np.ascontiguousarray(np.asarray(groups, np.float64))
+    if g.ndim != 2 or g.shape[1] != 6:
+        raise ValueError(f"adam: groups must be (G, 6) = (lr, beta1, beta2, eps, weight_decay, ramp), got {g.shape}")
+    return g
+
+
+def adam_table_host(table: np.ndarray, G: int, n_slots: int):
+    """isr_adam_table_host: checks a host table of ADAM_TENSOR rows -> (chunk_start (T + 1) i32, chunks)."""
+    if table.dtype != ADAM_TENSOR or table.ndim != 1 or not table.flags.c_contiguous:
+        raise ValueError("adam_table_host: table must be a contiguous 1-d array of ops.ADAM_TENSOR")
+    T = int(table.shape[0])
+    chunk_start = np.zeros(T + 1, np.int32)
+    chunks = ctypes.c_int64(0)
+    check(lib().isr_adam_table_host(_hp(table) if T else None, T, int(G), int(n_slots), _hp(chunk_start), ctypes.byref(chunks)),
+          "isr_adam_table_host")
+    return chunk_start, int(chunks.value)
+
+
+def adam_step(table: torch.Tensor, chunk_start: torch.Tensor, T: int, chunks: int, groups: np.ndarray, steps: torch.Tensor,
+              zero_grads: bool = False) -> None:
+    """isr_adam_step: table (the bytes of T ADAM_TENSOR rows) and chunk_start (T + 1) i32 on the device, copies of what
+    adam_table_host accepted; groups (G, 6) f64 on the host; steps i64 on the device.  Two launches, nothing synchronises."""
+    dev = require_cuda(table, chunk_start, steps)
+    if steps.dtype != torch.int64 or chunk_start.dtype != torch.int32 or not steps.is_contiguous():
+        raise ValueError("adam_step: steps must be contiguous int64, chunk_start int32")
+    groups = adam_groups(groups)
+    with torch.cuda.device(dev), _timed("adam_step", float(chunks) * ADAM_CHUNK):
+        rc = lib().isr_adam_step(ptr(table), ptr(chunk_start), int(T), int(chunks), _hp(groups), int(groups.shape[0]), ptr(steps),
+                                 int(bool(zero_grads)), current_stream(dev))
+    check(rc, "isr_adam_step")
+
+
+def adam_zero_grads(table: torch.Tensor, chunk_start: torch.Tensor, T: int, chunks: int) -> None:
+    """isr_adam_zero_grads: +0 to every gradient of the table, one launch."""
+    dev = require_cuda(table, chunk_start)
+    with torch.cuda.device(dev), _timed("adam_zero_grads", float(chunks) * ADAM_CHUNK):
+        rc = lib().isr_adam_zero_grads(ptr(table), ptr(chunk_start), int(T), int(chunks), current_stream(dev))
+    check(rc, "isr_adam_zero_grads")
+
+
+def adam_step_host(params, grads, exp_avgs, exp_avg_sqs, group_of, groups, steps: np.ndarray, slots=None,
+                   zero_grads: bool = False) -> None:
+    """isr_adam_step_host: one step, in place, over lists of 1-d float32 NumPy arrays (views allowed: their addresses are
+    used as they are); group_of: each tensor's row of groups (G, 6); steps: int64 counters, tensor i using steps[slots[i]]
+    (slots None: i).  For tests."""
+    T = len(params)
+    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(group_of) == T):
+        raise ValueError("adam_step_host: the lists differ in length")
+    if steps.dtype != np.int64 or not steps.flags.c_contiguous:
+        raise ValueError("adam_step_host: steps must be contiguous int64")
+    slots = list(range(T)) if slots is None else list(slots)
+    table = np.zeros(T, ADAM_TENSOR)
+    for i, arrays in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs)):
+        n = arrays[0].size
+        for name, a in zip("pgmv", arrays):
+            if a.dtype != np.float32 or a.size != n or (a.size > 1 and a.ndim == 1 and a.strides[0] != 4) \
+                    or (a.ndim != 1 and not a.flags.c_contiguous) or not a.flags.writeable:
+                raise ValueError(f"adam_step_host: tensor {i}: {name} must be writeable dense float32 of {n} elements")
+            table[name][i] = a.ctypes.data
+        table["n"][i], table["group"][i], table["slot"][i] = n, group_of[i], slots[i]
+    groups = adam_groups(groups)
+    check(lib().isr_adam_step_host(_hp(table) if T else None, T, _hp(groups), int(groups.shape[0]), _hp(steps), int(steps.size),
+                                   int(bool(zero_grads))), "isr_adam_step_host")
+
+
+def adam_scalars_host(group, t: int):
+    """isr_adam_scalars_host: group = (lr, beta1, beta2, eps, weight_decay, ramp), t the 1-based step ->
+    dict(lr_t, beta1_t, beta2_t as f64; step, r as f32)."""
+    g = adam_groups([group])
+    out4, out2 = np.zeros(4, np.float64), np.zeros(2, np.float32)
+    check(lib().isr_adam_scalars_host(_hp(g), int(t), _hp(out4), _hp(out2)), "isr_adam_scalars_host")
+    return {"lr_t": float(out4[0]), "beta1_t": float(out4[1]), "beta2_t": float(out4[2]), "step": out2[0], "r": out2[1]}
