@@ -19,7 +19,8 @@ def __getattr__(name):
                 "EmissionAbsorptionRaymarcherStratified", "ImplicitRendererStratified"):
         from . import rays
         return getattr(rays, name)
-    if name in ("contrastive_loss", "huber", "returnCrossEntropy", "returnCrossEntropy2", "returnCrossEntropyWithNeg"):
+    if name in ("contrastive_loss", "huber", "returnCrossEntropy", "returnCrossEntropy2", "returnCrossEntropyWithNeg",
+                "distortion_loss", "mip360loss", "render_loss"):
         from . import losses
         return getattr(losses, name)
     if name in ("pose_train_step", "nerf_train_step"):

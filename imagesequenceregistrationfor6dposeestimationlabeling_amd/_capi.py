@@ -303,6 +303,22 @@ ADAM_SIGNATURES = {
     "isr_adam_scalars_host": (_i, [_vp, _i64, _vp, _vp]),
 }
 
+# include/isr_ray_losses.h (the distortion loss and the render loss, with their gradients), bound the same way
+_RENDER_LOSS = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d]      # rendered, target_images, target_silhouettes, xys, B, n, F, H, W, scaling
+RAY_LOSSES_SIGNATURES = {
+    "isr_distortion_workspace_bytes": (_sz, [_i64, _i]),
+    "isr_distortion_forward": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _sz, _vp]),
+    "isr_distortion_backward": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "isr_distortion_forward_host": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
+    "isr_distortion_backward_host": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
+    "isr_render_loss_workspace_bytes": (_sz, [_i64, _i64]),
+    "isr_render_loss_forward": (_i, [*_RENDER_LOSS, _vp, _vp, _sz, _vp]),
+    "isr_render_loss_backward": (_i, [*_RENDER_LOSS, _vp, _vp, _vp]),
+    "isr_render_loss_forward_host": (_i, [*_RENDER_LOSS, _vp]),
+    "isr_render_loss_backward_host": (_i, [*_RENDER_LOSS, _vp, _vp]),
+    "isr_ray_losses_geometry": (_i, [_i]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libisr_hip.so (once).  Raises IsrError when it has not been built."""
@@ -323,7 +339,7 @@ def lib() -> C.CDLL:
                                **RAYS_SIGNATURES, **RADIANCE_SIGNATURES, **RESAMPLE_SIGNATURES,
                                **CONTRASTIVE_SIGNATURES, **FIELD_GRAD_SIGNATURES, **SAMPLE_GRAD_SIGNATURES,
                                **EA_GRAD_SIGNATURES, **RADIANCE_GRAD_SIGNATURES, **AUGMENT_SIGNATURES,
-                               **ADAM_SIGNATURES}.items():
+                               **ADAM_SIGNATURES, **RAY_LOSSES_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -2631,3 +2631,137 @@ def adam_scalars_host(group, t: int):
     out4, out2 = np.zeros(4, np.float64), np.zeros(2, np.float32)
     check(lib().isr_adam_scalars_host(_hp(g), int(t), _hp(out4), _hp(out2)), "isr_adam_scalars_host")
     return {"lr_t": float(out4[0]), "beta1_t": float(out4[1]), "beta2_t": float(out4[2]), "step": out2[0], "r": out2[1]}
+
+
+# ---- the ray losses and their gradients (include/isr_ray_losses.h)
+def ray_losses_geometry() -> dict:
+    """isr_ray_losses_geometry: the rays of a distortion workgroup, the lanes that share a ray, the leaves of a reduction tree
+    (the rays of a render-loss workgroup) and the largest P."""
+    L = lib()
+    return {k: int(L.isr_ray_losses_geometry(i)) for i, k in enumerate(("group_rays", "lanes", "reduce", "max_p"))}
+
+
+def _distortion_shape(name: str, lengths, weights):
+    """-> (N, P) of lengths (N, P) and weights (N, P); the library checks the limits."""
+    if lengths.ndim != 2 or tuple(weights.shape) != tuple(lengths.shape):
+        raise ValueError(f"{name}: lengths (N, P) and weights (N, P) expected, got {tuple(lengths.shape)} and {tuple(weights.shape)}")
+    return int(lengths.shape[0]), int(lengths.shape[1])
+
+
+def _ray_losses_workspace(dev, nbytes: int, what: str) -> torch.Tensor:
+    if nbytes == 0:
+        check(-1, what)
+    return workspace(dev, nbytes, "ray_losses")
+
+
+def distortion_forward(lengths: torch.Tensor, weights: torch.Tensor, want_ray_loss: bool = True):
+    """isr_distortion_forward: lengths (N, P), weights (N, P) contiguous f32 on the device -> (ray_loss (N) or None, loss (0-d)):
+    nutil.mip360loss as include/isr_ray_losses.h states it.  No (P, P) array is made; nothing synchronises."""
+    dev = _contrastive_device("distortion_forward", lengths, weights)
+    N, P = _distortion_shape("distortion_forward", lengths, weights)
+    ws = _ray_losses_workspace(dev, lib().isr_distortion_workspace_bytes(N, P), "isr_distortion_workspace_bytes")
+    ray_loss = torch.empty((N,), dtype=torch.float32, device=dev) if want_ray_loss else None
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timed("distortion_forward", 3.0 * N * P * P):
+        rc = lib().isr_distortion_forward(ptr(lengths), ptr(weights), N, P, ptr(ray_loss), ptr(loss), ptr(ws), ws.numel(),
+                                          current_stream(dev))
+    check(rc, "isr_distortion_forward")
+    return ray_loss, loss
+
+
+def distortion_backward(lengths: torch.Tensor, weights: torch.Tensor, upstream: torch.Tensor) -> torch.Tensor:
+    """isr_distortion_backward: dweights (N, P) of distortion_forward's loss; upstream: a device tensor of one f32, read on the
+    device.  One launch, nothing synchronises."""
+    dev = _contrastive_device("distortion_backward", lengths, weights, upstream)
+    N, P = _distortion_shape("distortion_backward", lengths, weights)
+    if upstream.numel() != 1:
+        raise ValueError("distortion_backward: upstream must hold one value")
+    dweights = torch.empty_like(weights)
+    with torch.cuda.device(dev), _timed("distortion_backward", 3.0 * N * P * P):
+        rc = lib().isr_distortion_backward(ptr(lengths), ptr(weights), N, P, ptr(upstream), ptr(dweights), current_stream(dev))
+    check(rc, "isr_distortion_backward")
+    return dweights
+
+
+def distortion_forward_host(lengths, weights, want_ray_loss: bool = True):
+    """isr_distortion_forward_host: distortion_forward as host code over NumPy arrays.  For tests."""
+    lengths, weights = _contrastive_host("distortion_forward_host", lengths, weights)
+    N, P = _distortion_shape("distortion_forward_host", lengths, weights)
+    ray_loss = np.empty((N,), np.float32) if want_ray_loss else None
+    loss = np.empty((), np.float32)
+    check(lib().isr_distortion_forward_host(_hp(lengths), _hp(weights), N, P, _hp(ray_loss), _hp(loss)), "isr_distortion_forward_host")
+    return ray_loss, loss
+
+
+def distortion_backward_host(lengths, weights, upstream: float = 1.0):
+    """isr_distortion_backward_host: distortion_backward as host code over NumPy arrays.  For tests."""
+    lengths, weights = _contrastive_host("distortion_backward_host", lengths, weights)
+    N, P = _distortion_shape("distortion_backward_host", lengths, weights)
+    up = np.array([upstream], np.float32)
+    dweights = np.empty_like(weights)
+    check(lib().isr_distortion_backward_host(_hp(lengths), _hp(weights), N, P, _hp(up), _hp(dweights)), "isr_distortion_backward_host")
+    return dweights
+
+
+def _render_loss_shape(name: str, rendered, target_images, target_silhouettes, xys):
+    """-> (B, n, F, H, W) of rendered (B, n, F+1), target_images (B, H, W, F), target_silhouettes (B, H, W), xys (B, n, 2)."""
+    ok = rendered.ndim == 3 and target_images.ndim == 4 and rendered.shape[2] == target_images.shape[3] + 1 \
+        and tuple(target_silhouettes.shape) == tuple(target_images.shape[:3]) and rendered.shape[0] == target_images.shape[0] \
+        and tuple(xys.shape) == (rendered.shape[0], rendered.shape[1], 2)
+    if not ok:
+        raise ValueError(f"{name}: rendered (B, n, F+1), target_images (B, H, W, F), target_silhouettes (B, H, W), xys (B, n, 2) "
+                         f"expected, got {tuple(rendered.shape)}, {tuple(target_images.shape)}, {tuple(target_silhouettes.shape)}, "
+                         f"{tuple(xys.shape)}")
+    return (int(rendered.shape[0]), int(rendered.shape[1]), int(target_images.shape[3]), int(target_images.shape[1]),
+            int(target_images.shape[2]))
+
+
+def render_loss_forward(rendered: torch.Tensor, target_images: torch.Tensor, target_silhouettes: torch.Tensor, xys: torch.Tensor,
+                        scaling: float = 0.1) -> torch.Tensor:
+    """isr_render_loss_forward: contiguous f32 device tensors -> out (2): the means of nutil.huber(...).abs() of the colours and
+    of the opacity of a render against its targets at the rays (trainNerfFine.py:314-326).  Nothing synchronises."""
+    dev = _contrastive_device("render_loss_forward", rendered, target_images, target_silhouettes, xys)
+    B, n, F, H, W = _render_loss_shape("render_loss_forward", rendered, target_images, target_silhouettes, xys)
+    ws = _ray_losses_workspace(dev, lib().isr_render_loss_workspace_bytes(B, n), "isr_render_loss_workspace_bytes")
+    out = torch.empty((2,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timed("render_loss_forward", 8.0 * B * n * (F + 1)):
+        rc = lib().isr_render_loss_forward(ptr(rendered), ptr(target_images), ptr(target_silhouettes), ptr(xys), B, n, F, H, W,
+                                           float(scaling), ptr(out), ptr(ws), ws.numel(), current_stream(dev))
+    check(rc, "isr_render_loss_forward")
+    return out
+
+
+def render_loss_backward(rendered: torch.Tensor, target_images: torch.Tensor, target_silhouettes: torch.Tensor, xys: torch.Tensor,
+                         upstream: torch.Tensor, scaling: float = 0.1) -> torch.Tensor:
+    """isr_render_loss_backward: drendered (B, n, F+1); upstream: a device tensor of two f32 (colour, silhouette), read on the
+    device.  One launch, nothing synchronises."""
+    dev = _contrastive_device("render_loss_backward", rendered, target_images, target_silhouettes, xys, upstream)
+    B, n, F, H, W = _render_loss_shape("render_loss_backward", rendered, target_images, target_silhouettes, xys)
+    if upstream.numel() != 2:
+        raise ValueError("render_loss_backward: upstream must hold two values")
+    drendered = torch.empty_like(rendered)
+    with torch.cuda.device(dev), _timed("render_loss_backward", 8.0 * B * n * (F + 1)):
+        rc = lib().isr_render_loss_backward(ptr(rendered), ptr(target_images), ptr(target_silhouettes), ptr(xys), B, n, F, H, W,
+                                            float(scaling), ptr(upstream), ptr(drendered), current_stream(dev))
+    check(rc, "isr_render_loss_backward")
+    return drendered
+
+
+def render_loss_forward_host(rendered, target_images, target_silhouettes, xys, scaling: float = 0.1):
+    """isr_render_loss_forward_host: render_loss_forward as host code over NumPy arrays.  For tests."""
+    a = _contrastive_host("render_loss_forward_host", rendered, target_images, target_silhouettes, xys)
+    B, n, F, H, W = _render_loss_shape("render_loss_forward_host", *a)
+    out = np.empty((2,), np.float32)
+    check(lib().isr_render_loss_forward_host(*map(_hp, a), B, n, F, H, W, float(scaling), _hp(out)), "isr_render_loss_forward_host")
+    return out
+
+
+def render_loss_backward_host(rendered, target_images, target_silhouettes, xys, upstream=(1.0, 1.0), scaling: float = 0.1):
+    """isr_render_loss_backward_host: render_loss_backward as host code over NumPy arrays.  For tests."""
+    a = _contrastive_host("render_loss_backward_host", rendered, target_images, target_silhouettes, xys)
+    B, n, F, H, W = _render_loss_shape("render_loss_backward_host", *a)
+    up = np.array(upstream, np.float32)
+    drendered = np.empty_like(a[0])
+    check(lib().isr_render_loss_backward_host(*map(_hp, a), B, n, F, H, W, float(scaling), _hp(up), _hp(drendered)),
+          "isr_render_loss_backward_host")
+    return drendered

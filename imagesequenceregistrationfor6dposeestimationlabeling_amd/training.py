@@ -11,7 +11,8 @@ back-face keys (computed by trainPose.py:380, unused by its loss) and the maskRa
 
 nerf_train_step is one optimisation step of trainNerfFine.py:238-354 the same way: a coarse and a fine render through
 rays.ImplicitRendererStratified, whose march carries gradients to the fields' densities and features (isr_ea_march_backward),
-the targets sampled at the rays, and losses.huber.  The two fields are unpinned: any callables that map a ray bundle to
+the targets sampled at the rays, and losses.huber — or, opt-in, losses.render_loss for the four Huber terms and
+losses.mip360loss (nutil.py:140-152) as a distortion regulariser on both renders' weights (include/isr_ray_losses.h).  The two fields are unpinned: any callables that map a ray bundle to
 (densities, features), differentiated by torch.  Out of scope: the loader, checkpoints, visualisation and trainNerfFine.py's
 batch_idx bookkeeping (the caller passes the batch's cameras and targets)."""
 from __future__ import annotations
@@ -51,28 +52,44 @@ def pose_train_step(encoder: torch.nn.Module, field, optimizer: torch.optim.Opti
 
 
 def nerf_train_step(coarse_field, fine_field, renderer_coarse, renderer_fine, optimizer: torch.optim.Optimizer, cameras,
-                    target_images: torch.Tensor, target_silhouettes: torch.Tensor) -> dict:
+                    target_images: torch.Tensor, target_silhouettes: torch.Tensor, *, distortion_weight: float = 0.0,
+                    fused_losses: bool = False) -> dict:
     """cameras: the batch's B rays.PerspectiveCameras; target_images (B, H, W, F) and target_silhouettes (B, H, W) on the
     device -> dict(loss, color_err, sil_err) of detached 0-d tensors, after one optimizer step.  The fields are callables
     (ray_bundle=..., cameras=...) -> (densities (..., P, 1), features (..., P, F)); renderer_coarse and renderer_fine are
-    rays.ImplicitRendererStratified over a Monte-Carlo sampler, renderer_fine built with fine_seed."""
+    rays.ImplicitRendererStratified over a Monte-Carlo sampler, renderer_fine built with fine_seed.
+
+    Both options are off by default, and the step then runs the statements it always ran.  distortion_weight > 0 adds
+    distortion_weight * (mip360loss of the coarse render + mip360loss of the fine render) to the loss (nutil.mip360loss, which
+    trainPose.py imports) and returns the unweighted sum under "distortion".  fused_losses=True computes the four Huber terms by
+    two losses.render_loss calls (include/isr_ray_losses.h) in place of two samplings and four elementwise chains."""
     optimizer.zero_grad()                                                             # trainNerfFine.py:238
     rendered, sampled_rays, weights = renderer_coarse(cameras=cameras, volumetric_function=coarse_field,
                                                       add_input_samples=False, stratified=False)      # :288-291
-    rendered_fine, sampled_rays2, _ = renderer_fine(cameras=cameras, volumetric_function=fine_field, add_input_samples=True,
+    rendered_fine, sampled_rays2, weights2 = renderer_fine(cameras=cameras, volumetric_function=fine_field, add_input_samples=True,
                                                     stratified=True, coarse=(sampled_rays, weights.detach()))      # :294-300
     xys = sampled_rays2.xys                                                           # :301
     last = rendered.shape[-1]
-    images, silhouettes = rendered.split([last - 1, 1], dim=-1)                       # :306-308
-    images_fine, silhouettes_fine = rendered_fine.split([last - 1, 1], dim=-1)        # :310-312
-    silhouettes_at_rays = rays.sample_images_at_mc_locs(target_silhouettes[..., None], xys)      # :314-317
-    colors_at_rays = rays.sample_images_at_mc_locs(target_images, xys)                # :320-323
-    sil_err = losses.huber(silhouettes, silhouettes_at_rays).abs().mean()             # :324
-    color_err = losses.huber(images, colors_at_rays).abs().mean()                     # :326
-    sil_err = sil_err + losses.huber(silhouettes_fine, silhouettes_at_rays).abs().mean()      # :328
-    color_err = color_err + losses.huber(images_fine, colors_at_rays).abs().mean()    # :329
+    if fused_losses:                                                                  # :314-329 in two calls
+        color_err, sil_err = losses.render_loss(rendered, target_images, target_silhouettes, xys)
+        color_fine, sil_fine = losses.render_loss(rendered_fine, target_images, target_silhouettes, xys)
+        sil_err, color_err = sil_err + sil_fine, color_err + color_fine
+    else:
+        images, silhouettes = rendered.split([last - 1, 1], dim=-1)                   # :306-308
+        images_fine, silhouettes_fine = rendered_fine.split([last - 1, 1], dim=-1)    # :310-312
+        silhouettes_at_rays = rays.sample_images_at_mc_locs(target_silhouettes[..., None], xys)      # :314-317
+        colors_at_rays = rays.sample_images_at_mc_locs(target_images, xys)            # :320-323
+        sil_err = losses.huber(silhouettes, silhouettes_at_rays).abs().mean()         # :324
+        color_err = losses.huber(images, colors_at_rays).abs().mean()                 # :326
+        sil_err = sil_err + losses.huber(silhouettes_fine, silhouettes_at_rays).abs().mean()      # :328
+        color_err = color_err + losses.huber(images_fine, colors_at_rays).abs().mean()      # :329
     sil_err, color_err = 500 * sil_err, 500 * color_err                               # :334-335
     loss = color_err + sil_err                                                        # :336
+    out = {}
+    if distortion_weight > 0:
+        distortion = losses.mip360loss(sampled_rays, weights) + losses.mip360loss(sampled_rays2, weights2)
+        loss = loss + distortion_weight * distortion
+        out["distortion"] = distortion.detach()
     loss.backward()                                                                   # :353
     optimizer.step()                                                                  # :354
-    return {"loss": loss.detach(), "color_err": color_err.detach(), "sil_err": sil_err.detach()}
+    return {"loss": loss.detach(), "color_err": color_err.detach(), "sil_err": sil_err.detach(), **out}
