@@ -26,7 +26,8 @@ def __getattr__(name):
     if name in ("pose_train_step", "nerf_train_step"):
         from . import training
         return getattr(training, name)
-    if name in ("PoseBatches", "CorrespondenceBank", "AugmentParams", "draw_params", "rotation_matrix_2d"):
+    if name in ("PoseBatches", "CorrespondenceBank", "AugmentParams", "draw_params", "rotation_matrix_2d", "ColorParams",
+                "draw_color_params"):
         from . import augment
         return getattr(augment, name)
     if name in ("Adam", "pose_optimizer", "nerf_optimizer"):

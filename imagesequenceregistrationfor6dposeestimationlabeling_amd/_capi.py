@@ -319,6 +319,16 @@ RAY_LOSSES_SIGNATURES = {
     "isr_ray_losses_geometry": (_i, [_i]),
 }
 
+# include/isr_color_aug.h (the colour augmentation pass), bound the same way
+_COLOR_AUG = [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]      # in, B, H, W, programs .. std3, out
+COLOR_AUG_SIGNATURES = {
+    "isr_color_aug_workspace_bytes": (_sz, [_i, _i, _i]),
+    "isr_augment_color": (_i, [*_COLOR_AUG, _vp, _sz, _vp]),
+    "isr_augment_color_host": (_i, _COLOR_AUG),
+    "isr_color_aug_draws_host": (_i, [_u64, _i, _d, _vp, _vp]),
+    "isr_color_aug_geometry": (_i, [_i]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libisr_hip.so (once).  Raises IsrError when it has not been built."""
@@ -339,7 +349,7 @@ def lib() -> C.CDLL:
                                **RAYS_SIGNATURES, **RADIANCE_SIGNATURES, **RESAMPLE_SIGNATURES,
                                **CONTRASTIVE_SIGNATURES, **FIELD_GRAD_SIGNATURES, **SAMPLE_GRAD_SIGNATURES,
                                **EA_GRAD_SIGNATURES, **RADIANCE_GRAD_SIGNATURES, **AUGMENT_SIGNATURES,
-                               **ADAM_SIGNATURES, **RAY_LOSSES_SIGNATURES}.items():
+                               **ADAM_SIGNATURES, **RAY_LOSSES_SIGNATURES, **COLOR_AUG_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -6,7 +6,12 @@ augment.generateImages (augment.py:284-432), dataGen.normalize (dataGen.py:16-20
 The host's part is the parameter draw (draw_params: a few numbers per image from a seeded CPU generator, augment.py:315-342);
 every output is a function of the inputs and the seed.
 
-Out of scope: the albumentations colour operations; reading COCO / T-LESS files and the T-LESS occluder paste (`canvases` is
+The albumentations colour pass (augment.py:344-350, applied at :394-397 and :422-423) is ops.augment_color under programs
+drawn by draw_color_params, as owned definitions (include/isr_color_aug.h states them and what differs from the libraries):
+PoseBatches(color=True) opts in.
+
+Out of scope: albumentations' and cv2's own bytes and draws (LAB-space CLAHE, cv2's 8-bit HSV, blur sizes above 3, image sides
+that are no multiple of 8); reading COCO / T-LESS files and the T-LESS occluder paste (`canvases` is
 what rgbtensor[a] already holds); the target_backgrounds branch; lineErode; the NOCS map (trainPose.py computes it, its loss
 does not read it); and the 0/255 mask branch, where the reference's `== 1` never matches.  cv2.getRotationMatrix2D's formula is
 the documented one, from memory: unpinned."""
@@ -21,7 +26,8 @@ import torch
 
 from . import formats, ops
 
-__all__ = ["AugmentParams", "CorrespondenceBank", "PoseBatches", "draw_params", "ray_transform", "rotation_matrix_2d"]
+__all__ = ["AugmentParams", "ColorParams", "CorrespondenceBank", "PoseBatches", "draw_color_params", "draw_params", "ray_transform",
+           "rotation_matrix_2d"]
 
 
 def rotation_matrix_2d(center, angle_deg, scale) -> np.ndarray:
@@ -133,6 +139,81 @@ def draw_params(B: int, seed, H: int, *, bbox=None, integral=None, imD=None, sca
                          scale=torch.from_numpy(scale), ray_rot=torch.from_numpy(ray_rot), ray_t=torch.from_numpy(ray_t))
 
 
+@dataclass
+class ColorParams:
+    """The colour programs of one pass over B images, plain CPU tensors (build one by hand for a fixed augmentation;
+    ColorParams.neutral(B) has every gate off): include/isr_color_aug.h's isr_color_program, field for field.  apply, jitter,
+    rbc, iso, clahe (B,) i32 gates (apply is the program's `pass`); order (B, 4) i32, a permutation of 0 brightness, 1 contrast,
+    2 saturation, 3 hue; ksize (B,) i32: 0 off, else 1 or 3; the factors (B,) f64; noise_key (B,) i64."""
+    apply: torch.Tensor
+    jitter: torch.Tensor
+    order: torch.Tensor
+    rbc: torch.Tensor
+    ksize: torch.Tensor
+    iso: torch.Tensor
+    clahe: torch.Tensor
+    brightness: torch.Tensor
+    contrast: torch.Tensor
+    saturation: torch.Tensor
+    hue: torch.Tensor
+    alpha: torch.Tensor
+    beta: torch.Tensor
+    color_shift: torch.Tensor
+    intensity: torch.Tensor
+    clip_limit: torch.Tensor
+    noise_key: torch.Tensor
+
+    def __len__(self) -> int:
+        return int(self.apply.shape[0])
+
+    @classmethod
+    def from_programs(cls, programs: np.ndarray) -> "ColorParams":
+        f = lambda name, dt: torch.from_numpy(np.ascontiguousarray(programs[name]).astype(dt))
+        return cls(apply=f("pass", np.int32), noise_key=f("noise_key", np.int64),
+                   **{k: f(k, np.int32) for k in ("jitter", "order", "rbc", "ksize", "iso", "clahe")},
+                   **{k: f(k, np.float64) for k in ("brightness", "contrast", "saturation", "hue", "alpha", "beta", "color_shift",
+                                                    "intensity", "clip_limit")})
+
+    @classmethod
+    def neutral(cls, B: int) -> "ColorParams":
+        return cls.from_programs(ops.color_programs(B))
+
+    def programs(self) -> np.ndarray:
+        """(B,) of ops.COLOR_PROGRAM: what ops.augment_color takes."""
+        p = np.zeros(len(self), ops.COLOR_PROGRAM)
+        for name in ops.COLOR_PROGRAM.names:
+            t = getattr(self, "apply" if name == "pass" else name)
+            p[name] = t.numpy().astype(np.uint64) if name == "noise_key" else t.numpy()
+        return p
+
+
+def draw_color_params(B: int, seed, *, p_pass: float = 0.7, p_jitter: float = 0.5, p_rbc: float = 0.2, p_blur: float = 0.5,
+                      p_iso: float = 0.5, p_clahe: float = 0.5) -> ColorParams:
+    """The draws of one albumentations pass (augment.py:344-350 under :394 / :422's `uniform > 0.3`) for B images, from
+    np.random.default_rng(seed): a stream of its own, neither draw_params' nor albumentations'.  A gate is on when its
+    uniform is below its probability.  Per image, in this order, every value drawn whether its gate is on or not: the pass
+    gate; ColorJitter's gate, order (a permutation), brightness, contrast, saturation from U[0.8, 1.2], hue from U[-0.2, 0.2];
+    RandomBrightnessContrast's gate, alpha = 1 + U(-0.2, 0.2), beta = U(-0.2, 0.2); GaussianBlur's gate and ksize from {1, 3};
+    ISONoise's gate, color_shift from U[0.01, 0.05], intensity from U[0.1, 0.5], the noise key; CLAHE's gate and clip_limit
+    from U[1, 4]."""
+    rng = np.random.default_rng(seed)
+    p = ops.color_programs(int(B))
+    on = lambda prob: int(rng.uniform(0, 1) < prob)
+    for b in range(int(B)):
+        q = p[b]
+        q["pass"] = on(p_pass)
+        q["jitter"], q["order"] = on(p_jitter), rng.permutation(4)
+        q["brightness"], q["contrast"], q["saturation"] = rng.uniform(0.8, 1.2, 3)
+        q["hue"] = rng.uniform(-0.2, 0.2)
+        q["rbc"], q["alpha"], q["beta"] = on(p_rbc), 1.0 + rng.uniform(-0.2, 0.2), rng.uniform(-0.2, 0.2)
+        blur, ksize = on(p_blur), int(rng.choice((1, 3)))
+        q["ksize"] = ksize if blur else 0
+        q["iso"], q["color_shift"], q["intensity"] = on(p_iso), rng.uniform(0.01, 0.05), rng.uniform(0.1, 0.5)
+        q["noise_key"] = int(rng.integers(0, 2 ** 63))
+        q["clahe"], q["clip_limit"] = on(p_clahe), rng.uniform(1.0, 4.0)
+    return ColorParams.from_programs(p)
+
+
 class CorrespondenceBank:
     """The correspondences of V views, concatenated on the device: per set (front, back) xys (sum n, 2) and pos (sum n, 3)
     f32, and the host offsets (V + 1) int64 — the layout of include/isr_augment.h."""
@@ -190,10 +271,18 @@ class PoseBatches:
     canvases (C, H, H, 3) f32 on the device or None: what generateImages' rgbtensor[a] holds before the paste; an image gets one
     with probability 0.9 (augment.py:300), else zeros.  Every iteration starts again from (seed, epoch): two fresh iterations
     give the same bytes; set_epoch changes the stream.  Batches are shuffled view indices, the last short one dropped.
-    Between batches the host only draws parameters; nothing synchronises."""
+    Between batches the host only draws parameters; nothing synchronises.
+
+    color=True adds the albumentations pass, as generateImages applies it: a batch is made by ops.augment_images without
+    canvas, border and normalize (mean 0 and std 1: exact identities in f32), then ops.augment_color over the warped object
+    with select = mask_out and under = the canvas (:394-397 with the paste), then ops.augment_color over the composite with
+    the border blanking and normalize as its tail (:422-428).  color_options: draw_color_params' keywords; the two passes'
+    programs come from a generator of their own, [seed, epoch, k + 1, 1], and are extras["color_params"] = (first, second).
+    The default route's bytes do not change, and p_pass = 0 gives them again.  H must then be a multiple of 8."""
 
     def __init__(self, images, silhouettes, bank: CorrespondenceBank, batch_size: int = 16, sample_size: int = 1024, seed: int = 0,
-                 canvases=None, imD=None, mean=ops.IMAGENET_MEAN, std=ops.IMAGENET_STD, **draw_options):
+                 canvases=None, imD=None, mean=ops.IMAGENET_MEAN, std=ops.IMAGENET_STD, color: bool = False, color_options=None,
+                 **draw_options):
         V = int(images.shape[0])
         if images.ndim != 4 or images.shape[3] != 3 or images.shape[1] != images.shape[2] or tuple(silhouettes.shape) != tuple(images.shape[:3]):
             raise ValueError(f"PoseBatches: images (V, H, H, 3) and silhouettes (V, H, H), got {tuple(images.shape)} and {tuple(silhouettes.shape)}")
@@ -201,6 +290,9 @@ class PoseBatches:
             raise ValueError(f"PoseBatches: {V} images and a bank of {len(bank)} views")
         if not 1 <= int(batch_size) <= V:
             raise ValueError(f"PoseBatches: batch_size {batch_size} for {V} views")
+        if color and (int(images.shape[1]) % 8 or int(images.shape[1]) < 8):
+            raise ValueError(f"PoseBatches: color=True needs an image side that is a multiple of 8, got {int(images.shape[1])}")
+        self.color, self.color_options = bool(color), dict(color_options or {})
         self.images = images.to(torch.float32).contiguous()
         sil = silhouettes.to(torch.uint8)                                             # augment.py:286
         if int(sil.max()) >= 2:
@@ -235,12 +327,22 @@ class PoseBatches:
                 pick = torch.from_numpy(np.where(rng.uniform(0, 1, B) > 0.1, rng.integers(0, C, B), C)).to(dev)
                 canvas = self.canvases[pick]
             masks = self.masks[ids_dev]
-            rgb, mask_orig, mask_out = ops.augment_images(self.images[ids_dev], masks, params.M.numpy(), orig_mask=masks, canvas=canvas,
-                                                          rect=params.rect.numpy(), tra=params.tra.numpy(), tra1=params.tra1.numpy(),
-                                                          border=params.border.numpy(), mean=self.mean, std=self.std)
+            geometry = dict(orig_mask=masks, rect=params.rect.numpy(), tra=params.tra.numpy(), tra1=params.tra1.numpy())
+            color_params = None
+            if self.color:
+                seeds = np.random.default_rng([self.seed, self.epoch, k + 1, 1]).integers(0, 2 ** 63, 2)
+                color_params = tuple(draw_color_params(B, int(s), **self.color_options) for s in seeds)
+                warped, mask_orig, mask_out = ops.augment_images(self.images[ids_dev], masks, params.M.numpy(), canvas=None, border=None,
+                                                                 mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), **geometry)
+                pasted = ops.augment_color(warped, color_params[0].programs(), select=mask_out, under=canvas)
+                rgb = ops.augment_color(pasted, color_params[1].programs(), border=params.border.numpy(), border_mask=mask_out,
+                                        mean=self.mean, std=self.std)
+            else:
+                rgb, mask_orig, mask_out = ops.augment_images(self.images[ids_dev], masks, params.M.numpy(), canvas=canvas,
+                                                              border=params.border.numpy(), mean=self.mean, std=self.std, **geometry)
             front, back = ops.augment_rays(self.bank.front, ids, params.ray_rot.numpy(), params.ray_t.numpy(), S, ray_seed,
                                            back=self.bank.back)
             extras = {"mask_out": mask_out, "pos_points_back": back.pos, "xys_back": back.xys, "index": front.index,
                       "index_back": back.index, "count": front.count, "count_back": back.count,
-                      "short": ((front.count < S) | (back.count < S)).any(), "view_ids": ids_dev, "params": params}
+                      "short": ((front.count < S) | (back.count < S)).any(), "view_ids": ids_dev, "params": params, "color_params": color_params}
             yield rgb, mask_orig, front.pos, front.xys, extras

@@ -2544,6 +2544,102 @@ def augment_rays_host(front, view_ids, rot, t, S: int, seed: int, back=None):
     return outs[0] if back is None else (outs[0], outs[1])
 
 
+# ---- the colour augmentation pass (include/isr_color_aug.h)
+# isr_color_program, 120 bytes: the gates, the jitter order, the factors and the noise key of one image
+COLOR_PROGRAM = np.dtype([("pass", "<i4"), ("jitter", "<i4"), ("order", "<i4", (4,)), ("rbc", "<i4"), ("ksize", "<i4"),
+                          ("iso", "<i4"), ("clahe", "<i4"), ("brightness", "<f8"), ("contrast", "<f8"), ("saturation", "<f8"),
+                          ("hue", "<f8"), ("alpha", "<f8"), ("beta", "<f8"), ("color_shift", "<f8"), ("intensity", "<f8"),
+                          ("clip_limit", "<f8"), ("noise_key", "<u8")])
+
+
+def color_aug_geometry() -> dict:
+    """isr_color_aug_geometry: the per-pixel workgroup's threads, the images per launch, the most launches per 16 images and the
+    program's bytes."""
+    L = lib()
+    return {k: int(L.isr_color_aug_geometry(i)) for i, k in enumerate(("threads", "images_per_launch", "max_launches", "program_bytes"))}
+
+
+def color_programs(B: int) -> np.ndarray:
+    """B programs with every gate off and neutral factors: what a hand-built program starts from."""
+    p = np.zeros(int(B), COLOR_PROGRAM)
+    p["order"] = (0, 1, 2, 3)
+    for k in ("brightness", "contrast", "saturation", "alpha", "clip_limit"):
+        p[k] = 1.0
+    return p
+
+
+def _color_aug_args(name: str, image, programs, select, under, border, border_mask, mean, std):
+    """Shape checks of isr_augment_color -> (B, H, W, programs, border, mean3, std3); the library checks the limits."""
+    if image.ndim != 4 or image.shape[3] != 3 or min(image.shape) < 1:
+        raise ValueError(f"{name}: image must be (B, H, W, 3) and not empty, got {tuple(image.shape)}")
+    B, H, W, _ = (int(v) for v in image.shape)
+    progs = np.ascontiguousarray(programs)
+    if progs.dtype != COLOR_PROGRAM or progs.shape != (B,):
+        raise ValueError(f"{name}: programs must be ({B},) of ops.COLOR_PROGRAM, got {progs.shape} of {progs.dtype}")
+    for what, t, shape in (("select", select, (B, H, W)), ("under", under, (B, H, W, 3)), ("border_mask", border_mask, (B, H, W))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name}: {what} must be {shape}, got {tuple(t.shape)}")
+    if under is not None and select is None:
+        raise ValueError(f"{name}: under needs select")
+    if (border is None) != (border_mask is None):
+        raise ValueError(f"{name}: border and border_mask go together")
+    if (mean is None) != (std is None):
+        raise ValueError(f"{name}: mean and std go together")
+    bd = None
+    if border is not None:
+        bd = np.ascontiguousarray(np.asarray(border, np.int64).reshape(-1))
+        if bd.size != 2 * B or (np.abs(bd) >= 2 ** 31).any():
+            raise ValueError(f"{name}: border must be ({B}, 2) and fit int32")
+        bd = bd.astype(np.int32)
+    mu = sd = None
+    if mean is not None:
+        mu, sd = np.ascontiguousarray(mean, np.float32).reshape(-1), np.ascontiguousarray(std, np.float32).reshape(-1)
+        if mu.size != 3 or sd.size != 3:
+            raise ValueError(f"{name}: mean and std must hold 3 values")
+    return B, H, W, progs, bd, mu, sd
+
+
+def augment_color(image: torch.Tensor, programs, *, select: torch.Tensor | None = None, under: torch.Tensor | None = None,
+                  border=None, border_mask: torch.Tensor | None = None, mean=None, std=None) -> torch.Tensor:
+    """isr_augment_color: image (B, H, W, 3) f32 in [0, 1] on the device, programs (B,) of COLOR_PROGRAM on the host -> (B, H, W, 3)
+    f32: the albumentations pass of augment.py:344-350 as include/isr_color_aug.h states it.  select (B, H, W) f32 holding 0/1
+    with under (B, H, W, 3) or None: the pass's pixels where select == 1, under (zeros) elsewhere.  border (B, 2) = (kh, kw) on
+    the host with border_mask (B, H, W), and mean / std: augment_images' blanking and normalize.  At most eight
+    launches per 16 images, nothing synchronises."""
+    dev = require_cuda(image, select, under, border_mask)
+    if any(t is not None and t.dtype != torch.float32 for t in (image, select, under, border_mask)):
+        raise ValueError("augment_color: image, select, under and border_mask must be float32")
+    B, H, W, progs, bd, mu, sd = _color_aug_args("augment_color", image, programs, select, under, border, border_mask, mean, std)
+    c = lambda t: None if t is None else t.contiguous()
+    image, select, under, border_mask = c(image), c(select), c(under), c(border_mask)
+    ws = workspace(dev, lib().isr_color_aug_workspace_bytes(B, H, W), "color_aug")      # 0 bytes: a shape the call refuses
+    out = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timed("augment_color", float(B) * H * W):
+        rc = lib().isr_augment_color(ptr(image), B, H, W, _hp(progs), ptr(select), ptr(under), _hp(bd), ptr(border_mask), _hp(mu),
+                                     _hp(sd), ptr(out), ptr(ws), ws.numel(), current_stream(dev))
+    check(rc, "isr_augment_color")
+    return out
+
+
+def augment_color_host(image, programs, *, select=None, under=None, border=None, border_mask=None, mean=None, std=None):
+    """isr_augment_color_host: the same pass as host code over NumPy arrays.  For tests."""
+    c = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    image, select, under, border_mask = c(image), c(select), c(under), c(border_mask)
+    B, H, W, progs, bd, mu, sd = _color_aug_args("augment_color_host", image, programs, select, under, border, border_mask, mean, std)
+    out = np.empty((B, H, W, 3), np.float32)
+    check(lib().isr_augment_color_host(_hp(image), B, H, W, _hp(progs), _hp(select), _hp(under), _hp(bd), _hp(border_mask), _hp(mu),
+                                       _hp(sd), _hp(out)), "isr_augment_color_host")
+    return out
+
+
+def color_aug_draws_host(noise_key: int, n: int, lam: float):
+    """isr_color_aug_draws_host: ISONoise's draws of pixels 0 .. n-1 at a given lambda -> (k (n,) i32, z (n,) f64).  For tests."""
+    k, z = np.empty(int(n), np.int32), np.empty(int(n), np.float64)
+    check(lib().isr_color_aug_draws_host(int(noise_key) & 0xFFFFFFFFFFFFFFFF, int(n), float(lam), _hp(k), _hp(z)),
+          "isr_color_aug_draws_host")
+    return k, z
+
+
 # ---- the fused multi-tensor Adam (include/isr_adam.h)
 ADAM_MAX_GROUPS = 8
 ADAM_CHUNK = 4096

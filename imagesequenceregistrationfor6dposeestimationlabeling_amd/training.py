@@ -6,7 +6,8 @@ encoder and the key field are trained together, and every gradient the package c
 The encoder is unpinned: the reference's UNet (dep/unet.py) is not part of it, so `encoder` is any torch.nn.Module that maps
 (B, 3, H, W) to (B, 13, H, W), and its own layers, forward and backward, are torch's.  Its arguments come from
 augment.PoseBatches, the loader of dataGen.AugmentedSamples on the device (the warps, the paste and the ray remap of
-augment.py; include/isr_augment.h).  Out of scope: the loader's colour augmentations (albumentations), checkpoints, the
+augment.py; include/isr_augment.h), with the loader's colour augmentations under PoseBatches(color=True)
+(include/isr_color_aug.h: owned definitions of the albumentations pass).  Out of scope: checkpoints, the
 back-face keys (computed by trainPose.py:380, unused by its loss) and the maskRays=False branch.
 
 nerf_train_step is one optimisation step of trainNerfFine.py:238-354 the same way: a coarse and a fine render through
