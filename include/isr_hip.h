@@ -408,6 +408,7 @@ int isr_adds_bounds(const float* verts, int V, const double* Tq, const double* T
  *                  mask_prob (n) = sigmoid(avg_pool(lgts)), queries (n,e) = avg_pool(query_img).
  *                  ws >= 2*n*4 + 512 bytes.
  * isr_ep_pool_corr :97-107  pooled[o][k] = max over the 3x3 pixel neighbourhood of corr_log[.][k].
+ *                  One workgroup row per pixel: res^2 <= 65535 (res <= 255), ISR_ERR_ARG beyond; pooled != corr_log.
  * isr_ep_sample    :111-119 corr_idx (n_samples,4) i64 = flat (pixel*m + key) indices drawn with
  *                  probability ~ (exp(corr_log) * mask_prob)^alpha by inversion of Philox uniforms
  *                  ((x+0.5)/2^32, counter (s,1,0,0)); no (n*m) cumulative array is formed.
@@ -429,7 +430,11 @@ int isr_ep_pool_corr(const float* corr_log, int res, int m, float* pooled, isr_s
  *                  log_softmax(queries @ keys^T) (n = res^2 pooled query pixels, e <= 128) and, when corr_pool is
  *                  not NULL, corr_pool (n, m) = its 3 x 3 spatial max-pool — the logits of the three image rows a
  *                  workgroup needs are recomputed in registers instead of re-reading the matrix nine times.
- *                  ws from isr_corr_logsoftmax_workspace_bytes(n, m, e, ISR_DTYPE_F32). */
+ *                  ws from isr_corr_logsoftmax_workspace_bytes(n, m, e, ISR_DTYPE_F32).
+ *                  The one-pass form holds three image rows of queries in LDS: 3 res (DP + 1) 4 <= 65536 bytes with
+ *                  DP = 16 | 32 | 64 | 128 the padded e (res <= 321 | 165 | 84 | 42).  Past that it writes corr_raw by
+ *                  the plain row kernel and calls isr_ep_pool_corr, which refuses res^2 > 65535: with a corr_pool,
+ *                  e <= 16 and res >= 322 the call returns ISR_ERR_ARG (corr_raw is written, corr_pool is not). */
 int isr_ep_corr_matrices(const float* queries, const float* keys, int res, int m, int e, float* corr_raw,
                          float* corr_pool, void* ws, size_t ws_bytes, isr_stream_t stream);
 /* isr_ep_patch_corr :72-96 (avg_queries = False): per-PIXEL log_softmax(query_img[y, x] . obj_keys) pooled per
@@ -439,7 +444,11 @@ int isr_ep_corr_matrices(const float* queries, const float* keys, int res, int m
 /* Round 3: the per-pixel log-sum-exps come from isr_corr_argmax's exact-f32 path (one row per pixel of the crop), then
  * one pass with thread = key and a workgroup per row of output cells writes both matrices (ws from
  * isr_ep_patch_corr_workspace_bytes; without ws, or when `scale` pixel rows of descriptors do not fit 64 KB of LDS, it falls
- * back to isr_ep_patch_corr_cells: one workgroup per cell, three sweeps over the keys, no scratch). */
+ * back to isr_ep_patch_corr_cells: one workgroup per cell, three sweeps over the keys, no scratch).
+ * The row kernel needs scale^2 res (DP + 1) 4 <= 65536 bytes of LDS (res = r / scale, DP = 16 | 32 | 64 | 128 the padded e)
+ * and e <= 128; isr_ep_patch_corr_cells takes e <= 64 and scale <= 4 and carries an f32 log-sum-exp of its own.  So past
+ * the row kernel's limit a call with e > 64 (e = 100, scale 4, r = 64) or scale >= 5 (e = 40, scale 5, r = 55) returns
+ * ISR_ERR_ARG and writes nothing. */
 size_t isr_ep_patch_corr_workspace_bytes(int r, int m, int e);
 int isr_ep_patch_corr(const float* query_img, const float* obj_keys, int r, int e, int scale, int m,
                       float* corr_centre, float* corr_blockmax, void* ws, size_t ws_bytes, isr_stream_t stream);

@@ -108,6 +108,14 @@ def test_corr_logsoftmax_and_topk_leaves(cuda0, dt):
     # ranking against the chain's own logits is test_corr_topk_without_the_matrix
     assert (idx == ri).float().mean() > 0.99
     np.testing.assert_allclose(vals.cpu().numpy(), rv.numpy(), atol=5e-5)
+    # and every mismatch is such a swap: the two f64 values lie closer than the sum of their derived bounds
+    from tests import corr_matrix_ref as cr
+    out, _, lse, w = cr.parts(q, k)
+    bnd = cr.bound(q, k, lse, w)
+    np.testing.assert_allclose(out, ref.numpy(), rtol=0, atol=1e-12)
+    for p, j in zip(*np.nonzero((idx != ri).numpy())):
+        a, b = int(idx[p, j]), int(ri[p, j])
+        assert abs(out[p, a] - out[p, b]) < bnd[p, a] + bnd[p, b], (p, j, a, b, out[p, a], out[p, b], bnd[p, a], bnd[p, b])
 
 
 @pytest.mark.parametrize("P,N,D", [(3, 5, 16), (1000, 20000, 64), (777, 3001, 128), (300, 999, 32), (2048, 50000, 64)])
@@ -631,6 +639,13 @@ def test_corr_topk_without_the_matrix(cuda0, P, N, D, k):
     assert float((vals[:, :kk] - rv[:, :kk]).abs().max()) < 2e-6 * (1.0 + float(rv[:, :kk].abs().max()))
     if N < k:
         assert bool((idx[:, N:] == -1).all())
+    if P * N < 10000:
+        # the two smallest shapes: vals against the plain f64 reference at the returned keys, under the derived bound
+        from tests import corr_matrix_ref as cr
+        out, _, lse, w = cr.parts(Q.cpu(), K.cpu())
+        bnd = cr.bound(Q.cpu(), K.cpu(), lse, w)
+        at = idx[:, :kk].long().cpu().numpy()
+        assert cr.compare(vals[:, :kk].cpu().numpy(), np.take_along_axis(out, at, 1), np.take_along_axis(bnd, at, 1))
     # ties: by ascending key
     assert idx[0, :kk].tolist() == list(range(kk))                                  # a zero row
     if N > 20 and k >= 3:
