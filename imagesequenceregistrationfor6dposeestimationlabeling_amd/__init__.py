@@ -33,6 +33,9 @@ def __getattr__(name):
     if name in ("Adam", "pose_optimizer", "nerf_optimizer"):
         from . import optim
         return getattr(optim, name)
+    if name in ("generate_bop_realsamples", "training_views", "TrainingViews", "read_bop_frames", "extract_rt"):
+        from . import ingest
+        return getattr(ingest, name)
     if name == "marching_cubes":
         from . import ops
         return ops.marching_cubes

@@ -329,6 +329,18 @@ COLOR_AUG_SIGNATURES = {
     "isr_color_aug_geometry": (_i, [_i]),
 }
 
+# include/isr_ingest.h (sequence ingest: BOP frames to training views and cameras), bound the same way
+_INGEST = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]      # rgb, mask, K_in, n .. sil_mode, images .. status
+INGEST_SIGNATURES = {
+    "isr_ingest_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "isr_ingest_views": (_i, [*_INGEST, _vp, _sz, _vp]),
+    "isr_ingest_views_host": (_i, _INGEST),
+    "isr_ingest_geometry": (_i, [_i]),
+    "isr_ingest_strip_rows": (_i, [_i, _i, _i]),
+    "isr_ingest_strips": (_i, [_i, _i, _i]),
+    "isr_ingest_launch_floor": (_i, [_i, _i, _i, _i, _i, _vp]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libisr_hip.so (once).  Raises IsrError when it has not been built."""
@@ -349,7 +361,7 @@ def lib() -> C.CDLL:
                                **RAYS_SIGNATURES, **RADIANCE_SIGNATURES, **RESAMPLE_SIGNATURES,
                                **CONTRASTIVE_SIGNATURES, **FIELD_GRAD_SIGNATURES, **SAMPLE_GRAD_SIGNATURES,
                                **EA_GRAD_SIGNATURES, **RADIANCE_GRAD_SIGNATURES, **AUGMENT_SIGNATURES,
-                               **ADAM_SIGNATURES, **RAY_LOSSES_SIGNATURES, **COLOR_AUG_SIGNATURES}.items():
+                               **ADAM_SIGNATURES, **RAY_LOSSES_SIGNATURES, **COLOR_AUG_SIGNATURES, **INGEST_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

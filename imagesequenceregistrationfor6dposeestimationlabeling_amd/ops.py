@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
@@ -2861,3 +2862,99 @@ def render_loss_backward_host(rendered, target_images, target_silhouettes, xys, 
     check(lib().isr_render_loss_backward_host(*map(_hp, a), B, n, F, H, W, float(scaling), _hp(up), _hp(drendered)),
           "isr_render_loss_backward_host")
     return drendered
+
+
+# ---- sequence ingest (include/isr_ingest.h)
+INGEST_SILHOUETTE = {"linear": 0, "nearest": 1}
+
+
+class IngestedViews(NamedTuple):
+    """ops.ingest_views' result: images (n, maxB, maxB, 3) f32, silhouettes (n, maxB, maxB) f32, K (n, 4, 4) f64,
+    geom (n, 8) i32 = (x2, y2, w2, h2, hw, hh, side, hs1), status (n,) i32 (1: the frame's square has side 0)."""
+    images: object
+    silhouettes: object
+    K: object
+    geom: object
+    status: object
+
+
+def ingest_geometry() -> dict:
+    """isr_ingest_geometry: threads per workgroup, frames per blockIdx.z group, launches per call."""
+    L = lib()
+    return {k: int(L.isr_ingest_geometry(i)) for i, k in enumerate(("threads", "frame_group", "launches"))}
+
+
+def ingest_strips(H: int, W: int, Cm: int) -> tuple[int, int]:
+    """(rows per strip, strips per frame) of the box pass; (0, 0) for a shape the call refuses."""
+    L = lib()
+    return int(L.isr_ingest_strip_rows(int(H), int(W), int(Cm))), int(L.isr_ingest_strips(int(H), int(W), int(Cm)))
+
+
+def ingest_workspace_bytes(n: int, H: int, W: int, Cm: int) -> int:
+    """isr_ingest_workspace_bytes: the box pass's partial boxes; 0 for a shape the call refuses."""
+    return int(lib().isr_ingest_workspace_bytes(int(n), int(H), int(W), int(Cm)))
+
+
+def _ingest_args(name: str, rgb, mask, K, silhouette):
+    """Shape checks of isr_ingest_views -> (n, H, W, Cm, sil_mode); the library checks the limits."""
+    if rgb.ndim != 4 or rgb.shape[3] != 3 or min(rgb.shape) < 1:
+        raise ValueError(f"{name}: rgb must be (n, H, W, 3) and not empty, got {tuple(rgb.shape)}")
+    n, H, W, _ = (int(v) for v in rgb.shape)
+    if mask.ndim == 3:
+        mask = mask[..., None]
+    if mask.ndim != 4 or tuple(mask.shape[:3]) != (n, H, W):
+        raise ValueError(f"{name}: mask must be ({n}, {H}, {W}[, Cm]), got {tuple(mask.shape)}")
+    if int(np.prod(tuple(K.shape))) != 9 * n:
+        raise ValueError(f"{name}: K must be ({n}, 3, 3), got {tuple(K.shape)}")
+    if silhouette not in INGEST_SILHOUETTE:
+        raise ValueError(f"{name}: silhouette must be 'linear' or 'nearest', got {silhouette!r}")
+    return mask, n, H, W, int(mask.shape[3]), INGEST_SILHOUETTE[silhouette]
+
+
+def ingest_views(rgb: torch.Tensor, mask: torch.Tensor, K: torch.Tensor, max_b: int, offset: int = 10, make_ndc: bool = True,
+                 silhouette: str = "linear", workspace_buf: torch.Tensor | None = None) -> IngestedViews:
+    """isr_ingest_views: rgb (n, H, W, 3) u8, mask (n, H, W[, Cm]) u8 with Cm in {1, 3} and K (n, 3, 3) f64 on the device ->
+    IngestedViews on the device: cowrendersynth.generate_bop_realsamples' gate, box, square canvas, resize to max_b and camera
+    as include/isr_ingest.h states them.  Three launches, nothing synchronises; the box never visits the host.
+    workspace_buf: a caller's u8 buffer of at least ingest_workspace_bytes(...) (default: the cached one)."""
+    dev = require_cuda(rgb, mask, K)
+    if rgb.dtype != torch.uint8 or mask.dtype != torch.uint8 or K.dtype != torch.float64:
+        raise ValueError("ingest_views: rgb and mask must be uint8, K float64")
+    mask, n, H, W, Cm, mode = _ingest_args("ingest_views", rgb, mask, K, silhouette)
+    rgb, mask, K = rgb.contiguous(), mask.contiguous(), K.contiguous()
+    B = int(max_b)
+    Bs = max(B, 0)
+    ws = workspace_buf if workspace_buf is not None else workspace(dev, ingest_workspace_bytes(n, H, W, Cm), "ingest")
+    images = torch.empty((n, Bs, Bs, 3), dtype=torch.float32, device=dev)
+    sil = torch.empty((n, Bs, Bs), dtype=torch.float32, device=dev)
+    K_out = torch.empty((n, 4, 4), dtype=torch.float64, device=dev)
+    geom = torch.empty((n, 8), dtype=torch.int32, device=dev)
+    status = torch.empty((n,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev), _timed("ingest_views", float(n) * H * W):
+        rc = lib().isr_ingest_views(ptr(rgb), ptr(mask), ptr(K), n, H, W, Cm, B, int(offset), int(bool(make_ndc)), mode, ptr(images),
+                                    ptr(sil), ptr(K_out), ptr(geom), ptr(status), ptr(ws), ws.numel() * ws.element_size(),
+                                    current_stream(dev))
+    check(rc, "isr_ingest_views")
+    return IngestedViews(images, sil, K_out, geom, status)
+
+
+def ingest_views_host(rgb, mask, K, max_b: int, offset: int = 10, make_ndc: bool = True, silhouette: str = "linear") -> IngestedViews:
+    """isr_ingest_views_host: the same views as host code over NumPy arrays (the tests' reference, and ingest's device="cpu")."""
+    rgb, mask = np.ascontiguousarray(rgb, np.uint8), np.ascontiguousarray(mask, np.uint8)
+    K = np.ascontiguousarray(K, np.float64)
+    mask, n, H, W, Cm, mode = _ingest_args("ingest_views_host", rgb, mask, K, silhouette)
+    mask = np.ascontiguousarray(mask)
+    B = int(max_b)
+    Bs = max(B, 0)
+    images, sil = np.empty((n, Bs, Bs, 3), np.float32), np.empty((n, Bs, Bs), np.float32)
+    K_out, geom, status = np.empty((n, 4, 4), np.float64), np.empty((n, 8), np.int32), np.empty((n,), np.int32)
+    check(lib().isr_ingest_views_host(_hp(rgb), _hp(mask), _hp(K), n, H, W, Cm, B, int(offset), int(bool(make_ndc)), mode, _hp(images),
+                                      _hp(sil), _hp(K_out), _hp(geom), _hp(status)), "isr_ingest_views_host")
+    return IngestedViews(images, sil, K_out, geom, status)
+
+
+def ingest_launch_floor(n: int, H: int, W: int, Cm: int, max_b: int, device) -> None:
+    """isr_ingest_launch_floor: the call's three launches with empty kernels (tools/bench_ingest.py)."""
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        check(lib().isr_ingest_launch_floor(int(n), int(H), int(W), int(Cm), int(max_b), current_stream(dev)), "isr_ingest_launch_floor")
