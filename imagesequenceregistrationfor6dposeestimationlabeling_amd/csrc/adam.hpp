@@ -12,11 +12,7 @@
 
 #include "../../include/isr_adam.h"
 
-#if defined(__HIPCC__)
-#define ISR_ADAM_FN __host__ __device__ inline
-#else
-#define ISR_ADAM_FN inline
-#endif
+#include "hd.hpp"
 
 namespace isr {
 namespace adam {
@@ -68,7 +64,7 @@ inline const char* make_group(const double* six, Group& out) {
 }
 
 // (h, l) = (ah + al) (ch + cl) in double-double: the product's rounding error by fma, both cross terms, one fast two-sum
-ISR_ADAM_FN void dd_mul(double ah, double al, double ch, double cl, double& h, double& l) {
+ISR_HD void dd_mul(double ah, double al, double ch, double cl, double& h, double& l) {
   const double p = ah * ch;
   double e = fma(ah, ch, -p);
   e = fma(ah, cl, e);
@@ -78,7 +74,7 @@ ISR_ADAM_FN void dd_mul(double ah, double al, double ch, double cl, double& h, d
 }
 
 // beta^t, t >= 0: binary powering over the bits of t, low bit first, in double-double; the high word is the answer
-ISR_ADAM_FN double pow_int(double beta, long long t) {
+ISR_HD double pow_int(double beta, long long t) {
   double rh = 1.0, rl = 0.0, bh = beta, bl = 0.0;
   while (t > 0) {
     if (t & 1) dd_mul(rh, rl, bh, bl, rh, rl);
@@ -88,14 +84,14 @@ ISR_ADAM_FN double pow_int(double beta, long long t) {
   return rh;
 }
 
-ISR_ADAM_FN double lr_at(double lr, double ramp, long long t) {
+ISR_HD double lr_at(double lr, double ramp, long long t) {
   if (!(ramp > 0.0)) return lr;
   const double frac = (double)(t + 1) / ramp;
   return lr * (frac < 1.0 ? frac : 1.0);
 }
 
 // t: the 1-based step
-ISR_ADAM_FN Scalars scalars_at(const Group& g, long long t) {
+ISR_HD Scalars scalars_at(const Group& g, long long t) {
   const double bc1 = 1.0 - pow_int(g.beta1, t), bc2 = 1.0 - pow_int(g.beta2, t);
   Scalars s;
   s.step = (float)(lr_at(g.lr, g.ramp, t) / bc1);
@@ -103,7 +99,7 @@ ISR_ADAM_FN Scalars scalars_at(const Group& g, long long t) {
   return s;
 }
 
-ISR_ADAM_FN void update1(const Group& G, const Scalars& s, float& p, float g, float& m, float& v) {
+ISR_HD void update1(const Group& G, const Scalars& s, float& p, float g, float& m, float& v) {
   const float g1 = G.wd != 0.f ? fmaf(G.wd, p, g) : g;
   const float m1 = fmaf(G.c1, g1 - m, m);
   const float v1 = fmaf(G.c2, g1 * g1, G.beta2f * v);
@@ -146,7 +142,7 @@ inline const char* check_table(const isr_adam_tensor* table, int T, int G, long 
 }
 
 // the tensor that owns chunk c: the i in [0, T) with chunk_start[i] <= c < chunk_start[i + 1]  (0 <= c < chunk_start[T])
-ISR_ADAM_FN int find_tensor(const int32_t* chunk_start, int T, int c) {
+ISR_HD int find_tensor(const int32_t* chunk_start, int T, int c) {
   int lo = 0, hi = T;      // chunk_start[lo] <= c < chunk_start[hi]
   while (hi - lo > 1) {
     const int mid = lo + (hi - lo) / 2;
@@ -157,7 +153,7 @@ ISR_ADAM_FN int find_tensor(const int32_t* chunk_start, int T, int c) {
 }
 
 // the elements before the first one at which p is 16-byte aligned, or -1 when p, g, m and v do not share one misalignment
-ISR_ADAM_FN int shared_head(const isr_adam_tensor& d) {
+ISR_HD int shared_head(const isr_adam_tensor& d) {
   const unsigned a = (unsigned)((uintptr_t)d.p & 15u);
   if (((uintptr_t)d.g & 15u) != a || ((uintptr_t)d.m & 15u) != a || ((uintptr_t)d.v & 15u) != a || (a & 3u)) return -1;
   return (int)(((16u - a) & 15u) >> 2);

@@ -6,6 +6,7 @@
 //     1024-thread workgroup per (image, set): count, radix select of the cut on the Philox word (as csrc/select_top.hip and
 //     csrc/knn.hip do), an ordered gather and a bitonic sort in LDS (as csrc/sample_grad.hip does).
 // The per-image parameters are made on the host and travel as kernel arguments: no copy, no synchronisation, no workspace.
+#include "block_prims.hpp"
 #include "isr_common.hpp"
 
 #include "../../include/isr_augment.h"
@@ -53,8 +54,7 @@ __global__ __launch_bounds__(kPixThreads) void augment_colours_kernel(const floa
 
 // the sum of v over the workgroup, to every thread; red: kRayWaves words of LDS
 __device__ __forceinline__ int block_sum(int v, int* red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  v = isr::wave_reduce(v, isr::Plus{});
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   int s = 0;

@@ -58,7 +58,7 @@ inline bool invert_affine(const double* M, double tx, double ty, double* inv) {
 
 // the bilinear sum at the source position of destination pixel (x, y); px(x, y): the pixel as f64, 0 outside the frame
 template <class Px>
-ISR_RAYS_FN double bilinear(const double* inv, long x, long y, Px px) {
+ISR_HD double bilinear(const double* inv, long x, long y, Px px) {
   const double sx = (inv[0] * (double)x + inv[1] * (double)y) + inv[2];
   const double sy = (inv[3] * (double)x + inv[4] * (double)y) + inv[5];
   const double fx0 = floor(sx), fy0 = floor(sy);
@@ -70,10 +70,10 @@ ISR_RAYS_FN double bilinear(const double* inv, long x, long y, Px px) {
   return ((px(x0, y0) * w00 + px(x0 + 1, y0) * w01) + px(x0, y0 + 1) * w10) + px(x0 + 1, y0 + 1) * w11;
 }
 
-ISR_RAYS_FN bool in_frame(const Frame& f, long x, long y) { return x >= 0 && x < f.W && y >= 0 && y < f.H; }
+ISR_HD bool in_frame(const Frame& f, long x, long y) { return x >= 0 && x < f.W && y >= 0 && y < f.H; }
 
 // warp(mask, A)(x, y) for a u8 mask: rounded half to even.  rw = 0 or rh = 0: no rectangle.
-ISR_RAYS_FN uint8_t warp_mask(const uint8_t* mask, const Frame& f, const double* inv, int rx, int ry, int rw, int rh, long x,
+ISR_HD uint8_t warp_mask(const uint8_t* mask, const Frame& f, const double* inv, int rx, int ry, int rw, int rh, long x,
                               long y) {
   const double v = bilinear(inv, x, y, [&](long xx, long yy) -> double {
     if (!in_frame(f, xx, yy)) return 0.0;
@@ -84,25 +84,25 @@ ISR_RAYS_FN uint8_t warp_mask(const uint8_t* mask, const Frame& f, const double*
 }
 
 // warp(rgb, A)(x, y, c) for an f32 image: one rounding
-ISR_RAYS_FN float warp_rgb(const float* rgb, const Frame& f, const double* inv, int c, long x, long y) {
+ISR_HD float warp_rgb(const float* rgb, const Frame& f, const double* inv, int c, long x, long y) {
   return (float)bilinear(inv, x, y, [&](long xx, long yy) -> double {
     return in_frame(f, xx, yy) ? (double)rgb[((size_t)yy * f.W + xx) * 3 + c] : 0.0;
   });
 }
 
 // dst_mask(x, y) and dst_mask_orig(x, y) of image parameters p
-ISR_RAYS_FN float mask_out_at(const uint8_t* mask, const Frame& f, const ImageParams& p, int x, int y) {
+ISR_HD float mask_out_at(const uint8_t* mask, const Frame& f, const ImageParams& p, int x, int y) {
   const long xs = (long)x - p.dx, ys = (long)y - p.dy;          // the second warp: an integer shift of the clipped first result
   if (!in_frame(f, xs, ys)) return 0.f;
   return (float)warp_mask(mask, f, p.inv1, p.rx, p.ry, p.rw, p.rh, xs, ys);
 }
 
-ISR_RAYS_FN float mask_orig_at(const uint8_t* orig_mask, const Frame& f, const ImageParams& p, int x, int y) {
+ISR_HD float mask_orig_at(const uint8_t* orig_mask, const Frame& f, const ImageParams& p, int x, int y) {
   return (float)warp_mask(orig_mask, f, p.inv2, 0, 0, 0, 0, x, y);
 }
 
 // is the kh x kw dilation of mask_out at (x, y) <= 0.9?  Anchor (kw / 2, kh / 2), positions outside the frame ignored.
-ISR_RAYS_FN bool border_blank(const float* mask_out, const Frame& f, int kh, int kw, int x, int y) {
+ISR_HD bool border_blank(const float* mask_out, const Frame& f, int kh, int kw, int x, int y) {
   const int y_lo = y - kh / 2, x_lo = x - kw / 2;
   const int y0 = y_lo < 0 ? 0 : y_lo, x0 = x_lo < 0 ? 0 : x_lo;
   const int y1 = y_lo + kh > f.H ? f.H : y_lo + kh, x1 = x_lo + kw > f.W ? f.W : x_lo + kw;
@@ -113,13 +113,13 @@ ISR_RAYS_FN bool border_blank(const float* mask_out, const Frame& f, int kh, int
 }
 
 // (x - mu) / std: an f32 subtraction, then an f32 division
-ISR_RAYS_FN float normalize1(float v, float mu, float sd) {
+ISR_HD float normalize1(float v, float mu, float sd) {
   const float d = v - mu;
   return d / sd;
 }
 
 // rgb_out(x, y, 0..2), given mask_out of the whole image
-ISR_RAYS_FN void rgb_out_at(const float* rgb, const float* canvas, const float* mask_out, const Frame& f, const ImageParams& p,
+ISR_HD void rgb_out_at(const float* rgb, const float* canvas, const float* mask_out, const Frame& f, const ImageParams& p,
                             const float* mu, const float* sd, int x, int y, float* out3) {
   const size_t pix = (size_t)y * f.W + x;
   const bool object = mask_out[pix] == 1.f;     // then (x - dx, y - dy) lies in the frame
@@ -204,19 +204,19 @@ struct RayBatch {
   float t[kMaxBatch][2];
 };
 
-ISR_RAYS_FN void remap(const float* m, const float* t, float x, float y, float& sx, float& sy) {
+ISR_HD void remap(const float* m, const float* t, float x, float y, float& sx, float& sy) {
   sx = fmaf(y, m[1], x * m[0]) - t[0];
   sy = fmaf(y, m[3], x * m[2]) - t[1];
 }
 
-ISR_RAYS_FN bool touches_outside(float sx, float sy) { return sx >= 1.f || sx <= -1.f || sy >= 1.f || sy <= -1.f; }
+ISR_HD bool touches_outside(float sx, float sy) { return sx >= 1.f || sx <= -1.f || sy >= 1.f || sy <= -1.f; }
 
-ISR_RAYS_FN bool strictly_inside(float sx, float sy) { return sx > -1.f && sx < 1.f && sy > -1.f && sy < 1.f; }
+ISR_HD bool strictly_inside(float sx, float sy) { return sx > -1.f && sx < 1.f && sy > -1.f && sy < 1.f; }
 
 // the high word of candidate i's key
-ISR_RAYS_FN uint32_t key_word(uint32_t i, uint32_t view, uint32_t set, uint32_t k0, uint32_t k1) {
+ISR_HD uint32_t key_word(uint32_t i, uint32_t view, uint32_t set, uint32_t k0, uint32_t k1) {
   uint32_t w[4];
-  rays::philox4x32_10(i, view, set, 0u, k0, k1, w);
+  philox4x32_10(i, view, set, 0u, k0, k1, w);
   return w[0];
 }
 

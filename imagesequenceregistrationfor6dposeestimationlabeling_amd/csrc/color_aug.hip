@@ -15,6 +15,7 @@
 // 0.81 ms for a 16 x 224 x 224 pass with every gate on, bound by the f64 work of 16 compute units (profiles/color_aug.json
 // keeps the figure); this chain spreads the same arithmetic over the chip.
 // The programs are made on the host and travel as kernel arguments: no copy, no synchronisation.
+#include "block_prims.hpp"
 #include "isr_common.hpp"
 
 #include "color_aug.hpp"
@@ -62,11 +63,8 @@ __device__ __forceinline__ uint8_t* current(const Work& w, const Program& pr) { 
 
 // the sums of a and b over a kSumThreads workgroup, to every thread
 __device__ __forceinline__ void block_sum2(uint64_t& a, uint64_t& b, uint64_t (*red)[kSumWaves]) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    a += __shfl_xor((unsigned long long)a, o, 64);
-    b += __shfl_xor((unsigned long long)b, o, 64);
-  }
+  a = isr::wave_reduce((unsigned long long)a, isr::Plus{});
+  b = isr::wave_reduce((unsigned long long)b, isr::Plus{});
   if ((threadIdx.x & 63) == 0) {
     red[0][threadIdx.x >> 6] = a;
     red[1][threadIdx.x >> 6] = b;

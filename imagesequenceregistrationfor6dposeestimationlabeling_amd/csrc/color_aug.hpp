@@ -39,34 +39,34 @@ struct Batch {
 
 // ---------------------------------------------------------------- bytes
 // (uint8)(x * 255): an f32 product, clamped, truncated; NaN -> 0
-ISR_RAYS_FN uint8_t to_u8(float x) {
+ISR_HD uint8_t to_u8(float x) {
   const float p = x * 255.0f;
   if (p >= 255.0f) return 255;
   if (p > 0.0f) return (uint8_t)(int)p;
   return 0;
 }
 
-ISR_RAYS_FN float from_u8(uint8_t q) { return (float)q / 255.0f; }
+ISR_HD float from_u8(uint8_t q) { return (float)q / 255.0f; }
 
 // clip(rint(v), 0, 255); v finite
-ISR_RAYS_FN uint8_t round8(double v) {
+ISR_HD uint8_t round8(double v) {
   const double r = rint(v);
   if (r <= 0.0) return 0;
   if (r >= 255.0) return 255;
   return (uint8_t)(int)r;
 }
 
-ISR_RAYS_FN int clamp8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+ISR_HD int clamp8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
 
-ISR_RAYS_FN int gray8(const uint8_t* p) {
+ISR_HD int gray8(const uint8_t* p) {
   return (int)round8((0.299 * (double)p[0] + 0.587 * (double)p[1]) + 0.114 * (double)p[2]);
 }
 
 // ---------------------------------------------------------------- colorsys
-ISR_RAYS_FN double frac1(double t) { return t - floor(t); }      // Python's t % 1.0
+ISR_HD double frac1(double t) { return t - floor(t); }      // Python's t % 1.0
 
 // colorsys.rgb_to_hls, operation for operation
-ISR_RAYS_FN void rgb_to_hls(double r, double g, double b, double& h, double& l, double& s) {
+ISR_HD void rgb_to_hls(double r, double g, double b, double& h, double& l, double& s) {
   const double maxc = r > g ? (r > b ? r : b) : (g > b ? g : b);
   const double minc = r < g ? (r < b ? r : b) : (g < b ? g : b);
   const double sumc = maxc + minc, rangec = maxc - minc;
@@ -84,7 +84,7 @@ ISR_RAYS_FN void rgb_to_hls(double r, double g, double b, double& h, double& l, 
   h = frac1(h / 6.0);
 }
 
-ISR_RAYS_FN double hls_v(double m1, double m2, double hue) {
+ISR_HD double hls_v(double m1, double m2, double hue) {
   hue = frac1(hue);
   if (hue < 1.0 / 6.0) return m1 + ((m2 - m1) * hue) * 6.0;
   if (hue < 0.5) return m2;
@@ -93,7 +93,7 @@ ISR_RAYS_FN double hls_v(double m1, double m2, double hue) {
 }
 
 // colorsys.hls_to_rgb, operation for operation
-ISR_RAYS_FN void hls_to_rgb(double h, double l, double s, double* rgb) {
+ISR_HD void hls_to_rgb(double h, double l, double s, double* rgb) {
   if (s == 0.0) {
     rgb[0] = rgb[1] = rgb[2] = l;
     return;
@@ -106,7 +106,7 @@ ISR_RAYS_FN void hls_to_rgb(double h, double l, double s, double* rgb) {
 }
 
 // the pixel in HLS, lightness raised by dl (1 - l), hue turned by dh, back to bytes
-ISR_RAYS_FN void hls_pixel(uint8_t* p, double dl, double dh) {
+ISR_HD void hls_pixel(uint8_t* p, double dl, double dh) {
   double h, l, s, rgb[3];
   rgb_to_hls((double)p[0] / 255.0, (double)p[1] / 255.0, (double)p[2] / 255.0, h, l, s);
   l = l + dl * (1.0 - l);
@@ -116,17 +116,17 @@ ISR_RAYS_FN void hls_pixel(uint8_t* p, double dl, double dh) {
 }
 
 // ---------------------------------------------------------------- ColorJitter and RandomBrightnessContrast
-ISR_RAYS_FN uint8_t scale8(uint8_t v, double f) { return round8((double)v * f); }
-ISR_RAYS_FN uint8_t blend8(uint8_t v, double f, double other) { return round8((double)v * f + other * (1.0 - f)); }
-ISR_RAYS_FN double mean_gray(uint64_t sum, uint64_t n) { return rint((double)sum / (double)n); }
-ISR_RAYS_FN void saturate_pixel(uint8_t* p, double f) {
+ISR_HD uint8_t scale8(uint8_t v, double f) { return round8((double)v * f); }
+ISR_HD uint8_t blend8(uint8_t v, double f, double other) { return round8((double)v * f + other * (1.0 - f)); }
+ISR_HD double mean_gray(uint64_t sum, uint64_t n) { return rint((double)sum / (double)n); }
+ISR_HD void saturate_pixel(uint8_t* p, double f) {
   const double g = (double)gray8(p);
   for (int c = 0; c < 3; ++c) p[c] = blend8(p[c], f, g);
 }
-ISR_RAYS_FN uint8_t rbc8(uint8_t v, double alpha, double beta) { return round8((double)v * alpha + beta * 255.0); }
+ISR_HD uint8_t rbc8(uint8_t v, double alpha, double beta) { return round8((double)v * alpha + beta * 255.0); }
 
 // one jitter step on one pixel; m: the image's mean gray at that step (the contrast step alone reads it)
-ISR_RAYS_FN void jitter_pixel(uint8_t* p, const Program& pr, int op, double m) {
+ISR_HD void jitter_pixel(uint8_t* p, const Program& pr, int op, double m) {
   if (op == 0) {
     for (int c = 0; c < 3; ++c) p[c] = scale8(p[c], pr.brightness);
   } else if (op == 1) {
@@ -139,16 +139,16 @@ ISR_RAYS_FN void jitter_pixel(uint8_t* p, const Program& pr, int op, double m) {
 }
 
 // the step at which the contrast runs: the steps before it need no sum over the image
-ISR_RAYS_FN int contrast_step(const Program& pr) {
+ISR_HD int contrast_step(const Program& pr) {
   for (int st = 0; st < 4; ++st)
     if (pr.order[st] == 1) return st;
   return 4;
 }
 
 // ---------------------------------------------------------------- GaussianBlur, ksize 3
-ISR_RAYS_FN int reflect101(int i, int n) { return i < 0 ? -i : i >= n ? 2 * n - 2 - i : i; }      // n >= 2, -1 <= i <= n
+ISR_HD int reflect101(int i, int n) { return i < 0 ? -i : i >= n ? 2 * n - 2 - i : i; }      // n >= 2, -1 <= i <= n
 
-ISR_RAYS_FN uint8_t blur_at(const uint8_t* src, const Frame& f, int x, int y, int c) {
+ISR_HD uint8_t blur_at(const uint8_t* src, const Frame& f, int x, int y, int c) {
   const int xs[3] = {reflect101(x - 1, f.W), x, reflect101(x + 1, f.W)};
   const int ys[3] = {reflect101(y - 1, f.H), y, reflect101(y + 1, f.H)};
   int sum = 0;
@@ -161,19 +161,19 @@ ISR_RAYS_FN uint8_t blur_at(const uint8_t* src, const Frame& f, int x, int y, in
 }
 
 // ---------------------------------------------------------------- ISONoise
-ISR_RAYS_FN int luma_sum(const uint8_t* p) {      // max + min
+ISR_HD int luma_sum(const uint8_t* p) {      // max + min
   const int mx = p[0] > p[1] ? (p[0] > p[2] ? p[0] : p[2]) : (p[1] > p[2] ? p[1] : p[2]);
   const int mn = p[0] < p[1] ? (p[0] < p[2] ? p[0] : p[2]) : (p[1] < p[2] ? p[1] : p[2]);
   return mx + mn;
 }
 
 // the population standard deviation of li / 510 from the exact sums; N <= 2^20 keeps N s2 and s1^2 below 2^63
-ISR_RAYS_FN double sigma_l(uint64_t s1, uint64_t s2, uint64_t n) {
+ISR_HD double sigma_l(uint64_t s1, uint64_t s2, uint64_t n) {
   const uint64_t d = n * s2 - s1 * s1;           // >= 0 (Cauchy-Schwarz), exact
   return sqrt((double)d) / (510.0 * (double)n);
 }
 
-ISR_RAYS_FN void poisson_cdf(double lambda, double* cdf) {
+ISR_HD void poisson_cdf(double lambda, double* cdf) {
   double p = density::exp64(-lambda), acc = p;
   cdf[0] = acc;
   for (int k = 1; k < kBins; ++k) {
@@ -184,7 +184,7 @@ ISR_RAYS_FN void poisson_cdf(double lambda, double* cdf) {
 }
 
 // the smallest k with u <= cdf[k], 255 when there is none; cdf does not decrease
-ISR_RAYS_FN int poisson_k(const double* cdf, uint32_t word) {
+ISR_HD int poisson_k(const double* cdf, uint32_t word) {
   const double u = ((double)word + 0.5) * 2.3283064365386962890625e-10;      // 2^-32
   int lo = 0, hi = kBins - 1;                    // the answer lies in [lo, hi]
   while (lo < hi) {
@@ -195,34 +195,34 @@ ISR_RAYS_FN int poisson_k(const double* cdf, uint32_t word) {
   return lo;
 }
 
-ISR_RAYS_FN uint32_t poisson_word(uint32_t pixel, uint32_t k0, uint32_t k1) {
+ISR_HD uint32_t poisson_word(uint32_t pixel, uint32_t k0, uint32_t k1) {
   uint32_t w[4];
-  rays::philox4x32_10(pixel, kTagPoisson, 0u, 0u, k0, k1, w);
+  philox4x32_10(pixel, kTagPoisson, 0u, 0u, k0, k1, w);
   return w[0];
 }
 
 // Irwin-Hall: twelve 24-bit uniforms summed as integers, minus 6
-ISR_RAYS_FN double irwin_hall(uint32_t pixel, uint32_t k0, uint32_t k1) {
+ISR_HD double irwin_hall(uint32_t pixel, uint32_t k0, uint32_t k1) {
   uint64_t sum = 0;
   for (uint32_t d = 0; d < 3; ++d) {
     uint32_t w[4];
-    rays::philox4x32_10(pixel, kTagHue, d, 0u, k0, k1, w);
+    philox4x32_10(pixel, kTagHue, d, 0u, k0, k1, w);
     for (int i = 0; i < 4; ++i) sum += w[i] >> 8;
   }
   return (double)sum * 5.9604644775390625e-08 - 6.0;      // 2^-24
 }
 
-ISR_RAYS_FN double sigma_hue(const Program& pr) { return (pr.color_shift * 360.0) * pr.intensity; }
-ISR_RAYS_FN double iso_lambda(const Program& pr, double sigma) { return (sigma * pr.intensity) * 255.0; }
+ISR_HD double sigma_hue(const Program& pr) { return (pr.color_shift * 360.0) * pr.intensity; }
+ISR_HD double iso_lambda(const Program& pr, double sigma) { return (sigma * pr.intensity) * 255.0; }
 
-ISR_RAYS_FN void iso_pixel(uint8_t* p, uint32_t pixel, const double* cdf, double sigma_h, uint32_t k0, uint32_t k1) {
+ISR_HD void iso_pixel(uint8_t* p, uint32_t pixel, const double* cdf, double sigma_h, uint32_t k0, uint32_t k1) {
   const int k = poisson_k(cdf, poisson_word(pixel, k0, k1));
   const double z = irwin_hall(pixel, k0, k1);
   hls_pixel(p, (double)k / 255.0, (sigma_h * z) / 360.0);
 }
 
 // ---------------------------------------------------------------- CLAHE
-ISR_RAYS_FN int clahe_clip(double clip_limit, int area) {
+ISR_HD int clahe_clip(double clip_limit, int area) {
   const double c = (clip_limit * (double)area) / 256.0;
   if (c >= 2147483647.0) return 2147483647;
   const int ci = (int)c;
@@ -231,7 +231,7 @@ ISR_RAYS_FN int clahe_clip(double clip_limit, int area) {
 
 // bin i of a tile's histogram after clipping at `clip` and spreading `excess` (the sum of what the clip cut off): excess / 256
 // to every bin, the residual one count at a time over bins 0, step, 2 step, ...
-ISR_RAYS_FN uint32_t clahe_bin(uint32_t h, uint32_t clip, uint32_t excess, uint32_t i) {
+ISR_HD uint32_t clahe_bin(uint32_t h, uint32_t clip, uint32_t excess, uint32_t i) {
   const uint32_t batch = excess / kBins, residual = excess - batch * kBins;
   uint32_t v = (h > clip ? clip : h) + batch;
   if (residual > 0) {
@@ -241,10 +241,10 @@ ISR_RAYS_FN uint32_t clahe_bin(uint32_t h, uint32_t clip, uint32_t excess, uint3
   return v;
 }
 
-ISR_RAYS_FN uint8_t clahe_lut_value(uint32_t cdf, int area) { return round8(((double)cdf * 255.0) / (double)area); }
+ISR_HD uint8_t clahe_lut_value(uint32_t cdf, int area) { return round8(((double)cdf * 255.0) / (double)area); }
 
 // one tile: hist (256 counts) -> lut (256 bytes)
-ISR_RAYS_FN void clahe_lut(const uint32_t* hist, int clip, int area, uint8_t* lut) {
+ISR_HD void clahe_lut(const uint32_t* hist, int clip, int area, uint8_t* lut) {
   uint32_t excess = 0, cdf = 0;
   for (int i = 0; i < kBins; ++i)
     if (hist[i] > (uint32_t)clip) excess += hist[i] - (uint32_t)clip;
@@ -254,10 +254,10 @@ ISR_RAYS_FN void clahe_lut(const uint32_t* hist, int clip, int area, uint8_t* lu
   }
 }
 
-ISR_RAYS_FN int tile_of(const Frame& f, int x, int y) { return (y / (f.H / kGrid)) * kGrid + x / (f.W / kGrid); }
+ISR_HD int tile_of(const Frame& f, int x, int y) { return (y / (f.H / kGrid)) * kGrid + x / (f.W / kGrid); }
 
 // luts: 64 tables of 256 bytes
-ISR_RAYS_FN void clahe_pixel(uint8_t* p, const Frame& f, int x, int y, const uint8_t* luts) {
+ISR_HD void clahe_pixel(uint8_t* p, const Frame& f, int x, int y, const uint8_t* luts) {
   const int Y = gray8(p);
   const double txf = (double)x / (double)(f.W / kGrid) - 0.5, tyf = (double)y / (double)(f.H / kGrid) - 0.5;
   const double fx = floor(txf), fy = floor(tyf);
@@ -277,7 +277,7 @@ ISR_RAYS_FN void clahe_pixel(uint8_t* p, const Frame& f, int x, int y, const uin
 
 // ---------------------------------------------------------------- the ends
 // out(x, y, 0..2) from the pass's value v3 of the pixel
-ISR_RAYS_FN void finish_pixel(const float* v3, const float* select, const float* under, const float* border_mask, const Frame& f,
+ISR_HD void finish_pixel(const float* v3, const float* select, const float* under, const float* border_mask, const Frame& f,
                               int kh, int kw, const Batch& bt, int x, int y, float* out3) {
   const size_t pix = (size_t)y * f.W + x;
   const bool keep = !select || select[pix] == 1.f;

@@ -11,7 +11,7 @@
 // within the limits overflows a grid dimension.
 //
 //   forward_kernel            m, t, pos, rows of 64 rows: pass 1 the maximum, pass 2 the sums
-//   reduce_kernel             reduce256 of contrastive.hpp, level by level, the last level writes loss
+//   isr::reduce_kernel        (ordered_sum.hpp) REDUCE ORDER level by level, the last level writes loss, LossFinish
 //   backward_rows_kernel      dq, dk of 64 rows
 //   backward_columns_kernel   dn of 64 columns; with Bn == 1 and few columns every 1024-row range is a work item of its own
 //                             that writes its middle accumulator to the workspace, and
@@ -26,6 +26,7 @@
 namespace {
 
 using namespace isr::contrastive;
+using isr::kReduce;
 
 constexpr int kThreads = 64;                   // rows (columns) of a workgroup: one wave
 constexpr unsigned kMaxGrid = 1u << 20;
@@ -107,34 +108,20 @@ __global__ __launch_bounds__(kThreads) void forward_kernel(const float* __restri
     }
     if (live) {
       const float t = log_sum(T);
-      m_out[row] = canonical(m);
+      m_out[row] = isr::canonical(m);
       t_out[row] = t;
-      pos_out[row] = canonical(pos);
-      rows_out[row] = canonical(t - (pos - m));
+      pos_out[row] = isr::canonical(pos);
+      rows_out[row] = isr::canonical(t - (pos - m));
     }
   }
 }
 
-// out[g] = reduce256(in[256 g ..]); the level that leaves one value also writes loss
-template <class In>
-__global__ __launch_bounds__(kReduce) void reduce_kernel(const In* __restrict__ in, long long L, double* __restrict__ out,
-                                                         double scale, long long rows, float* __restrict__ loss) {
-  __shared__ double w[kReduce];
-  for (long long g = blockIdx.x; g * kReduce < L; g += gridDim.x) {
-    const long long i = g * kReduce + threadIdx.x;
-    __syncthreads();
-    w[threadIdx.x] = i < L ? (double)in[i] : 0.0;
-    __syncthreads();
-    for (int s = kReduce / 2; s > 0; s >>= 1) {
-      if ((int)threadIdx.x < s) w[threadIdx.x] += w[threadIdx.x + s];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      out[g] = w[0];
-      if (L <= kReduce) *loss = loss_value(w[0], scale, rows);
-    }
-  }
-}
+// the last step of the sum of the rows: the loss
+struct LossFinish {
+  double scale;
+  long long rows;
+  __device__ float operator()(double R, int) const { return loss_value(R, scale, rows); }
+};
 
 template <int DP, bool EXACT>
 __global__ __launch_bounds__(kThreads) void backward_rows_kernel(const float* __restrict__ q, const float* __restrict__ k,
@@ -159,7 +146,7 @@ __global__ __launch_bounds__(kThreads) void backward_rows_kernel(const float* __
       const float ca = c * a;
 #pragma unroll
       for (int d = 0; d < DP; ++d)
-        if (EXACT || d < D) dk[row * D + d] = canonical(ca * qr[d]);
+        if (EXACT || d < D) dk[row * D + d] = isr::canonical(ca * qr[d]);
     }
     if (!dq) continue;                                   // uniform: the whole grid skips the tiles
     const float* nb = n + (Bn == 1 ? (size_t)0 : (size_t)b * M * D);
@@ -186,7 +173,7 @@ __global__ __launch_bounds__(kThreads) void backward_rows_kernel(const float* __
     if (live) {
 #pragma unroll
       for (int d = 0; d < DP; ++d)
-        if (EXACT || d < D) dq[row * D + d] = canonical(c * fmaf(a, kr[d], outer[d]));
+        if (EXACT || d < D) dq[row * D + d] = isr::canonical(c * fmaf(a, kr[d], outer[d]));
     }
   }
 }
@@ -256,7 +243,7 @@ __global__ __launch_bounds__(kThreads) void backward_columns_kernel(const float*
       } else {
 #pragma unroll
         for (int d = 0; d < DP; ++d)
-          if (EXACT || d < D) dn[col * D + d] = canonical(c * outer[d]);
+          if (EXACT || d < D) dn[col * D + d] = isr::canonical(c * outer[d]);
       }
     }
   }
@@ -269,7 +256,7 @@ __global__ __launch_bounds__(256) void combine_columns_kernel(const float* __res
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < count; e += (long long)gridDim.x * 256) {
     float outer = 0.f;
     for (long long sp = 0; sp < splits; ++sp) outer += partial[sp * count + e];
-    dn[e] = canonical(c * outer);
+    dn[e] = isr::canonical(c * outer);
   }
 }
 
@@ -297,11 +284,8 @@ long long column_splits(const Shape& sh) {
   return ranges;
 }
 
-size_t reduce_bytes(const Shape& sh, size_t* second) {
-  const size_t L1 = (size_t)ceil_div(sh.rows, kReduce), L2 = (size_t)ceil_div((long long)L1, kReduce);
-  if (second) *second = isr::align_up(L1 * 8, 256);
-  return isr::align_up(L1 * 8, 256) + isr::align_up(L2 * 8, 256);
-}
+// the first level reads the rows themselves: the buffers hold the sums from the second level on
+size_t reduce_bytes(const Shape& sh, size_t* second) { return isr::reduce_bytes(ceil_div(sh.rows, kReduce), 1, second); }
 
 size_t workspace_bytes(const Shape& sh) {
   const long long splits = column_splits(sh);
@@ -334,7 +318,7 @@ extern "C" int isr_contrastive_geometry(int what) {
     case 0: return kThreads;       // rows of a row workgroup, columns of a column workgroup
     case 1: return kBlock;         // vectors of an LDS tile = terms of an inner chain
     case 2: return kSuperRows;     // rows of a middle accumulator = rows of a split range
-    case 3: return kReduce;        // leaves of a reduce256 tree
+    case 3: return kReduce;   // leaves of a reduce256 tree
     default: isr::set_error("isr_contrastive_geometry: what = %d", what); return 0;
   }
 }
@@ -361,16 +345,7 @@ extern "C" int isr_contrastive_forward(const float* q, const float* k, const flo
   size_t second;
   reduce_bytes(sh, &second);
   double* bufs[2] = {static_cast<double*>(ws), reinterpret_cast<double*>(static_cast<char*>(ws) + second)};
-  long long L = sh.rows;
-  reduce_kernel<float><<<grid_of(ceil_div(L, kReduce)), kReduce, 0, st>>>(rows, L, bufs[0], scale, sh.rows, loss);
-  ISR_CHECK_LAUNCH("contrastive reduce_kernel");
-  L = ceil_div(L, kReduce);
-  for (int cur = 0; L > 1; cur ^= 1) {
-    reduce_kernel<double><<<grid_of(ceil_div(L, kReduce)), kReduce, 0, st>>>(bufs[cur], L, bufs[cur ^ 1], scale, sh.rows, loss);
-    ISR_CHECK_LAUNCH("contrastive reduce_kernel");
-    L = ceil_div(L, kReduce);
-  }
-  return ISR_OK;
+  return isr::reduce_levels<1>("contrastive reduce_kernel", rows, sh.rows, bufs, 0, LossFinish{scale, sh.rows}, loss, st);
 }
 
 extern "C" int isr_contrastive_backward(const float* q, const float* k, const float* n, int64_t B, int64_t S, int64_t M, int D,
@@ -415,7 +390,7 @@ extern "C" int isr_contrastive_forward_host(const float* q, const float* k, cons
     forward_row(q + (size_t)i * D, k + (size_t)i * D, nb, sh.M, D, m + i, t + i, pos + i, rows + i);
   });
   std::vector<double> scratch((size_t)ceil_div(sh.rows, kReduce));
-  *loss = loss_value(sum_rows(rows, sh.rows, scratch.data()), scale, sh.rows);
+  *loss = loss_value(isr::ordered_sum(rows, sh.rows, scratch.data()), scale, sh.rows);
   return ISR_OK;
 }
 

@@ -14,7 +14,7 @@
 //            (double)exp32(pos_i - m_i), and to an f32 accumulator from 0 for each component of sum_j p_ij n_j.
 //   t_i = (float)log1p64(T_i - 1.0), T_i the f64 accumulator (T_i >= 1: the maximum contributes exp32(0) = 1).
 //   row_i = t_i - (pos_i - m_i);   ppos_i = exp32((pos_i - m_i) - t_i);   p_ij = exp32((neg_ij - m_i) - t_i).
-//   loss = (float)(scale * (R / (double)(B S))), scale an f64, R the f64 sum of the row_i in the order of reduce256 below.
+//   loss = (float)(scale * (R / (double)(B S))), scale an f64, R the f64 sum of the row_i in REDUCE ORDER (ordered_sum.hpp).
 //   c = (float)(((double)g * scale) / (double)(B S)),  a_i = ppos_i - 1
 //   dq_id = c * fmaf(a_i, k_id, sum_j p_ij n_jd);   dk_id = (c * a_i) * q_id;   dn_jd = c * sum_i p_ij q_id
 //   sums over i (SUM ORDER I), over the rows of batch item b (Bn == B, i = s) or over all rows (Bn == 1, i = b S + s): the terms
@@ -26,8 +26,9 @@
 // logit beside a finite maximum has p = 0.  Every NaN written is the canonical quiet NaN 0x7FC00000.
 #pragma once
 #include "field_density.hpp"
+#include "ordered_sum.hpp"
 
-#define ISR_CON_FN __host__ __device__ inline
+#include "hd.hpp"
 
 namespace isr {
 namespace contrastive {
@@ -38,22 +39,12 @@ constexpr int kMaxM = 1 << 24;
 constexpr int kBlock = 64;                           // terms of one inner chain
 constexpr int kSuper = 16;                           // inner chains of one middle accumulator (SUM ORDER I)
 constexpr int kSuperRows = kBlock * kSuper;
-constexpr int kReduce = 256;                         // leaves of one reduce256 tree
-constexpr uint32_t kNanBits = 0x7FC00000u;
-
-ISR_CON_FN float bits_float(uint32_t u) {
-  float f;
-  __builtin_memcpy(&f, &u, 4);
-  return f;
-}
-
-ISR_CON_FN float canonical(float z) { return z != z ? bits_float(kNanBits) : z; }
 
 // exp(x) in f32 for x <= 0 (every argument of the rule is): 0 below -87 (no subnormal results), NaN for NaN, exp32(0) = 1.
 //   kf = rintf(x * log2(e));  r = fmaf(kf, -ln2_hi, x);  r = fmaf(kf, -ln2_lo, r)       (|r| <= 0.3466)
 //   P = the degree-5 polynomial below by Horner in fmaf;  e = fmaf(r * r, P, r) + 1;  exp32 = e * 2^kf, exact (kf >= -126).
 // Error against the correctly rounded exponential: tools/contrastive_host_check.cpp measures it over [-104, 0].
-ISR_CON_FN float exp32(float x) {
+ISR_HD float exp32(float x) {
   if (!(x == x)) return bits_float(kNanBits);
   if (x < -87.0f) return 0.0f;
   const float kf = rintf(x * 1.44269504088896341f);
@@ -69,33 +60,22 @@ ISR_CON_FN float exp32(float x) {
   return e * bits_float((uint32_t)((int)kf + 127) << 23);
 }
 
-ISR_CON_FN float dot(const float* a, const float* c, int D) {
+ISR_HD float dot(const float* a, const float* c, int D) {
   float l = a[0] * c[0];
   for (int d = 1; d < D; ++d) l = fmaf(a[d], c[d], l);
   return l;
 }
 
-ISR_CON_FN float max_step(float m, float l) { return (l > m || l != l) ? l : m; }
+ISR_HD float max_step(float m, float l) { return (l > m || l != l) ? l : m; }
 
-ISR_CON_FN float log_sum(double T) { return canonical((float)density::log1p64(T - 1.0)); }
+ISR_HD float log_sum(double T) { return canonical((float)density::log1p64(T - 1.0)); }
 
-ISR_CON_FN float grad_scale(float g, double scale, long long rows) {
+ISR_HD float grad_scale(float g, double scale, long long rows) {
   return (float)(((double)g * scale) / (double)rows);
 }
 
-ISR_CON_FN float loss_value(double R, double scale, long long rows) {
+ISR_HD float loss_value(double R, double scale, long long rows) {
   return canonical((float)(scale * (R / (double)rows)));
-}
-
-// reduce256: the sum of up to 256 doubles v[0 .. n-1] (the missing ones are +0) by the tree v[i] += v[i + s] for
-// s = 128, 64, .. 1.  The sum of L values: reduce256 of every 256 consecutive ones, ascending, then the same of the results,
-// until one is left.
-inline double reduce256(const double* v, int n) {
-  double w[kReduce];
-  for (int i = 0; i < kReduce; ++i) w[i] = i < n ? v[i] : 0.0;
-  for (int s = kReduce / 2; s > 0; s >>= 1)
-    for (int i = 0; i < s; ++i) w[i] += w[i + s];
-  return w[0];
 }
 
 // What is wrong with a shape, or null.
@@ -171,26 +151,6 @@ inline void backward_column(const float* q, const float* m, const float* t, long
     for (int d = 0; d < D; ++d) outer[d] += mid[d];
   }
   for (int d = 0; d < D; ++d) dn[d] = canonical(c * outer[d]);
-}
-
-// The sum of the rows' losses in the order of reduce256; scratch: (rows + 255) / 256 doubles at least.
-inline double sum_rows(const float* rows, long long count, double* scratch) {
-  long long L = (count + kReduce - 1) / kReduce;
-  for (long long g = 0; g < L; ++g) {
-    double v[kReduce];
-    const int nn = (int)(count - g * kReduce < kReduce ? count - g * kReduce : kReduce);
-    for (int i = 0; i < nn; ++i) v[i] = (double)rows[g * kReduce + i];
-    scratch[g] = reduce256(v, nn);
-  }
-  while (L > 1) {
-    const long long L2 = (L + kReduce - 1) / kReduce;
-    for (long long g = 0; g < L2; ++g) {
-      const int nn = (int)(L - g * kReduce < kReduce ? L - g * kReduce : kReduce);
-      scratch[g] = reduce256(scratch + g * kReduce, nn);       // reads [256 g, 256 g + nn), writes [g]: g <= 256 g
-    }
-    L = L2;
-  }
-  return scratch[0];
 }
 
 }  // namespace contrastive

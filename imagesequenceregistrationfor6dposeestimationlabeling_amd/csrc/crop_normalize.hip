@@ -14,6 +14,7 @@
 // [from memory] quantises the sample position to 1/32 px and the weights to 2^-15 before it sums, so its
 // bytes can differ from these by a grey level at some pixels.  oracle/preprocess_oracle.py states the
 // same arithmetic in NumPy, operation for operation.
+#include "block_prims.hpp"
 #include "isr_common.hpp"
 
 namespace {
@@ -37,11 +38,8 @@ __global__ __launch_bounds__(256) void mask_bbox_kernel(const uint8_t* __restric
       x0 = min(x0, x); x1 = max(x1, x); y0 = min(y0, y); y1 = max(y1, y);
     }
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    x0 = min(x0, __shfl_xor(x0, o, 64)); y0 = min(y0, __shfl_xor(y0, o, 64));
-    x1 = max(x1, __shfl_xor(x1, o, 64)); y1 = max(y1, __shfl_xor(y1, o, 64));
-  }
+  x0 = isr::wave_reduce(x0, isr::Min{}); y0 = isr::wave_reduce(y0, isr::Min{});
+  x1 = isr::wave_reduce(x1, isr::Max{}); y1 = isr::wave_reduce(y1, isr::Max{});
   if ((threadIdx.x & 63) == 0) {
     const int w = threadIdx.x >> 6;
     red[w][0] = x0; red[w][1] = y0; red[w][2] = x1; red[w][3] = y1;

@@ -8,11 +8,7 @@
 #pragma once
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define ISR_EA_FN __host__ __device__ inline
-#else
-#define ISR_EA_FN inline
-#endif
+#include "hd.hpp"
 
 namespace isr {
 namespace ea {
@@ -21,7 +17,7 @@ namespace ea {
 // hit; a sample that was not evaluated counts as below (a caller may stop evaluating a ray after its first hit: the later
 // c_k are multiplied by T = 0 whatever they are).  The reference writes (1.0 + 1e-10) - c, which is 1 - c in f32: the f64
 // scalar rounds to 1.0f.  threshold < 0: the density itself.
-ISR_EA_FN float absorbance(float rho, float threshold, bool evaluated = true) {
+ISR_HD float absorbance(float rho, float threshold, bool evaluated = true) {
   if (threshold >= 0.f) return evaluated && rho > threshold ? 1.0f : 0.0f;
   return rho;
 }
@@ -29,20 +25,20 @@ ISR_EA_FN float absorbance(float rho, float threshold, bool evaluated = true) {
 struct WeightChain {
   float T, m;
   int32_t any;
-  ISR_EA_FN void start() {
+  ISR_HD void start() {
     T = 1.0f;
     m = 0.f;
     any = 0;
   }
   // w_k into the maximum and the hit flag
-  ISR_EA_FN void take(int k, float len, float w) {
+  ISR_HD void take(int k, float len, float w) {
     if (w != 0.f) any = 1;
     const float v = len * w;
     if (k == 0) m = v;
     else if (m == m && (v != v || v > m)) m = v;      // a NaN stays
   }
   // sample k, k ascending -> w_k
-  ISR_EA_FN float step(int k, float len, float c) {
+  ISR_HD float step(int k, float len, float c) {
     const float w = c * T;
     T = T * (1.0f - c);
     take(k, len, w);

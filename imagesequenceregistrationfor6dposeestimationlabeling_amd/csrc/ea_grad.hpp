@@ -28,8 +28,8 @@ constexpr int kRowFloats = 4097;      // floats of LDS per array: (rays of a wor
 
 // The LDS row of a ray is P | 1 floats apart from the next: an odd stride, so the lanes that walk their rays in step
 // touch different banks.
-ISR_EA_FN int row_stride(int P) { return P | 1; }
-ISR_EA_FN int rays_per_group(int P) {
+ISR_HD int row_stride(int P) { return P | 1; }
+ISR_HD int rays_per_group(int P) {
   const int r = kRowFloats / row_stride(P);
   return r < 1 ? 1 : (r > kMaxGroupRays ? kMaxGroupRays : r);
 }
@@ -50,7 +50,7 @@ inline const char* check_call(const void* densities, const void* features, int N
 using ea::absorbance;      // c_k: the density itself, or in threshold mode a step function of it
 
 // g_k, everything that reaches w_k from above: dweights[k], then the image's channels in ascending order
-ISR_EA_FN float upstream(const float* dimage, const float* feat, int F, float dweight) {
+ISR_HD float upstream(const float* dimage, const float* feat, int F, float dweight) {
   float g = dweight;
   for (int ch = 0; ch < F; ++ch) g = __builtin_fmaf(dimage[ch], feat[ch], g);
   return g;
@@ -58,7 +58,7 @@ ISR_EA_FN float upstream(const float* dimage, const float* feat, int F, float dw
 
 // T[k] = T_k for k in [0, P): the forward's chain.  c and T do not overlap, and the loops of both walks are unrolled, so that
 // on the device a batch of LDS reads is in flight while the chain, one multiplication a sample, runs in registers.
-ISR_EA_FN void transmittance(int P, const float* __restrict__ c, float* __restrict__ T) {
+ISR_HD void transmittance(int P, const float* __restrict__ c, float* __restrict__ T) {
   float t = 1.0f;
 #pragma unroll 8
   for (int k = 0; k < P; ++k) {
@@ -68,7 +68,7 @@ ISR_EA_FN void transmittance(int P, const float* __restrict__ c, float* __restri
 }
 
 // The way down: g[k] holds g_k on entry and ddensities[k] on return.  dopacity = dimage[F]; the opacity is 1 - T_P.
-ISR_EA_FN void adjoint(int P, const float* __restrict__ c, const float* __restrict__ T, float dopacity, float* __restrict__ g) {
+ISR_HD void adjoint(int P, const float* __restrict__ c, const float* __restrict__ T, float dopacity, float* __restrict__ g) {
   float a = -dopacity;
 #pragma unroll 8
   for (int k = P - 1; k >= 0; --k) {
@@ -79,7 +79,7 @@ ISR_EA_FN void adjoint(int P, const float* __restrict__ c, const float* __restri
 }
 
 // dfeatures[k, ch] from the forward's weight of sample k
-ISR_EA_FN float feature_grad(float c, float T, float dimage_ch) { return (c * T) * dimage_ch; }
+ISR_HD float feature_grad(float c, float T, float dimage_ch) { return (c * T) * dimage_ch; }
 
 // ---- host build: the definition the kernel is compared with.  c, T: P floats of scratch each.
 inline void backward_ray_host(int P, int F, const float* rho, const float* features, float threshold, const float* dimage,

@@ -13,6 +13,7 @@
 // next dense step sums them in block order: the shape csrc/epnp.hpp replays on the host.  No device-scope fences, no atomics.
 // The dense steps run in one 64-lane workgroup per image with every matrix in LDS: lanes share the Jacobi rotations, one lane
 // runs the small serial steps.
+#include "block_prims.hpp"
 #include "isr_common.hpp"
 #include "epnp.hpp"
 
@@ -75,9 +76,7 @@ __global__ __launch_bounds__(kEpnpThreads) void epnp_pass_kernel(
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
   for (int k = 0; k < NA; ++k) {
-    double s = a[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    const double s = isr::wave_sum_down(a[k]);
     if (lane == 0) red[wave][k] = s;
   }
   __syncthreads();

@@ -16,6 +16,7 @@
 //                                              torch_scatter.scatter_min), mask / coordinate scores
 // The (n x m) matrix itself comes from isr_corr_logsoftmax.  RNG is explicit (Philox4x32-10): the
 // reference uses torch.rand on the device and an unseeded np.random.randint.
+#include "block_prims.hpp"
 #include "isr_common.hpp"
 #include "p3p_device.hpp"
 
@@ -552,7 +553,7 @@ __global__ __launch_bounds__(256) void ep_sample_kernel(const float* __restrict_
   const int t = min(blockIdx.x * 4 + wave, n_samples * 4 - 1);       // 4 draws per sample: the grid is exact
   const int smp = t >> 2, j = t & 3;
   uint32_t rnd[4];
-  philox4x32_10((uint32_t)smp, 1u, 0u, 0u, seed_lo, seed_hi, rnd);
+  isr::philox4x32_10((uint32_t)smp, 1u, 0u, 0u, seed_lo, seed_hi, rnd);
   const double u = ((double)rnd[j] + 0.5) * (1.0 / 4294967296.0);
   const double target = u * row_cum[n - 1];
   // row: first o with row_cum[o] >= target — a 64-ary search (three dependent loads at n = 5 476 instead of thirteen)
@@ -717,7 +718,7 @@ __global__ void ep_p3p_kernel(const int64_t* __restrict__ corr_idx, int res, int
         ord[b + 1] = x;
       }
       uint32_t rnd[4];
-      philox4x32_10((uint32_t)s, 2u, 0u, 0u, seed_lo, seed_hi, rnd);
+      isr::philox4x32_10((uint32_t)s, 2u, 0u, 0u, seed_lo, seed_hi, rnd);
       const int pick = (int)(((uint64_t)rnd[0] * (uint64_t)nv) >> 32);
       const int sel = ord[pick];
       ok = 1;
@@ -794,9 +795,7 @@ __global__ __launch_bounds__(256) void zbuf_score_kernel(const unsigned long lon
   double v[3] = {sm, sc, cnt};
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    double s = v[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    const double s = isr::wave_sum_down(v[i]);
     if ((threadIdx.x & 63) == 0) red[i][threadIdx.x >> 6] = s;
   }
   __syncthreads();
@@ -856,9 +855,7 @@ __global__ __launch_bounds__(256) void zbuf_score_direct_kernel(const unsigned l
   double v[3] = {sm, sc, cnt};
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    double s = v[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    const double s = isr::wave_sum_down(v[i]);
     if ((threadIdx.x & 63) == 0) red[i][threadIdx.x >> 6] = s;
   }
   __syncthreads();
@@ -1017,9 +1014,7 @@ __global__ __launch_bounds__(THREADS) void zbuf_fused_direct_kernel(const float*
     double v3[3] = {sm, sc, cnt};
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      double s = v3[i];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+      const double s = isr::wave_sum_down(v3[i]);
       if ((tid & 63) == 0) red[i][tid >> 6] = s;
     }
   }

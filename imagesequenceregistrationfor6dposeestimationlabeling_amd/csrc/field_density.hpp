@@ -48,7 +48,7 @@ struct Layout {
   Layer L[kMaxHidden];
 };
 
-ISR_FIELD_FN bool make_layout(int n_hidden, const int32_t* widths, int H, Layout& lay) {
+ISR_HD bool make_layout(int n_hidden, const int32_t* widths, int H, Layout& lay) {
   if (n_hidden < 1 || n_hidden > kMaxHidden || H < 1 || H > kMaxH) return false;
   int off = kHeaderWords;
   int K = 6 * H;
@@ -69,17 +69,17 @@ ISR_FIELD_FN bool make_layout(int n_hidden, const int32_t* widths, int H, Layout
   return true;
 }
 
-ISR_FIELD_FN double from_bits(uint64_t u) {
+ISR_HD double from_bits(uint64_t u) {
   double d;
   __builtin_memcpy(&d, &u, 8);
   return d;
 }
-ISR_FIELD_FN uint64_t to_bits(double d) {
+ISR_HD uint64_t to_bits(double d) {
   uint64_t u;
   __builtin_memcpy(&u, &d, 8);
   return u;
 }
-ISR_FIELD_FN uint32_t to_bits32(float f) {
+ISR_HD uint32_t to_bits32(float f) {
   uint32_t u;
   __builtin_memcpy(&u, &f, 4);
   return u;
@@ -88,7 +88,7 @@ ISR_FIELD_FN uint32_t to_bits32(float f) {
 // The first 320 bits of the binary fraction of 2/pi, most significant word first, behind one word of zeros (bit positions
 // <= 0).  Produced with mpmath at 600 bits of working precision:
 //     v = int(mpmath.floor(mpmath.mpf(2) / mpmath.pi * mpmath.mpf(2) ** 320));  word i = (v >> (32 * (9 - i))) & 0xffffffff
-ISR_FIELD_FN uint32_t two_over_pi_word(int i) {
+ISR_HD uint32_t two_over_pi_word(int i) {
   constexpr uint32_t kBits[11] = {0x00000000u, 0xa2f9836eu, 0x4e441529u, 0xfc2757d1u, 0xf534ddc0u, 0xdb629599u,
                                   0x3c439041u, 0xfe5163abu, 0xdebbc561u, 0xb7246e3au, 0x424dd2e0u};
   return kBits[i];
@@ -102,7 +102,7 @@ ISR_FIELD_FN uint32_t two_over_pi_word(int i) {
 // [-1/2, 1/2) with at least 60 significant bits even where a is nearest a multiple of pi/2; r = fraction * pi/2, then
 // field::sincos_kernel on |r| <= pi/4.  The table reaches past the largest finite f32 (e = 104 needs bit 262), so the rule
 // beyond 2^64 is the same rule and the same accuracy.  NaN and +-Inf give NaN for both; sin(-0) = -0, cos(-0) = 1.
-ISR_FIELD_FN void sincos32(float a, float* sn, float* cs) {
+ISR_HD void sincos32(float a, float* sn, float* cs) {
   const uint32_t ab = to_bits32(a);
   const uint32_t ax = ab & 0x7fffffffu;
   if (ax >= 0x7f800000u) {
@@ -151,7 +151,7 @@ ISR_FIELD_FN void sincos32(float a, float* sn, float* cs) {
 }
 
 // expm1(r) for |r| <= 0.35: fdlibm's e_exp.c kernel, exp(r) = 1 + r + r c / (2 - c), c = r - r^2 P(r^2)
-ISR_FIELD_FN double expm1_kernel(double r) {
+ISR_HD double expm1_kernel(double r) {
   const double t = r * r;
   const double c = r - t * (1.66666666666666019037e-01 +
                             t * (-2.77777777770155933842e-03 +
@@ -161,14 +161,14 @@ ISR_FIELD_FN double expm1_kernel(double r) {
 }
 
 // x = k ln2 + r, |r| <= ln2 / 2 (fdlibm's two-part ln2); x finite, |x| < 746
-ISR_FIELD_FN double reduce_ln2(double x, int* k) {
+ISR_HD double reduce_ln2(double x, int* k) {
   const double kf = rint(x * 1.44269504088896338700e+00);
   *k = (int)kf;
   return (x - kf * 6.93147180369123816490e-01) - kf * 1.90821492927058770002e-10;
 }
 
 // exp(x) in f64, error below 1 ulp; 0 below -708 (no subnormal results), +Inf above 709, NaN for NaN
-ISR_FIELD_FN double exp64(double x) {
+ISR_HD double exp64(double x) {
   if (!(x == x)) return x;
   if (x < -708.0) return 0.0;
   if (x > 709.0) return from_bits(0x7ff0000000000000ull);
@@ -179,7 +179,7 @@ ISR_FIELD_FN double exp64(double x) {
 
 // log(1 + y) in f64 for y >= 0 (NaN for NaN): fdlibm's s_log1p.c — u = 1 + y, the rounding of u put back as c / u, and
 // e_log.c's kernel on u = 2^k m with m in [sqrt(1/2), sqrt(2))
-ISR_FIELD_FN double log1p64(double y) {
+ISR_HD double log1p64(double y) {
   if (!(y == y)) return y;
   const double u = 1.0 + y;
   double c = (u >= 2.0) ? 1.0 - (u - y) : y - (u - 1.0);
@@ -209,14 +209,14 @@ ISR_FIELD_FN double log1p64(double y) {
 
 // torch.nn.Softplus(beta): z where beta z > 20, else log1p(exp(beta z)) / beta.  beta z is the exact f64 product of the two
 // f32 values, the result one rounding of an f64 value.
-ISR_FIELD_FN float softplus32(float z, float beta) {
+ISR_HD float softplus32(float z, float beta) {
   const double t = (double)beta * (double)z;
   if (t > 20.0) return z;
   return (float)(log1p64(exp64(t)) / (double)beta);
 }
 
 // 1 - exp(-s) as -expm1(-s): no cancellation for small s.  s >= 0 in the field; NaN gives NaN.
-ISR_FIELD_FN float density32(float s) {
+ISR_HD float density32(float s) {
   const double x = -(double)s;
   if (!(x == x)) return s;
   if (x < -40.0) return 1.0f;
@@ -232,7 +232,7 @@ ISR_FIELD_FN float density32(float s) {
 // The march of one ray: ea_chain.hpp's chain, threshold >= 0 (thresholdMode) or the emission-absorption weights.
 // Only rho[0 .. n_eval) counts: in threshold mode a caller may stop evaluating a ray after its first hit, the later c_k
 // are multiplied by 0 whatever they are.  weights may be null.
-ISR_FIELD_FN void march_ray(int P, const float* len, const float* rho, int n_eval, float threshold, float* weights, float* depth,
+ISR_HD void march_ray(int P, const float* len, const float* rho, int n_eval, float threshold, float* weights, float* depth,
                             int32_t* hit) {
   ea::WeightChain ch;
   ch.start();
@@ -251,7 +251,7 @@ ISR_FIELD_FN void march_ray(int P, const float* len, const float* rho, int n_eva
 // Only rho[lo_eval .. P) is read: in threshold mode a caller may leave the samples in front of the tile holding the last hit
 // unevaluated, their c_k is multiplied by A_k = 0 whatever it is.  rho[lo_eval .. P) is OVERWRITTEN with the weights (the
 // descending pass leaves them there for the ascending maximum); weights may be null.
-ISR_FIELD_FN void march_ray_back(int P, const float* len, float* rho, int lo_eval, float threshold, float* weights, float* depth,
+ISR_HD void march_ray_back(int P, const float* len, float* rho, int lo_eval, float threshold, float* weights, float* depth,
                                  int32_t* hit) {
   float absorb = 1.0f;
   for (int k = P - 1; k >= lo_eval; --k) {
@@ -290,7 +290,7 @@ inline void pack_host(const Layout& lay, const float* freqs, float beta, const f
 }
 
 // e (6H) of one point
-ISR_FIELD_FN void embed_point(const float* x, const float* freqs, int H, float* e) {
+ISR_HD void embed_point(const float* x, const float* freqs, int H, float* e) {
   for (int d = 0; d < 3; ++d)
     for (int i = 0; i < H; ++i) {
       const float a = x[d] * freqs[i];

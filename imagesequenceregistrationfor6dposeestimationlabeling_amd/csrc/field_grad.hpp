@@ -33,7 +33,7 @@ constexpr int kGradBatch = 8192;
 
 // cos(a) for an f32 a: sin32's reduction and kernels, the quadrant taken in f64, one rounding to f32.  cos32(+-0) = 1; NaN
 // and +-Inf give NaN.
-ISR_FIELD_FN float cos32(float a) {
+ISR_HD float cos32(float a) {
   double n, s, c;
   const double r = reduce_pio2((double)a, &n);
   sincos_kernel(r, &s, &c);
@@ -43,7 +43,7 @@ ISR_FIELD_FN float cos32(float a) {
 }
 
 // sin32(a) and cos32(a) from one reduction: the same bits as the two calls.
-ISR_FIELD_FN void sin_cos32(float a, float* sn, float* cs) {
+ISR_HD void sin_cos32(float a, float* sn, float* cs) {
   double n, s, c;
   const double r = reduce_pio2((double)a, &n);
   sincos_kernel(r, &s, &c);
@@ -53,7 +53,7 @@ ISR_FIELD_FN void sin_cos32(float a, float* sn, float* cs) {
 }
 
 // The layers of the transposed pack (L[0] is empty: nothing flows below layer 0).
-ISR_FIELD_FN void make_layout_t(const Layout& lay, Layout& t) {
+ISR_HD void make_layout_t(const Layout& lay, Layout& t) {
   int off = kHeaderWords;
   t.n_layers = lay.n_layers;
   t.L[0] = Layer{0, 0, 0, 0, 0, off, off};
@@ -65,7 +65,7 @@ ISR_FIELD_FN void make_layout_t(const Layout& lay, Layout& t) {
 }
 
 // Where the real entries of layer l sit in the standard layout (every W (out, in) row-major, layer after layer; every b).
-ISR_FIELD_FN void std_offsets(const Layout& lay, int* w_off, int* b_off, int* w_total, int* b_total) {
+ISR_HD void std_offsets(const Layout& lay, int* w_off, int* b_off, int* w_total, int* b_total) {
   int w = 0, b = 0;
   for (int l = 0; l < lay.n_layers; ++l) {
     w_off[l] = w;
@@ -133,7 +133,7 @@ inline void point_grads(const Layout& lay, const void* pack, const float* const*
 }
 
 // sum_n g[n gs] * h[n hs] over N points in the order of the rule (h == nullptr: every h is 1).
-ISR_FIELD_FN float blocked_sum(const float* g, long gs, const float* h, long hs, long N) {
+ISR_HD float blocked_sum(const float* g, long gs, const float* h, long hs, long N) {
   double total = 0.0;
   for (long n0 = 0; n0 < N; n0 += kGradChain) {
     const long n1 = n0 + kGradChain < N ? n0 + kGradChain : N;

@@ -16,7 +16,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#define ISR_FIELD_FN __host__ __device__ inline
+#include "hd.hpp"
 
 namespace isr {
 namespace field {
@@ -42,7 +42,7 @@ struct Layout {
 };
 
 // Layer `L` of a pack: K inputs, O outputs, in matrix-core order or not, its words from `off` on (which moves past them).
-ISR_FIELD_FN void add_layer(int K, int O, int mfma, int& off, Layer& L) {
+ISR_HD void add_layer(int K, int O, int mfma, int& off, Layer& L) {
   L.K = K;
   L.O = O;
   L.OP = (O + 31) / 32 * 32;
@@ -55,7 +55,7 @@ ISR_FIELD_FN void add_layer(int K, int O, int mfma, int& off, Layer& L) {
 }
 
 // false: a layer count or a width outside the limits (lay is then unspecified)
-ISR_FIELD_FN bool make_layout(int n_layers, const int32_t* widths, Layout& lay) {
+ISR_HD bool make_layout(int n_layers, const int32_t* widths, Layout& lay) {
   if (n_layers < 1 || n_layers > kMaxLayers || widths[0] != 3) return false;
   int off = kHeaderWords;
   for (int l = 0; l < n_layers; ++l) {
@@ -72,7 +72,7 @@ ISR_FIELD_FN bool make_layout(int n_layers, const int32_t* widths, Layout& lay) 
 // Where W[j, k] of a layer sits inside its weight block.  Matrix-core order: 32-row blocks; per block and per group of 8 k's,
 // lane (k & 1) * 32 + (j & 31) owns four consecutive words, the k's 8g + 2i + (k & 1) for i = 0..3 — one 16-byte load per
 // lane feeds four v_mfma_f32_32x32x2_f32 (A operand: lane (r, h) holds A[r][h]).
-ISR_FIELD_FN int w_index(const Layer& L, int j, int k) {
+ISR_HD int w_index(const Layer& L, int j, int k) {
   if (!L.mfma) return j * L.kstride + k;
   const int lane = (k & 1) * 32 + (j & 31);
   return (((j >> 5) * (L.kstride >> 3) + (k >> 3)) * 64 + lane) * 4 + ((k & 7) >> 1);
@@ -81,7 +81,7 @@ ISR_FIELD_FN int w_index(const Layer& L, int j, int k) {
 // The reduction and the kernels of sin32 below and of sincos32 (field_density.hpp), in f64.
 // Cody-Waite: n = rint(x * 2/pi), r = (x - n C1) - n C2 with C1 the leading 33 bits of pi/2 -- n C1 and the subtraction are
 // exact for |n| < 2^20 -- clamped to [-1, 1] (it is within pi/4 wherever the reduction is accurate).  -> r, n in *n.
-ISR_FIELD_FN double reduce_pio2(double x, double* n_out) {
+ISR_HD double reduce_pio2(double x, double* n_out) {
   const double n = rint(x * 6.36619772367581382433e-01);
   const double r0 = (x - n * 1.57079632673412561417e+00) - n * 6.07710050650619224932e-11;
   const double r = (n == 0.0) ? x : r0;
@@ -90,7 +90,7 @@ ISR_FIELD_FN double reduce_pio2(double x, double* n_out) {
 }
 
 // sin(r) and cos(r) on |r| <= pi/4: the degree-13 / degree-14 kernels of Sun's fdlibm
-ISR_FIELD_FN void sincos_kernel(double r, double* s, double* c) {
+ISR_HD void sincos_kernel(double r, double* s, double* c) {
   const double r2 = r * r;
   const double ps = -1.66666666666666324348e-01 +
                     r2 * (8.33333333332248946124e-03 +
@@ -110,7 +110,7 @@ ISR_FIELD_FN void sincos_kernel(double r, double* s, double* c) {
 // sine for |a| <= 2^17; measured 0.5 ulp).  Beyond 2^17 the reduction loses accuracy but r is clamped, so the value stays in
 // [-1, 1] and is the same on every build; n can reach 2e38 there, so the quadrant is taken in f64.  NaN and +-Inf give NaN
 // (every comparison is false for them); sin32(-0) = -0.
-ISR_FIELD_FN float sin32(float a) {
+ISR_HD float sin32(float a) {
   double n, s, c;
   const double r = reduce_pio2((double)a, &n);
   sincos_kernel(r, &s, &c);
@@ -120,7 +120,7 @@ ISR_FIELD_FN float sin32(float a) {
 }
 
 // A pre-activation to the layer's output.
-ISR_FIELD_FN float activate(float z, bool sine, float omega) {
+ISR_HD float activate(float z, bool sine, float omega) {
   if (!sine) return z;
   const float a = omega * z;
   return sin32(a);

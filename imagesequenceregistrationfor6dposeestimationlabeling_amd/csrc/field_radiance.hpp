@@ -29,7 +29,7 @@ struct Layout {
   Layer dir, trunk, out;
 };
 
-ISR_FIELD_FN bool make_layout(int n_hidden, const int32_t* widths, int H, int Wc, int C, Layout& lay) {
+ISR_HD bool make_layout(int n_hidden, const int32_t* widths, int H, int Wc, int C, Layout& lay) {
   if (!density::make_layout(n_hidden, widths, H, lay.d)) return false;
   if (Wc < 1 || Wc > kMaxWidth || C < 1 || C > kMaxC) return false;
   int off = lay.d.total_words;
@@ -45,14 +45,14 @@ ISR_FIELD_FN bool make_layout(int n_hidden, const int32_t* widths, int H, int Wc
 
 // 1 / (1 + exp(-z)): an f64 value with an error near 2e-16 rounded once to f32.  exp64 saturates to 0 and +Inf, which gives
 // the limits 1 and 0; NaN gives NaN.
-ISR_FIELD_FN float sigmoid32(float z) {
+ISR_HD float sigmoid32(float z) {
   const double e = density::exp64(-(double)z);
   return (float)(1.0 / (1.0 + e));
 }
 
 // d / max(||d||, 1e-12): torch.nn.functional.normalize on CPU f32 tensors.  The square root and the quotients are taken in
 // f64 and rounded to f32, which is the correctly rounded f32 result (53 >= 2 * 24 + 2 bits), on every build.
-ISR_FIELD_FN void normalize3(const float* d, float* out) {
+ISR_HD void normalize3(const float* d, float* out) {
   const float s = __builtin_fmaf(d[2], d[2], __builtin_fmaf(d[1], d[1], d[0] * d[0]));
   const float n = (float)__builtin_sqrt((double)s);
   const float m = n < 1e-12f ? 1e-12f : n;             // a NaN norm stays NaN
@@ -64,14 +64,14 @@ ISR_FIELD_FN void normalize3(const float* d, float* out) {
 template <int kChannels>
 struct RayState : ea::WeightChain {
   float feat[kChannels];
-  ISR_FIELD_FN void start() {
+  ISR_HD void start() {
     ea::WeightChain::start();
 #pragma unroll
     for (int c = 0; c < kChannels; ++c) feat[c] = 0.f;
   }
   // sample k: its length, its density (evaluated == false: a sample behind the first hit of thresholdMode, c_k * 0) and its
   // colours col[0 .. C) (nan_colour: the sample's point is not finite, every colour is NaN).  -> w_k
-  ISR_FIELD_FN float step(int k, float len, float rho, bool evaluated, float threshold, const float* col, int C, bool nan_colour) {
+  ISR_HD float step(int k, float len, float rho, bool evaluated, float threshold, const float* col, int C, bool nan_colour) {
     const float w = ea::WeightChain::step(k, len, ea::absorbance(rho, threshold, evaluated));
     if (col) {
 #pragma unroll
@@ -84,16 +84,16 @@ struct RayState : ea::WeightChain {
     }
     return w;
   }
-  ISR_FIELD_FN float opacity() const { return 1.0f - T; }
+  ISR_HD float opacity() const { return 1.0f - T; }
 };
 
-ISR_FIELD_FN bool finite3(const float* x) {
+ISR_HD bool finite3(const float* x) {
   return (x[0] - x[0] == 0.f) && (x[1] - x[1] == 0.f) && (x[2] - x[2] == 0.f);
 }
 
 // The march alone of one ray: rho (P), features (P, F) -> image (F + 1) and, where not null, weights (P).  The channels are
 // taken 16 at a time, each pass running the same weight chain again.
-ISR_FIELD_FN void ea_march_ray(int P, int F, const float* rho, const float* features, float threshold, float* image,
+ISR_HD void ea_march_ray(int P, int F, const float* rho, const float* features, float threshold, float* image,
                                float* weights) {
   RayState<16> st;
   for (int c0 = 0; c0 < F; c0 += 16) {

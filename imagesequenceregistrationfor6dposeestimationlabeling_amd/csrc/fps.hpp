@@ -18,11 +18,7 @@
 #include <cstdint>
 #include <limits>
 
-#if defined(__HIPCC__)
-#define ISR_FPS_FN __host__ __device__ inline
-#else
-#define ISR_FPS_FN inline
-#endif
+#include "hd.hpp"
 
 namespace isr {
 namespace fps {
@@ -30,20 +26,20 @@ namespace fps {
 constexpr int kMaxPoints = 1 << 30;      // indices and the padded loops stay inside int32
 
 // squared distance of (x, y, z) to (sx, sy, sz): three roundings for the differences, one for the square, two fused adds
-ISR_FPS_FN float dist2(float x, float y, float z, float sx, float sy, float sz) {
+ISR_HD float dist2(float x, float y, float z, float sx, float sy, float sz) {
   const float dx = x - sx, dy = y - sy, dz = z - sz;
   return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
 }
 
 // (v, i) is selected before (bv, bi): larger value, or the same value at a lower index
-ISR_FPS_FN bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+ISR_HD bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
 // a candidate that loses to every point (mind >= 0 for finite points)
 constexpr int kNoIndex = std::numeric_limits<int>::max();
-ISR_FPS_FN float no_value() { return -std::numeric_limits<float>::infinity(); }
+ISR_HD float no_value() { return -std::numeric_limits<float>::infinity(); }
 // the index an arg-max selected.  Finite points always give one; where the precondition is broken and nothing compared
 // greater than no_value(), index 0 stands in, so that a selection can never index outside the cloud.
-ISR_FPS_FN int selected(int bi) { return bi == kNoIndex ? 0 : bi; }
+ISR_HD int selected(int bi) { return bi == kNoIndex ? 0 : bi; }
 
 // The definition, as a plain loop: pts (len, 3) row-major, mind a scratch of len floats, idx and radius2 (nullable) K entries.
 inline void sample_host(const float* pts, int len, int start, int K, int32_t* idx, float* radius2, float* mind) {

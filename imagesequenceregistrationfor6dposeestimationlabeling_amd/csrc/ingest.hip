@@ -7,6 +7,7 @@
 //   resize pass    one lane per output pixel: three colours and the silhouette from the same four neighbour addresses.
 // HBM-bound byte work: the mask once for the box, then the boxes' footprint of rgb and mask, 4 f32 written per output pixel.
 // No atomics, no host synchronisation; the box never visits the host.
+#include "block_prims.hpp"
 #include "isr_common.hpp"
 
 #include "../../include/isr_ingest.h"
@@ -46,13 +47,10 @@ __global__ __launch_bounds__(kThreads) void ingest_box_kernel(const uint8_t* __r
   }
   if (tail0 + threadIdx.x < end) box_byte(b, tail0 + threadIdx.x, m[tail0 + threadIdx.x], row_bytes, Cm);      // < 16 bytes
 
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    b.x0 = min(b.x0, __shfl_xor(b.x0, o, 64));
-    b.y0 = min(b.y0, __shfl_xor(b.y0, o, 64));
-    b.x1 = max(b.x1, __shfl_xor(b.x1, o, 64));
-    b.y1 = max(b.y1, __shfl_xor(b.y1, o, 64));
-  }
+  b.x0 = isr::wave_reduce(b.x0, isr::Min{});
+  b.y0 = isr::wave_reduce(b.y0, isr::Min{});
+  b.x1 = isr::wave_reduce(b.x1, isr::Max{});
+  b.y1 = isr::wave_reduce(b.y1, isr::Max{});
   if ((threadIdx.x & 63) == 0) {
     const int w = threadIdx.x >> 6;
     red[w][0] = b.x0; red[w][1] = b.y0; red[w][2] = b.x1; red[w][3] = b.y1;

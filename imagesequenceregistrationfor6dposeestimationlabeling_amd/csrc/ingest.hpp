@@ -17,11 +17,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define ISR_INGEST_FN __host__ __device__ inline
-#else
-#define ISR_INGEST_FN inline
-#endif
+#include "hd.hpp"
 
 namespace isr {
 namespace ingest {
@@ -52,16 +48,16 @@ struct Box {
   int x0, y0, x1, y1;
 };
 
-ISR_INGEST_FN Box empty_box(int H, int W) { return Box{W, H, -1, -1}; }
+ISR_HD Box empty_box(int H, int W) { return Box{W, H, -1, -1}; }
 
-ISR_INGEST_FN void box_add(Box& b, int x, int y) {
+ISR_HD void box_add(Box& b, int x, int y) {
   b.x0 = x < b.x0 ? x : b.x0;
   b.x1 = x > b.x1 ? x : b.x1;
   b.y0 = y < b.y0 ? y : b.y0;
   b.y1 = y > b.y1 ? y : b.y1;
 }
 
-ISR_INGEST_FN void box_merge(Box& b, const Box& o) {
+ISR_HD void box_merge(Box& b, const Box& o) {
   b.x0 = o.x0 < b.x0 ? o.x0 : b.x0;
   b.x1 = o.x1 > b.x1 ? o.x1 : b.x1;
   b.y0 = o.y0 < b.y0 ? o.y0 : b.y0;
@@ -69,20 +65,20 @@ ISR_INGEST_FN void box_merge(Box& b, const Box& o) {
 }
 
 // rows per strip and strips per frame of the box pass
-ISR_INGEST_FN int strip_rows(int H, int W, int Cm) {
+ISR_HD int strip_rows(int H, int W, int Cm) {
   const long long row_bytes = (long long)W * Cm;
   long long r = kStripBytes / row_bytes;
   r = r < 1 ? 1 : r;
   r = r > kMaxStripRows ? kMaxStripRows : r;
   return (int)(r > H ? H : r);
 }
-ISR_INGEST_FN int strips_of(int H, int W, int Cm) {
+ISR_HD int strips_of(int H, int W, int Cm) {
   const int r = strip_rows(H, W, Cm);
   return (H + r - 1) / r;
 }
 
 // One mask byte at byte offset `off` of its frame (off < 3 * 2^28): channel 0 of pixel (off % row_bytes) / Cm when Cm divides.
-ISR_INGEST_FN void box_byte(Box& b, uint32_t off, uint8_t v, uint32_t row_bytes, int Cm) {
+ISR_HD void box_byte(Box& b, uint32_t off, uint8_t v, uint32_t row_bytes, int Cm) {
   if (!v) return;
   const uint32_t y = off / row_bytes, o = off - y * row_bytes;
   if (Cm == 3 && o % 3u) return;
@@ -90,7 +86,7 @@ ISR_INGEST_FN void box_byte(Box& b, uint32_t off, uint8_t v, uint32_t row_bytes,
 }
 
 // Sixteen mask bytes, as four little-endian words, at byte offset `off` of their frame.
-ISR_INGEST_FN void box_chunk(Box& b, uint32_t off, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t row_bytes,
+ISR_HD void box_chunk(Box& b, uint32_t off, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t row_bytes,
                              int Cm) {
   if (!(w0 | w1 | w2 | w3)) return;
   const uint32_t w[4] = {w0, w1, w2, w3};
@@ -117,7 +113,7 @@ ISR_INGEST_FN void box_chunk(Box& b, uint32_t off, uint32_t w0, uint32_t w1, uin
 }
 
 // cowrendersynth.py:668-690: the box (x, y, w, h) = cv2.boundingRect -> the even cut, the square side and its half
-ISR_INGEST_FN Geom make_geom(const Box& b, int offset) {
+ISR_HD Geom make_geom(const Box& b, int offset) {
   const bool any = b.x1 >= 0;
   Geom g;
   g.x2 = any ? b.x0 : 0;
@@ -135,14 +131,14 @@ ISR_INGEST_FN Geom make_geom(const Box& b, int offset) {
   return g;
 }
 
-ISR_INGEST_FN double quiet_nan() {
+ISR_HD double quiet_nan() {
   union { uint64_t u; double d; } c;
   c.u = 0x7ff8000000000000ull;
   return c.d;
 }
 
 // cowrendersynth.py:717-736 -> the row-major 4 x 4 of KObj; NaN everywhere when side == 0
-ISR_INGEST_FN void camera(const double* K_in, const Geom& g, int maxB, int make_ndc, double* K_out) {
+ISR_HD void camera(const double* K_in, const Geom& g, int maxB, int make_ndc, double* K_out) {
   if (g.side == 0) {
     for (int i = 0; i < 16; ++i) K_out[i] = quiet_nan();
     return;
@@ -167,7 +163,7 @@ ISR_INGEST_FN void camera(const double* K_in, const Geom& g, int maxB, int make_
 }
 
 // One axis of the resize: output index d -> the two clamped canvas indices and the weight of the second
-ISR_INGEST_FN void resize_axis(int d, int side, int maxB, int& i0, int& i1, double& fr) {
+ISR_HD void resize_axis(int d, int side, int maxB, int& i0, int& i1, double& fr) {
   const double s = (((double)d + 0.5) * (double)side) / (double)maxB - 0.5;
   const double f0 = floor(s);
   fr = s - f0;
@@ -178,7 +174,7 @@ ISR_INGEST_FN void resize_axis(int d, int side, int maxB, int& i0, int& i1, doub
 }
 
 // The canvas at (cy, cx), 0 <= cy, cx < side: the gated colours and the ungated mask channel 0, as f64
-ISR_INGEST_FN void canvas_at(const Frame& f, const Geom& g, int cy, int cx, double* col3, double& m0) {
+ISR_HD void canvas_at(const Frame& f, const Geom& g, int cy, int cx, double* col3, double& m0) {
   const int top = g.hs1 - g.hh, left = g.hs1 - g.hw;
   if (cy < top || cy >= g.hs1 + g.hh || cx < left || cx >= g.hs1 + g.hw) {
     col3[0] = col3[1] = col3[2] = m0 = 0.0;
@@ -191,10 +187,10 @@ ISR_INGEST_FN void canvas_at(const Frame& f, const Geom& g, int cy, int cx, doub
   for (int c = 0; c < 3; ++c) col3[c] = mk[c < f.Cm ? c : f.Cm - 1] ? (double)px[c] : 0.0;
 }
 
-ISR_INGEST_FN float to_unit(double v) { return (float)(uint8_t)rint(v) / 255.0f; }      // 0 <= v <= 255
+ISR_HD float to_unit(double v) { return (float)(uint8_t)rint(v) / 255.0f; }      // 0 <= v <= 255
 
 // Output pixel (dy, dx) of a frame with side > 0: rgb3 and sil
-ISR_INGEST_FN void view_pixel(const Frame& f, const Geom& g, int maxB, int sil_mode, int dy, int dx, float* rgb3, float& sil) {
+ISR_HD void view_pixel(const Frame& f, const Geom& g, int maxB, int sil_mode, int dy, int dx, float* rgb3, float& sil) {
   int x0, x1, y0, y1;
   double fx, fy;
   resize_axis(dx, g.side, maxB, x0, x1, fx);

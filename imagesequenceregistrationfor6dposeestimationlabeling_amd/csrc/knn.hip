@@ -13,6 +13,7 @@
 //
 // local_frames_kernel: one lane per point runs knn::local_frame, the host's code.
 #include "knn.hpp"
+#include "block_prims.hpp"
 #include "isr_common.hpp"
 
 #include "../../include/isr_knn.h"
@@ -27,12 +28,6 @@ constexpr int kTile = 1024;          // targets per staged tile (12 KiB)
 constexpr int kBins = 256;           // one 8-bit digit per pass
 constexpr size_t kWorkspaceBytes = 256;
 constexpr int kFrameThreads = 64;
-
-__host__ __device__ constexpr int pad_pow2(int K) {
-  int p = 1;
-  while (p < K) p <<= 1;
-  return p;
-}
 
 int waves_for(int Kpad) { return Kpad <= 256 ? 16 : (Kpad <= 512 ? 8 : 4); }
 
@@ -92,11 +87,7 @@ __global__ __launch_bounds__(1024) void knn_kernel(const float* __restrict__ qry
       c[b] = hist[4 * lane + b];
       own += c[b];
     }
-    uint32_t incl = own;
-    for (int off = 1; off < 64; off <<= 1) {
-      const uint32_t up = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += up;
-    }
+    const uint32_t incl = isr::wave_inclusive_scan(own);     // every wave has its own query: a scan of the wave alone
     const unsigned long long reach = __ballot(incl >= (uint32_t)k_rem);
     const int owner = reach ? __ffsll((long long)reach) - 1 : 63;
     uint32_t below = __shfl(incl - own, owner, 64);
@@ -215,7 +206,7 @@ extern "C" int isr_knn(const float* qry, int Nq, const float* tgt, int Nt, int K
   if (int rc = check_knn("isr_knn", qry, Nq, tgt, Nt, K, idx)) return rc;
   ISR_REQUIRE(ws, "isr_knn: null workspace");
   ISR_REQUIRE(ws_bytes >= kWorkspaceBytes, "isr_knn: workspace %zu bytes, needs %zu", ws_bytes, kWorkspaceBytes);
-  const int Kpad = pad_pow2(K), W = waves_for(Kpad);
+  const int Kpad = isr::pad_pow2(K), W = waves_for(Kpad);
   const unsigned blocks = (unsigned)(((long)Nq + W - 1) / W);
   knn_kernel<<<blocks, W * 64, lds_bytes(W, Kpad), isr::as_stream(stream)>>>(qry, Nq, tgt, Nt, K, Kpad, idx, d2);
   ISR_CHECK_LAUNCH("knn_kernel");

@@ -16,11 +16,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define ISR_KNN_FN __host__ __device__ inline
-#else
-#define ISR_KNN_FN inline
-#endif
+#include "hd.hpp"
 
 namespace isr {
 namespace knn {
@@ -30,20 +26,20 @@ constexpr int kMaxTargets = 1 << 24;
 constexpr int kJacobiSweeps = 30;
 constexpr double kJacobiTol = 1e-30;   // stop once sum_{p<q} c_pq^2 <= kJacobiTol sum_i c_ii^2
 
-ISR_KNN_FN uint32_t d2_bits(float qx, float qy, float qz, float tx, float ty, float tz) {
+ISR_HD uint32_t d2_bits(float qx, float qy, float qz, float tx, float ty, float tz) {
   const float dx = tx - qx, dy = ty - qy, dz = tz - qz;
   union { float f; uint32_t u; } c;
   c.f = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
   return c.f != c.f ? 0x7fc00000u : c.u;
 }
 
-ISR_KNN_FN float bits_d2(uint32_t u) {
+ISR_HD float bits_d2(uint32_t u) {
   union { float f; uint32_t u; } c;
   c.u = u;
   return c.f;
 }
 
-ISR_KNN_FN uint64_t make_key(uint32_t bits, int j) { return ((uint64_t)bits << 32) | (uint32_t)j; }
+ISR_HD uint64_t make_key(uint32_t bits, int j) { return ((uint64_t)bits << 32) | (uint32_t)j; }
 
 // The definition as host code, one query: keys is scratch for Nt entries; idx, d2 (nullable) the row's K entries.
 inline void knn_row_host(const float* q, const float* tgt, int Nt, int K, uint64_t* keys, int32_t* idx, float* d2) {
@@ -57,12 +53,12 @@ inline void knn_row_host(const float* q, const float* tgt, int Nt, int K, uint64
   }
 }
 
-ISR_KNN_FN int clamp_index(int j, int N) { return j < 0 ? 0 : (j < N ? j : N - 1); }
+ISR_HD int clamp_index(int j, int N) { return j < 0 ? 0 : (j < N ? j : N - 1); }
 
 // One rotation (p, q) of the cyclic Jacobi iteration on the symmetric 3 x 3 a (full storage), v <- v G.  csrc/epnp.hpp's
 // rotation: theta = (a_qq - a_pp) / (2 a_pq), t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)) (0.5 / theta for
 // |theta| > 1e150), c = 1 / sqrt(t^2 + 1), s = t c.
-ISR_KNN_FN void jacobi_rotate(double (&a)[3][3], double (&v)[3][3], int p, int q) {
+ISR_HD void jacobi_rotate(double (&a)[3][3], double (&v)[3][3], int p, int q) {
   const double apq = a[p][q];
   if (apq == 0.0) return;
   const double app = a[p][p], aqq = a[q][q];
@@ -86,7 +82,7 @@ ISR_KNN_FN void jacobi_rotate(double (&a)[3][3], double (&v)[3][3], int p, int q
 }
 
 // a = v diag(l) v^T: l ascending (a tie keeps the lower axis first), the columns of v the eigenvectors in that order.
-ISR_KNN_FN void eigen_sym3(double (&a)[3][3], double (&l)[3], double (&v)[3][3]) {
+ISR_HD void eigen_sym3(double (&a)[3][3], double (&l)[3], double (&v)[3][3]) {
   double w[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
   for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
     const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
@@ -110,7 +106,7 @@ ISR_KNN_FN void eigen_sym3(double (&a)[3][3], double (&l)[3], double (&v)[3][3])
 }
 
 // Point i's curvatures (3) and frame (3 x 3 row-major, columns = eigenvectors) from its row of K neighbours.
-ISR_KNN_FN void local_frame(const float* pts, int N, const int32_t* row, int K, int i, int disambiguate, double* curv,
+ISR_HD void local_frame(const float* pts, int N, const int32_t* row, int K, int i, int disambiguate, double* curv,
                             double* frame) {
   double s[3] = {0.0, 0.0, 0.0};
   for (int r = 0; r < K; ++r) {

@@ -8,7 +8,7 @@
 //           vol[p + ny nz + nz], each contiguous over the lanes of a wave — into LDS and takes the k + 1 values from its
 //           neighbour's slots (the last thread loads the one column past the workgroup): eight corners from four coalesced
 //           loads.  From them the point's crossing flags and the cell's case.
-//   count:  tally, then an exclusive scan of (vertices, triangles) over the workgroup (lanes by __shfl_up, waves through
+//   count:  tally, then an exclusive scan of (vertices, triangles) over the workgroup (block_prims.hpp: lanes by shuffle, waves through
 //           LDS); every point's slot word — its first vertex within the workgroup and the flags of axes 0 and 1, which is
 //           all a triangle corner needs to find a vertex id — and the workgroup's sums go to the workspace.
 //   scan:   ONE workgroup turns the sums into exclusive offsets, kThreads of them per pass with a running carry, and writes
@@ -18,6 +18,7 @@
 //           offsets), + the workgroup's offsets: vertices to their slots, and every triangle corner resolved through the
 //           slot word of the edge's owner and the offset of the owner's workgroup.
 #include "mc_extract.hpp"
+#include "block_prims.hpp"
 #include "isr_common.hpp"
 
 #include "../../include/isr_mc.h"
@@ -83,30 +84,6 @@ __device__ __forceinline__ void tally(const float* __restrict__ vol, const Grid&
   t.ntri = tri_count(t.cs);
 }
 
-// Exclusive scan of x over the workgroup in thread order, and the workgroup's total in every thread.  sw: kWaves entries.
-template <typename T>
-__device__ __forceinline__ T block_exclusive_scan(T x, T* sw, T& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  T inc = x;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const T y = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += y;
-  }
-  if (lane == 63) sw[w] = inc;
-  __syncthreads();
-  T base = 0;
-  total = 0;
-#pragma unroll
-  for (int v = 0; v < kWaves; ++v) {
-    const T sv = sw[v];
-    if (v < w) base += sv;
-    total += sv;
-  }
-  __syncthreads();                // sw is free again (the scan kernel's next pass)
-  return base + inc - x;
-}
-
 __device__ __forceinline__ uint32_t packed_counts(const Tally& t) { return (uint32_t)flag_count(t.flags) | (uint32_t)t.ntri << 16; }
 
 __global__ __launch_bounds__(kThreads) void mc_count_kernel(const float* __restrict__ vol, Grid g, Plan pl) {
@@ -115,7 +92,7 @@ __global__ __launch_bounds__(kThreads) void mc_count_kernel(const float* __restr
   Tally t;
   tally(vol, g, s, t);
   uint32_t total;
-  const uint32_t ex = block_exclusive_scan(packed_counts(t), sw, total);
+  const uint32_t ex = isr::block_exclusive_scan<kThreads>(packed_counts(t), sw, total);
   if (t.in) pl.slot[t.p] = (uint16_t)((ex & 0xffffu) << 2 | (uint32_t)(t.flags & 3));
   if (threadIdx.x == 0) pl.boff[blockIdx.x] = (uint64_t)(total & 0xffffu) | (uint64_t)(total >> 16) << 32;
 }
@@ -127,7 +104,8 @@ __global__ __launch_bounds__(kThreads) void mc_scan_kernel(Plan pl, int32_t* __r
     const int b = base + threadIdx.x;
     const unsigned long long x = b < pl.nb ? pl.boff[b] : 0ull;
     unsigned long long total;
-    const unsigned long long ex = block_exclusive_scan(x, sw, total);
+    const unsigned long long ex = isr::block_exclusive_scan<kThreads>(x, sw, total);
+    __syncthreads();              // sw is free for the next pass
     if (b < pl.nb) pl.boff[b] = carry + ex;
     carry += total;
   }
@@ -144,7 +122,7 @@ __global__ __launch_bounds__(kThreads) void mc_emit_kernel(const float* __restri
   Tally t;
   tally(vol, g, s, t);
   uint32_t total;
-  const uint32_t ex = block_exclusive_scan(packed_counts(t), sw, total);
+  const uint32_t ex = isr::block_exclusive_scan<kThreads>(packed_counts(t), sw, total);
   const uint64_t bo = pl.boff[blockIdx.x];
   const long long v0 = (long long)(uint32_t)bo + (ex & 0xffffu);
   const long long f0 = (long long)(bo >> 32) + (ex >> 16);

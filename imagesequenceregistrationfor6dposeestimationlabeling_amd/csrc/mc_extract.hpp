@@ -18,11 +18,7 @@
 
 #include "mc_table.hpp"
 
-#if defined(__HIPCC__)
-#define ISR_MC_FN __host__ __device__ inline
-#else
-#define ISR_MC_FN inline
-#endif
+#include "hd.hpp"
 
 namespace isr {
 namespace mc {
@@ -36,34 +32,34 @@ static_assert(3 * kMaxPoints < (1ll << 30) && kMaxTris * kMaxPoints < (1ll << 31
 constexpr uint8_t kTriCount[256] = {ISR_MC_TRI_COUNTS};
 constexpr int8_t kTriEdges[256][3 * kMaxTris] = {ISR_MC_TRI_EDGES};
 
-ISR_MC_FN bool below(float v, float iso) { return v < iso; }
+ISR_HD bool below(float v, float iso) { return v < iso; }
 
 // the case of a cell from its eight corner values, c[b] at offset (b & 1, (b >> 1) & 1, (b >> 2) & 1)
-ISR_MC_FN int case_index(const float* c, float iso) {
+ISR_HD int case_index(const float* c, float iso) {
   int m = 0;
   for (int b = 0; b < 8; ++b) m |= (int)below(c[b], iso) << b;
   return m;
 }
 
 // triangles of a case; the two uniform cases are answered without the table (most cells of a volume)
-ISR_MC_FN int tri_count(int cs) { return (cs == 0 || cs == 255) ? 0 : kTriCount[cs]; }
+ISR_HD int tri_count(int cs) { return (cs == 0 || cs == 255) ? 0 : kTriCount[cs]; }
 
 // bit a: the point's +axis-a edge exists (has[a]) and carries a vertex.  va: the point's value, vx / vy / vz: its +x / +y / +z
 // neighbours' (not read where the edge does not exist)
-ISR_MC_FN int point_flags(float va, float vx, float vy, float vz, bool hasx, bool hasy, bool hasz, float iso) {
+ISR_HD int point_flags(float va, float vx, float vy, float vz, bool hasx, bool hasy, bool hasz, float iso) {
   const bool b = below(va, iso);
   return (int)(hasx && below(vx, iso) != b) | (int)(hasy && below(vy, iso) != b) << 1 | (int)(hasz && below(vz, iso) != b) << 2;
 }
-ISR_MC_FN int flag_count(int flags) { return (flags & 1) + (flags >> 1 & 1) + (flags >> 2 & 1); }
+ISR_HD int flag_count(int flags) { return (flags & 1) + (flags >> 1 & 1) + (flags >> 2 & 1); }
 // rank of axis a among the crossing edges of a point with these flags (only bits below a are read)
-ISR_MC_FN int axis_rank(int flags, int axis) { return (axis >= 1 ? flags & 1 : 0) + (axis == 2 ? flags >> 1 & 1 : 0); }
+ISR_HD int axis_rank(int flags, int axis) { return (axis >= 1 ? flags & 1 : 0) + (axis == 2 ? flags >> 1 & 1 : 0); }
 
 // where on an edge the vertex sits, from the owner's end
-ISR_MC_FN double interp(float va, float vb, float iso) { return ((double)iso - (double)va) / ((double)vb - (double)va); }
+ISR_HD double interp(float va, float vb, float iso) { return ((double)iso - (double)va) / ((double)vb - (double)va); }
 
 // cube edge e = 4 * axis + idx: its axis, and its owner's offset from the cell's grid point
-ISR_MC_FN int edge_axis(int e) { return e >> 2; }
-ISR_MC_FN void edge_owner(int e, int& di, int& dj, int& dk) {
+ISR_HD int edge_axis(int e) { return e >> 2; }
+ISR_HD void edge_owner(int e, int& di, int& dj, int& dk) {
   const int a = e >> 2, u = e & 1, v = e >> 1 & 1;
   di = a == 0 ? 0 : u;
   dj = a == 0 ? u : (a == 1 ? 0 : v);

@@ -21,6 +21,7 @@
 // with d2 = fmaf(dz,dz,fmaf(dy,dy,dx*dx)) and strict '<'; the winner's distance re-evaluated in
 // f64.  Sums are fixed-shape trees, no float atomics.  oracle/isr_oracle.c:orc_nn_batched is the
 // CPU statement of the same arithmetic.
+#include "block_prims.hpp"
 #include "isr_common.hpp"
 
 #include <cstddef>
@@ -454,12 +455,6 @@ __global__ __launch_bounds__(kThreads) void nn_search_kernel(
 
 #include "nn_grid.hpp"   // the two exact grid searches, their build kernels and workspace helpers
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 // Merge the per-split winners, re-evaluate the distance in f64, apply the radius, and reduce
 // the block's sums into part_sums[b][blockIdx.x][kNV] (fixed tree: lanes, then waves in order).
 template <bool WANT_COV>
@@ -527,7 +522,7 @@ __global__ __launch_bounds__(kThreads) void nn_finalize_kernel(
   const int wave = tid >> 6, lane = tid & 63;
 #pragma unroll
   for (int k = 0; k < nv; ++k) {
-    const double s = wave_sum(v[k]);
+    const double s = isr::wave_sum_down(v[k]);
     if (lane == 0) red[wave][k] = s;
   }
   __syncthreads();
@@ -572,7 +567,7 @@ __global__ __launch_bounds__(kThreads) void add_metric_kernel(const float* __res
     const double ex = a0 - b0, ey = a1 - b1, ez = a2 - b2;
     s += sqrt(fma(ez, ez, fma(ey, ey, ex * ex)));
   }
-  s = wave_sum(s);
+  s = isr::wave_sum_down(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) out[b] = (((red[0] + red[1]) + red[2]) + red[3]) / (double)V;
@@ -829,7 +824,7 @@ __global__ __launch_bounds__(kThreads) void icp_finalize_update_kernel(
   const int wave = tid >> 6, lane = tid & 63;
 #pragma unroll
   for (int k = 0; k < kNV; ++k) {
-    const double s = wave_sum(v[k]);
+    const double s = isr::wave_sum_down(v[k]);
     if (lane == 0) red[wave][k] = s;
   }
   __syncthreads();

@@ -40,11 +40,8 @@ __global__ __launch_bounds__(1024) void grid_bbox_kernel(const float* __restrict
   }
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64));
-      hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64));
-    }
+    lo[a] = isr::wave_reduce(lo[a], isr::Min{});
+    hi[a] = isr::wave_reduce(hi[a], isr::Max{});
     if ((threadIdx.x & 63) == 0) { smin[a][threadIdx.x >> 6] = lo[a]; smax[a][threadIdx.x >> 6] = hi[a]; }
   }
   __syncthreads();
@@ -89,7 +86,8 @@ __global__ __launch_bounds__(kThreads) void grid_count_kernel(const float* __res
   atomicAdd(&count[c], 1);
 }
 
-// exclusive scan of count[0..ncell) into start[0..ncell]; one block, contiguous chunk per thread
+// exclusive scan of count[0..ncell) into start[0..ncell]; one block, contiguous chunk per thread (not block_prims'
+// block_offsets_kernel: ncell is read on the device, count stays, and start gets ncell + 1 entries)
 __global__ __launch_bounds__(1024) void grid_scan_kernel(const GridDesc* __restrict__ g, const int32_t* __restrict__ count,
                                                          int32_t* __restrict__ start) {
   __shared__ int32_t part[1024];
@@ -260,8 +258,7 @@ __global__ __launch_bounds__(kThreads) void qblocks_fill_kernel(const GridDesc* 
 
 template <int TB>
 __device__ __forceinline__ float block_reduce_max(float v, float* red) {   // red: TB / 64 floats
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  v = isr::wave_reduce(v, isr::Max{});
   if (TB == 64) return v;
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
@@ -456,22 +453,9 @@ __global__ __launch_bounds__(TB) void nn_tile_search_kernel(
             loc[j] = e < n_runs ? run_pref[e] : 0;
             sum += loc[j];
           }
-          int inc = sum;
-#pragma unroll
-          for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(inc, o, 64);
-            if ((tid & 63) >= o) inc += u;
-          }
-          if ((tid & 63) == 63) scan_w[tid >> 6] = inc;
-          __syncthreads();
-          int base = 0, total = 0;
-#pragma unroll
-          for (int w = 0; w < TB / 64; ++w) {
-            if (w < (tid >> 6)) base += scan_w[w];
-            total += scan_w[w];
-          }
+          int total;
+          int run = isr::block_exclusive_scan<TB>(sum, scan_w, total);
           if (2 * total > Nt) break;                             // block-uniform: cheaper to scan everything once
-          int run = base + inc - sum;
 #pragma unroll
           for (int j = 0; j < kTileRuns / TB; ++j) {
             const int e = tid * (kTileRuns / TB) + j;

@@ -1,27 +1,11 @@
-// p3p_device.hpp — device-side Philox4x32-10 and the f64 P3P solver shared by ransac.hip (K2,
+// p3p_device.hpp — the device-side f64 P3P solver shared by ransac.hip (K2,
 // cv2.solvePnPRansac replacement) and estimate_pose.hip (cv2.solveP3P replacement,
 // poseEstSurf.py:138).  Only + - x / sqrt fma: plain IEEE arithmetic, no libm transcendentals.
 #pragma once
+#include "hd.hpp"
 #include "isr_common.hpp"
 
 namespace isr_p3p {
-
-// ---------------------------------------------------------------------------------- Philox
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                              uint32_t k0, uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    const uint32_t n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 // ------------------------------------------------------------------------------ small f64 math
 struct V3 { double x, y, z; };

@@ -12,6 +12,7 @@
 // the count are zero queries), isr_select_top_batch / isr_gather_corr_batch / isr_pnp_ransac_batch
 // take the count from the device.
 // Ordered stream compaction: per-block counts -> one-block scan -> scatter (as select_top.hip).
+#include "block_prims.hpp"
 #include "isr_common.hpp"
 
 namespace {
@@ -24,27 +25,6 @@ __device__ __forceinline__ uint16_t bf16_rne(float f) {
   if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x0040u);   // NaN stays NaN
   u += 0x7fffu + ((u >> 16) & 1u);
   return (uint16_t)(u >> 16);
-}
-
-__device__ __forceinline__ int block_exclusive_scan(int v, int* total) {
-  __shared__ int wsum[kThreads / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += o;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kThreads / 64; ++w) {
-    if (w < wave) base += wsum[w];
-    tot += wsum[w];
-  }
-  *total = tot;
-  return base + inc - v;
 }
 
 // pixel s of the subsampled grid (row-major): is it inside the mask?
@@ -62,40 +42,10 @@ __global__ __launch_bounds__(kThreads) void prep_count_kernel(const uint8_t* __r
   block_counts += (size_t)blockIdx.z * gridDim.x;
   const int s = blockIdx.x * kThreads + threadIdx.x;
   const int f = (s < S) && masked(mask, mask_pix_stride, W, Ws, step, s);
+  __shared__ int sw[kThreads / 64];
   int total;
-  (void)block_exclusive_scan(f, &total);
+  (void)isr::block_exclusive_scan<kThreads>(f, sw, total);
   if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
-}
-
-__global__ void prep_scan_kernel(int32_t* __restrict__ block_counts, int nblocks, int32_t* __restrict__ n_dev) {
-  __shared__ int32_t tsum[1024];
-  block_counts += (size_t)blockIdx.z * nblocks;
-  n_dev += blockIdx.z;
-  const int t = threadIdx.x;
-  const int per = (nblocks + 1023) / 1024;
-  int32_t s = 0;
-  for (int j = 0; j < per; ++j) {
-    const int b = t * per + j;
-    if (b < nblocks) s += block_counts[b];
-  }
-  tsum[t] = s;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const int32_t v = (t >= off) ? tsum[t - off] : 0;
-    __syncthreads();
-    tsum[t] += v;
-    __syncthreads();
-  }
-  int32_t run = (t > 0) ? tsum[t - 1] : 0;
-  for (int j = 0; j < per; ++j) {
-    const int b = t * per + j;
-    if (b < nblocks) {
-      const int32_t c = block_counts[b];
-      block_counts[b] = run;
-      run += c;
-    }
-  }
-  if (t == 1023) *n_dev = tsum[1023];
 }
 
 template <int DTYPE>
@@ -111,8 +61,9 @@ __global__ __launch_bounds__(kThreads) void prep_scatter_kernel(
   pix_xy += img * (size_t)S * 2;
   const int s = blockIdx.x * kThreads + threadIdx.x;
   const int f = (s < S) && masked(mask, mask_pix_stride, W, Ws, step, s);
+  __shared__ int sw[kThreads / 64];
   int total;
-  const int o = block_off[blockIdx.x] + block_exclusive_scan(f, &total);
+  const int o = block_off[blockIdx.x] + isr::block_exclusive_scan<kThreads>(f, sw, total);
   if (!f) return;
   const int r = s / Ws, c = s % Ws;
   const float* src = feat + ((size_t)(r * step) * W + (size_t)c * step) * C + c0;
@@ -164,7 +115,7 @@ extern "C" int isr_prep_queries_batch(const float* feat, int B, int H, int W, in
   // rows past an image's count and the padding columns are zero: K1 runs over all B * S capacity rows
   ISR_CHECK_HIP(hipMemsetAsync(Q, 0, (size_t)B * S * ldq * esz, stream));
   prep_count_kernel<<<dim3(nblocks, 1, B), kThreads, 0, stream>>>(mask, mask_pix_stride, mstride, W, Ws, step, S, bc);
-  prep_scan_kernel<<<dim3(1, 1, B), 1024, 0, stream>>>(bc, nblocks, n_dev);
+  isr::block_offsets_kernel<int32_t><<<dim3(1, 1, B), isr::kOffsetsThreads, 0, stream>>>(bc, nblocks, n_dev);
 #define ISR_PREP(DT)                                                                                                    \
   prep_scatter_kernel<DT><<<dim3(nblocks, 1, B), kThreads, 0, stream>>>(feat, fstride, W, C, c0, D, mask, mask_pix_stride, \
                                                                         mstride, Ws, step, S, bc, ldq, Q, pix_xy)

@@ -47,14 +47,14 @@ constexpr int kGradBatch = 2048;
 constexpr int kMaxIn = 6 * kMaxH;       // the widest input of a layer: the embedding
 
 // d softplus32(z, beta) / dz = sigmoid(beta z): one f64 evaluation rounded once; 1 where softplus32 is the identity.
-ISR_FIELD_FN float slope32(float z, float beta) {
+ISR_HD float slope32(float z, float beta) {
   const double t = (double)beta * (double)z;
   if (t > 20.0) return 1.0f;
   return (float)(1.0 / (1.0 + density::exp64(-t)));
 }
 
 // exp(-s): what torch's backward of 1 - exp(-s) multiplies by.  NaN gives NaN.
-ISR_FIELD_FN float dexp32(float s) { return (float)density::exp64(-(double)s); }
+ISR_HD float dexp32(float s) { return (float)density::exp64(-(double)s); }
 
 struct GradLayout {
   int total_words;
@@ -62,7 +62,7 @@ struct GradLayout {
   Layer trunkT, outT;
 };
 
-ISR_FIELD_FN void make_layout_t(const Layout& lay, GradLayout& t) {
+ISR_HD void make_layout_t(const Layout& lay, GradLayout& t) {
   int off = field::kHeaderWords;
   t.T[0] = Layer{0, 0, 0, 0, 0, off, off};
   for (int l = 1; l < density::kMaxHidden; ++l) {
@@ -81,7 +81,7 @@ struct StdOffsets {
   int w_total, b_total;
 };
 
-ISR_FIELD_FN void std_offsets(const Layout& lay, StdOffsets& s) {
+ISR_HD void std_offsets(const Layout& lay, StdOffsets& s) {
   int w = 0, b = 0, i = 0;
   for (; i < lay.d.n_hidden; ++i) {
     s.w[i] = w;

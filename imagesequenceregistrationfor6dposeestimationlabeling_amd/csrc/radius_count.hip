@@ -11,6 +11,7 @@
 //   count:                one lane per point, radius::count_point over its 27 cells.
 // The order inside a cell depends on the atomics; the counts do not (radius_count.hpp).  No float atomics.
 #include "radius_count.hpp"
+#include "block_prims.hpp"
 #include "isr_common.hpp"
 
 #include "../../include/isr_radius.h"
@@ -54,10 +55,8 @@ __global__ __launch_bounds__(kThreads) void radius_bounds_kernel(Plan p, const f
       mx[d] = fmaxf(mx[d], v);
     }
   for (int d = 0; d < 3; ++d) {
-    for (int off = 32; off >= 1; off >>= 1) {
-      mn[d] = fminf(mn[d], __shfl_xor(mn[d], off, 64));
-      mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], off, 64));
-    }
+    mn[d] = isr::wave_reduce(mn[d], isr::Min{});
+    mx[d] = isr::wave_reduce(mx[d], isr::Max{});
     if ((threadIdx.x & 63) == 0) {
       atomicMin(&p.box[d], isr::ordered_bits(mn[d]));
       atomicMax(&p.box[3 + d], isr::ordered_bits(mx[d]));

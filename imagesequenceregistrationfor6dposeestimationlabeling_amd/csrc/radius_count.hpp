@@ -20,11 +20,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define ISR_RADIUS_FN __host__ __device__ inline
-#else
-#define ISR_RADIUS_FN inline
-#endif
+#include "hd.hpp"
 
 namespace isr {
 namespace radius {
@@ -41,13 +37,13 @@ struct Grid {
 };
 
 // the cell coordinate of x on an axis that starts at mn and has n cells
-ISR_RADIUS_FN int cell_coord(double x, double mn, double inv_h, int n) {
+ISR_HD int cell_coord(double x, double mn, double inv_h, int n) {
   const double c = floor((x - mn) * inv_h);
   if (!(c > 0.0)) return 0;
   return c < (double)(n - 1) ? (int)c : n - 1;
 }
 
-ISR_RADIUS_FN int cell_of(const Grid& g, float x, float y, float z) {
+ISR_HD int cell_of(const Grid& g, float x, float y, float z) {
   const int cx = cell_coord((double)x, g.mn[0], g.inv_h, g.n[0]);
   const int cy = cell_coord((double)y, g.mn[1], g.inv_h, g.n[1]);
   const int cz = cell_coord((double)z, g.mn[2], g.inv_h, g.n[2]);
@@ -55,7 +51,7 @@ ISR_RADIUS_FN int cell_of(const Grid& g, float x, float y, float z) {
 }
 
 // the grid of a box [mn, mx] (finite, mn <= mx) for radius r > 0
-ISR_RADIUS_FN void make_grid(const float* mn, const float* mx, float r, Grid& g) {
+ISR_HD void make_grid(const float* mn, const float* mx, float r, Grid& g) {
   double h = kSlack * (double)r;
   double ext[3];
   bool sane = true;
@@ -80,13 +76,13 @@ ISR_RADIUS_FN void make_grid(const float* mn, const float* mx, float r, Grid& g)
   g.cells = g.n[0] * g.n[1] * g.n[2];
 }
 
-ISR_RADIUS_FN float dist2(float x, float y, float z, float sx, float sy, float sz) {
+ISR_HD float dist2(float x, float y, float z, float sx, float sy, float sz) {
   const float dx = x - sx, dy = y - sy, dz = z - sz;
   return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
 }
 
 // The count of one point (x, y, z): sorted (N, 3) the points in cell order, cell c's in [start[c], end[c]).
-ISR_RADIUS_FN int count_point(const Grid& g, const float* sorted, const int32_t* start, const int32_t* end, float x, float y,
+ISR_HD int count_point(const Grid& g, const float* sorted, const int32_t* start, const int32_t* end, float x, float y,
                               float z, float r2, int cap) {
   const int cx = cell_coord((double)x, g.mn[0], g.inv_h, g.n[0]);
   const int cy = cell_coord((double)y, g.mn[1], g.inv_h, g.n[1]);

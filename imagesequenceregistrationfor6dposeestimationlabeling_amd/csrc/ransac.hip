@@ -52,6 +52,7 @@
 // images in the kernel arguments: the per-image chain of inference.py:293 over a group of images is
 // one chain of launches for the whole group (isr_pnp_ransac_batch, the one exported pnp entry).  One image
 // is the B = 1 call: its outputs do not depend on the group it rides in.
+#include "block_prims.hpp"
 #include "isr_common.hpp"
 #include "p3p_device.hpp"
 #include "ransac_seq.hpp"
@@ -102,7 +103,7 @@ __device__ __forceinline__ void p3p_body(const float* __restrict__ p3d, const fl
   int s[4] = {0, 0, 0, 0};
   if (M >= 4) {
     uint32_t rnd[4];
-    philox4x32_10((uint32_t)h, 0u, 0u, 0u, seed_lo, seed_hi, rnd);
+    isr::philox4x32_10((uint32_t)h, 0u, 0u, 0u, seed_lo, seed_hi, rnd);
 #pragma unroll
     for (int j = 0; j < 4; ++j) s[j] = (int)(((uint64_t)rnd[j] * (uint64_t)M) >> 32);
     // a sample that repeats a correspondence is rejected (degenerate, and its 4th-point test ties)
@@ -272,8 +273,7 @@ __global__ __launch_bounds__(kScoreThreads) void score_kernel(
     __shared__ int32_t cmax[kScoreThreads / 64];
     int c = 0;
     for (int i = threadIdx.x; i < h_lo; i += kScoreThreads) c = max(c, ok[i] ? n_inl[i] : 0);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) c = max(c, __shfl_xor(c, o, 64));
+    c = isr::wave_reduce(c, isr::Max{});
     if ((threadIdx.x & 63) == 0) cmax[threadIdx.x >> 6] = c;
     __syncthreads();
     c = max(max(cmax[0], cmax[1]), max(cmax[2], cmax[3]));
@@ -416,7 +416,7 @@ __global__ __launch_bounds__(256) void seq_best_kernel(const int32_t* __restrict
   const int lo = min(H, tid * per), hi = min(H, lo + per);
   int m = 0;
   for (int h = lo; h < hi; ++h) m = max(m, ok[h] ? n_inl[h] : 0);
-  int inc = m;   // inclusive prefix max over the wave's threads
+  int inc = m;   // inclusive prefix MAX over the wave's threads (not block_prims' scan, which sums), read again below
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) {
     const int o = __shfl_up(inc, off, 64);
@@ -663,9 +663,7 @@ __global__ __launch_bounds__(kRefThreads) void gn_accumulate_kernel(
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
   for (int i = 0; i < kNAcc; ++i) {
-    double s = acc[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    const double s = isr::wave_sum_down(acc[i]);
     if (lane == 0) red[wave][i] = s;
   }
   __syncthreads();
@@ -768,9 +766,7 @@ __global__ __launch_bounds__(kRefThreads) void gn_small_kernel(
       const int wave = tid >> 6, lane = tid & 63;
 #pragma unroll
       for (int i = 0; i < kNAcc; ++i) {
-        double v = acc[i];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        const double v = isr::wave_sum_down(acc[i]);
         if (lane == 0) red[wave][i] = v;
       }
       __syncthreads();
@@ -790,27 +786,6 @@ __global__ __launch_bounds__(kRefThreads) void gn_small_kernel(
 // every word scatters its set bits at its exclusive prefix.  kCompBlock words per block.
 constexpr int kCompBlock = 256;
 
-__device__ __forceinline__ int block_scan_excl(int v, int* total) {
-  __shared__ int wsum[kCompBlock / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += o;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kCompBlock / 64; ++w) {
-    if (w < wave) base += wsum[w];
-    tot += wsum[w];
-  }
-  *total = tot;
-  return base + inc - v;
-}
-
 __global__ __launch_bounds__(kCompBlock) void mask_count_kernel(const uint32_t* __restrict__ mask, int mask_words,
                                                                 const int32_t* __restrict__ M_dev,
                                                                 const int32_t* __restrict__ status_dev,
@@ -819,39 +794,10 @@ __global__ __launch_bounds__(kCompBlock) void mask_count_kernel(const uint32_t* 
   mask += (size_t)img * mask_words; block_counts += (size_t)img * gridDim.x;
   const int W = (status_dev && status_dev[img] == 0) ? 0 : (M_dev[img] + 31) / 32;
   const int w = blockIdx.x * kCompBlock + threadIdx.x;
+  __shared__ int sw[kCompBlock / 64];
   int total;
-  (void)block_scan_excl(w < W ? __popc(mask[w]) : 0, &total);
+  (void)isr::block_exclusive_scan<kCompBlock, int>(w < W ? __popc(mask[w]) : 0, sw, total);
   if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
-}
-
-__global__ void mask_scan_kernel(int32_t* __restrict__ block_counts, int nblocks, int32_t* __restrict__ n_out) {
-  __shared__ int32_t tsum[1024];
-  block_counts += (size_t)blockIdx.z * nblocks; n_out += blockIdx.z;
-  const int t = threadIdx.x;
-  const int per = (nblocks + 1023) / 1024;
-  int32_t s = 0;
-  for (int j = 0; j < per; ++j) {
-    const int b = t * per + j;
-    if (b < nblocks) s += block_counts[b];
-  }
-  tsum[t] = s;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const int32_t v = (t >= off) ? tsum[t - off] : 0;
-    __syncthreads();
-    tsum[t] += v;
-    __syncthreads();
-  }
-  int32_t run = (t > 0) ? tsum[t - 1] : 0;
-  for (int j = 0; j < per; ++j) {
-    const int b = t * per + j;
-    if (b < nblocks) {
-      const int32_t c = block_counts[b];
-      block_counts[b] = run;
-      run += c;
-    }
-  }
-  if (t == 1023) *n_out = tsum[1023];
 }
 
 __global__ __launch_bounds__(kCompBlock) void mask_scatter_kernel(const uint32_t* __restrict__ mask, int mask_words,
@@ -864,8 +810,9 @@ __global__ __launch_bounds__(kCompBlock) void mask_scatter_kernel(const uint32_t
   const int W = (status_dev && status_dev[img] == 0) ? 0 : (M_dev[img] + 31) / 32;
   const int w = blockIdx.x * kCompBlock + threadIdx.x;
   uint32_t bits = w < W ? mask[w] : 0u;
+  __shared__ int sw[kCompBlock / 64];
   int total;
-  int o = block_off[blockIdx.x] + block_scan_excl(__popc(bits), &total);
+  int o = block_off[blockIdx.x] + isr::block_exclusive_scan<kCompBlock, int>(__popc(bits), sw, total);
   while (bits) {
     out[o++] = w * 32 + (__ffs(bits) - 1);
     bits &= bits - 1;
@@ -1064,7 +1011,7 @@ static int compact_impl(const int32_t* M_dev, int M_cap, int B, const int32_t* s
                         const RansacWs& b, hipStream_t stream) {
   const int cb = comp_blocks_of(M_cap), mw = mask_words_of(M_cap);
   mask_count_kernel<<<dim3(cb, 1, B), kCompBlock, 0, stream>>>(b.mask, mw, M_dev, status_dev, b.cblocks);
-  mask_scan_kernel<<<dim3(1, 1, B), 1024, 0, stream>>>(b.cblocks, cb, n_inl_dev);
+  isr::block_offsets_kernel<int32_t><<<dim3(1, 1, B), isr::kOffsetsThreads, 0, stream>>>(b.cblocks, cb, n_inl_dev);
   mask_scatter_kernel<<<dim3(cb, 1, B), kCompBlock, 0, stream>>>(b.mask, mw, M_dev, status_dev, b.cblocks, inl_idx, M_cap);
   ISR_CHECK_LAUNCH("mask compaction kernels");
   return ISR_OK;

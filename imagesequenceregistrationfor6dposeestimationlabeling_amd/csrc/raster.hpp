@@ -20,11 +20,7 @@
 #include <cmath>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define ISR_RASTER_FN __host__ __device__ inline
-#else
-#define ISR_RASTER_FN inline
-#endif
+#include "hd.hpp"
 
 namespace isr {
 namespace raster {
@@ -51,11 +47,11 @@ struct Face {
   int status;
 };
 
-ISR_RASTER_FN int floor_sub(int32_t a) { return a >> kSubBits; }             // floor(a / 256)
-ISR_RASTER_FN int ceil_sub(int32_t a) { return -((-a) >> kSubBits); }        // ceil(a / 256)
+ISR_HD int floor_sub(int32_t a) { return a >> kSubBits; }             // floor(a / 256)
+ISR_HD int ceil_sub(int32_t a) { return -((-a) >> kSubBits); }        // ceil(a / 256)
 
 // Project one vertex; false when it is behind the near plane or does not land on the snapped grid.
-ISR_RASTER_FN bool project_vertex(const float* v, const Camera& cam, double near_, int32_t* xs, int32_t* ys, double* zc) {
+ISR_HD bool project_vertex(const float* v, const Camera& cam, double near_, int32_t* xs, int32_t* ys, double* zc) {
   const double vx = (double)v[0], vy = (double)v[1], vz = (double)v[2];
   const double* R = cam.Rt;
   const double x = ((R[0] * vx + R[1] * vy) + R[2] * vz) + R[3];
@@ -73,7 +69,7 @@ ISR_RASTER_FN bool project_vertex(const float* v, const Camera& cam, double near
   return true;
 }
 
-ISR_RASTER_FN void setup_face(const float* verts, int n_vert, const int32_t* faces, int f, const Camera& cam, double near_,
+ISR_HD void setup_face(const float* verts, int n_vert, const int32_t* faces, int f, const Camera& cam, double near_,
                               int h, int w, Face* out) {
   Face& F = *out;
   F.status = kFaceDropped;
@@ -125,7 +121,7 @@ ISR_RASTER_FN void setup_face(const float* verts, int n_vert, const int32_t* fac
 }
 
 // Edge a -> b of an oriented face at the pixel centre (px, py) in snapped units; `in` applies the top-left rule.
-ISR_RASTER_FN int64_t edge(int32_t xa, int32_t ya, int32_t xb, int32_t yb, int64_t px, int64_t py, bool* in) {
+ISR_HD int64_t edge(int32_t xa, int32_t ya, int32_t xb, int32_t yb, int64_t px, int64_t py, bool* in) {
   const int64_t dx = (int64_t)xb - xa, dy = (int64_t)yb - ya;
   const int64_t e = dx * (py - ya) - dy * (px - xa);
   const bool top_left = dy < 0 || (dy == 0 && dx > 0);
@@ -134,7 +130,7 @@ ISR_RASTER_FN int64_t edge(int32_t xa, int32_t ya, int32_t xb, int32_t yb, int64
 }
 
 // Coverage of pixel (r, c) by an ok face: the integer barycentrics lam[i] (weight of vertex i, sum = area2).
-ISR_RASTER_FN bool cover(const Face& F, int r, int c, int64_t* lam) {
+ISR_HD bool cover(const Face& F, int r, int c, int64_t* lam) {
   const int64_t px = (int64_t)c * kSub, py = (int64_t)r * kSub;
   bool i0, i1, i2;
   lam[0] = edge(F.x[1], F.y[1], F.x[2], F.y[2], px, py, &i0);
@@ -144,7 +140,7 @@ ISR_RASTER_FN bool cover(const Face& F, int r, int c, int64_t* lam) {
 }
 
 // w_i = lambda_i / z_i, S their sum; returns z_pix.
-ISR_RASTER_FN double pixel_depth(const Face& F, const int64_t* lam, double* wgt, double* S) {
+ISR_HD double pixel_depth(const Face& F, const int64_t* lam, double* wgt, double* S) {
   wgt[0] = (double)lam[0] / F.z[0];
   wgt[1] = (double)lam[1] / F.z[1];
   wgt[2] = (double)lam[2] / F.z[2];
@@ -152,19 +148,19 @@ ISR_RASTER_FN double pixel_depth(const Face& F, const int64_t* lam, double* wgt,
   return (double)F.area2 / *S;
 }
 
-ISR_RASTER_FN uint32_t f32_bits(float f) {
+ISR_HD uint32_t f32_bits(float f) {
   union { float f; uint32_t u; } c;
   c.f = f;
   return c.u;
 }
-ISR_RASTER_FN float bits_f32(uint32_t u) {
+ISR_HD float bits_f32(uint32_t u) {
   union { float f; uint32_t u; } c;
   c.u = u;
   return c.f;
 }
 
 // The fragment of face f at pixel (r, c): false when not covered or outside [near, far]; else its z-buffer key.
-ISR_RASTER_FN bool fragment_key(const Face& F, int f, int r, int c, double near_, double far_, unsigned long long* key) {
+ISR_HD bool fragment_key(const Face& F, int f, int r, int c, double near_, double far_, unsigned long long* key) {
   int64_t lam[3];
   if (!cover(F, r, c, lam)) return false;
   double wgt[3], S;
@@ -175,19 +171,19 @@ ISR_RASTER_FN bool fragment_key(const Face& F, int f, int r, int c, double near_
 }
 
 // The key a pixel starts a draw with: empty after a clear, else what the frame buffer holds (face field 0).
-ISR_RASTER_FN unsigned long long initial_key(int clear, float alpha, float depth) {
+ISR_HD unsigned long long initial_key(int clear, float alpha, float depth) {
   if (clear || !(alpha == 1.0f) || !(depth > 0.0f)) return kEmptyKey;
   return (unsigned long long)f32_bits(depth) << 32;
 }
 
-ISR_RASTER_FN float attribute(float v, float o, float scale) {
+ISR_HD float attribute(float v, float o, float scale) {
   const float d = v - o;
   return (float)((double)d / (double)scale);      // f64 quotient of two f32, rounded once: the correctly rounded f32 quotient
 }
 
 // Resolve pixel (r, c) whose winning key is `key`: writes rgba (4 floats) and depth in place; returns 1 when the pixel is
 // covered afterwards.  A key with face field 0 keeps what the frame buffer holds.
-ISR_RASTER_FN int resolve_pixel(unsigned long long key, int clear, const float* verts, int n_vert, const int32_t* faces,
+ISR_HD int resolve_pixel(unsigned long long key, int clear, const float* verts, int n_vert, const int32_t* faces,
                                 const Camera& cam, double near_, int h, int w, const float* offset3, float scale, int r, int c,
                                 float* rgba, float* depth) {
   if (key == kEmptyKey) {

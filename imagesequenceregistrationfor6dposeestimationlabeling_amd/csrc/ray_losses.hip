@@ -8,11 +8,12 @@
 //                                     is.  Forward: the lanes' f64 sums meet in a shuffle tree, lane 0 writes the ray's f64 value
 //                                     (and ray_loss).  Backward: every lane writes its rows of dweights, column P-1 gets +0.
 //   render_rows_kernel                a lane owns a ray of the render: (row_c, row_o), then the tree over the workgroup's 256 rays
-//   reduce_kernel<NV>                 one level of REDUCE ORDER over NV interleaved sums; the level that leaves one value also
-//                                     writes the mean(s)
+//   isr::reduce_kernel                (ordered_sum.hpp) one level of REDUCE ORDER over NV interleaved sums; the level that leaves
+//                                     one value also writes the mean(s), MeanFinish
 //   render_backward_kernel            a lane owns an element of drendered
 // A work item is taken from a grid-stride loop, so no shape within the limits overflows a grid dimension.
 #include "ray_losses.hpp"
+#include "block_prims.hpp"
 #include "isr_common.hpp"
 
 #include "../../include/isr_ray_losses.h"
@@ -22,6 +23,7 @@
 namespace {
 
 using namespace isr::ray_losses;
+using isr::kReduce;
 
 constexpr int kGroupRays = 4;                  // waves (rays) of a distortion workgroup
 constexpr int kThreads = kGroupRays * kLanes;
@@ -57,7 +59,7 @@ __global__ __launch_bounds__(kThreads) void distortion_kernel(const float* __res
       mx = max_step(mx, d);
       if (k < K) wsm[k] = w[k];
     }
-    for (int s = kLanes / 2; s > 0; s >>= 1) mx = max_step(mx, __shfl_xor(mx, s, kLanes));
+    mx = isr::wave_reduce(mx, [](float m, float d) { return max_step(m, d); });      // max_step keeps a NaN; fmaxf would drop it
     for (int k = lane; k < P; k += kLanes) ts[k] = ts[k] / mx;      // the lane's own entries
     __syncthreads();
     for (int i = lane; i < K; i += kLanes) us[i] = midpoint(ts[i + 1], ts[i]);
@@ -95,45 +97,26 @@ __global__ __launch_bounds__(kThreads) void distortion_kernel(const float* __res
     if (BACKWARD) {
       if (live && lane == 0) dweights[base + K] = 0.f;
     } else {
-      for (int s = kLanes / 2; s > 0; s >>= 1) part += __shfl_down(part, s, kLanes);      // lane l < s: v[l] += v[l + s]
+      part = isr::wave_sum_down(part);                   // lane l < s: v[l] += v[l + s]
       if (live && lane == 0) {
         ray_value[ray] = part;
-        if (ray_loss) ray_loss[ray] = canonical((float)part);
+        if (ray_loss) ray_loss[ray] = isr::canonical((float)part);
       }
     }
   }
 }
 
-// out[g * NV + v] = reduce256(in[(256 g ..) * NV + v]); the level that leaves one value also writes result[v]
-template <int NV>
-__global__ __launch_bounds__(kReduce) void reduce_kernel(const double* __restrict__ in, long long L, double* __restrict__ out,
-                                                         double count0, double count1, float* __restrict__ result) {
-  __shared__ double tree[NV][kReduce];
-  for (long long g = blockIdx.x; g * kReduce < L; g += gridDim.x) {
-    const long long i = g * kReduce + threadIdx.x;
-    __syncthreads();
-#pragma unroll
-    for (int v = 0; v < NV; ++v) tree[v][threadIdx.x] = i < L ? in[i * NV + v] : 0.0;
-    __syncthreads();
-    for (int s = kReduce / 2; s > 0; s >>= 1) {
-      if ((int)threadIdx.x < s) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v) tree[v][threadIdx.x] += tree[v][threadIdx.x + s];
-      }
-      __syncthreads();
-    }
-    if ((int)threadIdx.x < NV) {
-      out[g * NV + threadIdx.x] = tree[threadIdx.x][0];
-      if (L <= kReduce) result[threadIdx.x] = mean_value(tree[threadIdx.x][0], threadIdx.x == 0 ? count0 : count1);
-    }
-  }
-}
+// the last step of a sum of the ray losses: the mean over its count (sum 0: count0, sum 1: count1)
+struct MeanFinish {
+  double count0, count1;
+  __device__ float operator()(double S, int v) const { return mean_value(S, v == 0 ? count0 : count1); }
+};
 
 // (row_c, row_o) of 256 rays, summed by the tree: partial[g] = (sum of row_c, sum of row_o)
 __global__ __launch_bounds__(kReduce) void render_rows_kernel(const float* __restrict__ rendered, const float* __restrict__ images,
                                                               const float* __restrict__ sils, const float* __restrict__ xys,
                                                               long long rows, int n, int F, int H, int W, double s,
-                                                              double* __restrict__ partial, double count0, double count1,
+                                                              double* __restrict__ partial, MeanFinish finish,
                                                               float* __restrict__ result) {
   __shared__ double tree[2][kReduce];
   for (long long g = blockIdx.x; g * kReduce < rows; g += gridDim.x) {
@@ -144,16 +127,10 @@ __global__ __launch_bounds__(kReduce) void render_rows_kernel(const float* __res
     tree[0][threadIdx.x] = rc;
     tree[1][threadIdx.x] = ro;
     __syncthreads();
-    for (int st = kReduce / 2; st > 0; st >>= 1) {
-      if ((int)threadIdx.x < st) {
-        tree[0][threadIdx.x] += tree[0][threadIdx.x + st];
-        tree[1][threadIdx.x] += tree[1][threadIdx.x + st];
-      }
-      __syncthreads();
-    }
+    isr::tree256<2>(tree);
     if (threadIdx.x < 2) {
       partial[g * 2 + threadIdx.x] = tree[threadIdx.x][0];
-      if (rows <= kReduce) result[threadIdx.x] = mean_value(tree[threadIdx.x][0], threadIdx.x == 0 ? count0 : count1);
+      if (rows <= kReduce) result[threadIdx.x] = finish(tree[threadIdx.x][0], (int)threadIdx.x);
     }
   }
 }
@@ -176,25 +153,6 @@ __global__ __launch_bounds__(256) void render_backward_kernel(const float* __res
 long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
 
 unsigned grid_of(long long items) { return (unsigned)(items < (long long)kMaxGrid ? items : (long long)kMaxGrid); }
-
-// the two buffers the levels of REDUCE ORDER alternate between: `first` values (NV doubles each), then ceil(first / 256)
-size_t reduce_bytes(long long first, int NV, size_t* second) {
-  const size_t a = isr::align_up((size_t)first * NV * 8, 256), b = isr::align_up((size_t)ceil_div(first, kReduce) * NV * 8, 256);
-  if (second) *second = a;
-  return a + b;
-}
-
-// the levels after `cur` holds L values; they end with the mean(s) in result
-template <int NV>
-int reduce_levels(const char* what, double* bufs[2], int cur, long long L, double count0, double count1, float* result,
-                  hipStream_t st) {
-  for (;; cur ^= 1) {
-    reduce_kernel<NV><<<grid_of(ceil_div(L, kReduce)), kReduce, 0, st>>>(bufs[cur], L, bufs[cur ^ 1], count0, count1, result);
-    ISR_CHECK_LAUNCH(what);
-    if (L <= kReduce) return ISR_OK;
-    L = ceil_div(L, kReduce);
-  }
-}
 
 int check_distortion_call(const char* who, int64_t N, int P) {
   const char* wrong = check_distortion(N, P);
@@ -238,7 +196,7 @@ extern "C" int isr_ray_losses_geometry(int what) {
 
 extern "C" size_t isr_distortion_workspace_bytes(int64_t N, int P) {
   if (check_distortion_call("isr_distortion_workspace_bytes", N, P)) return 0;
-  return reduce_bytes(N, 1, nullptr);
+  return isr::reduce_bytes(N, 1, nullptr);
 }
 
 extern "C" int isr_distortion_forward(const float* lengths, const float* weights, int64_t N, int P, float* ray_loss_or_null,
@@ -246,12 +204,12 @@ extern "C" int isr_distortion_forward(const float* lengths, const float* weights
   if (int rc = check_distortion_call("isr_distortion_forward", N, P)) return rc;
   ISR_REQUIRE(lengths && weights && loss, "isr_distortion_forward: null pointer");
   size_t second;
-  const size_t need = reduce_bytes(N, 1, &second);
+  const size_t need = isr::reduce_bytes(N, 1, &second);
   ISR_REQUIRE(ws && ws_bytes >= need, "isr_distortion_forward: workspace of %zu bytes, %zu needed", ws_bytes, need);
   hipStream_t st = isr::as_stream(stream);
   double* bufs[2] = {static_cast<double*>(ws), reinterpret_cast<double*>(static_cast<char*>(ws) + second)};
   if (int rc = launch_distortion<false>(lengths, weights, N, P, nullptr, bufs[0], ray_loss_or_null, nullptr, st)) return rc;
-  return reduce_levels<1>("distortion reduce_kernel", bufs, 0, N, (double)N, (double)N, loss, st);
+  return isr::reduce_levels<1>("distortion reduce_kernel", bufs[0], N, bufs, 1, MeanFinish{(double)N, (double)N}, loss, st);
 }
 
 extern "C" int isr_distortion_backward(const float* lengths, const float* weights, int64_t N, int P, const float* upstream,
@@ -269,9 +227,9 @@ extern "C" int isr_distortion_forward_host(const float* lengths, const float* we
   double* v = value.data();
   isr::parallel_rows((long)N, 16, [=](long i) {
     v[i] = distortion_ray(lengths + (size_t)i * P, weights + (size_t)i * P, P);
-    if (ray_loss_or_null) ray_loss_or_null[i] = canonical((float)v[i]);
+    if (ray_loss_or_null) ray_loss_or_null[i] = isr::canonical((float)v[i]);
   });
-  *loss = mean_value(reduce_all(v, N), (double)N);
+  *loss = mean_value(isr::ordered_sum(v, N, v), (double)N);
   return ISR_OK;
 }
 
@@ -291,7 +249,7 @@ extern "C" size_t isr_render_loss_workspace_bytes(int64_t B, int64_t n) {
     isr::set_error("isr_render_loss_workspace_bytes: B %lld, n %lld", (long long)B, (long long)n);
     return 0;
   }
-  return reduce_bytes(ceil_div(B * n, kReduce), 2, nullptr);
+  return isr::reduce_bytes(ceil_div(B * n, kReduce), 2, nullptr);
 }
 
 extern "C" int isr_render_loss_forward(const float* rendered, const float* target_images, const float* target_silhouettes,
@@ -301,16 +259,16 @@ extern "C" int isr_render_loss_forward(const float* rendered, const float* targe
   ISR_REQUIRE(rendered && target_images && target_silhouettes && xys && out, "isr_render_loss_forward: null pointer");
   const long long rows = (long long)B * n, L1 = ceil_div(rows, kReduce);
   size_t second;
-  const size_t need = reduce_bytes(L1, 2, &second);
+  const size_t need = isr::reduce_bytes(L1, 2, &second);
   ISR_REQUIRE(ws && ws_bytes >= need, "isr_render_loss_forward: workspace of %zu bytes, %zu needed", ws_bytes, need);
   hipStream_t st = isr::as_stream(stream);
   double* bufs[2] = {static_cast<double*>(ws), reinterpret_cast<double*>(static_cast<char*>(ws) + second)};
   const double count0 = (double)rows * (double)F, count1 = (double)rows;
   render_rows_kernel<<<grid_of(L1), kReduce, 0, st>>>(rendered, target_images, target_silhouettes, xys, rows, n, F, H, W, scaling,
-                                                      bufs[0], count0, count1, out);
+                                                      bufs[0], MeanFinish{count0, count1}, out);
   ISR_CHECK_LAUNCH("render_rows_kernel");
   if (rows <= kReduce) return ISR_OK;
-  return reduce_levels<2>("render loss reduce_kernel", bufs, 0, L1, count0, count1, out, st);
+  return isr::reduce_levels<2>("render loss reduce_kernel", bufs[0], L1, bufs, 1, MeanFinish{count0, count1}, out, st);
 }
 
 extern "C" int isr_render_loss_backward(const float* rendered, const float* target_images, const float* target_silhouettes,
@@ -337,8 +295,8 @@ extern "C" int isr_render_loss_forward_host(const float* rendered, const float* 
   isr::parallel_rows((long)rows, 256, [=](long i) {
     render_row(rendered, target_images, target_silhouettes, xys, (size_t)i, n, F, H, W, scaling, pc + i, po + i);
   });
-  out[0] = mean_value(reduce_all(pc, rows), (double)rows * (double)F);
-  out[1] = mean_value(reduce_all(po, rows), (double)rows);
+  out[0] = mean_value(isr::ordered_sum(pc, rows, pc), (double)rows * (double)F);
+  out[1] = mean_value(isr::ordered_sum(po, rows, po), (double)rows);
   return ISR_OK;
 }
 

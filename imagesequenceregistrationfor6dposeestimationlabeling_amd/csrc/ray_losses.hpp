@@ -5,9 +5,8 @@
 // too (tools/ray_losses_host_check.cpp).  Only + - * / sqrt fabsf and conversions in f32 and f64, one explicit fma whose product
 // is exact, and everything is built with -ffp-contract=off: the host and the device build give the same bits.
 #pragma once
+#include "ordered_sum.hpp"
 #include "rays.hpp"
-
-#define ISR_RL_FN ISR_RAYS_FN
 
 namespace isr {
 namespace ray_losses {
@@ -16,58 +15,48 @@ constexpr int kMinP = 2, kMaxP = 1024;               // samples of a ray
 constexpr long long kMaxRays = 1ll << 28;            // N, and B n
 constexpr int kMaxF = 64;                            // colour channels of the render loss
 constexpr int kLanes = 64;                           // accumulators of LANE ORDER
-constexpr int kReduce = 256;                         // leaves of one tree of REDUCE ORDER
-constexpr uint32_t kNanBits = 0x7FC00000u;
-
-ISR_RL_FN float bits_float(uint32_t u) {
-  float f;
-  __builtin_memcpy(&f, &u, 4);
-  return f;
-}
-
-ISR_RL_FN float canonical(float z) { return z != z ? bits_float(kNanBits) : z; }
 
 // ---- the distortion loss
-ISR_RL_FN float depth(float l, float l0) { return (l - l0) + 0.0f; }
+ISR_HD float depth(float l, float l0) { return (l - l0) + 0.0f; }
 
 // the running maximum: a NaN on either side stays
-ISR_RL_FN float max_step(float m, float d) { return (d > m || d != d) ? d : m; }
+ISR_HD float max_step(float m, float d) { return (d > m || d != d) ? d : m; }
 
-ISR_RL_FN float midpoint(float t1, float t0) { return (t1 + t0) / 2.0f; }
+ISR_HD float midpoint(float t1, float t0) { return (t1 + t0) / 2.0f; }
 
 // one term of inner_i: acc + w_j |ut_i - ut_j|, the product exact in f64
-ISR_RL_FN double pair_step(double acc, double wj, float ui, float uj) { return fma(wj, (double)fabsf(ui - uj), acc); }
+ISR_HD double pair_step(double acc, double wj, float ui, float uj) { return fma(wj, (double)fabsf(ui - uj), acc); }
 
-ISR_RL_FN double ray_term(float w, double inner, float delta) {
+ISR_HD double ray_term(float w, double inner, float delta) {
   const double q = (((double)w * (double)w) * (double)delta) / 3.0;
   return (double)w * inner + q;
 }
 
-ISR_RL_FN float weight_grad(double c, float w, double inner, float delta) {
+ISR_HD float weight_grad(double c, float w, double inner, float delta) {
   const double g = 2.0 * inner + (2.0 * ((double)w * (double)delta)) / 3.0;
   return canonical((float)(c * g));
 }
 
-ISR_RL_FN double grad_scale(float upstream, long long N) { return (double)upstream / (double)N; }
+ISR_HD double grad_scale(float upstream, long long N) { return (double)upstream / (double)N; }
 
-ISR_RL_FN float mean_value(double S, double count) { return canonical((float)(S / count)); }
+ISR_HD float mean_value(double S, double count) { return canonical((float)(S / count)); }
 
 // ---- the render loss
 // z2 and q = sqrt(1 + z2) of a difference d
-ISR_RL_FN void huber_parts(float d, double s, double& z2, double& q) {
+ISR_HD void huber_parts(float d, double s, double& z2, double& q) {
   const double z = (double)d / s;
   z2 = z * z;
   q = sqrt(1.0 + z2);
 }
 
-ISR_RL_FN double huber_value(float d, double s) {
+ISR_HD double huber_value(float d, double s) {
   double z2, q;
   huber_parts(d, s, z2, q);
   if (!(z2 < __builtin_inf())) return z2;            // +Inf or NaN
   return (s * z2) / (1.0 + q);
 }
 
-ISR_RL_FN float huber_grad(float d, double s, double k) {
+ISR_HD float huber_grad(float d, double s, double k) {
   if (d == 0.f) return 0.f;
   double z2, q;
   huber_parts(d, s, z2, q);
@@ -75,13 +64,13 @@ ISR_RL_FN float huber_grad(float d, double s, double k) {
 }
 
 // the index of ray `row`'s pixel in a (H, W) image, -1 outside: the rule of isr_sample_nearest
-ISR_RL_FN long long target_pixel(const float* xys, size_t row, int H, int W) {
+ISR_HD long long target_pixel(const float* xys, size_t row, int H, int W) {
   const int ix = rays::nearest_pixel(xys[2 * row], W), iy = rays::nearest_pixel(xys[2 * row + 1], H);
   return ix < 0 || iy < 0 ? -1ll : (long long)iy * W + ix;
 }
 
 // the target of element (row, ch) of image b; pix from target_pixel
-ISR_RL_FN float target_value(const float* images, const float* sils, int b, int H, int W, int F, long long pix, int ch) {
+ISR_HD float target_value(const float* images, const float* sils, int b, int H, int W, int F, long long pix, int ch) {
   if (pix < 0) return 0.f;
   const size_t at = (size_t)b * H * W + (size_t)pix;
   return ch < F ? images[at * F + ch] : sils[at];
@@ -105,29 +94,6 @@ inline const char* check_render(long long B, long long n, long long F, long long
 }
 
 // ---- host builds: the definitions the kernels are compared with
-// reduce256: the sum of up to 256 doubles (the missing ones are +0) by the tree v[i] += v[i + s], s = 128 .. 1
-inline double reduce256(const double* v, int n) {
-  double w[kReduce];
-  for (int i = 0; i < kReduce; ++i) w[i] = i < n ? v[i] : 0.0;
-  for (int s = kReduce / 2; s > 0; s >>= 1)
-    for (int i = 0; i < s; ++i) w[i] += w[i + s];
-  return w[0];
-}
-
-// REDUCE ORDER over v[0 .. count), in place (v is scratch afterwards)
-inline double reduce_all(double* v, long long count) {
-  long long L = count;
-  do {
-    const long long L2 = (L + kReduce - 1) / kReduce;
-    for (long long g = 0; g < L2; ++g) {
-      const int nn = (int)(L - g * kReduce < kReduce ? L - g * kReduce : kReduce);
-      v[g] = reduce256(v + g * kReduce, nn);           // reads [256 g, 256 g + nn), writes [g]: g <= 256 g
-    }
-    L = L2;
-  } while (L > 1);
-  return v[0];
-}
-
 // t (P), then ut (K) and delta (K) of one ray
 inline void ray_depths(const float* l, int P, float* t, float* ut, float* delta) {
   float mx = depth(l[0], l[0]);
@@ -168,7 +134,7 @@ inline void distortion_ray_backward(const float* l, const float* w, int P, doubl
 }
 
 // one ray's (row_c, row_o) of the render loss
-ISR_RL_FN void render_row(const float* rendered, const float* images, const float* sils, const float* xys, size_t row, int n, int F,
+ISR_HD void render_row(const float* rendered, const float* images, const float* sils, const float* xys, size_t row, int n, int F,
                        int H, int W, double s, double* row_c, double* row_o) {
   const int b = (int)(row / (size_t)n);
   const long long pix = target_pixel(xys, row, H, W);

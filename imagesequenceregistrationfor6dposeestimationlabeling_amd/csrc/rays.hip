@@ -16,6 +16,7 @@
 //            Rows from count to cap are written as zeros by the whole grid.
 //   sample:  one thread per output value; the channels of a pixel are consecutive lanes.
 #include "rays.hpp"
+#include "block_prims.hpp"
 #include "isr_common.hpp"
 
 #include "../../include/isr_rays.h"
@@ -74,6 +75,7 @@ __device__ __forceinline__ bool thread_keeps(const Spec& s, const Cameras& c, co
 __global__ __launch_bounds__(kThreads) void rays_count_kernel(Spec s, Cameras c, const float* __restrict__ mask, int mh, int mw,
                                                               Plan pl) {
   __shared__ uint32_t sw[kWaves];
+  // a flag per thread: a ballot and a popcount per wave stand in for block_prims' scan (rays_emit_kernel needs the ballot itself)
   const unsigned long long m = __ballot(thread_keeps(s, c, mask, mh, mw));
   if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = (uint32_t)__popcll(m);
   __syncthreads();
@@ -86,26 +88,14 @@ __global__ __launch_bounds__(kThreads) void rays_count_kernel(Spec s, Cameras c,
 
 __global__ __launch_bounds__(kThreads) void rays_scan_kernel(Plan pl, int32_t* __restrict__ count_dev) {
   __shared__ uint32_t sw[kWaves];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   uint32_t carry = 0;                                // at most 2^28 in all
   for (int base = 0; base < pl.nb; base += kThreads) {
     const int b = base + threadIdx.x;
     const uint32_t x = b < pl.nb ? pl.boff[b] : 0u;
-    uint32_t inc = x;
-    for (int off = 1; off < 64; off <<= 1) {
-      const uint32_t y = __shfl_up(inc, off, 64);
-      if (lane >= off) inc += y;
-    }
-    if (lane == 63) sw[w] = inc;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-    for (int v = 0; v < kWaves; ++v) {
-      const uint32_t sv = sw[v];
-      if (v < w) before += sv;
-      total += sv;
-    }
+    uint32_t total;
+    const uint32_t ex = isr::block_exclusive_scan<kThreads>(x, sw, total);
     __syncthreads();                                 // sw is free for the next pass
-    if (b < pl.nb) pl.boff[b] = carry + before + inc - x;
+    if (b < pl.nb) pl.boff[b] = carry + ex;
     carry += total;
   }
   if (threadIdx.x == 0) pl.totals[0] = count_dev[0] = (int32_t)carry;
@@ -309,8 +299,8 @@ extern "C" int isr_sample_nearest_host(const float* images, int B, int H, int W,
 
 extern "C" int isr_rays_philox_host(const uint32_t* counter, const uint32_t* key, uint32_t* words, float* units) {
   ISR_REQUIRE(counter && key && words, "isr_rays_philox_host: null pointer");
-  philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1], words);
+  isr::philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1], words);
   if (units)
-    for (int i = 0; i < 4; ++i) units[i] = unit_float(words[i]);
+    for (int i = 0; i < 4; ++i) units[i] = isr::unit_float(words[i]);
   return ISR_OK;
 }

@@ -11,11 +11,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define ISR_RAYS_FN __host__ __device__ inline
-#else
-#define ISR_RAYS_FN inline
-#endif
+#include "hd.hpp"
 
 namespace isr {
 namespace rays {
@@ -47,40 +43,19 @@ struct Cameras {
   const int32_t* ids;         // (B,) or null: 0 .. B-1
 };
 
-// ---- Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; Random123's constants)
-ISR_RAYS_FN void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
-  for (int round = 0; round < 10; ++round) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1;
-    c3 = (uint32_t)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0;
-  out[1] = c1;
-  out[2] = c2;
-  out[3] = c3;
-}
-
-// u = (word >> 8) * 2^-24, in [0, 1): exact in f32
-ISR_RAYS_FN float unit_float(uint32_t word) { return (float)(word >> 8) * 5.9604644775390625e-08f; }
-
 // ---- linspace(a, b, P)[k] in f32 with step = (b - a) / (P - 1): torch.linspace's values (CPU, f32), bit for bit
-ISR_RAYS_FN float linspace_step(float a, float b, int P) { return P > 1 ? (b - a) / (float)(P - 1) : 0.f; }
+ISR_HD float linspace_step(float a, float b, int P) { return P > 1 ? (b - a) / (float)(P - 1) : 0.f; }
 
-ISR_RAYS_FN float linspace_at(float a, float b, float step, int P, int k) {
+ISR_HD float linspace_at(float a, float b, float step, int P, int k) {
   if (P == 1) return a;
   return k < P / 2 ? fmaf(step, (float)k, a) : fmaf(-step, (float)(P - 1 - k), b);
 }
 
 // the three-term dot product, in this order
-ISR_RAYS_FN float dot3(float a0, float a1, float a2, const float* r) { return fmaf(a2, r[2], fmaf(a1, r[1], a0 * r[0])); }
+ISR_HD float dot3(float a0, float a1, float a2, const float* r) { return fmaf(a2, r[2], fmaf(a1, r[1], a0 * r[0])); }
 
 // The ray of the NDC point (x, y) of camera (R, T, intr): c = ((x - px) / fx, (y - py) / fy, 1), d = c R^T, o = (-T) R^T.
-ISR_RAYS_FN void ndc_ray(const float* R, const float* T, const float* intr, float x, float y, float* o, float* d) {
+ISR_HD void ndc_ray(const float* R, const float* T, const float* intr, float x, float y, float* o, float* d) {
   const float cx = (x - intr[2]) / intr[0], cy = (y - intr[3]) / intr[1];
   for (int i = 0; i < 3; ++i) {
     d[i] = dot3(cx, cy, 1.f, R + 3 * i);
@@ -88,10 +63,10 @@ ISR_RAYS_FN void ndc_ray(const float* R, const float* T, const float* intr, floa
   }
 }
 
-ISR_RAYS_FN int camera_id(const Cameras& c, int b) { return c.ids ? c.ids[b] : b; }
+ISR_HD int camera_id(const Cameras& c, int b) { return c.ids ? c.ids[b] : b; }
 
 // xy of candidate ray r of camera b
-ISR_RAYS_FN void candidate_xy(const Spec& s, const Cameras& c, int b, int r, float& x, float& y) {
+ISR_HD void candidate_xy(const Spec& s, const Cameras& c, int b, int r, float& x, float& y) {
   if (s.mode == kGrid) {      // raster order, y outer
     x = linspace_at(s.ax, s.bx, s.xstep, s.W, r % s.W);
     y = linspace_at(s.ay, s.by, s.ystep, s.H, r / s.W);
@@ -104,7 +79,7 @@ ISR_RAYS_FN void candidate_xy(const Spec& s, const Cameras& c, int b, int r, flo
 }
 
 // length k of candidate ray r of camera b
-ISR_RAYS_FN float length_at(const Spec& s, const Cameras& c, int b, int r, int k) {
+ISR_HD float length_at(const Spec& s, const Cameras& c, int b, int r, int k) {
   const float l = linspace_at(s.lmin, s.lmax, s.lstep, s.P, k);
   if (s.mode == kGrid || !s.stratified) return l;
   const float lower = k == 0 ? l : 0.5f * (linspace_at(s.lmin, s.lmax, s.lstep, s.P, k - 1) + l);
@@ -116,7 +91,7 @@ ISR_RAYS_FN float length_at(const Spec& s, const Cameras& c, int b, int r, int k
 }
 
 // grid_sample's nearest pixel (align_corners=True) of NDC coordinate v on an axis of `size` pixels; -1 outside (or NaN)
-ISR_RAYS_FN int nearest_pixel(float v, int size) {
+ISR_HD int nearest_pixel(float v, int size) {
   const float g = -v;
   const float f = rintf(((g + 1.f) / 2.f) * (float)(size - 1));      // half to even
   if (!(f >= 0.f && f <= (float)(size - 1))) return -1;
@@ -124,13 +99,13 @@ ISR_RAYS_FN int nearest_pixel(float v, int size) {
 }
 
 // is candidate (x, y) of camera b kept by mask (B, mh, mw)?  Non-zero keeps, NaN included.
-ISR_RAYS_FN bool mask_keeps(const float* mask, int mh, int mw, int b, float x, float y) {
+ISR_HD bool mask_keeps(const float* mask, int mh, int mw, int b, float x, float y) {
   const int ix = nearest_pixel(x, mw), iy = nearest_pixel(y, mh);
   if (ix < 0 || iy < 0) return false;
   return mask[((size_t)b * mh + iy) * mw + ix] != 0.f;
 }
 
-ISR_RAYS_FN bool candidate_kept(const Spec& s, const Cameras& c, const float* mask, int mh, int mw, int b, int r) {
+ISR_HD bool candidate_kept(const Spec& s, const Cameras& c, const float* mask, int mh, int mw, int b, int r) {
   float x, y;
   candidate_xy(s, c, b, r, x, y);
   return mask_keeps(mask, mh, mw, b, x, y);

@@ -160,7 +160,7 @@ __device__ __forceinline__ void block_objective(const float* __restrict__ X, con
   }
 #pragma unroll
   for (int q = 0; q < kAcc; ++q) {
-    double s = acc[q];
+    double s = acc[q];   // wave_sum_down's tree, written out: through the shared function these kernels take two more registers
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = s;

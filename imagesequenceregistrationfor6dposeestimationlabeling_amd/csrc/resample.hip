@@ -47,12 +47,6 @@ struct Plan {
   int half_log2;  // log2(ksort / 2)
 };
 
-__host__ __device__ constexpr int pad_pow2(int K) {
-  int p = 1;
-  while (p < K) p <<= 1;
-  return p;
-}
-
 Plan make_plan(const Spec& sp, int sorted, int add_input) {
   Plan pl{};
   pl.sorted = sorted;
@@ -62,7 +56,7 @@ Plan make_plan(const Spec& sp, int sorted, int add_input) {
   pl.w_off = sorted ? 0 : 1;
   pl.stride = (sp.nb + 1) | 1;
   pl.P_out = sp.n + (pl.add_input ? pl.P_in : 0);
-  pl.ksort = sorted ? pad_pow2(pl.P_out) : 0;
+  pl.ksort = sorted ? isr::pad_pow2(pl.P_out) : 0;
   pl.Kpad = sorted ? (pl.ksort > pl.P_in ? pl.ksort : pl.P_in) : 0;
   while ((2 << pl.half_log2) < pl.ksort) ++pl.half_log2;
   const int per_ray = 4 * (2 * pl.stride + pl.Kpad + 1);
@@ -105,7 +99,7 @@ __global__ __launch_bounds__(kThreads) void resample_kernel(Spec sp, Plan pl, co
     for (int i = tid; i < live * (nb + 1); i += kThreads) {
       const int r = i / (nb + 1), j = i - r * (nb + 1);
       const uint32_t* l = keys + r * pl.Kpad + j;
-      bins[r * pl.stride + j] = mid_point(bits_float(l[0]), bits_float(l[1]));
+      bins[r * pl.stride + j] = mid_point(isr::bits_float(l[0]), isr::bits_float(l[1]));
     }
   float* sums = reinterpret_cast<float*>(keys + (size_t)pl.R * pl.Kpad);      // R words behind the keys
   if (tid < live) sums[tid] = weight_sum(c + tid * pl.stride, nb, sp.eps);
@@ -125,7 +119,7 @@ __global__ __launch_bounds__(kThreads) void resample_kernel(Spec sp, Plan pl, co
     for (int i = tid; i < live * pl.P_in; i += kThreads) {
       const int r = i / pl.P_in, k = i - r * pl.P_in;
       uint32_t* slot = keys + r * pl.Kpad + k;
-      *slot = sort_key(bits_float(*slot));
+      *slot = sort_key(isr::bits_float(*slot));
     }
   float* o0 = out + (size_t)ray0 * pl.P_out;
   for (int i = tid; i < live * sp.n; i += kThreads) {

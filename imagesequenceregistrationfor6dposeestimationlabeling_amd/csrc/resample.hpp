@@ -26,7 +26,7 @@ constexpr int kMinPoints = 3, kMaxPoints = 1024;     // P; nb = P - 2 bins carry
 constexpr int kMaxSamples = 1024;                    // n
 constexpr long long kMaxRays = 1ll << 28;            // N
 constexpr uint32_t kTagPdf = 2;                      // Philox stream tag (rays.hpp uses 0 and 1)
-constexpr uint32_t kNanBits = 0x7FC00000u, kNanKey = 0xFFFFFFFFu;
+constexpr uint32_t kNanKey = 0xFFFFFFFFu;
 
 // What a call asks for, made once on the host (make_spec) and read by host and device alike.
 struct Spec {
@@ -38,49 +38,41 @@ struct Spec {
   uint32_t key0, key1;    // Philox key = seed
 };
 
-ISR_RAYS_FN uint32_t float_bits(float f) {
+ISR_HD uint32_t float_bits(float f) {
   uint32_t u;
   __builtin_memcpy(&u, &f, 4);
   return u;
 }
 
-ISR_RAYS_FN float bits_float(uint32_t u) {
-  float f;
-  __builtin_memcpy(&f, &u, 4);
-  return f;
-}
-
-ISR_RAYS_FN float canonical(float z) { return z != z ? bits_float(kNanBits) : z; }
-
 // The sort key of a depth: the sign-corrected integer image of its bits (-0 before +0), every NaN the largest key.
-ISR_RAYS_FN uint32_t sort_key(float f) {
+ISR_HD uint32_t sort_key(float f) {
   if (f != f) return kNanKey;
   const uint32_t u = float_bits(f);
   return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
 
-ISR_RAYS_FN float key_value(uint32_t k) {
+ISR_HD float key_value(uint32_t k) {
   if (k == kNanKey) return bits_float(kNanBits);
   return bits_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
 }
 
 // bins_j of a ray's lengths: the mid-point of l_j and l_{j+1}
-ISR_RAYS_FN float mid_point(float lo, float hi) { return 0.5f * (hi + lo); }
+ISR_HD float mid_point(float lo, float hi) { return 0.5f * (hi + lo); }
 
 // The knots, in place: c[1 .. nb] holds the weights w_0 .. w_{nb-1} on entry and cdf_1 .. cdf_nb on return; c[0] = 0.
 //   S = f32(sum_j f64(w_j + eps)),   pdf_j = (w_j + eps) / S,   cdf_{j+1} = f32(sum_{i <= j} f64(pdf_i)).
 // The two sums are serial scans in this order — the order is the contract, one thread owns both; the quotients between
 // them are independent of each other, so the kernel spreads them over its lanes (the three steps are separate for that).
-ISR_RAYS_FN float weight_sum(const float* c, int nb, float eps) {
+ISR_HD float weight_sum(const float* c, int nb, float eps) {
   double acc = 0.0;
   for (int j = 0; j < nb; ++j) acc += (double)(c[j + 1] + eps);
   return (float)acc;
 }
 
-ISR_RAYS_FN float pdf_value(float w, float eps, float S) { return (w + eps) / S; }
+ISR_HD float pdf_value(float w, float eps, float S) { return (w + eps) / S; }
 
 // c[1 .. nb] holds pdf_0 .. pdf_{nb-1} on entry
-ISR_RAYS_FN void pdf_scan(float* c, int nb) {
+ISR_HD void pdf_scan(float* c, int nb) {
   c[0] = 0.f;
   double acc = 0.0;
   for (int j = 0; j < nb; ++j) {
@@ -89,24 +81,24 @@ ISR_RAYS_FN void pdf_scan(float* c, int nb) {
   }
 }
 
-ISR_RAYS_FN void build_cdf(float* c, int nb, float eps) {
+ISR_HD void build_cdf(float* c, int nb, float eps) {
   const float S = weight_sum(c, nb, eps);
   for (int j = 0; j < nb; ++j) c[j + 1] = pdf_value(c[j + 1], eps, S);
   pdf_scan(c, nb);
 }
 
 // unit s of ray `ray_id`
-ISR_RAYS_FN float unit_at(const Spec& sp, uint32_t ray_id, int s) {
+ISR_HD float unit_at(const Spec& sp, uint32_t ray_id, int s) {
   if (sp.det) return rays::linspace_at(0.f, 1.f, sp.ustep, sp.n, s);
   uint32_t w[4];
-  rays::philox4x32_10(ray_id, 0u, kTagPdf, (uint32_t)(s >> 2), sp.key0, sp.key1, w);
+  philox4x32_10(ray_id, 0u, kTagPdf, (uint32_t)(s >> 2), sp.key0, sp.key1, w);
   const uint32_t word = (s & 3) == 0 ? w[0] : (s & 3) == 1 ? w[1] : (s & 3) == 2 ? w[2] : w[3];
-  return rays::unit_float(word);
+  return unit_float(word);
 }
 
 // The sample of unit u: i = #{k in 0..nb : cdf_k <= u} by this binary search (searchsorted(right=True) on a monotone row;
 // on a row with NaN knots it is this search that is the rule), then the interpolation inside bin [i - 1, min(i, nb)].
-ISR_RAYS_FN float sample_at(const float* bins, const float* cdf, int nb, float eps, float u) {
+ISR_HD float sample_at(const float* bins, const float* cdf, int nb, float eps, float u) {
   int lo = 0, hi = nb + 1;
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;

@@ -19,7 +19,7 @@ constexpr int kDigitBits = 8;       // bits of a radix digit
 constexpr int kDigits = 1 << kDigitBits;
 
 // The pixel ray `row` (of all B * n) belongs to, iy * W + ix, or H * W when it belongs to none: such rays sort last.
-ISR_RAYS_FN uint32_t ray_pixel(const float* xys, size_t row, int H, int W) {
+ISR_HD uint32_t ray_pixel(const float* xys, size_t row, int H, int W) {
   const int ix = rays::nearest_pixel(xys[2 * row], W), iy = rays::nearest_pixel(xys[2 * row + 1], H);
   return ix < 0 || iy < 0 ? (uint32_t)H * (uint32_t)W : (uint32_t)iy * (uint32_t)W + (uint32_t)ix;
 }

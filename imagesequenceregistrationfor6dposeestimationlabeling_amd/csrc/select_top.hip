@@ -14,6 +14,7 @@
 // Every kernel carries an IMAGE dimension (blockIdx.z): the per-image loop of inference.py:163 over a
 // group of images becomes ten launches for the whole group (isr_select_top_batch); one image is the
 // B = 1 call, and an image's results do not depend on the group it rides in.
+#include "block_prims.hpp"
 #include "isr_common.hpp"
 
 namespace {
@@ -122,27 +123,6 @@ __global__ void pick_kernel(const int32_t* __restrict__ hist, SelState* __restri
   }
 }
 
-__device__ __forceinline__ int block_exclusive_scan(int v, int* total) {
-  __shared__ int wsum[kThreads / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += o;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kThreads / 64; ++w) {
-    if (w < wave) base += wsum[w];
-    tot += wsum[w];
-  }
-  *total = tot;
-  return base + inc - v;
-}
-
 // Thread t of a block owns the kPerThread CONSECUTIVE elements base + t*kPerThread .. (ordered).
 __global__ __launch_bounds__(kThreads) void count_kernel(const float* __restrict__ x, int64_t ld,
                                                          const SelState* __restrict__ st,
@@ -155,41 +135,10 @@ __global__ __launch_bounds__(kThreads) void count_kernel(const float* __restrict
 #pragma unroll
   for (int e = 0; e < kPerThread; ++e)
     if (i0 + e < P) c += x[i0 + e] > thr;
+  __shared__ int sw[kThreads / 64];
   int total;
-  (void)block_exclusive_scan(c, &total);
+  (void)isr::block_exclusive_scan<kThreads>(c, sw, total);
   if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
-}
-
-__global__ void scan_blocks_kernel(int32_t* __restrict__ block_counts, int nblocks,
-                                   int32_t* __restrict__ M_dev) {
-  // one block of 1024 threads per image; each thread scans a contiguous run
-  __shared__ int32_t tsum[1024];
-  block_counts += (size_t)blockIdx.z * nblocks; M_dev += blockIdx.z;
-  const int t = threadIdx.x;
-  const int per = (nblocks + 1023) / 1024;
-  int32_t s = 0;
-  for (int j = 0; j < per; ++j) {
-    const int b = t * per + j;
-    if (b < nblocks) s += block_counts[b];
-  }
-  tsum[t] = s;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const int32_t v = (t >= off) ? tsum[t - off] : 0;
-    __syncthreads();
-    tsum[t] += v;
-    __syncthreads();
-  }
-  int32_t run = (t > 0) ? tsum[t - 1] : 0;
-  for (int j = 0; j < per; ++j) {
-    const int b = t * per + j;
-    if (b < nblocks) {
-      const int32_t c = block_counts[b];
-      block_counts[b] = run;  // exclusive offset
-      run += c;
-    }
-  }
-  if (t == 1023) *M_dev = tsum[1023];
 }
 
 __global__ __launch_bounds__(kThreads) void scatter_kernel(const float* __restrict__ x, int64_t ld,
@@ -207,8 +156,9 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const float* __restri
     f[e] = (i0 + e < P) && (x[i0 + e] > thr);
     c += f[e];
   }
+  __shared__ int sw[kThreads / 64];
   int total;
-  int o = block_off[blockIdx.x] + block_exclusive_scan(c, &total);
+  int o = block_off[blockIdx.x] + isr::block_exclusive_scan<kThreads>(c, sw, total);
 #pragma unroll
   for (int e = 0; e < kPerThread; ++e)
     if (f[e]) keep[o++] = i0 + e;
@@ -305,7 +255,7 @@ static int select_top_impl(const float* logp, int P, int64_t ld, int B, const in
   hist_kernel<0, 10><<<gP, kThreads, 0, stream>>>(logp, ld, st, h2);
   pick_kernel<0, 10, true><<<gI, 1024, 0, stream>>>(h2, st, thr_dev);
   count_kernel<<<gP, kThreads, 0, stream>>>(logp, ld, st, bc);
-  scan_blocks_kernel<<<gI, 1024, 0, stream>>>(bc, nblocks, M_dev);
+  isr::block_offsets_kernel<int32_t><<<gI, isr::kOffsetsThreads, 0, stream>>>(bc, nblocks, M_dev);
   scatter_kernel<<<gP, kThreads, 0, stream>>>(logp, ld, st, bc, keep, (int64_t)P);
   ISR_CHECK_LAUNCH("select_top kernels");
   return ISR_OK;

@@ -15,7 +15,7 @@
  * WHAT IS PINNED TO WHAT.  The warp: to oracle/preprocess_oracle.warp_affine's definition (the textbook one, shared with
  * csrc/crop_normalize.hip) and, independently, to torch.nn.functional.grid_sample in f64.  normalize: to torch's f32
  * expression of dataGen.py:16-20, bit for bit.  The ray remap and the candidate set: to the executed lines of
- * augment.py:639-685 (tests/golden/ref_augment.npz).  Philox4x32-10: Random123's known answers (csrc/rays.hpp).  UNPINNED,
+ * augment.py:639-685 (tests/golden/ref_augment.npz).  Philox4x32-10: Random123's known answers (csrc/hd.hpp).  UNPINNED,
  * from memory: cv2.warpAffine's own bytes (OpenCV quantises the sample position to 1/32 px and the weights to 2^-15; this
  * definition does not, so parity with cv2 is unpinned and the definition is owned), cv2.dilate's anchor and border rule, and
  * cv2.getRotationMatrix2D's formula (made by the Python layer).  torch.randperm's stream is not reproduced.

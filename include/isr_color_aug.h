@@ -11,7 +11,7 @@
  * WHAT IS PINNED TO WHAT.  The u8 round trip: NumPy's (x * 255).astype(uint8) and .astype(float32) / 255.  The brightness,
  * contrast and saturation blends: PIL's ImageEnhance within one level; the blur's interior: PIL's ImageFilter.Kernel, byte for
  * byte.  The hue model: the standard library's colorsys, formula for formula.  Philox4x32-10: Random123's known answers
- * (csrc/rays.hpp).  UNPINNED, owned definitions written from the libraries' documented behaviour: every byte of
+ * (csrc/hd.hpp).  UNPINNED, owned definitions written from the libraries' documented behaviour: every byte of
  * albumentations' and cv2's own output.  Stated differences: (a) cv2 rotates hue in 8-bit HSV with a 2-degree hue; here the
  * rotation is colorsys' HLS in f64 (a rotation keeps a pixel's channel maximum and minimum in both models, so they agree up to
  * cv2's quantisation), and one colour model serves ColorJitter and ISONoise; (b) ISONoise's hue noise is an Irwin-Hall sum of

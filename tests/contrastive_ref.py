@@ -147,6 +147,14 @@ def inputs(rng, B, S, M, D, Bn, sigma=1.0):
     return q, k, (rng.standard_normal((Bn, M, D)) * sigma).astype(f32)
 
 
+TREE_EDGES = (1, 256, 257, 65536, 65537)                  # REDUCE ORDER's level edges: one tree, two levels, three
+
+
+def tree_edge_inputs(rows):
+    """q, k, n of B S = rows rows with M = 1 and D = 4: the loss is a sum over `rows` leaves and little else."""
+    return inputs(np.random.default_rng(20261022 + rows), 1, rows, 1, 4, 1)
+
+
 def same(a, b) -> bool:
     a, b = np.asarray(a), np.asarray(b)
     return a.shape == b.shape and a.dtype == b.dtype == f32 and np.array_equal(a.view(np.uint32), b.view(np.uint32))

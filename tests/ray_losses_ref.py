@@ -262,6 +262,15 @@ def distortion_cases():
     return out
 
 
+TREE_EDGES = (1, 256, 257, 65536, 65537)                  # REDUCE ORDER's level edges: one tree, two levels, three
+
+
+def tree_edge_cases():
+    """name -> (lengths, weights): N rays at every level edge of REDUCE ORDER, P = 2 (a ray's value is w_0^2 / 3)."""
+    rng = np.random.default_rng(20261022)
+    return {f"N = {N}, P = 2": (fine_depths(rng, N, 2), march_weights(rng, N, 2)) for N in TREE_EDGES}
+
+
 UPSTREAMS = (1.0, -2.5, 0.0)
 RENDER_UPSTREAMS = ((1.0, 1.0), (-2.5, 0.0), (0.0, 3.0))
 

@@ -39,6 +39,16 @@ def test_host_equals_the_restatement(hip_lib, B, S, M, D, shared):
     assert (t >= 0).all() and (rows >= 0).all()
 
 
+@pytest.mark.parametrize("rows", cr.TREE_EDGES)
+def test_loss_host_at_the_level_edges_of_the_ordered_sum(hip_lib, rows):
+    """B S = 1, 256, 257, 65 536 and 65 537 leaves: below, at and above one tree of 256 and two levels of trees."""
+    q, k, n = cr.tree_edge_inputs(rows)
+    fwd = ops.contrastive_forward_host(q, k, n, 1e-3)
+    for name, a, b in zip(NAMES, fwd, cr.forward(q, k, n, 1e-3)):
+        assert same(a, b), name
+    assert np.isfinite(fwd[4]) and fwd[4] > 0
+
+
 @pytest.mark.parametrize("g", [1.0, -2.5, 0.0])
 def test_upstream_gradient(hip_lib, g):
     q, k, n = cr.inputs(np.random.default_rng(5), 2, 9, 70, 12, 2)

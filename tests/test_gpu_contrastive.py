@@ -57,6 +57,18 @@ def test_device_equals_host_over_S(cuda0, S):
     _check(cuda0, 2, S, 63, 12, 2, g=-2.5)
 
 
+@pytest.mark.parametrize("rows", cr.TREE_EDGES)
+def test_loss_at_the_level_edges_of_the_ordered_sum(cuda0, rows):
+    """B S = 1, 256, 257, 65 536 and 65 537 leaves (M = 1, D = 4): the device, the host build and the f64 tree of
+    tests/contrastive_ref.py give the same bits below, at and above one tree of 256 and two levels of trees."""
+    q, k, n = cr.tree_edge_inputs(rows)
+    want = cr.forward(q, k, n, 1e-3)
+    host = ops.contrastive_forward_host(q, k, n, 1e-3)
+    got = [x.cpu().numpy() for x in ops.contrastive_forward(_t(q, cuda0), _t(k, cuda0), _t(n, cuda0), 1e-3)]
+    for name, d, h, w in zip(NAMES, got, host, want):
+        assert same(d, h) and same(d, w) and same(h, w), (name, rows)
+
+
 @pytest.mark.parametrize("D", [1, 2, 4, 5, 12, 13, 16, 17, 32, 33, 64])
 def test_device_equals_host_over_D(cuda0, D):
     _check(cuda0, 2, 65, 130, D, 2, sigma=3.0 / np.sqrt(D))

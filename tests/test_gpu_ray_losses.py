@@ -76,6 +76,23 @@ def test_distortion_device_equals_host_at_the_shapes(cuda0, name):
     assert _distortion_agrees(*SHAPES[name], cuda0, upstreams=(-2.5,))
 
 
+EDGES = ref.tree_edge_cases()
+
+
+@pytest.mark.parametrize("name", list(EDGES))
+def test_distortion_at_the_level_edges_of_the_ordered_sum(cuda0, name):
+    """N = 1, 256, 257, 65 536 and 65 537 leaves (P = 2): the device, the host build and the f64 tree of
+    tests/ray_losses_ref.py give the same bits below, at and above one tree of 256 and two levels of trees."""
+    L, W = EDGES[name]
+    want_rays, want_loss = ref.distortion_forward(L, W)
+    rays_h, loss_h = ops.distortion_forward_host(L, W)
+    rays_d, loss_d = ops.distortion_forward(_dev(L, cuda0), _dev(W, cuda0))
+    rays_d, loss_d = rays_d.cpu().numpy(), loss_d.cpu().numpy()
+    assert ref.same(rays_d, rays_h) and ref.same(loss_d, loss_h)
+    assert ref.same(rays_d, want_rays) and ref.same(loss_d, want_loss)
+    assert ref.same(rays_h, want_rays) and ref.same(loss_h, want_loss)
+
+
 def test_a_row_alone_among_4097_and_beside_a_nan_row(cuda0):
     L, W = (a.copy() for a in SHAPES["N = 4097"])
     Ld, Wd = _dev(L, cuda0), _dev(W, cuda0)

@@ -52,6 +52,19 @@ def test_distortion_host_is_the_restatement(ops, name):
         assert not dw[:, -1].view(np.uint32).any()                                    # column P-1 is +0, NaN rows included
 
 
+EDGES = ref.tree_edge_cases()
+
+
+@pytest.mark.parametrize("name", list(EDGES))
+def test_distortion_host_at_the_level_edges_of_the_ordered_sum(ops, name):
+    """N = 1, 256, 257, 65 536 and 65 537 leaves: below, at and above one tree of 256 and two levels of trees."""
+    L, W = EDGES[name]
+    ray_loss, loss = ops.distortion_forward_host(L, W)
+    want_rays, want_loss = ref.distortion_forward(L, W)
+    assert ref.same(ray_loss, want_rays) and ref.same(loss, want_loss)
+    assert np.isfinite(loss) and loss > 0
+
+
 def test_two_samples_closed_form(ops):
     """P = 2: inter = 0 and intra = w_0^2 / 3, whatever the two ascending depths are."""
     L = np.array([[1.0, 4.0], [2.0, 2.5], [3.0, 7.0]], f32)

@@ -1,11 +1,11 @@
 // contrastive_host_check.cpp — csrc/contrastive.hpp as plain host code, for a sanitizer build:
 //     c++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all \
 //         tools/contrastive_host_check.cpp -o contrastive_host_check && ./contrastive_host_check
-// Drives forward_row, backward_row, backward_column and sum_rows over the shapes of the tests, with arrays of exactly the
+// Drives forward_row, backward_row, backward_column and isr::ordered_sum over the shapes of the tests, with arrays of exactly the
 // sizes the header asks for, and over the value cases: equal logits, a dominating positive, logits beyond the exponential's
 // cut, a NaN and an infinity.  Checks what can be checked without a second implementation: the softmax of a clean row sums
 // to 1 (ppos + sum_j p_ij, to 1e-5), t and row are not negative, dq + the k-term and dk follow the formulas to f32 accuracy
-// against an f64 evaluation, a NaN row is canonical NaN, sum_rows equals a plain f64 sum to 1e-12 relative, check_shape
+// against an f64 evaluation, a NaN row is canonical NaN, ordered_sum equals a plain f64 sum to 1e-12 relative, check_shape
 // refuses what the header says.  Then measures exp32 against the f64 exponential over [-104, 0]: every 997th f32 bit pattern
 // of the range, the error in units of the f32 ulp of the true value for results that are normal numbers (x >= -87), the
 // absolute error below.  Prints one line per case; exit status 0 = all hold.  The log of one such run is
@@ -67,8 +67,8 @@ void run(int S, int M, int D, float sigma, Kind kind) {
   }
   for (int s = 0; s < S; ++s)
     forward_row(&q[(size_t)s * D], &k[(size_t)s * D], n.data(), M, D, &m[s], &t[s], &pos[s], &row[s]);
-  std::vector<double> scratch((size_t)(S + kReduce - 1) / kReduce);
-  const double R = sum_rows(row.data(), S, scratch.data());
+  std::vector<double> scratch((size_t)(S + isr::kReduce - 1) / isr::kReduce);
+  const double R = isr::ordered_sum(row.data(), S, scratch.data());
   double plain = 0.0;
   for (int s = 0; s < S; ++s) plain += (double)row[s];
   const float c = grad_scale(-2.5f, 1e-3, S);
@@ -81,7 +81,7 @@ void run(int S, int M, int D, float sigma, Kind kind) {
   bool ok = true;
   const bool clean = kind <= kFar;
   int nans = 0;
-  for (int s = 0; s < S; ++s) nans += bits_of(row[s]) == kNanBits;
+  for (int s = 0; s < S; ++s) nans += bits_of(row[s]) == isr::kNanBits;
   if (clean) {
     ok = ok && nans == 0 && (R == plain || std::fabs(R - plain) <= 1e-12 * std::fabs(plain));
     for (int s = 0; s < S; ++s) {
@@ -105,9 +105,9 @@ void run(int S, int M, int D, float sigma, Kind kind) {
     if (kind == kDominant) ok = ok && row[0] == 0.f && t[0] == 0.f;
   }
   if (kind == kNan) {
-    ok = ok && nans == 1 && bits_of(row[S / 2]) == kNanBits && bits_of(m[S / 2]) == kNanBits && bits_of(dq[(size_t)(S / 2) * D]) == kNanBits;
-    for (int j = 0; j < M; ++j) ok = ok && bits_of(dn[(size_t)j * D]) == kNanBits;
-    ok = ok && bits_of(loss_value(R, 1e-3, S)) == kNanBits;
+    ok = ok && nans == 1 && bits_of(row[S / 2]) == isr::kNanBits && bits_of(m[S / 2]) == isr::kNanBits && bits_of(dq[(size_t)(S / 2) * D]) == isr::kNanBits;
+    for (int j = 0; j < M; ++j) ok = ok && bits_of(dn[(size_t)j * D]) == isr::kNanBits;
+    ok = ok && bits_of(loss_value(R, 1e-3, S)) == isr::kNanBits;
   }
   if (kind == kPosInf) ok = ok && nans == S;
   if (kind == kNegInf) ok = ok && nans == 0;
@@ -140,7 +140,7 @@ void measure_exp() {
   }
   const bool ok = worst < 1.0 && exp32(0.f) == 1.f && exp32(-0.f) == 1.f && worst_abs < 1.7e-38 &&
                   exp32(-std::numeric_limits<float>::infinity()) == 0.f &&
-                  bits_of(exp32(std::numeric_limits<float>::quiet_NaN())) == kNanBits;
+                  bits_of(exp32(std::numeric_limits<float>::quiet_NaN())) == isr::kNanBits;
   std::printf("exp32 over [-87, 0]: %ld arguments, largest error %.4f f32 ulp of the f64 exponential (at x = %.9g)\n", count, worst, worst_at);
   std::printf("exp32 over [-104, -87): %ld arguments, result 0 by the rule, largest absolute error %.3e   %s\n", below, worst_abs,
               ok ? "ok" : "FAILED");

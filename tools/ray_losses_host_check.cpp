@@ -1,12 +1,12 @@
 // ray_losses_host_check.cpp — csrc/ray_losses.hpp as plain host code, for a sanitizer build:
 //     c++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all \
 //         tools/ray_losses_host_check.cpp -o ray_losses_host_check && ./ray_losses_host_check
-// Drives distortion_ray, distortion_ray_backward, render_row, render_row_backward and reduce_all with arrays of exactly the sizes
+// Drives distortion_ray, distortion_ray_backward, render_row, render_row_backward and isr::ordered_sum with arrays of exactly the sizes
 // the header asks for, at the size edges (P = 2, 3, 64, 65, 128, 257, 1 024; ray counts around a reduction tree and two levels of
 // trees; F = 1, 3, 64; H = 1 and W = 1), and checks what can be checked without a second implementation: the loss against a plain
 // f64 evaluation of the reference's formula to f32 accuracy, the gradient against central differences of that evaluation, P = 2
 // in closed form, +0 in column P-1, a NaN row that is canonical NaN and alone, exact +0 where d = 0, the Huber value against
-// s (sqrt(1 + z^2) - 1) in long double, reduce_all against a plain sum, and the refusals of check_distortion and check_render.
+// s (sqrt(1 + z^2) - 1) in long double, ordered_sum against a plain sum, and the refusals of check_distortion and check_render.
 // Prints one line per case; exit status 0 = all hold.  The log of one such run is profiles/ray_losses_host_sanitizers.txt.
 #include <algorithm>
 #include <cmath>
@@ -95,7 +95,7 @@ void distortion_edges() {
   const double ray = distortion_ray(l.data(), w.data(), kMaxP);
   distortion_ray_backward(l.data(), w.data(), kMaxP, 1.0, dw.data());
   bool ok = ray != ray && bits_of(dw[kMaxP - 1]) == 0;
-  for (int i = 0; i + 1 < kMaxP; ++i) ok = ok && bits_of(dw[i]) == kNanBits;
+  for (int i = 0; i + 1 < kMaxP; ++i) ok = ok && bits_of(dw[i]) == isr::kNanBits;
   report("P = 1 024, all depths equal: NaN, canonical in every dweights but column P-1", ok);
   for (int i = 0; i < kMaxP; ++i) l[i] = 1.f + (float)i;
   std::fill(w.begin(), w.end(), 0.f);
@@ -106,7 +106,7 @@ void distortion_edges() {
   w[3] = std::numeric_limits<float>::quiet_NaN();
   distortion_ray_backward(l.data(), w.data(), 5, 1.0, dw.data());
   report("a NaN weight: a NaN ray, +0 in column P-1", distortion_ray(l.data(), w.data(), 5) != distortion_ray(l.data(), w.data(), 5) &&
-                                                       bits_of(dw[4]) == 0 && bits_of(dw[0]) == kNanBits);
+                                                       bits_of(dw[4]) == 0 && bits_of(dw[0]) == isr::kNanBits);
 }
 
 void reduction() {
@@ -115,9 +115,9 @@ void reduction() {
     std::vector<double> v((size_t)count);
     double plain = 0.0;
     for (auto& x : v) plain += (x = uni());
-    ok = ok && std::fabs(reduce_all(v.data(), count) - plain) <= 1e-12 * plain;
+    ok = ok && std::fabs(isr::ordered_sum(v.data(), count, v.data()) - plain) <= 1e-12 * plain;
   }
-  report("reduce_all over 1, 255, 256, 257, 65 536 and 65 537 values equals a plain sum to 1e-12", ok);
+  report("ordered_sum over 1, 255, 256, 257, 65 536 and 65 537 values equals a plain sum to 1e-12", ok);
 }
 
 void render(int B, int n, int F, int H, int W) {
@@ -161,7 +161,7 @@ void huber_edges() {
   bool ok = huber_value(0.f, 0.1) == 0.0 && huber_value(inf, 0.1) == (double)inf && huber_value(-inf, 0.1) == (double)inf;
   ok = ok && huber_value(nan, 0.1) != huber_value(nan, 0.1) && std::isfinite(huber_value(3.4e38f, 0.1)) && huber_value(1e-30f, 0.1) > 0.0;
   ok = ok && bits_of(huber_grad(0.f, 0.1, (double)nan)) == 0 && bits_of(huber_grad(-0.f, 0.1, 1.0)) == 0;
-  ok = ok && bits_of(huber_grad(nan, 0.1, 1.0)) == kNanBits && std::fabs(huber_grad(3e38f, 0.1, 1.0) - 1.f) <= 1e-6f;
+  ok = ok && bits_of(huber_grad(nan, 0.1, 1.0)) == isr::kNanBits && std::fabs(huber_grad(3e38f, 0.1, 1.0) - 1.f) <= 1e-6f;
   report("huber: d = 0, +-inf, NaN, 3.4e38, 1e-30; the gradient's +0 and its limit 1", ok);
 }
 

@@ -116,13 +116,13 @@ int check(const char* name, int mode, int B, int W, int H, int n, int P, float l
 int main() {
   int bad = 0;
   uint32_t w[4];
-  philox4x32_10(0, 0, 0, 0, 0, 0, w);
+  isr::philox4x32_10(0, 0, 0, 0, 0, 0, w);
   const bool kat0 = w[0] == 0x6627e8d5u && w[1] == 0xe169c58du && w[2] == 0xbc57ac4cu && w[3] == 0x9b00dbd8u;
-  philox4x32_10(~0u, ~0u, ~0u, ~0u, ~0u, ~0u, w);
+  isr::philox4x32_10(~0u, ~0u, ~0u, ~0u, ~0u, ~0u, w);
   const bool kat1 = w[0] == 0x408f276du && w[1] == 0x41c83b0eu && w[2] == 0xa20bc7c6u && w[3] == 0x6d5451fdu;
   std::printf("%-58s %s\n", "Philox4x32-10: Random123's known answers", kat0 && kat1 ? "ok" : "MISMATCH");
   bad += !(kat0 && kat1);
-  bad += !(unit_float(0xffffffffu) < 1.f && unit_float(0u) == 0.f);
+  bad += !(isr::unit_float(0xffffffffu) < 1.f && isr::unit_float(0u) == 0.f);
 
   for (int kind = 0; kind < 4; ++kind) {
     bad += check("grid 1x1", kGrid, 2, 1, 1, 0, 1, -1, 1, 0, 1, 1, kind);

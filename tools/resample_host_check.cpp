@@ -70,7 +70,7 @@ void run(int P, int n, int add, int det, Kind kind) {
       ok = ok && found;
     }
   int nans = 0;
-  for (float v : out) nans += float_bits(v) == kNanBits;
+  for (float v : out) nans += float_bits(v) == isr::kNanBits;
   const bool clean = kind <= kRepeated;
   if (clean) {
     ok = ok && nans == 0;
@@ -81,7 +81,7 @@ void run(int P, int n, int add, int det, Kind kind) {
   }
   if (kind == kNanWeight) {
     ok = ok && nans == n;
-    for (int s = 0; s < n; ++s) ok = ok && float_bits(out[out.size() - 1 - s]) == kNanBits;
+    for (int s = 0; s < n; ++s) ok = ok && float_bits(out[out.size() - 1 - s]) == isr::kNanBits;
   }
   resample_row(sp, ln.data(), w.data(), add, 18u, bins.data(), cdf.data(), keys.data(), again.data());
   bool equal = true;
