@@ -341,6 +341,16 @@ INGEST_SIGNATURES = {
     "isr_ingest_launch_floor": (_i, [_i, _i, _i, _i, _i, _vp]),
 }
 
+# include/isr_icp_plane.h (point-to-plane ICP with robust weights), bound the same way
+ICP_L2, ICP_HUBER, ICP_TUKEY = 0, 1, 2       # ISR_ICP_*
+ICP_PLANE_STATE_DOUBLES = 24
+_ICP_PLANE = [_vp, _sz, _i, _vp, _vp, _i, _i, _d, _i, _d, _d, _i, _d, _vp]      # src .. state
+ICP_PLANE_SIGNATURES = {
+    "isr_icp_point_to_plane_batch_workspace_bytes": (_sz, [_i, _i, _i]),
+    "isr_icp_point_to_plane_batch": (_i, [*_ICP_PLANE, _vp, _sz, _vp]),
+    "isr_icp_point_to_plane_batch_host": (_i, _ICP_PLANE),
+}
+
 
 def lib() -> C.CDLL:
     """Load libisr_hip.so (once).  Raises IsrError when it has not been built."""
@@ -361,7 +371,8 @@ def lib() -> C.CDLL:
                                **RAYS_SIGNATURES, **RADIANCE_SIGNATURES, **RESAMPLE_SIGNATURES,
                                **CONTRASTIVE_SIGNATURES, **FIELD_GRAD_SIGNATURES, **SAMPLE_GRAD_SIGNATURES,
                                **EA_GRAD_SIGNATURES, **RADIANCE_GRAD_SIGNATURES, **AUGMENT_SIGNATURES,
-                               **ADAM_SIGNATURES, **RAY_LOSSES_SIGNATURES, **COLOR_AUG_SIGNATURES, **INGEST_SIGNATURES}.items():
+                               **ADAM_SIGNATURES, **RAY_LOSSES_SIGNATURES, **COLOR_AUG_SIGNATURES, **INGEST_SIGNATURES,
+                               **ICP_PLANE_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

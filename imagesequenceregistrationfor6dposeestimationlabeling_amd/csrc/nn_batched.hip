@@ -1193,3 +1193,253 @@ extern "C" int isr_icp_point_to_point_batch(const float* src, size_t src_item_st
   ISR_CHECK_LAUNCH("icp batch kernels");
   return ISR_OK;
 }
+
+// ------------------------------------------------------------------------------- point-to-plane ICP
+// include/isr_icp_plane.h: the batched loop above with another estimator.  The searches are the very launches of
+// isr_icp_point_to_point_batch (nn_search_kernel<.., EXACT, .., ITEMS>, unchanged); the finalize is a sibling of
+// icp_finalize_update_kernel that gathers the winner's normal, forms the row of csrc/icp_plane.hpp and reduces its 31 sums
+// in the same fixed shape; the item's last workgroup solves the 6x6 system and composes T.  The arithmetic is icp_plane.hpp's
+// and nothing else, so that the host entry at the end of this file gives the same bits.
+#include "../../include/isr_icp_plane.h"
+#include "icp_plane.hpp"
+
+namespace {
+
+namespace ipl = isr::icp_plane;
+static_assert(ipl::kLanes == kIcpLanes && ipl::kStateDoubles == ISR_ICP_PLANE_STATE_DOUBLES && ipl::kL2 == ISR_ICP_L2 &&
+                  ipl::kHuber == ISR_ICP_HUBER && ipl::kTukey == ISR_ICP_TUKEY,
+              "csrc/icp_plane.hpp, include/isr_icp_plane.h and the point-to-point loop disagree");
+
+// The searches read an item's T from rows kIcpItemDoubles apart (their instantiation is point-to-point's): the loop keeps
+// its working T in the workspace in that layout (Tw) and mirrors it into the caller's (B, 24) state after every pass.
+__global__ void icp_plane_init_kernel(IcpState* st, double* __restrict__ state, double* __restrict__ Tw,
+                                      unsigned long long* packed, int32_t* amb, int Ns) {
+  const size_t b = blockIdx.y;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < Ns) { packed[b * Ns + i] = ~0ull; amb[b * Ns + i] = 0; }
+  if (i != 0) return;
+  st += b; state += b * ipl::kStateDoubles; Tw += b * kIcpItemDoubles;
+  st->prev_fit = 0; st->prev_rmse = 0; st->iter = 0; st->done = 0; st->ticket = 0;
+  for (int k = 0; k < 12; ++k) Tw[k] = state[k];
+  state[12] = 0; state[13] = 0; state[14] = 0; state[15] = 1;
+}
+
+// icp_finalize_update_kernel with the point-to-plane row.  blockIdx.y is the item; no workgroup waits for another: each
+// delivers its 31 block sums and takes a ticket, and the last one OF THE ITEM reduces, decides and updates.
+__global__ __launch_bounds__(kThreads) void icp_plane_finalize_update_kernel(
+    const float* __restrict__ src, int Ns, const float* __restrict__ tgt, const float* __restrict__ nrm, int Nt,
+    double threshold, unsigned long long* __restrict__ packed, int32_t* __restrict__ prev_idx, int32_t* __restrict__ amb,
+    double* __restrict__ part_sums, int max_iter, double rel_fitness, double rel_rmse, int kernel, double kw,
+    double* __restrict__ Tw, IcpState* __restrict__ st, double* __restrict__ state, size_t src_item_stride) {
+  __shared__ double red[kThreads / 64][ipl::kSums];
+  __shared__ double part[ipl::kSums][kIcpLanes];
+  __shared__ double tot[ipl::kSums];
+  __shared__ int last;
+  __shared__ int nflag, flist[kThreads];
+  __shared__ double wd[4][kThreads / 64];
+  __shared__ int wi[4][kThreads / 64];
+  {
+    const size_t b = blockIdx.y;
+    src += b * src_item_stride;
+    packed += b * Ns; prev_idx += b * Ns; amb += b * Ns;
+    part_sums += b * gridDim.x * ipl::kSums;
+    st += b;
+    Tw += b * kIcpItemDoubles; state += b * ipl::kStateDoubles;
+  }
+  if (st->done) return;
+  const int tid = threadIdx.x;
+  const int qi = blockIdx.x * kThreads + tid;
+  // ---- near ties the search flagged: decided over all targets in f64, exactly as icp_finalize_update_kernel does (the
+  // same code: that kernel keeps its own copy so that its instructions stay what they are)
+  if (tid == 0) nflag = 0;
+  __syncthreads();
+  if (qi < Ns && amb[qi]) {
+    amb[qi] = 0;
+    flist[atomicAdd(&nflag, 1)] = qi;
+  }
+  __syncthreads();
+  const int nf = nflag;                             // block-uniform
+  constexpr int kRes = 4;
+  for (int f0 = 0; f0 < nf; f0 += kRes) {
+    double qx[kRes], qy[kRes], qz[kRes], bd[kRes];
+    int bi[kRes];
+#pragma unroll
+    for (int k = 0; k < kRes; ++k) {
+      const int pq = flist[min(f0 + k, nf - 1)];
+      xform64(Tw, src[3 * (size_t)pq], src[3 * (size_t)pq + 1], src[3 * (size_t)pq + 2], qx[k], qy[k], qz[k]);
+      bd[k] = __builtin_inf();
+      bi[k] = 0x7fffffff;
+    }
+#pragma unroll 4
+    for (int j = tid; j < Nt; j += kThreads) {
+      const double tx = tgt[3 * (size_t)j], ty = tgt[3 * (size_t)j + 1], tz = tgt[3 * (size_t)j + 2];
+#pragma unroll
+      for (int k = 0; k < kRes; ++k) {
+        const double ex = qx[k] - tx, ey = qy[k] - ty, ez = qz[k] - tz;
+        const double s2 = fma(ez, ez, fma(ey, ey, ex * ex));
+        if (s2 < bd[k]) { bd[k] = s2; bi[k] = j; }  // ascending j per thread: ties keep the lower index
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kRes; ++k) {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        const double od = __shfl_xor(bd[k], off, 64);
+        const int oi = __shfl_xor(bi[k], off, 64);
+        if (od < bd[k] || (od == bd[k] && oi < bi[k])) { bd[k] = od; bi[k] = oi; }
+      }
+      if ((tid & 63) == 0) { wd[k][tid >> 6] = bd[k]; wi[k][tid >> 6] = bi[k]; }
+    }
+    __syncthreads();
+    if (tid < kRes && f0 + tid < nf) {
+      double d = wd[tid][0];
+      int i = wi[tid][0];
+      for (int w = 1; w < kThreads / 64; ++w)
+        if (wd[tid][w] < d || (wd[tid][w] == d && wi[tid][w] < i)) { d = wd[tid][w]; i = wi[tid][w]; }
+      packed[flist[f0 + tid]] = ((unsigned long long)__float_as_uint((float)d) << 32) | (unsigned int)i;
+    }
+    __syncthreads();
+  }
+  // ---- the row of this thread's source point (zeros for no neighbour, a pair beyond the radius, a row past Ns)
+  double v[ipl::kSums];
+#pragma unroll
+  for (int k = 0; k < ipl::kSums; ++k) v[k] = 0.0;
+  if (qi < Ns) {
+    const unsigned long long pk = packed[qi];
+    packed[qi] = ~0ull;
+    prev_idx[qi] = pk != ~0ull ? (int)(unsigned int)pk : -1;     // the next pass starts from this neighbour
+    if (pk != ~0ull) {
+      const size_t bi = (unsigned int)pk;           // < Nt: the search posts indices of the target only
+      double p[3];
+      ipl::xform(Tw, src[3 * (size_t)qi], src[3 * (size_t)qi + 1], src[3 * (size_t)qi + 2], p);
+      const double t[3] = {tgt[3 * bi], tgt[3 * bi + 1], tgt[3 * bi + 2]};
+      const double nt[3] = {nrm[3 * bi], nrm[3 * bi + 1], nrm[3 * bi + 2]};
+      ipl::row(p, t, nt, threshold, kernel, kw, v);
+    }
+  }
+  // ---- 31 sums, one wave tree each (a sum's 64 values cross lanes in registers; LDS sees four doubles per sum)
+  const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+  for (int k = 0; k < ipl::kSums; ++k) {
+    const double s = isr::wave_sum_down(v[k]);
+    if (lane == 0) red[wave][k] = s;
+  }
+  __syncthreads();
+  if (tid < ipl::kSums) part_sums[(size_t)blockIdx.x * ipl::kSums + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+  __threadfence();                                  // the block's sums are visible device-wide ...
+  __syncthreads();
+  if (tid == 0) last = (atomicAdd(&st->ticket, 1) == (int)gridDim.x - 1);   // ... before its ticket is
+  __syncthreads();
+  if (!last) return;                                // block-uniform
+  __threadfence();
+  if (tid == 0) st->ticket = 0;
+  // ---- the item's last workgroup: blocks -> lanes -> sums in icp_reduce_and_update's order, then the rule
+  const int nblk = gridDim.x;
+  for (int idx = tid; idx < ipl::kSums * kIcpLanes; idx += kThreads) {
+    const int k = idx / kIcpLanes, l = idx % kIcpLanes;
+    double s = 0.0;
+    for (int i = l; i < nblk; i += kIcpLanes) s += part_sums[(size_t)i * ipl::kSums + k];
+    part[k][l] = s;
+  }
+  __syncthreads();
+  if (tid < ipl::kSums) {
+    double s = 0.0;
+    for (int l = 0; l < kIcpLanes; ++l) s += part[tid][l];
+    tot[tid] = s;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  double sums[ipl::kSums];
+#pragma unroll
+  for (int k = 0; k < ipl::kSums; ++k) sums[k] = tot[k];
+  ipl::Loop lp{st->prev_fit, st->prev_rmse, st->iter, st->done};
+  double T[12], out[8];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) T[k] = Tw[k];
+  ipl::finish_pass(sums, Ns, max_iter, rel_fitness, rel_rmse, T, &lp, out);
+#pragma unroll
+  for (int k = 0; k < 12; ++k) { Tw[k] = T[k]; state[k] = T[k]; }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) state[16 + k] = out[k];
+  st->prev_fit = lp.prev_fit; st->prev_rmse = lp.prev_rmse; st->iter = lp.iter;
+  __threadfence();
+  st->done = lp.done;
+}
+
+}  // namespace
+
+extern "C" size_t isr_icp_point_to_plane_batch_workspace_bytes(int Ns, int Nt, int B) {
+  if (Ns <= 0 || Nt <= 0 || B <= 0) return 0;
+  const NNPlan p = make_plan(Ns, Nt, B, true);
+  return isr::align_up((size_t)B * p.fblocks * ipl::kSums * sizeof(double), 256) + isr::align_up((size_t)B * sizeof(IcpState), 256) +
+         isr::align_up((size_t)B * kIcpItemDoubles * sizeof(double), 256) + isr::align_up((size_t)B * Ns * 8, 256) +
+         2 * isr::align_up((size_t)B * Ns * 4, 256) + isr::align_up((size_t)((Nt + kTile - 1) / kTile) * 6 * sizeof(float), 256) + 2048;
+}
+
+extern "C" int isr_icp_point_to_plane_batch(const float* src, size_t src_item_stride, int Ns, const float* tgt,
+                                            const float* tgt_normals, int Nt, int B, double threshold, int max_iter,
+                                            double rel_fitness, double rel_rmse, int kernel, double k, double* state, void* ws,
+                                            size_t ws_bytes, isr_stream_t stream_) {
+  if (const char* why = ipl::refuse(src, tgt, tgt_normals, state, src_item_stride, Ns, Nt, B, threshold, max_iter, kernel, k)) {
+    isr::set_error("isr_icp_point_to_plane_batch: %s (Ns=%d Nt=%d B=%d threshold=%g max_iter=%d kernel=%d k=%g)", why, Ns, Nt, B,
+                   threshold, max_iter, kernel, k);
+    return ISR_ERR_ARG;
+  }
+  if (B == 0) return ISR_OK;
+  if (!ws || ws_bytes < isr_icp_point_to_plane_batch_workspace_bytes(Ns, Nt, B)) {
+    isr::set_error("isr_icp_point_to_plane_batch: workspace %zu < %zu", ws_bytes,
+                   isr_icp_point_to_plane_batch_workspace_bytes(Ns, Nt, B));
+    return ISR_ERR_WORKSPACE;
+  }
+  hipStream_t stream = isr::as_stream(stream_);
+  const NNPlan p = make_plan(Ns, Nt, B, true);      // the plan of isr_icp_point_to_point_batch
+  isr::Workspace w(ws, ws_bytes);
+  double* part_sums = w.take<double>((size_t)B * p.fblocks * ipl::kSums);
+  IcpState* st = w.take<IcpState>(B);
+  double* Tw = w.take<double>((size_t)B * kIcpItemDoubles);
+  unsigned long long* packed = w.take<unsigned long long>((size_t)B * Ns);
+  int32_t* prev_idx = w.take<int32_t>((size_t)B * Ns);
+  int32_t* amb = w.take<int32_t>((size_t)B * Ns);
+  float* t2_bound = w.take<float>(1);
+  float* tile_box = w.take<float>((size_t)((Nt + kTile - 1) / kTile) * 6);
+  const bool warm = isr::tuning(ISR_TUNE_ICP_WARM) != 0;
+  icp_plane_init_kernel<<<dim3((Ns + kThreads - 1) / kThreads, B), kThreads, 0, stream>>>(st, state, Tw, packed, amb, Ns);
+  cloud_r2max_kernel<<<1, kThreads, 0, stream>>>(tgt, Nt, t2_bound);
+  const float cull_r2 = (float)(threshold * threshold * 1.0001 + 1e-6);
+  if (ISR_ICP_CULL) tile_box_kernel<<<(Nt + kTile - 1) / kTile, 256, 0, stream>>>(tgt, Nt, tile_box);
+  const dim3 grid(p.qblocks, p.nsplit, B);
+  for (int it = 0; it <= max_iter; ++it) {
+    const int32_t* w_idx = (it > 0 && warm) ? prev_idx : nullptr;
+    launch_search(p, grid, stream, src, Ns, tgt, Nt, Tw, nullptr, nullptr, nullptr, &st->done, nullptr, packed, w_idx, amb,
+                  t2_bound, ISR_ICP_CULL ? tile_box : nullptr, cull_r2, true, src_item_stride);
+    icp_plane_finalize_update_kernel<<<dim3(p.fblocks, B), kThreads, 0, stream>>>(
+        src, Ns, tgt, tgt_normals, Nt, threshold, packed, prev_idx, amb, part_sums, max_iter, rel_fitness, rel_rmse, kernel, k, Tw,
+        st, state, src_item_stride);
+  }
+  ISR_CHECK_LAUNCH("icp plane kernels");
+  return ISR_OK;
+}
+
+// The same loop as host code over HOST pointers (csrc/icp_plane.hpp): the tests' reference, and the entry of CPU users.
+extern "C" int isr_icp_point_to_plane_batch_host(const float* src, size_t src_item_stride, int Ns, const float* tgt,
+                                                 const float* tgt_normals, int Nt, int B, double threshold, int max_iter,
+                                                 double rel_fitness, double rel_rmse, int kernel, double k, double* state) {
+  if (const char* why = ipl::refuse(src, tgt, tgt_normals, state, src_item_stride, Ns, Nt, B, threshold, max_iter, kernel, k)) {
+    isr::set_error("isr_icp_point_to_plane_batch_host: %s (Ns=%d Nt=%d B=%d threshold=%g max_iter=%d kernel=%d k=%g)", why, Ns, Nt,
+                   B, threshold, max_iter, kernel, k);
+    return ISR_ERR_ARG;
+  }
+  std::vector<double> block_sums((size_t)((Ns + 255) / 256) * ipl::kSums);
+  std::vector<int> nearest(Ns);
+  for (int b = 0; b < B; ++b) {
+    const float* s = src + (size_t)b * src_item_stride;
+    ipl::host_item(s, Ns, tgt, tgt_normals, Nt, threshold, max_iter, rel_fitness, rel_rmse, kernel, k,
+                   state + (size_t)b * ipl::kStateDoubles, block_sums.data(), nearest.data(), [&](const double* T, int* out) {
+                     isr::parallel_rows((Ns + 63) / 64, 4, [&](long c) {
+                       const long i0 = c * 64, i1 = i0 + 64 < Ns ? i0 + 64 : Ns;
+                       ipl::host_search(T, s, tgt, Nt, i0, i1, out);
+                     });
+                   });
+  }
+  return ISR_OK;
+}

@@ -197,6 +197,75 @@ def icp_point_to_point_batch(sources: torch.Tensor, target: torch.Tensor, state:
     return state
 
 
+ICP_KERNELS = {"l2": _capi.ICP_L2, "huber": _capi.ICP_HUBER, "tukey": _capi.ICP_TUKEY}
+
+
+def _icp_plane_args(name, sources, target, normals, state, kernel, check_finite, xp):
+    """The shape, dtype and value checks both point-to-plane wrappers share -> (B, Ns, Nt, stride, kernel id)."""
+    f32, f64 = (torch.float32, torch.float64) if xp is torch else (np.float32, np.float64)
+    contiguous = (lambda a: a.is_contiguous()) if xp is torch else (lambda a: a.flags.c_contiguous)
+    if any(a.dtype != f32 or not contiguous(a) for a in (sources, target, normals)):
+        raise ValueError(f"{name}: sources, target and target_normals must be contiguous float32")
+    if state.dtype != f64 or state.ndim != 2 or state.shape[1] != _capi.ICP_PLANE_STATE_DOUBLES or not contiguous(state):
+        raise ValueError(f"{name}: state must be contiguous (B,24) float64, got {tuple(state.shape)} {state.dtype}")
+    if target.ndim != 2 or target.shape[1] != 3 or sources.ndim not in (2, 3) or sources.shape[-1] != 3:
+        raise ValueError(f"{name}: sources {tuple(sources.shape)} must be (Ns,3) or (B,Ns,3), target {tuple(target.shape)} (Nt,3)")
+    if tuple(normals.shape) != tuple(target.shape):
+        raise ValueError(f"{name}: target_normals {tuple(normals.shape)} must have the target's shape {tuple(target.shape)}")
+    B, Ns, Nt = state.shape[0], sources.shape[-2], target.shape[0]
+    if sources.ndim == 3 and sources.shape[0] != B:
+        raise ValueError(f"{name}: sources {tuple(sources.shape)} and state {tuple(state.shape)} disagree on B")
+    if kernel not in ICP_KERNELS:
+        raise ValueError(f"{name}: kernel {kernel!r} must be one of {sorted(ICP_KERNELS)}")
+    if check_finite:
+        for what, a in (("sources", sources), ("target", target), ("target_normals", normals), ("state[:, :12]", state[:, :12])):
+            if not bool(xp.isfinite(a).all()):
+                raise ValueError(f"{name}: non-finite values in {what} (finite inputs are a precondition)")
+    return B, Ns, Nt, (3 * Ns if sources.ndim == 3 else 0), ICP_KERNELS[kernel]
+
+
+def icp_point_to_plane_batch(sources: torch.Tensor, target: torch.Tensor, target_normals: torch.Tensor, state: torch.Tensor,
+                             threshold: float, max_iter: int = 30, rel_fitness: float = 1e-6, rel_rmse: float = 1e-6,
+                             kernel: str = "tukey", k: float = 1.0, check_finite: bool = False) -> torch.Tensor:
+    """isr_icp_point_to_plane_batch (include/isr_icp_plane.h states the rule): B point-to-plane ICP loops with robust weights
+    against one target in one call, in place on `state`.  sources (Ns,3) f32 — one source, B starts — or (B,Ns,3); target and
+    target_normals (Nt,3) f32; state (B,24) f64 contiguous, per item T 4x4 row-major (start in, result out) | fitness,
+    inlier_rmse, iterations, correspondences | status, sum w r^2, 0, 0.  kernel: "l2", "huber" or "tukey" with scale k.
+    Nothing synchronises but check_finite, which refuses non-finite inputs.  Returns `state`."""
+    dev = require_cuda(sources, target, target_normals, state)
+    B, Ns, Nt, stride, kid = _icp_plane_args("icp_point_to_plane_batch", sources, target, target_normals, state, kernel,
+                                             check_finite, torch)
+    if B == 0:                  # nothing to do (an empty tensor has no address to hand over)
+        return state
+    L = lib()
+    ws = workspace(dev, L.isr_icp_point_to_plane_batch_workspace_bytes(Ns, Nt, B), "icp")
+    with torch.cuda.device(dev), _timed("icp_plane_batch", float(B) * Ns * Nt * (max_iter + 1)):
+        rc = L.isr_icp_point_to_plane_batch(ptr(sources), stride, Ns, ptr(target), ptr(target_normals), Nt, B, float(threshold),
+                                            int(max_iter), float(rel_fitness), float(rel_rmse), kid, float(k), ptr(state),
+                                            ptr(ws), ws.numel(), current_stream(dev))
+    check(rc, "isr_icp_point_to_plane_batch")
+    return state
+
+
+def icp_point_to_plane_batch_host(sources, target, target_normals, state, threshold: float, max_iter: int = 30,
+                                  rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, kernel: str = "tukey", k: float = 1.0,
+                                  check_finite: bool = False):
+    """isr_icp_point_to_plane_batch_host: the same loop as host code with an f64 brute-force search, NumPy arrays of the
+    shapes icp_point_to_plane_batch takes, in place on `state`: the same bits.  For tests and CPU users."""
+    for a in (sources, target, target_normals, state):
+        if not isinstance(a, np.ndarray):
+            raise ValueError("icp_point_to_plane_batch_host: NumPy arrays only (device tensors go to icp_point_to_plane_batch)")
+    B, Ns, Nt, stride, kid = _icp_plane_args("icp_point_to_plane_batch_host", sources, target, target_normals, state, kernel,
+                                             check_finite, np)
+    if B == 0:
+        return state
+    hp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    check(lib().isr_icp_point_to_plane_batch_host(hp(sources), stride, Ns, hp(target), hp(target_normals), Nt, B, float(threshold),
+                                                  int(max_iter), float(rel_fitness), float(rel_rmse), kid, float(k), hp(state)),
+          "isr_icp_point_to_plane_batch_host")
+    return state
+
+
 @dataclass
 class DistField:
     """Distances from the cell centres of a uniform grid to a (static) cloud: what isr_adds_bounds reads."""

@@ -452,6 +452,77 @@ def icp_point_to_point_batch(sources, target, threshold, inits=None, max_iter=30
     return h[:, :16].reshape(-1, 4, 4).copy(), h[:, 16].copy(), h[:, 17].copy(), h[:, 18].astype(np.int64)
 
 
+ICP_PLANE_STATUS = ("converged", "max_iter", "n<6", "singular")       # state[20] of isr_icp_point_to_plane_batch
+
+
+def icp_plane_batch_state(sources, target, threshold, inits=None, target_normals=None, normals_k=16, kernel="tukey", k=1.0,
+                          max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6, spatial_order=True, check_finite=False) -> np.ndarray:
+    """icp_point_to_plane_batch's work; returns the (B,24) f64 state block of isr_icp_point_to_plane_batch on the host — per
+    item T (16) | fitness, inlier_rmse, iterations, correspondences | status, sum w r^2, 0, 0."""
+    what = "icp_point_to_plane_batch"
+    src, tgt = _batch_clouds(sources, target, what)
+    if inits is None:
+        B = src.shape[0] if src.ndim == 3 else 1
+        T0 = np.broadcast_to(np.eye(4), (B, 4, 4))
+    else:
+        T0 = inits.detach().cpu().numpy() if isinstance(inits, torch.Tensor) else np.asarray(inits, np.float64)
+        if T0.ndim != 3 or T0.shape[1:] != (4, 4):
+            raise ValueError(f"{what}: inits {tuple(T0.shape)} must be (B,4,4)")
+        B = T0.shape[0]
+    if src.ndim == 3 and src.shape[0] != B:
+        raise ValueError(f"{what}: sources {tuple(src.shape)} and inits {tuple(T0.shape)} disagree on B")
+    if B == 0:
+        return np.zeros((0, 24))
+    if target_normals is None:
+        # once per call, on the device; the estimator does not read a normal's sign, so none is chosen
+        from . import sampling
+        nrm = sampling.estimate_pointcloud_normals(tgt, neighborhood_size=int(normals_k), disambiguate_directions=False)
+    else:
+        nrm = _dev_strict(target_normals, torch.float32, what)
+        if tuple(nrm.shape) != tuple(tgt.shape):
+            raise ValueError(f"{what}: target_normals {tuple(nrm.shape)} must have the target's shape {tuple(tgt.shape)}")
+    nrm = nrm.contiguous()
+    if spatial_order and min(src.shape[-2], tgt.shape[0]) > MORTON_MIN_ROWS:
+        order = morton_order(tgt)
+        tgt, nrm = tgt[order].contiguous(), nrm[order].contiguous()        # a normal travels with its point
+        if src.ndim == 2:
+            src = src[morton_order(src)].contiguous()
+        else:
+            src = torch.gather(src, 1, morton_order_batch(src)[:, :, None].expand(-1, -1, 3)).contiguous()
+    state = torch.empty((B, 24), dtype=torch.float64, device=src.device)
+    state[:, :16] = torch.from_numpy(np.array(T0, np.float64).reshape(B, 16)).to(src.device)
+    ops.icp_point_to_plane_batch(src, tgt, nrm, state, threshold, max_iter, rel_fitness, rel_rmse, kernel, k, check_finite)
+    return state.cpu().numpy()
+
+
+def icp_point_to_plane_batch(sources, target, threshold, inits=None, target_normals=None, normals_k=16, kernel="tukey", k=1.0,
+                             max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6, spatial_order=True, check_finite=False):
+    """open3d registration_icp(source, target, threshold, init, TransformationEstimationPointToPlane(kernel)) for B starts in
+    one call (isr_icp_point_to_plane_batch; include/isr_icp_plane.h states the rule and what of it is unpinned).  The
+    arguments are icp_point_to_point_batch's, plus: target_normals (Nt,3), as given (not normalised; their sign does not
+    matter) — None estimates them once on the device with sampling.estimate_pointcloud_normals over normals_k neighbours;
+    kernel "l2" | "huber" | "tukey" with scale k on the plane residual.  Returns icp_point_to_point_batch's tuple plus the
+    status: (T (B,4,4) f64, fitness, inlier_rmse (B,) f64, iterations (B,) int64, status (B,) int64 — an index into
+    ICP_PLANE_STATUS).  With spatial_order the normals follow the target's Morton permutation."""
+    h = icp_plane_batch_state(sources, target, threshold, inits, target_normals, normals_k, kernel, k, max_iter, rel_fitness,
+                              rel_rmse, spatial_order, check_finite)
+    return (h[:, :16].reshape(-1, 4, 4).copy(), h[:, 16].copy(), h[:, 17].copy(), h[:, 18].astype(np.int64),
+            h[:, 20].astype(np.int64))
+
+
+def icp_point_to_plane(source, target, threshold, init=None, target_normals=None, normals_k=16, kernel="tukey", k=1.0,
+                       max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6, spatial_order=True, check_finite=False):
+    """icp_point_to_plane_batch for one start: (T (4,4) f64, fitness, inlier_rmse, status) — icp_point_to_point's tuple plus
+    the status.  icp.py:101-103 with the estimator changed."""
+    src = source if isinstance(source, torch.Tensor) else np.asarray(source)
+    if src.ndim != 2:
+        raise ValueError(f"icp_point_to_plane: source {tuple(src.shape)} must be (Ns,3)")
+    T0 = None if init is None else np.asarray(init, np.float64).reshape(1, 4, 4)
+    T, fit, rmse, _, status = icp_point_to_plane_batch(src, target, threshold, T0, target_normals, normals_k, kernel, k, max_iter,
+                                                       rel_fitness, rel_rmse, spatial_order, check_finite)
+    return T[0], float(fit[0]), float(rmse[0]), int(status[0])
+
+
 def final_chamfer_batch(sources, target, Ts, cad_points):
     """final_chamfer (icp.py:110-117) for B transforms at once -> (B,) f64 NumPy, one device->host copy.
     sources (Ns,3), one cloud under B transforms: four isr_nn_batched calls for the whole batch (source -> CAD and CAD ->

@@ -658,7 +658,8 @@ def pick_refined(fitness, inlier_rmse, n_inliers, chamfer=None):
     return best
 
 
-def refine_top_choices(upper, lower, R_gt, t_gt, R_pred, t_pred, choices, threshold=20.0, cad_points=None, **icp_kw):
+def refine_top_choices(upper, lower, R_gt, t_gt, R_pred, t_pred, choices, threshold=20.0, cad_points=None,
+                       estimation="point_to_point", target_normals=None, kernel="tukey", k=1.0, **icp_kw):
     """icp.py:37-117 for EVERY image listed in `choices` (the lines of top_50_choices.txt) instead of the first.
     Per choice i: source_i = (upper @ R_gt[i].T + t_gt[i]).astype(float32), formed in f64 on the host (icp.py:68); start
     init_i = inv([R_pred[i] | t_pred[i]]) (icp.py:88-92); target = lower.  One registration.icp_point_to_point_batch for all
@@ -666,10 +667,15 @@ def refine_top_choices(upper, lower, R_gt, t_gt, R_pred, t_pred, choices, thresh
     A choice whose predicted pose is a failure (formats.is_failure, or non-finite) is not run: NaN results, iterations -1,
     never best.  Returns a dict: choices (k,) int64, T (k,4,4), fitness, inlier_rmse (k,) f64, iterations (k,) int64,
     chamfer (k,) f64 or None, best (position in choices, pick_refined's rule; None when every choice failed) and
-    image_id (choices[best] or None).  choices[0]'s numbers are what icp.py computes today."""
+    image_id (choices[best] or None).  choices[0]'s numbers are what icp.py computes today.
+    estimation="point_to_plane" runs registration.icp_point_to_plane_batch instead (target_normals: the lower model's,
+    None = estimated on the device; kernel and k: the robust weight) and adds "status" (k,) int64, -1 for a choice not
+    run; the default, "point_to_point", is unchanged and takes none of the three."""
     from . import formats
+    if estimation not in ("point_to_point", "point_to_plane"):
+        raise ValueError(f"refine_top_choices: estimation {estimation!r} must be 'point_to_point' or 'point_to_plane'")
     choices = np.asarray(choices, np.int64).reshape(-1)
-    k = len(choices)
+    weight_k, k = k, len(choices)
     up = np.asarray(upper, np.float64)
     run, srcs, inits = [], [], []
     for pos, i in enumerate(choices):
@@ -685,10 +691,16 @@ def refine_top_choices(upper, lower, R_gt, t_gt, R_pred, t_pred, choices, thresh
     out = {"choices": choices, "T": np.full((k, 4, 4), np.nan), "fitness": np.full(k, np.nan),
            "inlier_rmse": np.full(k, np.nan), "iterations": np.full(k, -1, np.int64),
            "chamfer": None if cad_points is None else np.full(k, np.nan), "best": None, "image_id": None}
+    if estimation == "point_to_plane":
+        out["status"] = np.full(k, -1, np.int64)
     if not run:
         return out
     srcs = np.stack(srcs)
-    T, fit, rmse, iters = registration.icp_point_to_point_batch(srcs, lower, threshold, np.stack(inits), **icp_kw)
+    if estimation == "point_to_plane":
+        T, fit, rmse, iters, out["status"][run] = registration.icp_point_to_plane_batch(
+            srcs, lower, threshold, np.stack(inits), target_normals, kernel=kernel, k=weight_k, **icp_kw)
+    else:
+        T, fit, rmse, iters = registration.icp_point_to_point_batch(srcs, lower, threshold, np.stack(inits), **icp_kw)
     out["T"][run], out["fitness"][run], out["inlier_rmse"][run], out["iterations"][run] = T, fit, rmse, iters
     if cad_points is not None:
         out["chamfer"][run] = registration.final_chamfer_batch(srcs, lower, T, cad_points)
