@@ -6,29 +6,21 @@
 //     sine layer:    s_j = omega * cos32(a_j) (one f32 multiply),  g_j = u_j * s_j (one f32 multiply)
 //     linear layer:  g_j = u_j
 //     u_{l-1}[k] = acc after  acc = fmaf(W_l[j,k], g_j, acc)  for j ascending from acc = +0      (not below layer 0)
-// and over the N points   dW_l[j,k] = sum_n g_l[n,j] h_{l-1}[n,k],   db_l[j] = sum_n g_l[n,j]   in THIS order (blocked_sum):
-// the points are cut into consecutive blocks of kGradChain; inside a block the sum is the f32 chain acc = fmaf(g, h, acc) for n
-// ascending from +0 (db: h = 1); the block sums are added in block order in f64 and rounded to f32 once.  So a gradient is a
-// function of the inputs and N alone: no float atomics, nothing depends on a grid, a slab or a stream.
-// v_mfma_f32_32x32x2_f32 is the k-ordered fmaf chain (field_tile.hpp), so u_{l-1} is a tile layer over the TRANSPOSED weights
-// from a zero accumulator, and a block sum of dW is a matrix-core product whose k index is the point.
+// and over the N points   dW_l[j,k] = sum_n g_l[n,j] h_{l-1}[n,k],   db_l[j] = sum_n g_l[n,j]   in the order of grad_sums.hpp, a bias
+// by the f32 chain of ones.  u_{l-1} is a tile layer over the TRANSPOSED weights from a zero accumulator (field_tile.hpp).
 //
 // The transposed pack: 64 zero header words, then for every layer l >= 1 the weights W_l^T as a layer with in = O_l rounded up
 // to 32 (matrix-core order; a layer with K_l < 32 is row-major with in = O_l) and out = K_l, zero padded, and a zero bias.
 #pragma once
 #include "field_mlp.hpp"
+#include "grad_sums.hpp"
 
 namespace isr {
 namespace field {
 
-// Points per f32 chain of a weight sum: the tile.  Against torch autograd in f64 at 4 096 points the worst dW_l / db_l of the
-// tests' fields lies at 2.5 x torch-f32's own deviation with chains of 64, 3.2 x with 128 and 4.9 x with 256 (a db of seven
-// entries, which torch sums pairwise): 64 keeps the project's 4 x margin with room.
-constexpr int kGradChain = 64;
-// Points whose activations the workspace holds at a time, at most: 256 tiles, a workgroup for every CU (measured: two slabs
-// of 16 384 take 0.69 ms where one of 32 768, two workgroups a CU, takes 0.74 ms and four of 8 192 take 1.02 ms).  Their block
-// sums are formed and added kGradBatch points at a time.
-constexpr int kGradSlab = 16384;
+using grad::kGradChain;
+using grad::kGradSlab;
+// Points whose block sums are formed and added at a time (grad_sums.hpp).
 constexpr int kGradBatch = 8192;
 
 // cos(a) for an f32 a: sin32's reduction and kernels, the quadrant taken in f64, one rounding to f32.  cos32(+-0) = 1; NaN
@@ -130,36 +122,6 @@ inline void point_grads(const Layout& lay, const void* pack, const float* const*
     }
     for (int k = 0; k < L.K; ++k) u[k] = v[k];
   }
-}
-
-// sum_n g[n gs] * h[n hs] over N points in the order of the rule (h == nullptr: every h is 1).
-ISR_HD float blocked_sum(const float* g, long gs, const float* h, long hs, long N) {
-  double total = 0.0;
-  for (long n0 = 0; n0 < N; n0 += kGradChain) {
-    const long n1 = n0 + kGradChain < N ? n0 + kGradChain : N;
-    float acc = 0.f;
-    for (long n = n0; n < n1; ++n) acc = fmaf(g[n * gs], h ? h[n * hs] : 1.f, acc);
-    total += (double)acc;
-  }
-  return (float)total;
-}
-
-// Host: out[k] = blocked_sum(g, gs, H + k, K, N) for every k < K (K <= kMaxWidth), the points walked once: the same chains.
-inline void blocked_row(const float* g, long gs, const float* H, int K, long N, float* out) {
-  double total[kMaxWidth];
-  float acc[kMaxWidth];
-  for (int k = 0; k < K; ++k) total[k] = 0.0;
-  for (long n0 = 0; n0 < N; n0 += kGradChain) {
-    const long n1 = n0 + kGradChain < N ? n0 + kGradChain : N;
-    for (int k = 0; k < K; ++k) acc[k] = 0.f;
-    for (long n = n0; n < n1; ++n) {
-      const float gv = g[n * gs];
-      const float* h = H + (size_t)n * K;
-      for (int k = 0; k < K; ++k) acc[k] = fmaf(gv, h[k], acc[k]);
-    }
-    for (int k = 0; k < K; ++k) total[k] += (double)acc[k];
-  }
-  for (int k = 0; k < K; ++k) out[k] = (float)total[k];
 }
 
 }  // namespace field

@@ -1,7 +1,8 @@
 // radiance_grad.hip — the radiance field's backward (radiance_grad.hpp) and the device-side packing of a trainable field:
 // the entries of include/isr_radiance_grad.h.  No call synchronises, no float atomics.
 //
-// The N * P points are worked through in memory order in slabs of whole chains (kGradChain points).  Per slab:
+// grad_core.hpp has the scheme (slabs, batches, the dW and combine kernels, the words of a pack) and what it shares with the
+// key field's backward.  The radiance field's own, per slab of the N * P points in memory order:
 //   * radiance_grad_dir_kernel, 64 of the slab's RAYS per workgroup (field_radiance.hip's radiance_dir_kernel): the
 //     embedding e_dir of the normalised direction into the workspace (rays, 6H rounded up to 32) and the direction term u, the
 //     chain from b1 over W1's direction columns on the matrix cores (rays, Wc rounded up to 32).
@@ -13,16 +14,12 @@
 //     rays as in the render: the sums are chains over points in memory order and a slab boundary cuts a ray, so the tile is
 //     the chain; a point's ray is its index / P.  Rows past the end carry g = 0.
 //     LDS: the 96 KB activation buffer of the trunk scheme, 768 bytes of points and 256 bytes of g_o: one workgroup per CU.
-//   * per batch of kGradBatch points, radiance_grad_dw_kernel, one wave per (32 x 32 block of a gradient matrix, chain):
-//     v_mfma_f32_32x32x2_f32 with the point as its k index, A = the output-side factor and B = the input-side factor straight
-//     from the workspace, the accumulator from +0: the chain of the rule.  The direction columns of dW1 read e_dir[ray of the
-//     point].  Layers narrower than 32 on the input side, the density row and every bias are the same chain on the vector
-//     unit, a lane per entry (a bias: the f64 sum of the rule).  A block sum goes to the workspace, real entries only, in the
-//     standard layout, the weights' as f32 and the biases' as f64;
-//   * and radiance_grad_combine_kernel, a lane per entry: the batch's block sums onto an f64 accumulator that lives in the
-//     workspace from batch to batch and slab to slab, in block order; the last one rounds to f32 and writes dW and db.
+//   * the dW launch has a part per hidden layer, the density row, W1's trunk columns, W1's direction columns (a per-ray input:
+//     e_dir[ray of the point]) and W2, and a bias is the f64 sum (grad_dw_kernel<true, kMaxDw>, grad_combine_kernel<true>).
+//   * radiance_pack_kernel writes the header words (beta, H, the layer count, the frequencies) and the density row itself.
 #include "radiance_grad.hpp"
 #include "field_trunk.hpp"
+#include "grad_core.hpp"
 
 #include "../../include/isr_radiance_grad.h"
 
@@ -38,14 +35,18 @@ using isr::density::kThreads;
 using isr::density::softplus32;
 using isr::density::tile_embed;
 using isr::field::act_index;
-using isr::field::f32x16;
 using isr::field::kTP;
+using isr::grad::add_part;
+using isr::grad::for_tile;
+using isr::grad::kFlat;
+using isr::grad::pack_layer_word;
+using isr::grad::pack_t_word;
+using isr::grad::ZeroInit;
 
-constexpr int kFlat = 256;                  // the per-entry kernels' workgroup
 constexpr int kMaxDw = kMaxHidden + 4;      // hidden layers, density row, W1's trunk part, W1's direction part, W2
+using DwArgs = isr::grad::DwArgs<kMaxDw>;
 
-static_assert(kGradChain == kTP && kGradBatch % kGradChain == 0 && kGradSlab % kGradBatch == 0,
-              "a tile is a chain, chains make batches and slabs");
+static_assert(kGradChain == kTP, "a tile is a chain");
 
 // What the tile kernel leaves in the slab workspace (S rows each; widths rounded up to 32).
 struct TileArgs {
@@ -61,10 +62,6 @@ struct TileArgs {
   float* u;                  // (R, WcP): the direction terms of the slab's rays
   float* edir;               // (R, ldE): their embeddings
   int ldE;
-};
-
-struct ZeroInit {
-  __device__ __forceinline__ float operator()(int, int) const { return 0.f; }
 };
 
 // where colour layer 1's chains start: u of the point's ray.  k0: the slab's first point's sample index within its ray
@@ -84,29 +81,6 @@ struct DensityInit {
   int Wt;
   __device__ __forceinline__ float operator()(int k, int p) const { return k < Wt ? wo[k] * go[p] : 0.f; }
 };
-
-// Every (point, neuron) pair of the tile below OP over the workgroup, a wave step 8 points x 8 neurons (32-byte pieces of the
-// workspace's rows): v = load(point, neuron) for a batch of steps at once, so that their memory latencies overlap, then
-// f(point, neuron, v) for each.  OP is a multiple of 32, a batch of every wave.  (field_grad.hip's for_tile.)
-template <class Ld, class F>
-__device__ __forceinline__ void for_tile(int OP, Ld load, F f) {
-  constexpr int kWaves = kThreads / 64, kBatch = 32 / kWaves;
-  static_assert(kBatch * kWaves == 32, "a batch of every wave covers 32 steps, which divides every OP");
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, pl = lane >> 3, jl = lane & 7;
-  for (int item0 = w; item0 < OP; item0 += kBatch * kWaves) {
-    float v[kBatch];
-#pragma unroll
-    for (int i = 0; i < kBatch; ++i) {
-      const int item = item0 + i * kWaves;
-      v[i] = load((item & 7) * 8 + pl, (item >> 3) * 8 + jl);
-    }
-#pragma unroll
-    for (int i = 0; i < kBatch; ++i) {
-      const int item = item0 + i * kWaves;
-      f((item & 7) * 8 + pl, (item >> 3) * 8 + jl, v[i]);
-    }
-  }
-}
 
 // e_dir (R, ldE) and u (R, WcP) of the rays [ray_base, ray_base + R): 64 rays per workgroup
 __global__ __launch_bounds__(kThreads) void radiance_grad_dir_kernel(Layout lay, const float* __restrict__ pack,
@@ -168,7 +142,7 @@ __global__ __launch_bounds__(kThreads) void radiance_grad_tile_kernel(TileArgs A
   {
     const int E = 6 * A.lay.d.H, ldE = A.ldE;
     float* Er = A.e + (size_t)row0 * ldE;
-    for_tile(ldE, [&](int p, int k) { return k < E ? act[act_index(k, p)] : 0.f; }, [&](int p, int k, float v) { Er[p * ldE + k] = v; });
+    for_tile<kThreads>(ldE, [&](int p, int k) { return k < E ? act[act_index(k, p)] : 0.f; }, [&](int p, int k, float v) { Er[p * ldE + k] = v; });
   }
 
   // the forward: act holds a layer's z, then its activations
@@ -177,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void radiance_grad_tile_kernel(TileArgs A
     isr::field::mfma_tile_layer<kThreads / 64>(L, pack, act, false, ident);
     float* Hn = A.h[l] + (size_t)row0 * L.OP;
     float* S = A.g[l] + (size_t)row0 * L.OP;
-    for_tile(L.OP, [&](int p, int j) { return act[act_index(j, p)]; }, [&](int p, int j, float z) {
+    for_tile<kThreads>(L.OP, [&](int p, int j) { return act[act_index(j, p)]; }, [&](int p, int j, float z) {
       float hv = 0.f, sv = 0.f;
       if (j < L.O) {
         hv = softplus32(z, beta);
@@ -207,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void radiance_grad_tile_kernel(TileArgs A
   {
     float* A1 = A.a1 + (size_t)row0 * WcP;
     float* S = A.g1 + (size_t)row0 * WcP;
-    for_tile(WcP, [&](int p, int j) { return act[act_index(j, p)]; }, [&](int p, int j, float z) {
+    for_tile<kThreads>(WcP, [&](int p, int j) { return act[act_index(j, p)]; }, [&](int p, int j, float z) {
       float hv = 0.f, sv = 0.f;
       if (j < Wc) {
         hv = softplus32(z, beta);
@@ -224,7 +198,7 @@ __global__ __launch_bounds__(kThreads) void radiance_grad_tile_kernel(TileArgs A
   // the way down: act holds q, then u of a layer, then its g
   {
     float* Q = A.q + (size_t)row0 * 32;
-    for_tile(32, [&](int p, int c) { return (c < C && row0 + p < n && d_col) ? d_col[(size_t)(s0 + row0 + p) * C + c] : 0.f; },
+    for_tile<kThreads>(32, [&](int p, int c) { return (c < C && row0 + p < n && d_col) ? d_col[(size_t)(s0 + row0 + p) * C + c] : 0.f; },
              [&](int p, int c, float dc) {
                const int idx = act_index(c, p);
                float qv = 0.f;
@@ -240,7 +214,7 @@ __global__ __launch_bounds__(kThreads) void radiance_grad_tile_kernel(TileArgs A
   isr::field::mfma_tile_layer_from<kThreads / 64>(A.T.outT, packT, act, false, ident, ZeroInit{});
   {
     float* G = A.g1 + (size_t)row0 * WcP;
-    for_tile(WcP, [&](int p, int j) { return G[p * WcP + j]; }, [&](int p, int j, float sv) {
+    for_tile<kThreads>(WcP, [&](int p, int j) { return G[p * WcP + j]; }, [&](int p, int j, float sv) {
       const int idx = act_index(j, p);
       float gv = 0.f;
       if (j < Wc && row0 + p < n) gv = act[idx] * sv;
@@ -254,7 +228,7 @@ __global__ __launch_bounds__(kThreads) void radiance_grad_tile_kernel(TileArgs A
   for (int l = nh - 1; l >= 0; --l) {
     const Layer L = A.lay.d.L[l];
     float* G = A.g[l] + (size_t)row0 * L.OP;
-    for_tile(L.OP, [&](int p, int j) { return G[p * L.OP + j]; }, [&](int p, int j, float sv) {
+    for_tile<kThreads>(L.OP, [&](int p, int j) { return G[p * L.OP + j]; }, [&](int p, int j, float sv) {
       const int idx = act_index(j, p);
       float gv = 0.f;
       if (j < L.O && row0 + p < n) gv = act[idx] * sv;
@@ -267,141 +241,6 @@ __global__ __launch_bounds__(kThreads) void radiance_grad_tile_kernel(TileArgs A
   }
 }
 
-// One gradient matrix (or part of one) of the dW launch: dW[w_off + j * w_ld + k] = sum_n g[n, j] * h[n or ray of n, k].
-struct DwLayer {
-  const float* g;
-  const float* h;
-  int ldg, O, ldh, K;
-  int per_ray;               // h has a row per ray of the slab
-  int mf;                    // the weights run on the matrix cores; the vector items are then the biases alone
-  int w_off, w_ld, b_off;    // b_off < 0: no bias goes with this part
-};
-
-// The work items of the dW launch: part l owns items [first[l], first[l + 1]), the matrix-core blocks first (nmf[l]).
-struct DwArgs {
-  DwLayer L[kMaxDw];
-  int first[kMaxDw + 1];
-  int nmf[kMaxDw];
-  int n_parts, w_total, b_total;
-};
-
-// (ray of the slab, sample) of a point, stepped forward through the slab
-struct RayWalk {
-  int rel, kk, P;
-  __device__ __forceinline__ RayWalk(long s0, int row, int P_, long ray_base) : P(P_) {
-    const long ng = s0 + row, ray = ng / P_;
-    rel = (int)(ray - ray_base);
-    kk = (int)(ng - ray * P_);
-  }
-  __device__ __forceinline__ void step(int by) {
-    kk += by;
-    while (kk >= P) {
-      kk -= P;
-      ++rel;
-    }
-  }
-};
-
-__global__ __launch_bounds__(64) void radiance_grad_dw_kernel(DwArgs D, int n, int chain0, long s0, int P, long ray_base,
-                                                              float* __restrict__ part, double* __restrict__ part_b) {
-  const int lane = threadIdx.x, c = blockIdx.y;                         // chain chain0 + c of the slab, the batch's c-th
-  int item = blockIdx.x, l = 0;
-  while (item >= D.first[l + 1]) ++l;
-  item -= D.first[l];
-  const DwLayer L = D.L[l];
-  const int p0 = (chain0 + c) * kGradChain;
-  const int left = n - p0;
-  const int real = left < kGradChain ? left : kGradChain;               // the chain's points; the tile kernel wrote g = 0 past n
-  const float* G = L.g + (size_t)p0 * L.ldg;
-  float* out = part + (size_t)c * D.w_total;
-  if (item < D.nmf[l]) {
-    const int KB = (L.K + 31) / 32, jb = item / KB, kb = item - jb * KB;
-    const int r = lane & 31, hh = lane >> 5;
-    const int k = kb * 32 + r;
-    const float* ga = G + (size_t)hh * L.ldg + jb * 32 + r;            // ldg is the layer's width rounded up to 32
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    if (!L.per_ray) {
-      const float* hb = L.h + (size_t)(p0 + hh) * L.ldh + k;            // ldh likewise: k is inside the row
-      for (int s = 0; s < kGradChain / 2; s += 8) {                     // eight loads of each operand in flight
-        float av[8], bv[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          av[i] = ga[(size_t)2 * (s + i) * L.ldg];
-          bv[i] = hb[(size_t)2 * (s + i) * L.ldh];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[i], acc, 0, 0, 0);
-      }
-    } else {
-      RayWalk rw(s0, p0 + hh, P, ray_base);
-      for (int s = 0; s < kGradChain / 2; s += 8) {
-        float av[8], bv[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          av[i] = ga[(size_t)2 * (s + i) * L.ldg];
-          bv[i] = 2 * (s + i) + hh < real ? L.h[(size_t)rw.rel * L.ldh + k] : 0.f;      // past the end: no such ray
-          rw.step(2);
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[i], acc, 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const int j = jb * 32 + 8 * a + 4 * hh + b;
-        if (j < L.O && k < L.K) out[L.w_off + j * L.w_ld + k] = acc[4 * a + b];
-      }
-    return;
-  }
-  // the vector unit: a lane per entry.  A matrix-core part leaves its bias here; a narrow one its K columns as well.
-  const int e = (item - D.nmf[l]) * 64 + lane;
-  const int kw = L.mf ? 0 : L.K, cols = kw + (L.b_off >= 0 ? 1 : 0);
-  if (e >= L.O * cols) return;
-  const int j = e / cols, k = e - j * cols;
-  if (k >= kw) {
-    double acc64 = 0.0;
-    for (int nn = 0; nn < real; ++nn) acc64 += (double)G[(size_t)nn * L.ldg + j];
-    part_b[(size_t)c * D.b_total + L.b_off + j] = acc64;
-    return;
-  }
-  float acc = 0.f;
-  if (!L.per_ray) {
-    const float* hp = L.h + (size_t)p0 * L.ldh + k;
-    for (int nn = 0; nn < real; ++nn) acc = fmaf(G[(size_t)nn * L.ldg + j], hp[(size_t)nn * L.ldh], acc);
-  } else {
-    RayWalk rw(s0, p0, P, ray_base);
-    for (int nn = 0; nn < real; ++nn) {
-      acc = fmaf(G[(size_t)nn * L.ldg + j], L.h[(size_t)rw.rel * L.ldh + k], acc);
-      rw.step(1);
-    }
-  }
-  out[L.w_off + j * L.w_ld + k] = acc;
-}
-
-__global__ __launch_bounds__(kFlat) void radiance_grad_combine_kernel(const float* __restrict__ part,
-                                                                      const double* __restrict__ part_b, int nblk, int w_total,
-                                                                      int b_total, double* __restrict__ acc64, int first, int last,
-                                                                      float* __restrict__ dW, float* __restrict__ db) {
-  const int e = blockIdx.x * kFlat + threadIdx.x;
-  if (e >= w_total + b_total) return;
-  double acc = first ? 0.0 : acc64[e];
-  if (e < w_total)
-    for (int c = 0; c < nblk; ++c) acc += (double)part[(size_t)c * w_total + e];
-  else
-    for (int c = 0; c < nblk; ++c) acc += part_b[(size_t)c * b_total + e - w_total];
-  acc64[e] = acc;
-  if (!last) return;
-  if (e < w_total) {
-    if (dW) dW[e] = (float)acc;
-  } else if (db) {
-    db[e - w_total] = (float)acc;
-  }
-}
-
 struct PackArgs {
   Layout lay;
   GradLayout T;
@@ -409,38 +248,6 @@ struct PackArgs {
   float freqs[kMaxH];
   float beta;
 };
-
-// the inverse of w_index for a matrix-core layer: word idx of its weight block -> (j, k), padding included
-__device__ __forceinline__ void w_unindex(const Layer& L, int idx, int& j, int& k) {
-  const int q = idx & 3, lane = (idx >> 2) & 63, blk = idx >> 8, S8 = L.kstride >> 3;
-  k = (blk % S8) * 8 + 2 * q + (lane >> 5);
-  j = (blk / S8) * 32 + (lane & 31);
-}
-
-// word i of a forward layer whose weights are W[w0 + j * ld + col0 + k] and whose bias is b[b0 + j] (b0 < 0: zeros)
-__device__ __forceinline__ bool pack_layer_word(const Layer& L, int i, const uint32_t* W, int w0, int ld, int col0,
-                                                const uint32_t* b, int b0, uint32_t& bits) {
-  if (i < L.w_off || i >= L.b_off + L.OP) return false;
-  if (i < L.b_off) {
-    int j, k;
-    w_unindex(L, i - L.w_off, j, k);
-    if (j < L.O && k < L.K) bits = W[w0 + j * ld + col0 + k];
-  } else if (i - L.b_off < L.O && b0 >= 0) {
-    bits = b[b0 + i - L.b_off];
-  }
-  return true;
-}
-
-// word t of a transposed layer over W[w0 + j * ld + k]: T's neuron is W's input k, T's input W's neuron j
-__device__ __forceinline__ bool pack_t_word(const Layer& T, int t, const uint32_t* W, int w0, int ld, int O, uint32_t& bits) {
-  if (t < T.w_off || t >= T.b_off + T.OP) return false;
-  if (t < T.b_off) {
-    int k, j;
-    w_unindex(T, t - T.w_off, k, j);
-    if (k < T.O && j < O) bits = W[w0 + j * ld + k];
-  }
-  return true;
-}
 
 // a thread per word of the two packs: its source entry, or zero
 __global__ __launch_bounds__(kFlat) void radiance_pack_kernel(PackArgs A, const uint32_t* __restrict__ W,
@@ -500,14 +307,6 @@ int check_field(const char* who, const void* pack, size_t pack_bytes, int n_hidd
   return isr::check_pack_bytes(who, pack_bytes, lay.total_words);
 }
 
-int check_pack_t(const char* who, const Layout& lay, const void* packT, size_t packT_bytes, GradLayout& T) {
-  make_layout_t(lay, T);
-  ISR_REQUIRE(packT, "%s: null pointer", who);
-  ISR_REQUIRE(packT_bytes == (size_t)T.total_words * 4, "%s: packT_bytes %zu, this field's transposed pack has %zu", who,
-              packT_bytes, (size_t)T.total_words * 4);
-  return ISR_OK;
-}
-
 int rays_of_slab(int slab, int N, int P) {                       // the rays `slab` consecutive points can touch, at most
   const long r = (long)slab / P + 2;
   return r < N ? (int)r : N;
@@ -545,21 +344,6 @@ Carve carve(const Layout& lay, int slab, int R, const StdOffsets& so, void* base
   return c;
 }
 
-int slab_for(long points) {
-  const long up = (points + kGradChain - 1) / kGradChain * kGradChain;
-  return up < kGradChain ? kGradChain : up > kGradSlab ? kGradSlab : (int)up;
-}
-
-void add_part(DwArgs& D, const float* g, int ldg, int O, const float* h, int ldh, int K, int per_ray, bool allow_mf, int w_off,
-              int w_ld, int b_off) {
-  const int l = D.n_parts++;
-  DwLayer& L = D.L[l];
-  L = DwLayer{g, h, ldg, O, ldh, K, per_ray, (allow_mf && K >= isr::field::kMfmaMinK) ? 1 : 0, w_off, w_ld, b_off};
-  D.nmf[l] = L.mf ? ((O + 31) / 32) * ((K + 31) / 32) : 0;
-  const int cols = (L.mf ? 0 : K) + (b_off >= 0 ? 1 : 0);
-  D.first[l + 1] = D.first[l] + D.nmf[l] + (O * cols + 63) / 64;
-}
-
 }  // namespace
 
 extern "C" size_t isr_radiance_grad_pack_bytes(int n_hidden, const int32_t* widths, int H, int Wc, int C) {
@@ -579,7 +363,7 @@ extern "C" int isr_radiance_pack_device(int n_hidden, const int32_t* widths, int
   const char* who = "isr_radiance_pack_device";
   PackArgs A;
   if (int rc = check_field(who, pack, pack_bytes, n_hidden, widths, H, Wc, C, A.lay)) return rc;
-  if (int rc = check_pack_t(who, A.lay, packT, packT_bytes, A.T)) return rc;
+  if (int rc = isr::grad::check_pack_t(who, A.lay, packT, packT_bytes, A.T)) return rc;
   ISR_REQUIRE(freqs && W && b, "%s: null pointer", who);
   ISR_REQUIRE(beta > 0.f && beta <= 3.0e38f, "%s: beta = %g must be positive and finite", who, (double)beta);
   std_offsets(A.lay, A.so);
@@ -605,7 +389,7 @@ extern "C" size_t isr_radiance_grad_workspace_bytes(int n_hidden, const int32_t*
   }
   StdOffsets so;
   std_offsets(lay, so);
-  const int slab = slab_for((long)N * P);
+  const int slab = isr::grad::slab_for((long)N * P);
   return carve(lay, slab, rays_of_slab(slab, N > 1 ? N : 1, P), so, nullptr).bytes;
 }
 
@@ -617,21 +401,16 @@ extern "C" int isr_radiance_backward(const void* pack, size_t pack_bytes, const 
   Layout lay;
   GradLayout T;
   if (int rc = check_field(who, pack, pack_bytes, n_hidden, widths, H, Wc, C, lay)) return rc;
-  if (int rc = check_pack_t(who, lay, packT, packT_bytes, T)) return rc;
+  if (int rc = isr::grad::check_pack_t(who, lay, packT, packT_bytes, T)) return rc;
   if (int rc = check_march(who, N, origins && directions && lengths, P, 0.f)) return rc;
   StdOffsets so;
   std_offsets(lay, so);
-  const int E = so.w_total + so.b_total;
   hipStream_t st = isr::as_stream(stream);
-  if (N == 0) {
-    if (dW) ISR_CHECK_HIP(hipMemsetAsync(dW, 0, (size_t)so.w_total * 4, st));
-    if (db) ISR_CHECK_HIP(hipMemsetAsync(db, 0, (size_t)so.b_total * 4, st));
-    return ISR_OK;
-  }
+  if (N == 0) return isr::grad::zero_grads(dW, so.w_total, db, so.b_total, st);
   ISR_REQUIRE(ws, "%s: null workspace", who);
   ISR_REQUIRE(((uintptr_t)ws & 15) == 0, "%s: the workspace is not 16-byte aligned", who);
   const long NP = (long)N * P;
-  int slab = slab_for(NP);
+  int slab = isr::grad::slab_for(NP);
   while (slab > kGradChain && carve(lay, slab, rays_of_slab(slab, N, P), so, nullptr).bytes > ws_bytes) slab -= kGradChain;
   const int Rcap = rays_of_slab(slab, N, P);
   const Carve cv = carve(lay, slab, Rcap, so, ws);
@@ -639,9 +418,7 @@ extern "C" int isr_radiance_backward(const void* pack, size_t pack_bytes, const 
   TileArgs A = cv.t;
   A.lay = lay;
   A.T = T;
-  DwArgs D;
-  D.n_parts = 0;
-  D.first[0] = 0;
+  DwArgs D{};
   D.w_total = so.w_total;
   D.b_total = so.b_total;
   const int nh = lay.d.n_hidden, Wt = lay.d.out_K, E6 = 6 * H;
@@ -655,34 +432,17 @@ extern "C" int isr_radiance_backward(const void* pack, size_t pack_bytes, const 
   add_part(D, A.g1, lay.WcP, Wc, h_top, ld_top, Wt, 0, true, so.w[nh + 1], Wt + E6, so.b[nh + 1]);
   add_part(D, A.g1, lay.WcP, Wc, A.edir, A.ldE, E6, 1, true, so.w[nh + 1] + Wt, Wt + E6, -1);
   add_part(D, A.q, 32, C, A.a1, lay.WcP, Wc, 0, true, so.w[nh + 2], Wc, so.b[nh + 2]);
-  for (int l = D.n_parts; l < kMaxDw; ++l) {
-    D.L[l] = DwLayer{nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, 0, -1};
-    D.nmf[l] = 0;
-    D.first[l + 1] = D.first[l];
-  }
   const float* pk = static_cast<const float*>(pack);
   const float* pkT = static_cast<const float*>(packT);
-  for (long s0 = 0; s0 < NP; s0 += slab) {
-    const int n = NP - s0 < slab ? (int)(NP - s0) : slab;
-    const long ray_base = s0 / P;
+  return isr::grad::for_slabs<true, kGradBatch>(D, NP, slab, P, cv.part, cv.part_b, cv.acc64, dW, db, st, [&](long s0, int n, long ray_base) -> int {
     const int R = (int)((s0 + n - 1) / P - ray_base) + 1;             // <= Rcap
     radiance_grad_dir_kernel<<<(R + kTP - 1) / kTP, kThreads, 0, st>>>(lay, pk, directions, ray_base, R, A.u, A.edir, A.ldE);
     ISR_CHECK_LAUNCH("radiance_grad_dir_kernel");
     radiance_grad_tile_kernel<<<(n + kTP - 1) / kTP, kThreads, 0, st>>>(A, pk, pkT, origins, directions, lengths, s0, n, P, ray_base,
                                                                          d_densities, d_colours);
     ISR_CHECK_LAUNCH("radiance_grad_tile_kernel");
-    for (int b0 = 0; b0 < n; b0 += kGradBatch) {
-      const int nb = n - b0 < kGradBatch ? n - b0 : kGradBatch;
-      const int nblk = (nb + kGradChain - 1) / kGradChain;
-      radiance_grad_dw_kernel<<<dim3(D.first[D.n_parts], nblk), 64, 0, st>>>(D, n, b0 / kGradChain, s0, P, ray_base, cv.part,
-                                                                             cv.part_b);
-      ISR_CHECK_LAUNCH("radiance_grad_dw_kernel");
-      radiance_grad_combine_kernel<<<(E + kFlat - 1) / kFlat, kFlat, 0, st>>>(cv.part, cv.part_b, nblk, so.w_total, so.b_total,
-                                                                              cv.acc64, s0 + b0 == 0, s0 + b0 + nb == NP, dW, db);
-      ISR_CHECK_LAUNCH("radiance_grad_combine_kernel");
-    }
-  }
-  return ISR_OK;
+    return ISR_OK;
+  });
 }
 
 extern "C" int isr_radiance_backward_host(const void* pack, size_t pack_bytes, int n_hidden, const int32_t* widths, int H, int Wc,

@@ -20,12 +20,8 @@
 // Over the points every gradient is sum_n (output-side factor)[n] * (input-side factor)[n]:
 //     dW_l  g_l x h_{l-1} (layer 0: the 6H embedding e);  density row  g_o x h_top;  dW1  g1 x [h_top, e_dir(ray of n)];
 //     dW2  q x a1;  every bias: the same output-side factor x 1
-// in field_grad.hpp's order (blocked sums): the points in memory order in consecutive blocks of kGradChain; inside a block the
-// f32 chain acc = fmaf(g, h, acc) from +0; the block sums added in block order in f64 and rounded to f32 once.  The direction
-// block of dW1 is summed like every other column, e_dir read per ray.  A BIAS is summed in f64 throughout: inside a block
-// acc = acc + (double)g from +0 in point order, the block sums added in block order, one rounding to f32.  (An f32 chain of
-// ones has no products that average out: against the reference's executed code the density bias came to 14 x the reference's
-// own f32 error with f32 chains of 64 and 11 x with chains of 8, and to 2 x with f64 sums; the weights hold 4 x at 64.)
+// in the order of grad_sums.hpp, the points in memory order.  The direction block of dW1 is summed like every other column,
+// e_dir read per ray.  A bias is summed by the f64 policy.
 // So a gradient is a function of the inputs, N and P alone.  Origins, directions, lengths and the frequencies get no gradient.
 //
 // The transposed pack: 64 zero header words, then, each as a matrix-core layer (field_mlp.hpp's w_index) with a zero bias,
@@ -34,14 +30,13 @@
 //     W2^T:                                      in = 32,                    out = Wc
 #pragma once
 #include "field_radiance.hpp"
+#include "grad_sums.hpp"
 
 namespace isr {
 namespace radiance {
 
-// Points per f32 chain of a weight sum, and per tile of the first kernel (field_grad.hpp: chains of 256 left the 4 x margin).
-constexpr int kGradChain = 64;
-// Points whose per-layer inputs and gradients the workspace holds at a time, at most: 256 tiles, a workgroup for every CU.
-constexpr int kGradSlab = 16384;
+using grad::kGradChain;      // also the tile of the first kernel
+using grad::kGradSlab;
 // Points whose block sums the workspace holds at a time: 32 chains x every entry (40 MB for the 256-wide field at H = 60).
 constexpr int kGradBatch = 2048;
 constexpr int kMaxIn = 6 * kMaxH;       // the widest input of a layer: the embedding
@@ -130,7 +125,7 @@ inline void ray_grad_term(const Layout& lay, const void* pack, const float* dirT
   for (int k = 0; k < 6 * lay.d.H; ++k) {
     const float ek = e[k];
     const float* wk = dirT + (size_t)k * lay.Wc;
-    for (int j = 0; j < lay.Wc; ++j) u[j] = __builtin_fmaf(wk[j], ek, u[j]);
+    for (int j = 0; j < lay.Wc; ++j) u[j] = fmaf(wk[j], ek, u[j]);
   }
 }
 
@@ -150,7 +145,7 @@ inline void point_grads(const Layout& lay, const void* pack, const HostNet& net,
     for (int j = 0; j < L.O; ++j) {
       const float* w = net.rows[l] + (size_t)j * L.K;
       float z = pf[L.b_off + j];
-      for (int k = 0; k < L.K; ++k) z = __builtin_fmaf(w[k], h[k], z);
+      for (int k = 0; k < L.K; ++k) z = fmaf(w[k], h[k], z);
       Hh[l][j] = density::softplus32(z, beta);
       G[l][j] = slope32(z, beta);            // the slope, until the way down replaces it by g
     }
@@ -158,32 +153,32 @@ inline void point_grads(const Layout& lay, const void* pack, const HostNet& net,
   }
   {
     float zo = pf[lay.d.out_b_off];
-    for (int k = 0; k < Wt; ++k) zo = __builtin_fmaf(pf[lay.d.out_w_off + k], h[k], zo);
+    for (int k = 0; k < Wt; ++k) zo = fmaf(pf[lay.d.out_w_off + k], h[k], zo);
     const float s = density::softplus32(zo, beta);
     *go = (drho * dexp32(s)) * slope32(zo, beta);
   }
   for (int j = 0; j < Wc; ++j) {
     const float* w = net.trunk.data() + (size_t)j * Wt;
     float z = uray[j];
-    for (int k = 0; k < Wt; ++k) z = __builtin_fmaf(w[k], h[k], z);
+    for (int k = 0; k < Wt; ++k) z = fmaf(w[k], h[k], z);
     a1[j] = density::softplus32(z, beta);
     g1[j] = slope32(z, beta);
   }
   for (int c = 0; c < C; ++c) {
     const float* w = net.out.data() + (size_t)c * Wc;
     float z = pf[lay.out.b_off + c];
-    for (int k = 0; k < Wc; ++k) z = __builtin_fmaf(w[k], a1[k], z);
+    for (int k = 0; k < Wc; ++k) z = fmaf(w[k], a1[k], z);
     const float col = sigmoid32(z);
     q[c] = dcol[c] * (col * (1.0f - col));
   }
   for (int k = 0; k < Wc; ++k) {
     float acc = 0.f;
-    for (int c = 0; c < C; ++c) acc = __builtin_fmaf(net.out[(size_t)c * Wc + k], q[c], acc);
+    for (int c = 0; c < C; ++c) acc = fmaf(net.out[(size_t)c * Wc + k], q[c], acc);
     g1[k] = acc * g1[k];
   }
   for (int k = 0; k < Wt; ++k) {
     float acc = pf[lay.d.out_w_off + k] * *go;
-    for (int j = 0; j < Wc; ++j) acc = __builtin_fmaf(net.trunk[(size_t)j * Wt + k], g1[j], acc);
+    for (int j = 0; j < Wc; ++j) acc = fmaf(net.trunk[(size_t)j * Wt + k], g1[j], acc);
     u[k] = acc;
   }
   for (int l = nh - 1; l >= 0; --l) {
@@ -192,36 +187,11 @@ inline void point_grads(const Layout& lay, const void* pack, const HostNet& net,
     if (l == 0) break;
     for (int k = 0; k < L.K; ++k) {
       float acc = 0.f;
-      for (int j = 0; j < L.O; ++j) acc = __builtin_fmaf(net.rows[l][(size_t)j * L.K + k], G[l][j], acc);
+      for (int j = 0; j < L.O; ++j) acc = fmaf(net.rows[l][(size_t)j * L.K + k], G[l][j], acc);
       v[k] = acc;
     }
     for (int k = 0; k < L.K; ++k) u[k] = v[k];
   }
-}
-
-// Host: out[k] = the blocked sum over n < N of g[n gs] * Hm[(n / div) K + k] for every k < K (K <= kMaxIn), the points walked
-// once.  div = 1: a row of Hm per point; div = P: a row per ray.  Hm == nullptr: K = 1, a bias: the f64 sum of the rule.
-inline void blocked_row(const float* g, long gs, const float* Hm, int K, long div, long N, float* out) {
-  double total[kMaxIn];
-  float acc[kMaxIn];
-  for (int k = 0; k < K; ++k) total[k] = 0.0;
-  for (long n0 = 0; n0 < N; n0 += kGradChain) {
-    const long n1 = n0 + kGradChain < N ? n0 + kGradChain : N;
-    if (!Hm) {
-      double acc64 = 0.0;
-      for (long n = n0; n < n1; ++n) acc64 += (double)g[n * gs];
-      total[0] += acc64;
-      continue;
-    }
-    for (int k = 0; k < K; ++k) acc[k] = 0.f;
-    for (long n = n0; n < n1; ++n) {
-      const float gv = g[n * gs];
-      const float* h = Hm + (size_t)(n / div) * K;
-      for (int k = 0; k < K; ++k) acc[k] = __builtin_fmaf(gv, h[k], acc[k]);
-    }
-    for (int k = 0; k < K; ++k) total[k] += (double)acc[k];
-  }
-  for (int k = 0; k < K; ++k) out[k] = (float)total[k];
 }
 
 // Host: the whole backward over host arrays.  d_densities / d_colours null: zeros.  dW / db null: not written.
@@ -288,10 +258,10 @@ void backward_host(const Par& par, const Layout& lay, const void* pack, const fl
     }
     const int ld = l == nh + 1 ? Wt + E : K;
     if (dW) {
-      blocked_row(g, gs, hm, K, 1, NP, dW + so.w[l] + (size_t)j * ld);
-      if (l == nh + 1) blocked_row(g, gs, edir.data(), E, P, NP, dW + so.w[l] + (size_t)j * ld + Wt);
+      grad::blocked_row<kMaxIn>(g, gs, hm, K, 1, NP, true, dW + so.w[l] + (size_t)j * ld);
+      if (l == nh + 1) grad::blocked_row<kMaxIn>(g, gs, edir.data(), E, P, NP, true, dW + so.w[l] + (size_t)j * ld + Wt);
     }
-    if (db) blocked_row(g, gs, nullptr, 1, 1, NP, db + so.b[l] + j);
+    if (db) grad::blocked_row<kMaxIn>(g, gs, nullptr, 1, 1, NP, true, db + so.b[l] + j);
   });
 }
 

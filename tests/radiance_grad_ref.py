@@ -127,8 +127,9 @@ def blocked_bias(g, chain):
     return total.astype(f32)
 
 
-def backward(w, freqs, beta, origins, directions, lengths, d_densities, d_colours, chain):
-    """-> (dW, db) flat in isr_radiance_pack's layout, by the rule of include/isr_radiance_grad.h."""
+def backward(w, freqs, beta, origins, directions, lengths, d_densities, d_colours, chain, blocked_bias=blocked_bias):
+    """-> (dW, db) flat in isr_radiance_pack's layout, by the rule of include/isr_radiance_grad.h.  blocked_bias(g, chain): how
+    a bias is summed (the rule's f64 sum; tests/test_grad_sums_cpu.py also passes the other policy, to tell the two apart)."""
     Ws, bs, cWs, cbs = w
     o, d, ln = (np.asarray(a, f32) for a in (origins, directions, lengths))
     N, P = ln.shape

@@ -1,4 +1,4 @@
-// field_grad_host_check.cpp — csrc/field_grad.hpp (over csrc/field_mlp.hpp) as plain host code, for a sanitizer build:
+// field_grad_host_check.cpp — csrc/field_grad.hpp (over csrc/field_mlp.hpp and csrc/grad_sums.hpp) as plain host code, for a sanitizer build:
 //     c++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all \
 //         tools/field_grad_host_check.cpp -o field_grad_host_check && ./field_grad_host_check
 // Drives make_layout / make_layout_t, pack_host / pack_t_host, point_grads, blocked_sum and blocked_row over the fields and
@@ -22,6 +22,7 @@
 #include "../imagesequenceregistrationfor6dposeestimationlabeling_amd/csrc/field_grad.hpp"
 
 using namespace isr::field;
+using isr::grad::blocked_sum;
 
 namespace {
 
@@ -104,8 +105,10 @@ void run(int n_layers, const int32_t* widths, const float* omega, const int32_t*
   for (int l = 0; l < n_layers; ++l) {
     const Layer& L = lay.L[l];
     for (int j = 0; j < L.O; ++j) {
-      blocked_row(G[(size_t)l].data() + j, L.O, H[(size_t)l].data(), L.K, N, &dW[(size_t)w_std[l] + (size_t)j * L.K]);
-      db[(size_t)b_std[l] + j] = blocked_sum(G[(size_t)l].data() + j, L.O, nullptr, 0, N);
+      isr::grad::blocked_row<kMaxWidth>(G[(size_t)l].data() + j, L.O, H[(size_t)l].data(), L.K, 1, N, false, &dW[(size_t)w_std[l] + (size_t)j * L.K]);
+      isr::grad::blocked_row<kMaxWidth>(G[(size_t)l].data() + j, L.O, nullptr, 1, 1, N, false, &db[(size_t)b_std[l] + j]);
+      const float bias = blocked_sum(G[(size_t)l].data() + j, L.O, nullptr, 0, N);
+      ok = ok && (std::memcmp(&bias, &db[(size_t)b_std[l] + j], 4) == 0 || (bias != bias && db[(size_t)b_std[l] + j] != db[(size_t)b_std[l] + j]));
       for (int k = 0; k < L.K; ++k) {
         const float one = blocked_sum(G[(size_t)l].data() + j, L.O, H[(size_t)l].data() + k, L.K, N);
         const float row = dW[(size_t)w_std[l] + (size_t)j * L.K + k];

@@ -1,4 +1,4 @@
-// radiance_grad_host_check.cpp — csrc/radiance_grad.hpp (over csrc/field_radiance.hpp) as plain host code, for a sanitizer build:
+// radiance_grad_host_check.cpp — csrc/radiance_grad.hpp (over csrc/field_radiance.hpp and csrc/grad_sums.hpp) as plain host code, for a sanitizer build:
 //     c++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all \
 //         tools/radiance_grad_host_check.cpp -o radiance_grad_host_check && ./radiance_grad_host_check
 // Drives make_layout / make_layout_t / std_offsets, pack_host, HostNet, ray_grad_term, point_grads, blocked_row and
