@@ -351,6 +351,17 @@ ICP_PLANE_SIGNATURES = {
     "isr_icp_point_to_plane_batch_host": (_i, _ICP_PLANE),
 }
 
+# include/isr_seq_refit.h (the sequence-level pose: one robust refit over every frame's matches), bound the same way
+SEQ_REFIT_STATE_DOUBLES = 24
+SEQ_REFIT_FRAME_STATS = 4
+_SEQ_REFIT = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _d, _i, _d, _d, _vp, _vp]      # p3d .. frame_stats
+SEQ_REFIT_SIGNATURES = {
+    "isr_seq_refit_workspace_bytes": (_sz, [_i, _i]),
+    "isr_seq_refit": (_i, [*_SEQ_REFIT, _vp, _sz, _vp]),
+    "isr_seq_refit_host": (_i, _SEQ_REFIT),
+    "isr_seq_refit_sums_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _d, _vp, _vp, _vp]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libisr_hip.so (once).  Raises IsrError when it has not been built."""
@@ -372,7 +383,7 @@ def lib() -> C.CDLL:
                                **CONTRASTIVE_SIGNATURES, **FIELD_GRAD_SIGNATURES, **SAMPLE_GRAD_SIGNATURES,
                                **EA_GRAD_SIGNATURES, **RADIANCE_GRAD_SIGNATURES, **AUGMENT_SIGNATURES,
                                **ADAM_SIGNATURES, **RAY_LOSSES_SIGNATURES, **COLOR_AUG_SIGNATURES, **INGEST_SIGNATURES,
-                               **ICP_PLANE_SIGNATURES}.items():
+                               **ICP_PLANE_SIGNATURES, **SEQ_REFIT_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

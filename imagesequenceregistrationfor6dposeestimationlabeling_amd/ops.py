@@ -266,6 +266,80 @@ def icp_point_to_plane_batch_host(sources, target, target_normals, state, thresh
     return state
 
 
+def _seq_refit_args(name, p3d, p2d, counts, frame_w, K, G, state, kernel, xp):
+    """The shape and dtype checks both sequence-refit wrappers share -> (n, cap, kernel id)."""
+    f32, f64, i32 = (torch.float32, torch.float64, torch.int32) if xp is torch else (np.float32, np.float64, np.int32)
+    contiguous = (lambda a: a.is_contiguous()) if xp is torch else (lambda a: a.flags.c_contiguous)
+    if p3d.ndim != 3 or p3d.shape[2] != 3 or p2d.ndim != 3 or tuple(p2d.shape) != (p3d.shape[0], p3d.shape[1], 2):
+        raise ValueError(f"{name}: p3d {tuple(p3d.shape)} must be (n, cap, 3) and p2d {tuple(p2d.shape)} (n, cap, 2)")
+    n, cap = p3d.shape[0], p3d.shape[1]
+    if p3d.dtype != f32 or p2d.dtype != f32 or not contiguous(p3d) or not contiguous(p2d):
+        raise ValueError(f"{name}: p3d and p2d must be contiguous float32")
+    if counts.dtype != i32 or tuple(counts.shape) != (n,) or not contiguous(counts):
+        raise ValueError(f"{name}: counts must be contiguous (n,) int32, got {tuple(counts.shape)} {counts.dtype}")
+    for what, a, shape in (("K", K, (n, 9)), ("G", G, (n, 12)), ("state", state, (_capi.SEQ_REFIT_STATE_DOUBLES,)),
+                           ("frame_w", frame_w, (n,))):
+        if a is None and what == "frame_w":
+            continue
+        if a.dtype != f64 or tuple(a.shape) != shape or not contiguous(a):
+            raise ValueError(f"{name}: {what} must be contiguous {shape} float64, got {tuple(a.shape)} {a.dtype}")
+    if cap < 1:
+        raise ValueError(f"{name}: cap must be at least 1")
+    if kernel not in ICP_KERNELS:
+        raise ValueError(f"{name}: kernel {kernel!r} must be one of {sorted(ICP_KERNELS)}")
+    return n, cap, ICP_KERNELS[kernel]
+
+
+def seq_refit(p3d: torch.Tensor, p2d: torch.Tensor, counts: torch.Tensor, K: torch.Tensor, G: torch.Tensor, state: torch.Tensor,
+              frame_w: torch.Tensor | None = None, kernel: str = "tukey", k: float = 6.0, max_iter: int = 30,
+              tol_r: float = 1e-10, tol_t: float = 1e-8, workspace_buf: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """isr_seq_refit (include/isr_seq_refit.h states the rule): one robust Gauss-Newton for the sequence transform Y over the
+    reprojection residuals of every frame's matches, in place on `state`.  p3d (n, cap, 3) f32, p2d (n, cap, 2) f32, counts
+    (n,) i32, K (n, 9) f64, G (n, 12) f64 [R_i | t_i], state (24,) f64 = Y 4x4 (start in, result out) | mean a, rms, passes,
+    rows | status, sum w r.r, 0, 0; frame_w (n,) f64 or None; workspace_buf: a caller's uint8 scratch instead of the cached one
+    (whatever it holds).  Nothing synchronises.  Returns (state, frame_stats (n, 4))."""
+    dev = require_cuda(p3d, p2d, counts, K, G, state, *(() if frame_w is None else (frame_w,)))
+    n, cap, kid = _seq_refit_args("seq_refit", p3d, p2d, counts, frame_w, K, G, state, kernel, torch)
+    stats = torch.empty((n, _capi.SEQ_REFIT_FRAME_STATS), dtype=torch.float64, device=dev)
+    L = lib()
+    nbytes = L.isr_seq_refit_workspace_bytes(n, cap)
+    ws = None if not n else workspace_buf if workspace_buf is not None else workspace(dev, nbytes, "seq_refit")
+    with torch.cuda.device(dev), _timed("seq_refit", float(n) * cap * (max_iter + 1)):
+        rc = L.isr_seq_refit(ptr(p3d), ptr(p2d), ptr(counts), ptr(frame_w), ptr(K), ptr(G), n, cap, kid, float(k), int(max_iter),
+                             float(tol_r), float(tol_t), ptr(state), ptr(stats), ptr(ws), ws.numel() if n else 0,
+                             current_stream(dev))
+    check(rc, "isr_seq_refit")
+    return state, stats
+
+
+def seq_refit_host(p3d, p2d, counts, K, G, state, frame_w=None, kernel: str = "tukey", k: float = 6.0, max_iter: int = 30,
+                   tol_r: float = 1e-10, tol_t: float = 1e-8):
+    """isr_seq_refit_host: the same loop as host code, NumPy arrays of the shapes seq_refit takes, in place on `state`: the
+    same bits.  For tests and CPU users.  Returns (state, frame_stats (n, 4))."""
+    for a in (p3d, p2d, counts, K, G, state, *(() if frame_w is None else (frame_w,))):
+        if not isinstance(a, np.ndarray):
+            raise ValueError("seq_refit_host: NumPy arrays only (device tensors go to seq_refit)")
+    n, cap, kid = _seq_refit_args("seq_refit_host", p3d, p2d, counts, frame_w, K, G, state, kernel, np)
+    stats = np.empty((n, _capi.SEQ_REFIT_FRAME_STATS), np.float64)
+    hp = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p)
+    check(lib().isr_seq_refit_host(hp(p3d), hp(p2d), hp(counts), hp(frame_w), hp(K), hp(G), n, cap, kid, float(k), int(max_iter),
+                                   float(tol_r), float(tol_t), hp(state), hp(stats)), "isr_seq_refit_host")
+    return state, stats
+
+
+def seq_refit_sums_host(p3d, p2d, counts, K, G, Y, frame_w=None, kernel: str = "tukey", k: float = 6.0):
+    """isr_seq_refit_sums_host: the 31 sums of one pass at Y (4x4 f64), formed as the loop forms them, NumPy arrays.
+    Returns (sums (31,), frame_stats (n, 4)).  For tests."""
+    state = np.zeros(_capi.SEQ_REFIT_STATE_DOUBLES)
+    state[:16] = np.asarray(Y, np.float64).reshape(16)
+    n, cap, kid = _seq_refit_args("seq_refit_sums_host", p3d, p2d, counts, frame_w, K, G, state, kernel, np)
+    sums, stats = np.empty(31), np.empty((n, _capi.SEQ_REFIT_FRAME_STATS), np.float64)
+    hp = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p)
+    check(lib().isr_seq_refit_sums_host(hp(p3d), hp(p2d), hp(counts), hp(frame_w), hp(K), hp(G), n, cap, kid, float(k), hp(state),
+                                        hp(sums), hp(stats)), "isr_seq_refit_sums_host")
+    return sums, stats
+
+
 @dataclass
 class DistField:
     """Distances from the cell centres of a uniform grid to a (static) cloud: what isr_adds_bounds reads."""

@@ -707,3 +707,115 @@ def refine_top_choices(upper, lower, R_gt, t_gt, R_pred, t_pred, choices, thresh
     out["best"] = pick_refined(out["fitness"], out["inlier_rmse"], np.rint(out["fitness"] * up.shape[0]), out["chamfer"])
     out["image_id"] = None if out["best"] is None else int(choices[out["best"]])
     return out
+
+
+# ------------------------------------------------------------------ the sequence-level pose (include/isr_seq_refit.h)
+def stack_correspondences(model: SequenceModel, results: list[ImageResult], pix_xy: torch.Tensor, use: str = "kept"):
+    """The 2D-3D matches of every registered frame as one padded block on the device, for joint_transform:
+    -> p3d (n, P, 3) f32 model-frame points, p2d (n, P, 2) f32 pixels, counts (n,) i32 (the first counts[i] rows of frame i
+    are real).  use="kept": the rows pnp saw (ops.gather_corr's, the top-80 % cut); use="inliers": its consensus set
+    (keep[inl_idx[:n_inl]]).  pix_xy (P, 2) shared or (n, P, 2).  A frame whose pnp failed (status 0) gets count 0.  One
+    isr_gather_corr_batch launch and tensor plumbing: nothing synchronises, the counts stay on the device."""
+    if use not in ("kept", "inliers"):
+        raise ValueError(f"stack_correspondences: use {use!r} must be 'kept' or 'inliers'")
+    if len(results) == 0:
+        raise ValueError("stack_correspondences: no results")
+    n = len(results)
+    if pix_xy.ndim not in (2, 3) or pix_xy.shape[-1] != 2 or (pix_xy.ndim == 3 and pix_xy.shape[0] != n):
+        raise ValueError(f"stack_correspondences: pix_xy {tuple(pix_xy.shape)} must be (P, 2) or ({n}, P, 2)")
+    idx = torch.stack([r.idx for r in results])
+    keep = torch.stack([r.keep for r in results])
+    ok = torch.cat([r.status for r in results]) != 0
+    if use == "kept":
+        counts = torch.cat([r.M for r in results])
+    else:
+        P = keep.shape[1]
+        inl = torch.stack([r.inl_idx for r in results]).to(torch.int64).clamp_(0, P - 1)     # rows past n_inl are never read
+        keep = keep.gather(1, inl).contiguous()
+        counts = torch.cat([r.n_inl for r in results])
+    counts = torch.where(ok, counts, torch.zeros_like(counts)).to(torch.int32).contiguous()
+    p3d, p2d = ops.gather_corr_batch(idx, keep, counts, model.pts, pix_xy)
+    return p3d, p2d, counts
+
+
+def _frames_g(R_gt, t_gt) -> torch.Tensor:
+    """(n, 12) f64 [R_i | t_i] on the device."""
+    R = registration._dev(np.asarray(R_gt, np.float64) if not isinstance(R_gt, torch.Tensor) else R_gt, torch.float64)
+    t = registration._dev(np.asarray(t_gt, np.float64) if not isinstance(t_gt, torch.Tensor) else t_gt, torch.float64)
+    n = R.shape[0]
+    return torch.cat([R.reshape(n, 3, 3), t.reshape(n, 3, 1)], dim=2).reshape(n, 12).contiguous()
+
+
+def joint_transform(p3d: torch.Tensor, p2d: torch.Tensor, counts: torch.Tensor, cams, R_gt, t_gt, start, frames=None,
+                    kernel: str = "tukey", k: float = 6.0, max_iter: int = 30, tol_r: float = 1e-10, tol_t: float = 1e-8,
+                    poses=None) -> dict:
+    """The rigid transform Y between the two sequences from EVERY frame's matches (ops.seq_refit): frame i has the known pose
+    G_i = [R_gt[i] | t_gt[i]] in its own sequence and sees the first sequence's model under P_i = G_i Y.
+    p3d, p2d, counts: stack_correspondences'.  cams: one 3x3 or (n, 3, 3).  start: a 4x4 Y0, or an image id s, which gives
+    Y0 = G_s^-1 P_s and needs poses= ((n, 12) or (n, 3, 4) predicted [R|t], e.g. stack_poses(results)[0]).  frames: a boolean
+    vector or a list of frame indices that take part (the others weigh 0), e.g. the winner's row of the vote's agreement
+    matrix; None: all.  kernel / k: the robust weight on the pixel residual; k = 6 is three times the 2 px inlier bound of
+    pnp, so an inlier keeps a weight of at least (1 - 1/9)^2 = 0.79.  Nothing synchronises.  Returns a dict of device tensors:
+    Y (4, 4), status, rms, rows, iterations (0-d f64: status 0 converged, 1 max_iter, 2 fewer than 6 rows, 3 singular),
+    frame_stats (n, 4) = rows, sum w, sum w r.r, sum r.r per frame at the last pass, and state (24,)."""
+    if p3d.ndim != 3:
+        raise ValueError(f"joint_transform: p3d {tuple(p3d.shape)} must be (n, cap, 3)")
+    n = p3d.shape[0]
+    K = np.asarray(cams, np.float64)
+    if K.shape not in ((3, 3), (n, 3, 3)):
+        raise ValueError(f"joint_transform: cams {K.shape} must be (3, 3) or ({n}, 3, 3)")
+    if len(R_gt) != n or len(t_gt) != n:
+        raise ValueError(f"joint_transform: {len(R_gt)} R_gt and {len(t_gt)} t_gt for {n} frames")
+    frame_w = None
+    if frames is not None:
+        f = np.asarray(frames)
+        if f.dtype == np.bool_:
+            if f.shape != (n,):
+                raise ValueError(f"joint_transform: a boolean frames must have shape ({n},), got {f.shape}")
+            w = f.astype(np.float64)
+        else:
+            f = f.astype(np.int64).reshape(-1)
+            if f.size and (f.min() < 0 or f.max() >= n):
+                raise ValueError(f"joint_transform: frames holds an index outside [0, {n})")
+            w = np.zeros(n)
+            w[f] = 1.0
+        frame_w = w
+    by_id = isinstance(start, (int, np.integer)) and not isinstance(start, bool)
+    if by_id:
+        if poses is None:
+            raise ValueError("joint_transform: start as an image id needs poses=")
+        if not 0 <= int(start) < n:
+            raise ValueError(f"joint_transform: start {start} outside [0, {n})")
+    else:
+        Y0 = start.detach().cpu().numpy() if isinstance(start, torch.Tensor) else np.asarray(start, np.float64)
+        if Y0.shape != (4, 4):
+            raise ValueError(f"joint_transform: start must be an image id or a 4x4, got shape {Y0.shape}")
+    dev = ops.require_cuda(p3d, p2d, counts)
+    G = _frames_g(R_gt, t_gt)
+    Kd = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(K, (n, 3, 3)).reshape(n, 9))).to(dev)
+    state = torch.zeros(24, dtype=torch.float64, device=dev)
+    if by_id:
+        s = int(start)
+        P = registration._dev(poses, torch.float64).reshape(n, 3, 4)[s]
+        Rg, tg = G[s].reshape(3, 4)[:, :3], G[s].reshape(3, 4)[:, 3:]
+        state[:12] = torch.cat([Rg.T @ P[:, :3], Rg.T @ (P[:, 3:] - tg)], dim=1).reshape(12)      # G_s^-1 P_s, G_s rigid
+    else:
+        state[:16] = torch.from_numpy(np.ascontiguousarray(Y0, np.float64).reshape(16)).to(dev)
+    fw = None if frame_w is None else torch.from_numpy(frame_w).to(dev)
+    state, stats = ops.seq_refit(p3d, p2d, counts, Kd, G, state, fw, kernel, k, max_iter, tol_r, tol_t)
+    return dict(Y=state[:16].reshape(4, 4), status=state[20], rms=state[17], rows=state[19], iterations=state[18],
+                frame_stats=stats, state=state)
+
+
+def label_frames(Y, R_gt, t_gt) -> tuple[np.ndarray, np.ndarray]:
+    """P_i = G_i Y for every frame: the labels of the second sequence in the first sequence's model frame, as
+    (R (n, 3, 3), t (n, 3)) f64 host arrays — what formats.write_pred6d_json takes.  Y: a 4x4 (tensor or array)."""
+    Y = Y.detach().cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
+    Y = np.asarray(Y, np.float64)
+    if Y.shape != (4, 4):
+        raise ValueError(f"label_frames: Y must be 4x4, got {Y.shape}")
+    R = np.asarray(R_gt, np.float64).reshape(-1, 3, 3)
+    t = np.asarray(t_gt, np.float64).reshape(-1, 3)
+    if len(R) != len(t):
+        raise ValueError(f"label_frames: {len(R)} rotations and {len(t)} translations")
+    return R @ Y[:3, :3], R @ Y[:3, 3] + t
