@@ -619,12 +619,46 @@ __launch_bounds__(kThreads, direct_min_waves(DK, SP)) void corr_bf16_direct_kern
         // issue order: the item's 33 VALU instructions (16 exp2, 15 + 1 add, the screen's compare; NAT: 16 mul more) spread
         // evenly behind the DK MFMAs of the next item; the empty asm ties the item's results to a fixed point of the
         // instruction stream (without it instruction selection sinks all eight epilogues below all eight MFMA chains)
+        if constexpr (DK == 4 && DKU == 4) {
+          // D = 64: the four matrix instructions are ONE dependent chain on nxt, so each waits for the one before it (32
+          // cycles) and the next item's first v_exp_f32 waits for the last.  They go a quarter of the epilogue apart, the
+          // last one a quarter before the item's end: a wave then has issue work of its own through every one of those
+          // waits.  v_exp_f32 is not in the scheduler's VALU class (0x002) but in the transcendental one (0x400): groups of
+          // "G VALU" take the additions alone and leave the third and fourth of them empty — the chain's last two
+          // instructions then sit back to back at the very end of the item (profiles/k1_chain_order.txt, "before").
+          // Asked for instead, one matrix instruction (and, qb == 0, one ds_read) in front of each quarter:
+          //   log2     E E E E E A A A | E E E E A A A A | the same | E E E A A A A A     the first quarter's fifth exponential
+          //            lets every later quarter add what the one before it produced; the screen's compare comes last
+          //   natural  per quarter 2 VALU, 2 exp, 4 VALU, 2 exp, 2 VALU (the last: 2, 2, 3, 2, 3): the multiplies run ahead
+          // No addition stands directly behind its own exponential (a wait state), and the additions, one dependent chain,
+          // keep their register order whatever the groups hold.
+          auto quarter = [&](auto s_tag) {
+            constexpr int s = decltype(s_tag)::value;
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            if (qb == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // this fragment's next ds_read
+            if constexpr (!NAT) {
+              __builtin_amdgcn_sched_group_barrier(0x400, s == 0 ? 5 : s == 3 ? 3 : 4, 0);
+              __builtin_amdgcn_sched_group_barrier(0x002, s == 0 ? 3 : s == 3 ? 5 : 4, 0);
+            } else {
+              __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+              __builtin_amdgcn_sched_group_barrier(0x400, 2, 0);
+              __builtin_amdgcn_sched_group_barrier(0x002, s == 3 ? 3 : 4, 0);
+              __builtin_amdgcn_sched_group_barrier(0x400, 2, 0);
+              __builtin_amdgcn_sched_group_barrier(0x002, s == 3 ? 3 : 2, 0);
+            }
+          };
+          quarter(std::integral_constant<int, 0>{});
+          quarter(std::integral_constant<int, 1>{});
+          quarter(std::integral_constant<int, 2>{});
+          quarter(std::integral_constant<int, 3>{});
+        } else {
         constexpr int G = ((NAT ? 49 : 33) + NMF - 1) / NMF;
 #pragma unroll
         for (int s = 0; s < NMF; ++s) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
           if (qb == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);    // this fragment's next ds_read
           __builtin_amdgcn_sched_group_barrier(0x002, G, 0);
+        }
         }
         asm volatile("" : "+v"(nxt), "+v"(st[qb].l), "+v"(ts));
 #ifndef ISR_ABL_DNOMAX   // timing-only ablation (tools/ablate_direct.sh): no maxima at all
