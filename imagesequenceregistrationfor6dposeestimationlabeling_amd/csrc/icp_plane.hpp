@@ -25,7 +25,8 @@
 //
 // SUMS, all f64, kSums = 31 per item: [0] sum d (d = sqrt(s2)), [1] sum s2, [2] n, [3..23] the upper triangle of sum w J J^T
 // row by row, [24..29] sum w J r, [30] sum w r^2.  A row that does not count (and a row past Ns in the last block) adds +0.0
-// to each.  Order (reduce_rows / reduce_blocks; that of icp_finalize_update_kernel and icp_reduce_and_update):
+// to each.  Order (tree64 / reduce_blocks here; on the device block_tree_sums of csrc/nn_batched.hip and reduce_blocks of
+// csrc/icp_loop.hpp, which both estimators share):
 //   per 64 rows the tree v[l] += v[l + s], s = 32, 16, .. 1 (row l = 0 holds the sum);
 //   per 256-row block ((w0 + w1) + w2) + w3;
 //   lane l of kLanes = 16 adds blocks l, l + 16, .. in that order onto 0.0; the 16 partials are added in lane order onto 0.0.
@@ -59,7 +60,7 @@ namespace icp_plane {
 
 constexpr int kSums = 31;
 constexpr int kA = 3, kB = 24, kWr2 = 30;       // where A's upper triangle, b and sum w r^2 start
-constexpr int kLanes = 16;                      // kIcpLanes of csrc/nn_batched.hip (asserted there)
+constexpr int kLanes = 16;                      // kIcpLanes of csrc/icp_loop.hpp (asserted there)
 constexpr int kStateDoubles = 24;               // T 4x4 | fitness, rmse, iterations, correspondences | status, sum w r^2, 0, 0
 constexpr int kL2 = 0, kHuber = 1, kTukey = 2;  // ISR_ICP_L2 / _HUBER / _TUKEY
 constexpr int kConverged = 0, kMaxIter = 1, kFewPairs = 2, kSingular = 3;

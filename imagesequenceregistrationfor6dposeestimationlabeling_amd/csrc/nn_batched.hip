@@ -32,6 +32,9 @@ namespace {
 #ifndef ISR_NN_PACKED_BATCH
 #define ISR_NN_PACKED_BATCH 1   // 0: per-split partial arrays in the batched brute-force search (rounds 1-3)
 #endif
+#ifndef ISR_ICP_CULL
+#define ISR_ICP_CULL 1          // 0: the ICP loop's searches skip no target tile (csrc/icp_loop.hpp: run_icp_loop)
+#endif
 constexpr int kThreads = 256;
 constexpr int kTile = 256;  // targets per LDS tile
 constexpr int kGroup = 8;   // targets per min3 group
@@ -111,8 +114,8 @@ __global__ __launch_bounds__(256) void tile_box_kernel(const float* __restrict__
 // coordinates; with u = 2^-24 and delta = u (|q| + max |t|) (the rounding displacement of the two points) the f32 value
 // D32 of a pair differs from its exact squared distance by at most tol(D) = 6u D + 2 sqrt(D) delta + delta^2.  A target
 // other than the lane's winner whose D32 lies within  best + 2.5 tol(best)  may be the exact (f64) nearest neighbour —
-// Open3D's KD-tree (icp.py:96-103) searches doubles — so the lane raises amb[query]; icp_finalize_update_kernel then
-// decides that query over all targets in f64.  Any such target is seen: the slow path is entered on  m <= thx  (thx =
+// Open3D's KD-tree (icp.py:96-103) searches doubles — so the lane raises amb[query]; resolve_flagged (csrc/icp_loop.hpp)
+// then decides that query over all targets in f64.  Any such target is seen: the slow path is entered on  m <= thx  (thx =
 // that widened bound, which only shrinks as best does) instead of  m < best, the filter's gate is built from thx, a
 // winner that displaces a near-tied predecessor raises the flag too, and so does the packed atomicMin when the value
 // it displaces (or fails to displace) — another target split's winner — is a near tie.  Cost in the fast path: none
@@ -455,8 +458,28 @@ __global__ __launch_bounds__(kThreads) void nn_search_kernel(
 
 #include "nn_grid.hpp"   // the two exact grid searches, their build kernels and workspace helpers
 
+// A workgroup's N per-thread terms -> its N sums at out[0 .. N), in a fixed shape: one wave tree per term (a term's 64 values
+// cross lanes in registers; LDS sees four doubles per term), then ((w0 + w1) + w2) + w3.  Only the first NV terms are
+// reduced; the others are stored as 0.0.  Shared by nn_finalize_kernel and the ICP passes (csrc/icp_loop.hpp: block_sums).
+template <int N, int NV = N>
+__device__ __forceinline__ void block_tree_sums(const double (&v)[N], double* __restrict__ out) {
+  __shared__ double red[kThreads / 64][N];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const double s = isr::wave_sum_down(v[k]);
+    if (lane == 0) red[wave][k] = s;
+  }
+  __syncthreads();
+  if (tid < N) {
+    double s = 0.0;
+    if (tid < NV) s = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    out[tid] = s;
+  }
+}
+
 // Merge the per-split winners, re-evaluate the distance in f64, apply the radius, and reduce
-// the block's sums into part_sums[b][blockIdx.x][kNV] (fixed tree: lanes, then waves in order).
+// the block's sums into part_sums[b][blockIdx.x][kNV] (block_tree_sums).
 template <bool WANT_COV>
 __global__ __launch_bounds__(kThreads) void nn_finalize_kernel(
     const float* __restrict__ qry, int Nq, const float* __restrict__ tgt,
@@ -464,7 +487,6 @@ __global__ __launch_bounds__(kThreads) void nn_finalize_kernel(
     const float* __restrict__ part_d2, const int32_t* __restrict__ part_idx, int b0,
     int32_t* __restrict__ nn_idx, double* __restrict__ nn_d, double* __restrict__ part_sums,
     const int32_t* __restrict__ skip, const unsigned long long* __restrict__ packed = nullptr) {
-  __shared__ double red[kThreads / 64][kNV];
   if (skip && *skip) return;
   const int tid = threadIdx.x;
   const int bl = blockIdx.y;  // batch item inside this chunk
@@ -518,19 +540,7 @@ __global__ __launch_bounds__(kThreads) void nn_finalize_kernel(
     if (nn_d) nn_d[(size_t)b * Nq + qi] = d;
   }
 
-  constexpr int nv = WANT_COV ? kNV : 3;
-  const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-  for (int k = 0; k < nv; ++k) {
-    const double s = isr::wave_sum_down(v[k]);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (tid < kNV) {
-    double s = 0.0;
-    if (tid < nv) s = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-    part_sums[((size_t)b * gridDim.x + blockIdx.x) * kNV + tid] = s;
-  }
+  block_tree_sums<kNV, WANT_COV ? kNV : 3>(v, part_sums + ((size_t)b * gridDim.x + blockIdx.x) * kNV);
 }
 
 __global__ void nn_reduce_kernel(const double* __restrict__ part_sums, int nblk, int B,
@@ -573,298 +583,6 @@ __global__ __launch_bounds__(kThreads) void add_metric_kernel(const float* __res
   if (threadIdx.x == 0) out[b] = (((red[0] + red[1]) + red[2]) + red[3]) / (double)V;
 }
 
-
-// ------------------------------------------------------------------------------- K4 ICP loop
-// registration_icp(source, target, threshold, init, PointToPoint) of icp.py:101-103, enqueued as
-// max_iter + 1 evaluation passes with NO host round trip: after each pass one thread reduces the
-// block sums, applies Open3D's stopping rule (|d fitness| < rel_fitness and |d rmse| < rel_rmse, or
-// the iteration budget) and, if it continues, composes T <- dT T where dT is the rigid fit of the
-// matched pairs (Horn's closed form: largest eigenvector of the 4x4 quaternion matrix by cyclic
-// Jacobi — always a proper rotation, equal to the SVD/Kabsch solution).  A device flag turns the
-// remaining launches into no-ops once the rule fires.
-struct IcpState {
-  double prev_fit, prev_rmse;
-  int32_t iter, done;
-  int32_t ticket, pad;   // workgroups that have delivered their sums in the current pass
-};
-static_assert(sizeof(IcpState) == kIcpStateInts * sizeof(int32_t) && offsetof(IcpState, done) == 5 * sizeof(int32_t),
-              "nn_search_kernel<.., ITEMS> steps from one item's done flag to the next by kIcpStateInts");
-
-// Cyclic Jacobi on a symmetric 4x4; every loop has constant bounds and is unrolled so A and V
-// stay in registers (indexed dynamically they live in scratch memory: 60 us per call instead of 10).
-__device__ void jacobi4_largest(double A[4][4], double q[4]) {
-  double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-  for (int sweep = 0; sweep < 16; ++sweep) {
-    double off = 0.0, dia = 0.0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      dia += A[p][p] * A[p][p];
-#pragma unroll
-      for (int r = p + 1; r < 4; ++r) off += A[p][r] * A[p][r];
-    }
-    // off-diagonal mass below 1e-34 of the diagonal's: the eigenvector is converged to ~1e-17 — Jacobi
-    // converges quadratically, so the sweeps this saves (it used to run until off underflowed) are pure
-    // serial latency in a one-thread tail
-    if (off <= 1e-34 * dia) break;
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int r = p + 1; r < 4; ++r) {
-        if (A[p][r] != 0.0) {
-          const double theta = (A[r][r] - A[p][p]) / (2.0 * A[p][r]);
-          const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-          const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {  // A <- A J
-            const double akp = A[k][p], akr = A[k][r];
-            A[k][p] = c * akp - sn * akr;
-            A[k][r] = sn * akp + c * akr;
-          }
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {  // A <- J^T A
-            const double apk = A[p][k], ark = A[r][k];
-            A[p][k] = c * apk - sn * ark;
-            A[r][k] = sn * apk + c * ark;
-          }
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const double vkp = V[k][p], vkr = V[k][r];
-            V[k][p] = c * vkp - sn * vkr;
-            V[k][r] = sn * vkp + c * vkr;
-          }
-        }
-      }
-  }
-  double lam = A[0][0];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) q[k] = V[k][0];
-#pragma unroll
-  for (int j = 1; j < 4; ++j) {
-    if (A[j][j] > lam) {
-      lam = A[j][j];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) q[k] = V[k][j];
-    }
-  }
-}
-
-constexpr int kIcpLanes = 16;
-
-// The end of an ICP evaluation pass, by ONE workgroup of any size: reduce the block sums in a fixed
-// shape (lane l of sum k adds blocks l, l + kIcpLanes, ...; the kIcpLanes partials are added in lane
-// order: run-to-run reproducible and the same for every caller), apply the stopping rule, compose T.
-__device__ void icp_reduce_and_update(const double* __restrict__ part_sums, int nblk, int Ns, int max_iter,
-                                      double rel_fitness, double rel_rmse, double* __restrict__ T,
-                                      IcpState* __restrict__ st, double* __restrict__ result) {
-  __shared__ double part[kNV][kIcpLanes];
-  __shared__ double v[kNV];
-  for (int idx = threadIdx.x; idx < kNV * kIcpLanes; idx += blockDim.x) {
-    const int k = idx / kIcpLanes, l = idx % kIcpLanes;
-    double s = 0.0;
-    for (int i = l; i < nblk; i += kIcpLanes) s += part_sums[(size_t)i * kNV + k];
-    part[k][l] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kNV) {
-    double s = 0.0;
-    for (int l = 0; l < kIcpLanes; ++l) s += part[threadIdx.x][l];
-    v[threadIdx.x] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  const double n = v[2];
-  const double fit = n / (double)Ns;
-  const double rmse = n > 0 ? sqrt(v[1] / n) : 0.0;
-  const int it = st->iter;
-  result[0] = fit; result[1] = rmse; result[2] = (double)it; result[3] = n;
-  const bool conv = it > 0 && fabs(st->prev_fit - fit) < rel_fitness && fabs(st->prev_rmse - rmse) < rel_rmse;
-  if (conv || it >= max_iter || n < 3) { st->done = 1; return; }
-  st->prev_fit = fit; st->prev_rmse = rmse; st->iter = it + 1;
-  // rigid fit of the matched pairs: S = sum (q - mq)(t - mt)^T
-  double mq[3], mt[3], S[3][3];
-  for (int a = 0; a < 3; ++a) { mq[a] = v[3 + a] / n; mt[a] = v[6 + a] / n; }
-  for (int a = 0; a < 3; ++a)
-    for (int b = 0; b < 3; ++b) S[a][b] = v[9 + 3 * a + b] - n * mq[a] * mt[b];
-  double N4[4][4] = {
-      {S[0][0] + S[1][1] + S[2][2], S[1][2] - S[2][1], S[2][0] - S[0][2], S[0][1] - S[1][0]},
-      {S[1][2] - S[2][1], S[0][0] - S[1][1] - S[2][2], S[0][1] + S[1][0], S[2][0] + S[0][2]},
-      {S[2][0] - S[0][2], S[0][1] + S[1][0], -S[0][0] + S[1][1] - S[2][2], S[1][2] + S[2][1]},
-      {S[0][1] - S[1][0], S[2][0] + S[0][2], S[1][2] + S[2][1], -S[0][0] - S[1][1] + S[2][2]}};
-  double q[4];
-  jacobi4_largest(N4, q);
-  const double nq = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  const double w = q[0] * nq, x = q[1] * nq, y = q[2] * nq, z = q[3] * nq;
-  const double R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)},
-                          {2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)},
-                          {2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)}};
-  double U[3][4];
-  for (int a = 0; a < 3; ++a) {
-    for (int b = 0; b < 3; ++b) U[a][b] = R[a][b];
-    U[a][3] = mt[a] - (R[a][0] * mq[0] + R[a][1] * mq[1] + R[a][2] * mq[2]);
-  }
-  double Tn[12];
-  for (int a = 0; a < 3; ++a)
-    for (int b = 0; b < 4; ++b)
-      Tn[4 * a + b] = U[a][0] * T[b] + U[a][1] * T[4 + b] + U[a][2] * T[8 + b] + (b == 3 ? U[a][3] : 0.0);
-  for (int k = 0; k < 12; ++k) T[k] = Tn[k];
-}
-
-// Brute-force loop: the search left one packed (f32 d2 bits, index) minimum per source point.  Every
-// workgroup finishes its 256 points exactly as nn_finalize_kernel<true> does (f64 distance of the
-// winner, radius test, the 18 sums by the same fixed tree), re-arms the packed slots, and takes a
-// ticket; the LAST workgroup to arrive (agent-scope fences order the block sums before the ticket)
-// runs the update.  Two launches per ICP iteration, no partial arrays.
-// blockIdx.y is the problem (isr_icp_point_to_point_batch; the single call is a grid of one): every per-problem pointer
-// moves to the item's slice — source (src_item_stride floats apart, 0 = shared), packed / prev_idx / amb (Ns apart), block
-// sums (gridDim.x rows apart), IcpState (own ticket: the last workgroup OF THE ITEM runs its update), T and result
-// (out_item_stride doubles apart) — and the code below is the single problem's, sum for sum.
-__global__ __launch_bounds__(kThreads) void icp_finalize_update_kernel(
-    const float* __restrict__ src, int Ns, const float* __restrict__ tgt, int Nt, double radius,
-    unsigned long long* __restrict__ packed, int32_t* __restrict__ prev_idx, int32_t* __restrict__ amb,
-    double* __restrict__ part_sums, int max_iter,
-    double rel_fitness, double rel_rmse, double* __restrict__ T, IcpState* __restrict__ st, double* __restrict__ result,
-    size_t src_item_stride = 0, size_t out_item_stride = 0) {
-  __shared__ double red[kThreads / 64][kNV];
-  __shared__ int last;
-  __shared__ int nflag, flist[kThreads];
-  __shared__ double wd[4][kThreads / 64];
-  __shared__ int wi[4][kThreads / 64];
-  {
-    const size_t b = blockIdx.y;
-    src += b * src_item_stride;
-    packed += b * Ns; prev_idx += b * Ns; amb += b * Ns;
-    part_sums += b * gridDim.x * kNV;
-    st += b;
-    T += b * out_item_stride; result += b * out_item_stride;
-  }
-  if (st->done) return;
-  const int tid = threadIdx.x;
-  const int qi = blockIdx.x * kThreads + tid;
-  // ---- near ties the search flagged (nn_search_kernel<.., EXACT>): the exact nearest neighbour over ALL targets in
-  // f64 — squared distance by the fma chain the sums below use, lowest index on exact ties — decided by the whole
-  // workgroup, one flagged point at a time (one or two points per pass on 20 000-point clouds, in one or two workgroups)
-  if (tid == 0) nflag = 0;
-  __syncthreads();
-  if (qi < Ns && amb[qi]) {
-    amb[qi] = 0;
-    flist[atomicAdd(&nflag, 1)] = qi;
-  }
-  __syncthreads();
-  const int nf = nflag;                             // block-uniform
-  // up to kRes flagged points per sweep over the targets: a target is loaded once and tried against each of them
-  // (the sweep is bound by load latency — round 3's first version resolved one point per sweep, ~35 us each)
-  constexpr int kRes = 4;
-  for (int f0 = 0; f0 < nf; f0 += kRes) {
-    double qx[kRes], qy[kRes], qz[kRes], bd[kRes];
-    int bi[kRes];
-#pragma unroll
-    for (int k = 0; k < kRes; ++k) {
-      const int pq = flist[min(f0 + k, nf - 1)];
-      xform64(T, src[3 * (size_t)pq], src[3 * (size_t)pq + 1], src[3 * (size_t)pq + 2], qx[k], qy[k], qz[k]);
-      bd[k] = __builtin_inf();
-      bi[k] = 0x7fffffff;
-    }
-#pragma unroll 4
-    for (int j = tid; j < Nt; j += kThreads) {
-      const double tx = tgt[3 * (size_t)j], ty = tgt[3 * (size_t)j + 1], tz = tgt[3 * (size_t)j + 2];
-#pragma unroll
-      for (int k = 0; k < kRes; ++k) {
-        const double ex = qx[k] - tx, ey = qy[k] - ty, ez = qz[k] - tz;
-        const double s2 = fma(ez, ez, fma(ey, ey, ex * ex));
-        if (s2 < bd[k]) { bd[k] = s2; bi[k] = j; }  // ascending j per thread: ties keep the lower index
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < kRes; ++k) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const double od = __shfl_xor(bd[k], off, 64);
-        const int oi = __shfl_xor(bi[k], off, 64);
-        if (od < bd[k] || (od == bd[k] && oi < bi[k])) { bd[k] = od; bi[k] = oi; }
-      }
-      if ((tid & 63) == 0) { wd[k][tid >> 6] = bd[k]; wi[k][tid >> 6] = bi[k]; }
-    }
-    __syncthreads();
-    if (tid < kRes && f0 + tid < nf) {
-      double d = wd[tid][0];
-      int i = wi[tid][0];
-      for (int w = 1; w < kThreads / 64; ++w)
-        if (wd[tid][w] < d || (wd[tid][w] == d && wi[tid][w] < i)) { d = wd[tid][w]; i = wi[tid][w]; }
-      packed[flist[f0 + tid]] = ((unsigned long long)__float_as_uint((float)d) << 32) | (unsigned int)i;
-    }
-    __syncthreads();
-  }
-  double v[kNV];
-#pragma unroll
-  for (int k = 0; k < kNV; ++k) v[k] = 0.0;
-  if (qi < Ns) {
-    const unsigned long long pk = packed[qi];
-    packed[qi] = ~0ull;
-    prev_idx[qi] = pk != ~0ull ? (int)(unsigned int)pk : -1;     // the next pass starts from this neighbour
-    if (pk != ~0ull) {
-      const int bi = (int)(unsigned int)pk;
-      double q0, q1, q2;
-      xform64(T, src[3 * (size_t)qi], src[3 * (size_t)qi + 1], src[3 * (size_t)qi + 2], q0, q1, q2);
-      const double t0 = tgt[3 * (size_t)bi], t1 = tgt[3 * (size_t)bi + 1], t2 = tgt[3 * (size_t)bi + 2];
-      const double ex = q0 - t0, ey = q1 - t1, ez = q2 - t2;
-      const double s2 = fma(ez, ez, fma(ey, ey, ex * ex));
-      if (s2 <= radius * radius) {
-        v[0] = sqrt(s2); v[1] = s2; v[2] = 1.0;
-        const double q[3] = {q0, q1, q2}, t[3] = {t0, t1, t2};
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          v[3 + r] = q[r];
-          v[6 + r] = t[r];
-#pragma unroll
-          for (int c = 0; c < 3; ++c) v[9 + 3 * r + c] = q[r] * t[c];
-        }
-      }
-    }
-  }
-  const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-  for (int k = 0; k < kNV; ++k) {
-    const double s = isr::wave_sum_down(v[k]);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (tid < kNV) part_sums[(size_t)blockIdx.x * kNV + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-  __threadfence();                                  // the block's sums are visible device-wide ...
-  __syncthreads();
-  if (tid == 0) last = (atomicAdd(&st->ticket, 1) == (int)gridDim.x - 1);   // ... before its ticket is
-  __syncthreads();
-  if (!last) return;                                // block-uniform
-  __threadfence();
-  if (tid == 0) st->ticket = 0;
-  icp_reduce_and_update(part_sums, gridDim.x, Ns, max_iter, rel_fitness, rel_rmse, T, st, result);
-}
-
-// (blockIdx.y: the problem, as in icp_finalize_update_kernel)
-__global__ void icp_init_kernel(IcpState* st, double* T, unsigned long long* packed, int32_t* amb, int Ns,
-                                size_t out_item_stride = 0) {
-  const size_t b = blockIdx.y;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < Ns) { packed[b * Ns + i] = ~0ull; amb[b * Ns + i] = 0; }
-  if (i != 0) return;
-  st += b; T += b * out_item_stride;
-  st->prev_fit = 0; st->prev_rmse = 0; st->iter = 0; st->done = 0; st->ticket = 0;
-  T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1;
-}
-
-// max |t|^2 over the target cloud (f32, rounded up a little): the rounding-displacement bound of the EXACT search
-__global__ __launch_bounds__(kThreads) void cloud_r2max_kernel(const float* __restrict__ tgt, int Nt, float* __restrict__ out) {
-  __shared__ float red[kThreads / 64];
-  float m = 0.f;
-  for (int j = threadIdx.x; j < Nt; j += kThreads) {
-    const float x = tgt[3 * (size_t)j], y = tgt[3 * (size_t)j + 1], z = tgt[3 * (size_t)j + 2];
-    m = fmaxf(m, __builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x)));
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = 1.0001f * fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
 
 struct NNPlan {
   int rq;          // queries per lane
@@ -1077,74 +795,33 @@ extern "C" int isr_add_metric(const float* verts, int V, const double* Ta, const
   return ISR_OK;
 }
 
-extern "C" size_t isr_icp_workspace_bytes(int Ns, int Nt) {
-  if (Ns <= 0 || Nt <= 0) return 0;
-  const NNPlan p = make_plan(Ns, Nt, 1, true);
-  return isr::align_up((size_t)p.fblocks * kNV * sizeof(double), 256) + isr::align_up((size_t)Ns * 8, 256) +
-         2 * isr::align_up((size_t)Ns * 4, 256) + isr::align_up((size_t)((Nt + kTile - 1) / kTile) * 6 * sizeof(float), 256) + 2048;
-}
+// ------------------------------------------------------------------------------- K4 ICP loop
+#include "icp_loop.hpp"   // the pass and its two estimators, their kernels, the workspace carve, run_icp_loop
+
+extern "C" size_t isr_icp_workspace_bytes(int Ns, int Nt) { return icp_workspace_bytes(Ns, Nt, 1, kNV, 0); }
 
 extern "C" int isr_icp_point_to_point(const float* src, int Ns, const float* tgt, int Nt, double threshold,
                                       int max_iter, double rel_fitness, double rel_rmse, double* T_io,
                                       double* result, void* ws, size_t ws_bytes, isr_stream_t stream_) {
   ISR_REQUIRE(src && tgt && T_io && result, "isr_icp_point_to_point: null pointer");
   ISR_REQUIRE(Ns > 0 && Nt > 0 && max_iter >= 0 && threshold > 0, "isr_icp_point_to_point: Ns=%d Nt=%d max_iter=%d", Ns, Nt, max_iter);
-  if (!ws || ws_bytes < isr_icp_workspace_bytes(Ns, Nt)) {
-    isr::set_error("isr_icp_point_to_point: workspace %zu < %zu", ws_bytes, isr_icp_workspace_bytes(Ns, Nt));
-    return ISR_ERR_WORKSPACE;
-  }
-  hipStream_t stream = isr::as_stream(stream_);
-  // Always the brute-force search (the grid searches lose here: most source points have their neighbour 5-20 mm
-  // away and a 20 mm ball covers a large part of the object — 18 ms / 103 ms against 2.5 ms per loop, round 2), with
-  // near ties decided in f64: every pass returns the EXACT nearest neighbours, as a KD-tree on doubles does.
   const NNPlan p = make_plan(Ns, Nt, 1, true);
   isr::Workspace w(ws, ws_bytes);
-  double* part_sums = w.take<double>((size_t)p.fblocks * kNV);
-  IcpState* st = w.take<IcpState>(1);
-  unsigned long long* packed = w.take<unsigned long long>(Ns);
-  int32_t* prev_idx = w.take<int32_t>(Ns);
-  int32_t* amb = w.take<int32_t>(Ns);
-  float* t2_bound = w.take<float>(1);
-  float* tile_box = w.take<float>((size_t)((Nt + kTile - 1) / kTile) * 6);
-  const bool warm = isr::tuning(ISR_TUNE_ICP_WARM) != 0;          // tuning knob: 0 keeps every pass on the cold kernel
-  icp_init_kernel<<<(Ns + kThreads - 1) / kThreads, kThreads, 0, stream>>>(st, T_io, packed, amb, Ns);
-  cloud_r2max_kernel<<<1, kThreads, 0, stream>>>(tgt, Nt, t2_bound);
-  // per-wave tile cull of the searches (nn_search_kernel): boxes of the target's 256-point tiles, once per call; the radius
-  // caps every lane's bound (f32, rounded up: the finalize's f64 test s2 <= threshold^2 decides what counts).  Pays when the
-  // clouds' rows are spatially ordered (registration.icp_point_to_point sorts them); otherwise every box is the whole cloud
-  // and nothing is skipped.
-#ifndef ISR_ICP_CULL
-#define ISR_ICP_CULL 1
-#endif
-  const float cull_r2 = (float)(threshold * threshold * 1.0001 + 1e-6);
-  if (ISR_ICP_CULL) tile_box_kernel<<<(Nt + kTile - 1) / kTile, 256, 0, stream>>>(tgt, Nt, tile_box);
-  const dim3 grid(p.qblocks, p.nsplit, 1);
-  for (int it = 0; it <= max_iter; ++it) {
-    // two launches per pass: search with one packed atomic min per (point, target split), then the
-    // finalize whose last workgroup runs the update
-    // (from the second pass on: the warm-started filter search, bounded by the previous pass's neighbour)
-    const int32_t* w_idx = (it > 0 && warm) ? prev_idx : nullptr;
-    launch_search(p, grid, stream, src, Ns, tgt, Nt, T_io, nullptr, nullptr, nullptr, &st->done, nullptr, packed, w_idx, amb,
-                  t2_bound, ISR_ICP_CULL ? tile_box : nullptr, cull_r2);
-    icp_finalize_update_kernel<<<p.fblocks, kThreads, 0, stream>>>(src, Ns, tgt, Nt, threshold, packed, prev_idx, amb, part_sums,
-                                                                   max_iter, rel_fitness, rel_rmse, T_io, st, result);
+  const IcpBufs b = carve(w, p, Ns, Nt, 1, kNV, 0);
+  if (!ws || !w.ok()) {
+    isr::set_error("isr_icp_point_to_point: workspace %zu < %zu", ws_bytes, w.off);
+    return ISR_ERR_WORKSPACE;
   }
-  ISR_CHECK_LAUNCH("icp kernels");
-  return ISR_OK;
+  // the single call's own search instantiations (items = false): a grid of one problem
+  return run_icp_loop("icp kernels", p, b, isr::as_stream(stream_), src, 0, Ns, tgt, Nt, 1, false, threshold, max_iter, rel_fitness,
+                      rel_rmse, PointToPoint{T_io, result, 0});
 }
 
-// The loop above for B independent problems against one target, the item on a grid axis: the same 3 + 2 (max_iter + 1)
-// launches whatever B is.  Every item keeps the single call's arithmetic — the search returns the lexicographic minimum of
-// (f32 d2, index) whatever the key ranges, near ties are decided in f64 over all targets, the sums are reduced per 256-row
-// block and across blocks in the fixed order of icp_reduce_and_update, which depends on Ns alone — so item b's 20 doubles
-// are those of isr_icp_point_to_point on (src_b, tgt, T0_b).  An item that has stopped raises its own done flag: its
-// workgroups of the remaining launches leave at once.
+// B independent problems against one target, the item on a grid axis.  Item b's 20 doubles are those of
+// isr_icp_point_to_point on (src_b, tgt, T0_b): the search returns the lexicographic minimum of (f32 d2, index) whatever the
+// key ranges (with B items on the grid the plan cuts fewer of them), and every sum's order depends on Ns alone.
 extern "C" size_t isr_icp_point_to_point_batch_workspace_bytes(int Ns, int Nt, int B) {
-  if (Ns <= 0 || Nt <= 0 || B <= 0) return 0;
-  const NNPlan p = make_plan(Ns, Nt, B, true);
-  return isr::align_up((size_t)B * p.fblocks * kNV * sizeof(double), 256) + isr::align_up((size_t)B * sizeof(IcpState), 256) +
-         isr::align_up((size_t)B * Ns * 8, 256) + 2 * isr::align_up((size_t)B * Ns * 4, 256) +
-         isr::align_up((size_t)((Nt + kTile - 1) / kTile) * 6 * sizeof(float), 256) + 2048;
+  return icp_workspace_bytes(Ns, Nt, B, kNV, 0);
 }
 
 extern "C" int isr_icp_point_to_point_batch(const float* src, size_t src_item_stride, int Ns, const float* tgt, int Nt, int B,
@@ -1159,221 +836,21 @@ extern "C" int isr_icp_point_to_point_batch(const float* src, size_t src_item_st
               "isr_icp_point_to_point_batch: src_item_stride=%zu must be 0 (one source for all items) or at least 3*Ns=%zu floats",
               src_item_stride, 3 * (size_t)Ns);
   if (B == 0) return ISR_OK;
-  if (!ws || ws_bytes < isr_icp_point_to_point_batch_workspace_bytes(Ns, Nt, B)) {
-    isr::set_error("isr_icp_point_to_point_batch: workspace %zu < %zu", ws_bytes,
-                   isr_icp_point_to_point_batch_workspace_bytes(Ns, Nt, B));
-    return ISR_ERR_WORKSPACE;
-  }
-  hipStream_t stream = isr::as_stream(stream_);
-  // with B items on the grid the target needs fewer key ranges than the single call's plan cuts
   const NNPlan p = make_plan(Ns, Nt, B, true);
   isr::Workspace w(ws, ws_bytes);
-  double* part_sums = w.take<double>((size_t)B * p.fblocks * kNV);
-  IcpState* st = w.take<IcpState>(B);
-  unsigned long long* packed = w.take<unsigned long long>((size_t)B * Ns);
-  int32_t* prev_idx = w.take<int32_t>((size_t)B * Ns);
-  int32_t* amb = w.take<int32_t>((size_t)B * Ns);
-  float* t2_bound = w.take<float>(1);
-  float* tile_box = w.take<float>((size_t)((Nt + kTile - 1) / kTile) * 6);
-  const bool warm = isr::tuning(ISR_TUNE_ICP_WARM) != 0;
-  icp_init_kernel<<<dim3((Ns + kThreads - 1) / kThreads, B), kThreads, 0, stream>>>(st, state, packed, amb, Ns, kIcpItemDoubles);
-  // the target is shared: its bound and its tile boxes once per call
-  cloud_r2max_kernel<<<1, kThreads, 0, stream>>>(tgt, Nt, t2_bound);
-  const float cull_r2 = (float)(threshold * threshold * 1.0001 + 1e-6);
-  if (ISR_ICP_CULL) tile_box_kernel<<<(Nt + kTile - 1) / kTile, 256, 0, stream>>>(tgt, Nt, tile_box);
-  const dim3 grid(p.qblocks, p.nsplit, B);
-  for (int it = 0; it <= max_iter; ++it) {
-    const int32_t* w_idx = (it > 0 && warm) ? prev_idx : nullptr;
-    launch_search(p, grid, stream, src, Ns, tgt, Nt, state, nullptr, nullptr, nullptr, &st->done, nullptr, packed, w_idx, amb,
-                  t2_bound, ISR_ICP_CULL ? tile_box : nullptr, cull_r2, true, src_item_stride);
-    icp_finalize_update_kernel<<<dim3(p.fblocks, B), kThreads, 0, stream>>>(src, Ns, tgt, Nt, threshold, packed, prev_idx, amb,
-                                                                             part_sums, max_iter, rel_fitness, rel_rmse, state,
-                                                                             st, state + 16, src_item_stride, kIcpItemDoubles);
+  const IcpBufs b = carve(w, p, Ns, Nt, B, kNV, 0);
+  if (!ws || !w.ok()) {
+    isr::set_error("isr_icp_point_to_point_batch: workspace %zu < %zu", ws_bytes, w.off);
+    return ISR_ERR_WORKSPACE;
   }
-  ISR_CHECK_LAUNCH("icp batch kernels");
-  return ISR_OK;
+  return run_icp_loop("icp batch kernels", p, b, isr::as_stream(stream_), src, src_item_stride, Ns, tgt, Nt, B, true, threshold,
+                      max_iter, rel_fitness, rel_rmse, PointToPoint{state, state + 16, kIcpItemDoubles});
 }
 
-// ------------------------------------------------------------------------------- point-to-plane ICP
-// include/isr_icp_plane.h: the batched loop above with another estimator.  The searches are the very launches of
-// isr_icp_point_to_point_batch (nn_search_kernel<.., EXACT, .., ITEMS>, unchanged); the finalize is a sibling of
-// icp_finalize_update_kernel that gathers the winner's normal, forms the row of csrc/icp_plane.hpp and reduces its 31 sums
-// in the same fixed shape; the item's last workgroup solves the 6x6 system and composes T.  The arithmetic is icp_plane.hpp's
-// and nothing else, so that the host entry at the end of this file gives the same bits.
-#include "../../include/isr_icp_plane.h"
-#include "icp_plane.hpp"
-
-namespace {
-
-namespace ipl = isr::icp_plane;
-static_assert(ipl::kLanes == kIcpLanes && ipl::kStateDoubles == ISR_ICP_PLANE_STATE_DOUBLES && ipl::kL2 == ISR_ICP_L2 &&
-                  ipl::kHuber == ISR_ICP_HUBER && ipl::kTukey == ISR_ICP_TUKEY,
-              "csrc/icp_plane.hpp, include/isr_icp_plane.h and the point-to-point loop disagree");
-
-// The searches read an item's T from rows kIcpItemDoubles apart (their instantiation is point-to-point's): the loop keeps
-// its working T in the workspace in that layout (Tw) and mirrors it into the caller's (B, 24) state after every pass.
-__global__ void icp_plane_init_kernel(IcpState* st, double* __restrict__ state, double* __restrict__ Tw,
-                                      unsigned long long* packed, int32_t* amb, int Ns) {
-  const size_t b = blockIdx.y;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < Ns) { packed[b * Ns + i] = ~0ull; amb[b * Ns + i] = 0; }
-  if (i != 0) return;
-  st += b; state += b * ipl::kStateDoubles; Tw += b * kIcpItemDoubles;
-  st->prev_fit = 0; st->prev_rmse = 0; st->iter = 0; st->done = 0; st->ticket = 0;
-  for (int k = 0; k < 12; ++k) Tw[k] = state[k];
-  state[12] = 0; state[13] = 0; state[14] = 0; state[15] = 1;
-}
-
-// icp_finalize_update_kernel with the point-to-plane row.  blockIdx.y is the item; no workgroup waits for another: each
-// delivers its 31 block sums and takes a ticket, and the last one OF THE ITEM reduces, decides and updates.
-__global__ __launch_bounds__(kThreads) void icp_plane_finalize_update_kernel(
-    const float* __restrict__ src, int Ns, const float* __restrict__ tgt, const float* __restrict__ nrm, int Nt,
-    double threshold, unsigned long long* __restrict__ packed, int32_t* __restrict__ prev_idx, int32_t* __restrict__ amb,
-    double* __restrict__ part_sums, int max_iter, double rel_fitness, double rel_rmse, int kernel, double kw,
-    double* __restrict__ Tw, IcpState* __restrict__ st, double* __restrict__ state, size_t src_item_stride) {
-  __shared__ double red[kThreads / 64][ipl::kSums];
-  __shared__ double part[ipl::kSums][kIcpLanes];
-  __shared__ double tot[ipl::kSums];
-  __shared__ int last;
-  __shared__ int nflag, flist[kThreads];
-  __shared__ double wd[4][kThreads / 64];
-  __shared__ int wi[4][kThreads / 64];
-  {
-    const size_t b = blockIdx.y;
-    src += b * src_item_stride;
-    packed += b * Ns; prev_idx += b * Ns; amb += b * Ns;
-    part_sums += b * gridDim.x * ipl::kSums;
-    st += b;
-    Tw += b * kIcpItemDoubles; state += b * ipl::kStateDoubles;
-  }
-  if (st->done) return;
-  const int tid = threadIdx.x;
-  const int qi = blockIdx.x * kThreads + tid;
-  // ---- near ties the search flagged: decided over all targets in f64, exactly as icp_finalize_update_kernel does (the
-  // same code: that kernel keeps its own copy so that its instructions stay what they are)
-  if (tid == 0) nflag = 0;
-  __syncthreads();
-  if (qi < Ns && amb[qi]) {
-    amb[qi] = 0;
-    flist[atomicAdd(&nflag, 1)] = qi;
-  }
-  __syncthreads();
-  const int nf = nflag;                             // block-uniform
-  constexpr int kRes = 4;
-  for (int f0 = 0; f0 < nf; f0 += kRes) {
-    double qx[kRes], qy[kRes], qz[kRes], bd[kRes];
-    int bi[kRes];
-#pragma unroll
-    for (int k = 0; k < kRes; ++k) {
-      const int pq = flist[min(f0 + k, nf - 1)];
-      xform64(Tw, src[3 * (size_t)pq], src[3 * (size_t)pq + 1], src[3 * (size_t)pq + 2], qx[k], qy[k], qz[k]);
-      bd[k] = __builtin_inf();
-      bi[k] = 0x7fffffff;
-    }
-#pragma unroll 4
-    for (int j = tid; j < Nt; j += kThreads) {
-      const double tx = tgt[3 * (size_t)j], ty = tgt[3 * (size_t)j + 1], tz = tgt[3 * (size_t)j + 2];
-#pragma unroll
-      for (int k = 0; k < kRes; ++k) {
-        const double ex = qx[k] - tx, ey = qy[k] - ty, ez = qz[k] - tz;
-        const double s2 = fma(ez, ez, fma(ey, ey, ex * ex));
-        if (s2 < bd[k]) { bd[k] = s2; bi[k] = j; }  // ascending j per thread: ties keep the lower index
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < kRes; ++k) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const double od = __shfl_xor(bd[k], off, 64);
-        const int oi = __shfl_xor(bi[k], off, 64);
-        if (od < bd[k] || (od == bd[k] && oi < bi[k])) { bd[k] = od; bi[k] = oi; }
-      }
-      if ((tid & 63) == 0) { wd[k][tid >> 6] = bd[k]; wi[k][tid >> 6] = bi[k]; }
-    }
-    __syncthreads();
-    if (tid < kRes && f0 + tid < nf) {
-      double d = wd[tid][0];
-      int i = wi[tid][0];
-      for (int w = 1; w < kThreads / 64; ++w)
-        if (wd[tid][w] < d || (wd[tid][w] == d && wi[tid][w] < i)) { d = wd[tid][w]; i = wi[tid][w]; }
-      packed[flist[f0 + tid]] = ((unsigned long long)__float_as_uint((float)d) << 32) | (unsigned int)i;
-    }
-    __syncthreads();
-  }
-  // ---- the row of this thread's source point (zeros for no neighbour, a pair beyond the radius, a row past Ns)
-  double v[ipl::kSums];
-#pragma unroll
-  for (int k = 0; k < ipl::kSums; ++k) v[k] = 0.0;
-  if (qi < Ns) {
-    const unsigned long long pk = packed[qi];
-    packed[qi] = ~0ull;
-    prev_idx[qi] = pk != ~0ull ? (int)(unsigned int)pk : -1;     // the next pass starts from this neighbour
-    if (pk != ~0ull) {
-      const size_t bi = (unsigned int)pk;           // < Nt: the search posts indices of the target only
-      double p[3];
-      ipl::xform(Tw, src[3 * (size_t)qi], src[3 * (size_t)qi + 1], src[3 * (size_t)qi + 2], p);
-      const double t[3] = {tgt[3 * bi], tgt[3 * bi + 1], tgt[3 * bi + 2]};
-      const double nt[3] = {nrm[3 * bi], nrm[3 * bi + 1], nrm[3 * bi + 2]};
-      ipl::row(p, t, nt, threshold, kernel, kw, v);
-    }
-  }
-  // ---- 31 sums, one wave tree each (a sum's 64 values cross lanes in registers; LDS sees four doubles per sum)
-  const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-  for (int k = 0; k < ipl::kSums; ++k) {
-    const double s = isr::wave_sum_down(v[k]);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (tid < ipl::kSums) part_sums[(size_t)blockIdx.x * ipl::kSums + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-  __threadfence();                                  // the block's sums are visible device-wide ...
-  __syncthreads();
-  if (tid == 0) last = (atomicAdd(&st->ticket, 1) == (int)gridDim.x - 1);   // ... before its ticket is
-  __syncthreads();
-  if (!last) return;                                // block-uniform
-  __threadfence();
-  if (tid == 0) st->ticket = 0;
-  // ---- the item's last workgroup: blocks -> lanes -> sums in icp_reduce_and_update's order, then the rule
-  const int nblk = gridDim.x;
-  for (int idx = tid; idx < ipl::kSums * kIcpLanes; idx += kThreads) {
-    const int k = idx / kIcpLanes, l = idx % kIcpLanes;
-    double s = 0.0;
-    for (int i = l; i < nblk; i += kIcpLanes) s += part_sums[(size_t)i * ipl::kSums + k];
-    part[k][l] = s;
-  }
-  __syncthreads();
-  if (tid < ipl::kSums) {
-    double s = 0.0;
-    for (int l = 0; l < kIcpLanes; ++l) s += part[tid][l];
-    tot[tid] = s;
-  }
-  __syncthreads();
-  if (tid != 0) return;
-  double sums[ipl::kSums];
-#pragma unroll
-  for (int k = 0; k < ipl::kSums; ++k) sums[k] = tot[k];
-  ipl::Loop lp{st->prev_fit, st->prev_rmse, st->iter, st->done};
-  double T[12], out[8];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) T[k] = Tw[k];
-  ipl::finish_pass(sums, Ns, max_iter, rel_fitness, rel_rmse, T, &lp, out);
-#pragma unroll
-  for (int k = 0; k < 12; ++k) { Tw[k] = T[k]; state[k] = T[k]; }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) state[16 + k] = out[k];
-  st->prev_fit = lp.prev_fit; st->prev_rmse = lp.prev_rmse; st->iter = lp.iter;
-  __threadfence();
-  st->done = lp.done;
-}
-
-}  // namespace
-
+// include/isr_icp_plane.h: the batched loop with the point-to-plane estimator; the searches are the very launches of
+// isr_icp_point_to_point_batch, on its plan.
 extern "C" size_t isr_icp_point_to_plane_batch_workspace_bytes(int Ns, int Nt, int B) {
-  if (Ns <= 0 || Nt <= 0 || B <= 0) return 0;
-  const NNPlan p = make_plan(Ns, Nt, B, true);
-  return isr::align_up((size_t)B * p.fblocks * ipl::kSums * sizeof(double), 256) + isr::align_up((size_t)B * sizeof(IcpState), 256) +
-         isr::align_up((size_t)B * kIcpItemDoubles * sizeof(double), 256) + isr::align_up((size_t)B * Ns * 8, 256) +
-         2 * isr::align_up((size_t)B * Ns * 4, 256) + isr::align_up((size_t)((Nt + kTile - 1) / kTile) * 6 * sizeof(float), 256) + 2048;
+  return icp_workspace_bytes(Ns, Nt, B, ipl::kSums, kIcpItemDoubles);
 }
 
 extern "C" int isr_icp_point_to_plane_batch(const float* src, size_t src_item_stride, int Ns, const float* tgt,
@@ -1386,38 +863,15 @@ extern "C" int isr_icp_point_to_plane_batch(const float* src, size_t src_item_st
     return ISR_ERR_ARG;
   }
   if (B == 0) return ISR_OK;
-  if (!ws || ws_bytes < isr_icp_point_to_plane_batch_workspace_bytes(Ns, Nt, B)) {
-    isr::set_error("isr_icp_point_to_plane_batch: workspace %zu < %zu", ws_bytes,
-                   isr_icp_point_to_plane_batch_workspace_bytes(Ns, Nt, B));
+  const NNPlan p = make_plan(Ns, Nt, B, true);
+  isr::Workspace w(ws, ws_bytes);
+  const IcpBufs b = carve(w, p, Ns, Nt, B, ipl::kSums, kIcpItemDoubles);
+  if (!ws || !w.ok()) {
+    isr::set_error("isr_icp_point_to_plane_batch: workspace %zu < %zu", ws_bytes, w.off);
     return ISR_ERR_WORKSPACE;
   }
-  hipStream_t stream = isr::as_stream(stream_);
-  const NNPlan p = make_plan(Ns, Nt, B, true);      // the plan of isr_icp_point_to_point_batch
-  isr::Workspace w(ws, ws_bytes);
-  double* part_sums = w.take<double>((size_t)B * p.fblocks * ipl::kSums);
-  IcpState* st = w.take<IcpState>(B);
-  double* Tw = w.take<double>((size_t)B * kIcpItemDoubles);
-  unsigned long long* packed = w.take<unsigned long long>((size_t)B * Ns);
-  int32_t* prev_idx = w.take<int32_t>((size_t)B * Ns);
-  int32_t* amb = w.take<int32_t>((size_t)B * Ns);
-  float* t2_bound = w.take<float>(1);
-  float* tile_box = w.take<float>((size_t)((Nt + kTile - 1) / kTile) * 6);
-  const bool warm = isr::tuning(ISR_TUNE_ICP_WARM) != 0;
-  icp_plane_init_kernel<<<dim3((Ns + kThreads - 1) / kThreads, B), kThreads, 0, stream>>>(st, state, Tw, packed, amb, Ns);
-  cloud_r2max_kernel<<<1, kThreads, 0, stream>>>(tgt, Nt, t2_bound);
-  const float cull_r2 = (float)(threshold * threshold * 1.0001 + 1e-6);
-  if (ISR_ICP_CULL) tile_box_kernel<<<(Nt + kTile - 1) / kTile, 256, 0, stream>>>(tgt, Nt, tile_box);
-  const dim3 grid(p.qblocks, p.nsplit, B);
-  for (int it = 0; it <= max_iter; ++it) {
-    const int32_t* w_idx = (it > 0 && warm) ? prev_idx : nullptr;
-    launch_search(p, grid, stream, src, Ns, tgt, Nt, Tw, nullptr, nullptr, nullptr, &st->done, nullptr, packed, w_idx, amb,
-                  t2_bound, ISR_ICP_CULL ? tile_box : nullptr, cull_r2, true, src_item_stride);
-    icp_plane_finalize_update_kernel<<<dim3(p.fblocks, B), kThreads, 0, stream>>>(
-        src, Ns, tgt, tgt_normals, Nt, threshold, packed, prev_idx, amb, part_sums, max_iter, rel_fitness, rel_rmse, kernel, k, Tw,
-        st, state, src_item_stride);
-  }
-  ISR_CHECK_LAUNCH("icp plane kernels");
-  return ISR_OK;
+  return run_icp_loop("icp plane kernels", p, b, isr::as_stream(stream_), src, src_item_stride, Ns, tgt, Nt, B, true, threshold,
+                      max_iter, rel_fitness, rel_rmse, PointToPlane{tgt_normals, kernel, k, b.item, state});
 }
 
 // The same loop as host code over HOST pointers (csrc/icp_plane.hpp): the tests' reference, and the entry of CPU users.

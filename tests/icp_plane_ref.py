@@ -52,10 +52,10 @@ def _sum(rows, shape):
 
 
 def icp_plane_ref(src_f32, tgt_f32, nrm_f32, threshold, init=None, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6,
-                  kernel="tukey", k=1.0, shape="forward"):
+                  kernel="tukey", k=1.0, shape="forward", search_fn=search):
     """-> trajectory: a list of dicts T, fitness, rmse, n, iterations, status (None while the loop goes on), wr2, and the
     margins gap, thr_margin, ties of icp_ref.search; entry m holds the state after m updates, the last one is where the loop
-    stopped."""
+    stopped.  search_fn: as in icp_ref.icp_ref (icp_ref.search_f32_lowest models a search without the f64 decision)."""
     src = np.asarray(src_f32, np.float32).astype(np.float64)
     tgt = np.asarray(tgt_f32, np.float32).astype(np.float64)
     nrm = np.asarray(nrm_f32, np.float32).astype(np.float64)
@@ -65,7 +65,7 @@ def icp_plane_ref(src_f32, tgt_f32, nrm_f32, threshold, init=None, max_iter=30, 
     traj, it, prev = [], 0, None
     while True:
         p = transform(T, src)
-        idx, d2, gap, thr_margin, ties = search(p, tgt, threshold)
+        idx, d2, gap, thr_margin, ties = search_fn(p, tgt, threshold)
         m = d2 <= threshold * threshold
         n = int(m.sum())
         fit = n / len(src)
@@ -182,6 +182,22 @@ def pca_normals(pts, K=16):
         c = nb - nb.mean(1, keepdims=True)
         out[i0:i0 + 512] = np.linalg.eigh(np.einsum("nki,nkj->nij", c, c))[1][:, :, 0]
     return out.astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------ near ties
+NEAR_TIES = {"near_tie_pos": dict(sign=1.0), "near_tie_neg": dict(sign=-1.0), "near_tie_pos_permuted": dict(sign=1.0, permute=True)}
+NEAR_TIE_KERNELS = ("l2", "tukey")
+NEAR_TIE_K = 2.0
+NEAR_TIE_SEED = 0       # tests/test_icp_plane_cpu.py shows that this seed's normals tell the tied targets apart
+
+
+def near_tie_case(name, seed=NEAR_TIE_SEED):
+    """icp_ref.near_tie_case (125 sources, 216 targets, threshold 2: eight targets at one f32 distance from every source
+    point) with seeded random f32 normals, so that the eight carry different normals and the winner shows in every sum."""
+    from .icp_ref import near_tie_case as lattice_case
+    c = lattice_case(seed=seed, **NEAR_TIES[name])
+    c["nrm"] = np.random.default_rng([seed, 81]).normal(size=c["tgt"].shape).astype(np.float32)
+    return c
 
 
 def mean_error(T, src):

@@ -1,7 +1,7 @@
 """Point-to-point ICP in plain NumPy f64, pass by pass: the reference of tests/test_gpu_icp_edges.py (checked itself by
 tests/test_icp_ref_cpu.py).  Nothing here uses oracle/ or the package.
 
-The loop, as the project states it (csrc/nn_batched.hip, icp_reduce_and_update):
+The loop, as the project states it (csrc/icp_loop.hpp, PointToPoint::finish):
   pass it:  p = T src in f64; every source point's nearest target by exact brute force on doubles, the LOWEST index on
             exact equality; a pair counts iff d2 <= threshold * threshold; fitness = n / Ns, rmse = sqrt(sum d2 / n) (0 for
             n = 0);

@@ -16,7 +16,7 @@ tiling, the stopping rule, lattices on which EVERY point is an exact or a sub-f3
 cull, degenerate correspondences for the Horn step, clouds far from the origin.
 
 Sensitivity (tried on scratch builds): with the search's near-tie flag never raised, or with the f64 resolution sweep of
-icp_finalize_update_kernel dropped, test_lattice_ties[near_tie_pos] and [near_tie_pos_permuted] fail at k = 0; the
+the pass (resolve_flagged, csrc/icp_loop.hpp) dropped, test_lattice_ties[near_tie_pos] and [near_tie_pos_permuted] fail at k = 0; the
 one-point-at-the-origin case failed before the near-tie bound returned inf for a best of inf.
 
 Measured agreement: profiles/icp_edges_parity.json (rewritten by running this module with ISR_ICP_EDGES_PARITY_OUT=<file>)."""

@@ -193,6 +193,27 @@ def test_ties_take_the_lowest_index_normal(cuda0, max_iter):
         assert twice[0, 21] == pytest.approx(float((w * r * r).sum()), rel=1e-12)
 
 
+@pytest.mark.parametrize("name", list(pr.NEAR_TIES))
+def test_near_tie_lattices(cuda0, name):
+    """icp_ref's near-tie lattices with random normals: every source point has eight targets at one f32 distance that f64
+    tells apart by a relative 1.3e-9, each with a normal of its own, so the f64 decision of the flagged points (the sweep the
+    pass shares with point-to-point) shows in every sum.  tests/test_icp_plane_cpu.py::
+    test_near_tie_normals_tell_the_winners_apart shows that the host build's state is not that of the f32-lowest winner.
+    B = 3: one source, the case's start with its offset of a few 1e-9 taken once, twice and three times."""
+    c = pr.near_tie_case(name)
+    inits = [ir.pose(t=m * c["init"][:3, 3]) for m in (1.0, 2.0, 3.0)]
+    bad = []
+    for kernel in pr.NEAR_TIE_KERNELS:
+        for max_iter in (0, 1, 3):
+            kw = dict(max_iter=max_iter, kernel=kernel, k=pr.NEAR_TIE_K)
+            want = host(c["src"], c["tgt"], c["nrm"], c["threshold"], inits, **kw)
+            if not same(device(cuda0, c["src"], c["tgt"], c["nrm"], c["threshold"], inits[:1], **kw), want[:1]):
+                bad.append((kernel, max_iter, "B=1"))
+            if not same(device(cuda0, c["src"], c["tgt"], c["nrm"], c["threshold"], inits, **kw), want):
+                bad.append((kernel, max_iter, "B=3"))
+    assert not bad, bad
+
+
 # ------------------------------------------------------------------------------------------------ 8
 def test_normal_sign_changes_no_byte(cuda0):
     srcs, tgt, nrm, inits = size_case(513, 600)

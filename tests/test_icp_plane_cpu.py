@@ -138,6 +138,38 @@ def test_every_double_is_written(hip_lib):
         assert a[18] <= max_iter
 
 
+@pytest.mark.parametrize("kernel", pr.NEAR_TIE_KERNELS)
+@pytest.mark.parametrize("name", list(pr.NEAR_TIES))
+def test_near_tie_normals_tell_the_winners_apart(hip_lib, name, kernel):
+    """The precondition of tests/test_gpu_icp_plane.py::test_near_tie_lattices: the host build's state shows WHICH of a source
+    point's eight f32-tied targets won.  The winner of a search without the f64 decision (icp_ref.search_f32_lowest: the
+    lowest index of the eight) is restated through icp_plane_ref at max_iter = 0; the state of a run fed that winner differs
+    from the host build's in bytes, and by far more than rounding: sum w r^2 moves by over 1e-3 of itself, while the host
+    build agrees with the reference on the exact winner to 1e-12.
+    near_tie_neg is the control: there the f64 winner, the (-,-,-) corner, IS the lowest index of the eight (tests/
+    test_icp_ref_cpu.py::test_lattice_one_step_translations asserts both), so no state can tell the two searches apart; the
+    case asserts that they coincide, and on the device it shows that the sweep leaves a right winner alone."""
+    c = pr.near_tie_case(name)
+    assert c["src"].shape == (125, 3) and c["tgt"].shape == (216, 3) and c["threshold"] == 2.0
+    args = (c["src"], c["tgt"], c["nrm"], c["threshold"], c["init"], 0)
+    kw = dict(kernel=kernel, k=pr.NEAR_TIE_K)
+    h = host(*args, **kw)
+    exact = pr.icp_plane_ref(*args, **kw)[-1]
+    lowest = pr.icp_plane_ref(*args, search_fn=ir.search_f32_lowest, **kw)[-1]
+    p, t = ir.transform(c["init"], c["src"].astype(np.float64)), c["tgt"].astype(np.float64)
+    i64, i32 = ir.search(p, t, 2.0)[0], ir.search_f32_lowest(p, t)[0]
+    assert h[19] == 125 and h[20] == 1 and h[21] == pytest.approx(exact["wr2"], rel=1e-12) and exact["wr2"] > 0
+    if name == "near_tie_neg":
+        assert np.array_equal(i64, i32) and lowest["wr2"] == exact["wr2"]
+        return
+    assert (i64 != i32).all() and (c["nrm"][i64] != c["nrm"][i32]).any(1).all()
+    fed = h.copy()
+    fed[16:22] = [lowest[key] for key in ("fitness", "rmse", "iterations", "n", "status", "wr2")]
+    print(name, kernel, "sum w r^2: host", h[21], "exact winner", exact["wr2"], "f32-lowest winner", lowest["wr2"])
+    assert abs(lowest["wr2"] - exact["wr2"]) > 1e-3 * exact["wr2"]
+    assert fed.tobytes() != h.tobytes()
+
+
 def test_batch_items_equal_single_calls(hip_lib):
     rng = np.random.default_rng(7)
     tgt = ir.surface(rng, 400)
